@@ -11,12 +11,20 @@ equal WORLD_SIZE; without it, bench.py starts `torch.distributed.run
 --nproc-per-node N` itself as a child process (before touching a GPU) and
 exits with its status.  Every rank CRCs its own 64k x 64 KiB slice of an
 N-times larger batch (weak scaling, no data-path collective; a gloo barrier
-brackets the timed region and the time is the max over ranks).  For N > 1
-the line also carries "strong_scaling": BASELINE configs[3] (Zipf 4M, one
+brackets the timed region and the time is the max over ranks).  With --full,
+for N > 1 the line also carries "strong_scaling": BASELINE configs[3] (Zipf 4M, one
 batch split byte-balanced over the N ranks) timed across the ranks and, in
 the same run, the whole batch on rank 0's GPU alone -- the measured speed-up.
 
 Output: one JSON line on rank 0 (see README/DESIGN.md for fields).
+
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline
+figure needs: set up the batch, settle, W warmup steps, the K timed steps,
+the result line.  `--dump-outputs DIR` also writes the CRCs the last timed
+step returned as DIR/crc32c.npy.  Everything else this benchmark measures on
+that path -- the planned and declared legs, the HIP-event pass behind the
+roofline's kernel figures, the parity check against the CPU oracle, the CPU
+baseline, the strong-scaled Zipf object for N > 1 -- runs only with `--full`.
 """
 import argparse
 import json
@@ -73,12 +81,31 @@ CONFIGS = {
 UNIFORM_SIZES = {"1k_x_4KiB": 4096, "64k_x_64KiB": 65536, "1M_x_256B": 256,
                  "16_x_256MiB": 256 << 20}
 
+# --dump-outputs: every BASELINE config (at most 4M messages, 32 MiB of
+# float64) is written whole; a larger experiment as a sample with its indices
+# (2 x 16 MiB), so a dump never passes 64 MB
+DUMP_MAX_MSGS = 4 << 20
+DUMP_SAMPLE_MSGS = 2 << 20
+
 
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other measurement and check of "
+                        "the batch path: the planned and declared legs, the HIP-event pass "
+                        "(roofline kernel figures), the parity check against the CPU oracle, "
+                        "the CPU baseline and, for N > 1, the strong-scaled Zipf object "
+                        "(--no-cpu-baseline, --cpu-seconds, --check, --no-kernel-timing and "
+                        "--no-strong-scaling tune these and mean nothing without --full)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the CRCs the last timed step returned "
+                        "(one per message, in batch order) as DIR/crc32c.npy (float64; "
+                        "crc32c_rank<r>.npy per rank for N > 1); a batch of more than %d "
+                        "messages is written as a fixed seeded sample of %d, their indices "
+                        "in DIR/crc32c_index.npy" % (DUMP_MAX_MSGS, DUMP_SAMPLE_MSGS))
     p.add_argument("--config", default=None, choices=list(CONFIGS),
                    help="default 64k_x_64KiB (the headline); --cpu-table: all configs")
     p.add_argument("--seg-bytes", type=int, default=0)
@@ -138,6 +165,9 @@ def parse():
                    help="test hook: start the ranks, rendezvous over gloo and print the "
                         "world as rank 0 sees it, without touching a GPU")
     a = p.parse_args()
+    if a.dump_outputs and (a.cpu_table or a.scalar or a.protocol or a.e2e or a.launch_check):
+        p.error("--dump-outputs writes the batch path's CRCs: not with --cpu-table, --scalar, "
+                "--protocol, --e2e or --launch-check")
     a.config_given = a.config is not None
     if a.rotate is None:
         a.rotate = 4 if a.config == "1M_x_256B" else 1
@@ -643,6 +673,21 @@ def pmc_traffic(config):
     return int(s["traffic_bytes_per_launch"]), os.path.relpath(paths[-1], ROOT)
 
 
+def dump_outputs(path, crcs, world, rank):
+    """--dump-outputs: what the last timed step handed its caller, this rank's
+    CRC per message in batch order, as float64 (every uint32 is exact in it).
+    The batch, and so the file, is the same from run to run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    name = "crc32c" if world == 1 else "crc32c_rank%d" % rank
+    if crcs.size > DUMP_MAX_MSGS // world:
+        idx = np.sort(np.random.default_rng(0).choice(crcs.size, DUMP_SAMPLE_MSGS // world,
+                                                      replace=False))
+        np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+        crcs = crcs[idx]
+    np.save(os.path.join(path, name + ".npy"), crcs.astype(np.float64))
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
@@ -797,45 +842,51 @@ def main():
     elapsed = t1 - t0
     launch = bmq.last_launch(local, stream)  # the steady-state step's launch plan
     voided1 = bmq.plan_wait(local, stream, wait_us)
-    # The same K steps with the shape prediction off (BMQCRC_F_PLAN): what a
-    # caller whose batch shapes alternate on one stream pays per batch.
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step(False, plan=True)
-    torch.cuda.synchronize(dev)
-    planned = time.perf_counter() - t0
-    planned_launch = bmq.last_launch(local, stream)
-    voided2 = bmq.plan_wait(local, stream, wait_us)
-    # ... and with the prediction dropped before every step but the batch's
-    # length bounds declared (bmqcrc_opts.max_len / min_len, ABI 2.4 / 2.5): what a
-    # caller that knows its message sizes pays when shapes alternate.
-    max_len = int(lens_np.max()) if n else 0
-    min_len = int(lens_np.min()) if n else 0
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        bmq.forget_shape(local, stream)
-        step(False, max_len=max_len, min_len=min_len)
-    torch.cuda.synchronize(dev)
-    declared = time.perf_counter() - t0
-    declared_launch = bmq.last_launch(local, stream)
-    if world > 1:
-        dist.barrier()
-    step(False)  # back to the predicted shape
-    # Second timed pass of the same K steps with HIP events recorded around
-    # the dominant kernel (k_fold) on its launch stream: its average duration
-    # prices the roofline (events add launch gaps, so `value` comes from the
-    # clean pass above).
-    if not args.no_kernel_timing:
-        for _ in range(args.steps):
-            step(True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out.cpu().numpy().view(np.uint32), world, rank)
+    planned = declared = kern_ms = 0.0
+    kern_cnt = 0
+    voided2 = voided1
+    if args.full:
+        # The same K steps with the shape prediction off (BMQCRC_F_PLAN): what a
+        # caller whose batch shapes alternate on one stream pays per batch.
+        if world > 1:
+            dist.barrier()
         torch.cuda.synchronize(dev)
-    kern_ms, kern_cnt = bmq.kernel_timing(local, stream)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step(False, plan=True)
+        torch.cuda.synchronize(dev)
+        planned = time.perf_counter() - t0
+        planned_launch = bmq.last_launch(local, stream)
+        voided2 = bmq.plan_wait(local, stream, wait_us)
+        # ... and with the prediction dropped before every step but the batch's
+        # length bounds declared (bmqcrc_opts.max_len / min_len, ABI 2.4 / 2.5): what a
+        # caller that knows its message sizes pays when shapes alternate.
+        max_len = int(lens_np.max()) if n else 0
+        min_len = int(lens_np.min()) if n else 0
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            bmq.forget_shape(local, stream)
+            step(False, max_len=max_len, min_len=min_len)
+        torch.cuda.synchronize(dev)
+        declared = time.perf_counter() - t0
+        declared_launch = bmq.last_launch(local, stream)
+        if world > 1:
+            dist.barrier()
+        step(False)  # back to the predicted shape
+        # Second timed pass of the same K steps with HIP events recorded around
+        # the dominant kernel (k_fold) on its launch stream: its average duration
+        # prices the roofline (events add launch gaps, so `value` comes from the
+        # clean pass above).
+        if not args.no_kernel_timing:
+            for _ in range(args.steps):
+                step(True)
+            torch.cuda.synchronize(dev)
+        kern_ms, kern_cnt = bmq.kernel_timing(local, stream)
     del arena, copies  # the strong-scaling leg below needs the memory
     bytes_all = total_bytes
     kern_max = kern_ms / max(kern_cnt, 1)
@@ -854,35 +905,35 @@ def main():
     else:
         n_all = n
 
-    # parity spot check against the CPU oracle (sampled messages)
-    import oracle
-    got = out.cpu().numpy().view(np.uint32)
-    rng = np.random.default_rng(rank)
-    idx = np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, size=max(0, args.check - 2))]))
-    budget = 256 << 20  # bytes of payload regenerated on the host for checking
     bad, checked = 0, 0
-    for i in idx:
-        ln = int(lens_np[i])
-        if checked and ln > budget:
-            continue
-        budget -= ln
-        exp = oracle.crc32c(oracle.fill_payload(begin + int(offs_np[i]), ln, seed), 0, "hw")
-        bad += int(got[i] != exp)
-        checked += 1
-    if world > 1:
-        bt = torch.tensor([bad, checked], dtype=torch.int64)
-        dist.all_reduce(bt)
-        bad, checked = int(bt[0]), int(bt[1])
     strong = None
-    if world > 1 and not args.no_strong_scaling and not args.config_given:
-        strong = strong_scaling(args, bmq, Crc32c, dev, stream, world, rank, dist)
-        bad += strong.pop("_bad")
+    if args.full:
+        # parity spot check against the CPU oracle (sampled messages)
+        import oracle
+        got = out.cpu().numpy().view(np.uint32)
+        rng = np.random.default_rng(rank)
+        idx = np.unique(np.concatenate([[0, n - 1],
+                                        rng.integers(0, n, size=max(0, args.check - 2))]))
+        budget = 256 << 20  # bytes of payload regenerated on the host for checking
+        for i in idx:
+            ln = int(lens_np[i])
+            if checked and ln > budget:
+                continue
+            budget -= ln
+            exp = oracle.crc32c(oracle.fill_payload(begin + int(offs_np[i]), ln, seed), 0, "hw")
+            bad += int(got[i] != exp)
+            checked += 1
+        if world > 1:
+            bt = torch.tensor([bad, checked], dtype=torch.int64)
+            dist.all_reduce(bt)
+            bad, checked = int(bt[0]), int(bt[1])
+        if world > 1 and not args.no_strong_scaling and not args.config_given:
+            strong = strong_scaling(args, bmq, Crc32c, dev, stream, world, rank, dist)
+            bad += strong.pop("_bad")
 
     if rank == 0:
         value = bytes_all / 2**30 * args.steps / elapsed
-        avg_kern_s = kern_max / 1e3 if kern_cnt else float("nan")
         alg_bytes = total_bytes + 4 * n  # this GPU's payload read once + CRCs written
-        achieved = alg_bytes / avg_kern_s / 1e9
         traffic, traffic_src = pmc_traffic(args.config)
         res = {
             "metric": "device-resident CRC32C GiB/s over batched payloads, 1/2/4/8 MI355X",
@@ -905,38 +956,47 @@ def main():
                        "seg_bytes": args.seg_bytes or "auto",
                        "whole_messages": bool(args.whole_messages),
                        "parallelism": "dp%d (sharded batch, no collective)" % world},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+            # the figures the K timed steps give by themselves; --full adds
+            # the kernel's own time (achieved, frac, kernel_avg_us)
+            "roofline": {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": "k_fold", "kernel_avg_us": round(avg_kern_s * 1e6, 2),
-                         "kernel_time_source": "HIP events around each k_fold launch on its "
-                                               "stream, K extra steps (event-priced: includes "
-                                               "the launch gap, so frac is a lower bound; the "
-                                               "traced kernel time is in profiles/)",
                          "frac_per_step": round(alg_bytes / (elapsed / args.steps) / 1e9
                                                 / HBM_PEAK_GBS, 4),
                          "alg_bytes_per_launch": alg_bytes},
-            "parity": {"checked_msgs": checked, "mismatches": bad},
             "kernels_per_step": launch["kernels"],
             "speculative_segments_per_msg": launch["spec"],
-            "planned_ms_per_step": round(1e3 * planned / args.steps, 4),
-            "planned_value": round(bytes_all / 2**30 * args.steps / planned, 2),
-            "planned_kernels_per_step": planned_launch["kernels"],
             # single-pass planner launches (all ranks) whose size-class map was
-            # given up, in the K timed steps and in the K planned steps
+            # given up in the K timed steps
             "plan_voided": plan_voided[0],
-            "planned_plan_voided": plan_voided[1],
             "plan_wait_us": wait_us,
+            "full": bool(args.full),
         }
-        # the bounds buy one launch only when every length in them has the
-        # same u segments, u dividing 64; otherwise an in-flight batch may
-        # restore the dropped prediction mid-loop, so the leg is not reported
-        sb = max(declared_launch["seg_bytes"], 1)
-        u_hi, u_lo = (max_len - 1) // sb + 1, (max(min_len, 1) - 1) // sb + 1
-        if max_len and (u_hi == 1 or (min_len and u_hi == u_lo and 64 % u_hi == 0)):
-            res.update({"declared_max_len": max_len, "declared_min_len": min_len,
-                        "declared_ms_per_step": round(1e3 * declared / args.steps, 4),
-                        "declared_kernels_per_step": declared_launch["kernels"]})
+        if args.full:
+            avg_kern_s = kern_max / 1e3 if kern_cnt else float("nan")
+            achieved = alg_bytes / avg_kern_s / 1e9
+            res["roofline"].update({
+                "achieved": round(achieved, 1), "frac": round(achieved / HBM_PEAK_GBS, 4),
+                "kernel": "k_fold", "kernel_avg_us": round(avg_kern_s * 1e6, 2),
+                "kernel_time_source": "HIP events around each k_fold launch on its "
+                                      "stream, K extra steps (event-priced: includes "
+                                      "the launch gap, so frac is a lower bound; the "
+                                      "traced kernel time is in profiles/)"})
+            res.update({
+                "parity": {"checked_msgs": checked, "mismatches": bad},
+                "planned_ms_per_step": round(1e3 * planned / args.steps, 4),
+                "planned_value": round(bytes_all / 2**30 * args.steps / planned, 2),
+                "planned_kernels_per_step": planned_launch["kernels"],
+                # ... and in the K planned steps
+                "planned_plan_voided": plan_voided[1]})
+            # the bounds buy one launch only when every length in them has the
+            # same u segments, u dividing 64; otherwise an in-flight batch may
+            # restore the dropped prediction mid-loop, so the leg is not reported
+            sb = max(declared_launch["seg_bytes"], 1)
+            u_hi, u_lo = (max_len - 1) // sb + 1, (max(min_len, 1) - 1) // sb + 1
+            if max_len and (u_hi == 1 or (min_len and u_hi == u_lo and 64 % u_hi == 0)):
+                res.update({"declared_max_len": max_len, "declared_min_len": min_len,
+                            "declared_ms_per_step": round(1e3 * declared / args.steps, 4),
+                            "declared_kernels_per_step": declared_launch["kernels"]})
         if rehearsal:
             res["rehearsal_single_gpu"] = True
             res["ranks_on_one_gpu"] = world
@@ -945,7 +1005,7 @@ def main():
                 strong["n_gpus"] = 1
                 strong["ranks_on_one_gpu"] = world
             res["strong_scaling"] = strong
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(lens_np, seed, args.cpu_seconds, dev.index or 0)
         print(json.dumps(res), flush=True)
     if world > 1:

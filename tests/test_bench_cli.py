@@ -27,6 +27,56 @@ def test_parse_experiment_options():
     assert a.config == "64k_x_64KiB" and not a.config_given and a.gpus == 1
 
 
+def test_parse_full_and_dump_outputs(tmp_path):
+    """--full is off unless given, --dump-outputs takes a directory and is
+    refused with the modes that never run the batch path."""
+    sys.path.insert(0, ROOT)
+    import pytest
+
+    import bench
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"]
+        a = bench.parse()
+        assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+        sys.argv = ["bench.py", "--full", "--dump-outputs", str(tmp_path)]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == str(tmp_path)
+        sys.argv = ["bench.py", "--cpu-table", "--dump-outputs", str(tmp_path)]
+        with pytest.raises(SystemExit):
+            bench.parse()
+    finally:
+        sys.argv = argv
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """A batch within the limit is written whole, a larger one as the same
+    seeded sample every time with its indices; float64 holds every CRC."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+    crcs = np.random.default_rng(5).integers(0, 1 << 32, size=1000, dtype=np.uint64).astype(
+        np.uint32)
+    crcs[0], crcs[1] = 0xFFFFFFFF, 0
+    bench.dump_outputs(str(tmp_path / "whole"), crcs, 1, 0)
+    got = np.load(tmp_path / "whole" / "crc32c.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint32), crcs)
+    assert os.listdir(tmp_path / "whole") == ["crc32c.npy"]
+    monkeypatch.setattr(bench, "DUMP_MAX_MSGS", 999)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_MSGS", 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), crcs, 1, 0)
+    idx = np.load(tmp_path / "a" / "crc32c_index.npy")
+    assert idx.size == 100 and np.all(np.diff(idx) > 0) and idx[-1] < 1000
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "crc32c_index.npy"))
+    got = np.load(tmp_path / "a" / "crc32c.npy")
+    assert np.array_equal(got.astype(np.uint32), crcs[idx.astype(np.int64)])
+    assert np.array_equal(got, np.load(tmp_path / "b" / "crc32c.npy"))
+    bench.dump_outputs(str(tmp_path / "r"), crcs[:10], 2, 1)
+    assert os.listdir(tmp_path / "r") == ["crc32c_rank1.npy"]
+
+
 def test_cpu_table_runs_without_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-table",
                         "--config", "1k_x_4KiB", "--cpu-seconds", "0.2"],

@@ -26,7 +26,7 @@ for rep in $(seq 1 ${REPS:-2}); do
       args=${spec#*:}
       log=gpurun_out/${prefix}_${v}_${tag}_$rep.log
       rc=0
-      timeout -k 10 240 python3 bench.py $args --steps ${STEPS:-20} --warmup ${WARMUP:-5} \
+      timeout -k 10 240 python3 bench.py --full $args --steps ${STEPS:-20} --warmup ${WARMUP:-5} \
           --no-cpu-baseline > "$log" 2>&1 || rc=$?
       # 1 = parity mismatches (diagnostic builds); anything else ends the call
       if [ "$rc" -ne 0 ] && [ "$rc" -ne 1 ]; then

@@ -21,7 +21,7 @@ for v in $variants; do
     for c in $configs; do
         echo "== variant=$v $c $(date +%T)"
         rc=0
-        timeout -k 10 240 python3 bench.py --config "$c" --steps ${STEPS:-20} --warmup ${WARMUP:-5} \
+        timeout -k 10 240 python3 bench.py --full --config "$c" --steps ${STEPS:-20} --warmup ${WARMUP:-5} \
             --no-cpu-baseline > "gpurun_out/${prefix}_${v}_$c.log" \
             2> "gpurun_out/${prefix}_${v}_$c.err" || rc=$?
         # 1 = parity mismatches reported by bench.py (diagnostic builds); anything

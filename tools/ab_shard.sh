@@ -10,7 +10,7 @@ out=gpurun_out/$prefix.jsonl
 : > $out
 run() {  # tag, extra args
     rc=0
-    timeout -k 10 200 python3 bench.py --config zipf_4M --no-cpu-baseline "${@:2}" \
+    timeout -k 10 200 python3 bench.py --full --config zipf_4M --no-cpu-baseline "${@:2}" \
         > gpurun_out/${prefix}_tmp.log 2>> gpurun_out/$prefix.err || rc=$?
     [ "$rc" -eq 0 ] || { echo "bench exited $rc"; exit "$rc"; }
     line=$(tail -1 gpurun_out/${prefix}_tmp.log)

@@ -13,7 +13,7 @@ mkdir -p gpurun_out
 for n in $counts; do
     d=gpurun_out/${prefix}_$n
     timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $d -o run --output-format csv -- \
-        python3 bench.py --config $cfg --msgs $n ${mb:+--msg-bytes $mb} --steps 50 --warmup 5 \
+        python3 bench.py --full --config $cfg --msgs $n ${mb:+--msg-bytes $mb} --steps 50 --warmup 5 \
         --no-cpu-baseline --check 16 --no-kernel-timing > $d.log 2>&1
     python3 - "$d" "$n" "$cfg" "${mb:-0}" >> gpurun_out/$prefix.jsonl <<'PY'
 import csv, json, sys

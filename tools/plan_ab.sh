@@ -15,7 +15,7 @@ for rep in 1 2; do
     for args in "" "--shard 7/8"; do
       tag=${prefix}_${v}_${rep}_$(echo "$args" | tr -d ' /-')
       timeout -k 10 200 rocprofv3 --kernel-trace --stats -d gpurun_out/$tag -o run --output-format csv -- \
-          python3 bench.py --config zipf_4M --steps 10 --warmup 2 --no-cpu-baseline --settle-seconds 0.5 $args \
+          python3 bench.py --full --config zipf_4M --steps 10 --warmup 2 --no-cpu-baseline --settle-seconds 0.5 $args \
           > gpurun_out/$tag.log 2>&1 || { cp /tmp/plan_ab_base.so $lib/libbmqcrc.so; exit 3; }
       echo "$v rep$rep [$args] $(tail -1 gpurun_out/$tag.log | python3 -c 'import json,sys; d=json.load(sys.stdin); print(d["ms_per_step"], d["parity"]["mismatches"])') $(grep -h 'k_plan\|k_fold' gpurun_out/$tag/run_kernel_stats.csv | awk -F, '{printf "%s=%.1f ", $1, $4/1000}')"
     done

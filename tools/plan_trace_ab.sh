@@ -17,7 +17,7 @@ for v in $variants; do
         tag=$(echo "$i $v $args" | tr ' /' '__')
         echo "== $v $args $(date +%T)"
         timeout -k 10 200 rocprofv3 --kernel-trace --stats -d gpurun_out/${prefix}_$tag -o run \
-            --output-format csv -- python3 bench.py --config zipf_4M --steps 20 --warmup 5 \
+            --output-format csv -- python3 bench.py --full --config zipf_4M --steps 20 --warmup 5 \
             --no-cpu-baseline $args > gpurun_out/${prefix}_$tag.log 2>&1
     done
 done

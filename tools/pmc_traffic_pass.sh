@@ -9,7 +9,7 @@ out=$1; shift
 mkdir -p "$out"
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 120 rocprofv3 --pmc $c --kernel-trace -d $out/$c -o run --output-format csv -- \
-    python3 bench.py "$@" --steps 5 --warmup 2 --no-cpu-baseline --settle-seconds 0 \
+    python3 bench.py --full "$@" --steps 5 --warmup 2 --no-cpu-baseline --settle-seconds 0 \
     --no-kernel-timing > $out/$c.log 2>&1 || exit $?
   echo "done $c"
 done

@@ -11,5 +11,5 @@ out=$1; shift
 mkdir -p "$out"
 timeout -s KILL 120 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum --kernel-trace \
     -d $out/rdreq -o run --output-format csv -- \
-    python3 bench.py "$@" --steps 5 --warmup 2 --no-cpu-baseline --settle-seconds 0 \
+    python3 bench.py --full "$@" --steps 5 --warmup 2 --no-cpu-baseline --settle-seconds 0 \
     --no-kernel-timing > $out/rdreq.log 2>&1

@@ -39,7 +39,7 @@ def main():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_DEVICE="0")
     log = out + ".log"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n)] + extra
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", str(n)] + extra
     t0 = time.time()
     peak = 0
     last_note = t0

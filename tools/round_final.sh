@@ -24,7 +24,7 @@ for w in "1048576 256" "2097152 256" "4194304 256" "2097152 128" "4194304 64" "1
   set -- $w
   tag=rot_$1_$2
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$tag -o run --output-format csv \
-      -- python3 bench.py --config 1M_x_256B --msgs $1 --msg-bytes $2 --rotate 4 --steps 30 --warmup 5 \
+      -- python3 bench.py --full --config 1M_x_256B --msgs $1 --msg-bytes $2 --rotate 4 --steps 30 --warmup 5 \
       --no-cpu-baseline > $O/prof_$tag.log 2>&1 || exit $?
   tail -1 $O/prof_$tag.log | cut -c1-160
 done

@@ -11,7 +11,7 @@ cp $lib/libbmqcrc.so /tmp/seg_sweep_base.so
 for v in bpc1 bpc2; do
   cp $lib/variant_$v.so $lib/libbmqcrc.so
   for seg in 16384 32768 65536 131072; do
-    timeout -k 10 200 python bench.py --config $cfg --seg-bytes $seg --steps 20 \
+    timeout -k 10 200 python bench.py --full --config $cfg --seg-bytes $seg --steps 20 \
         --warmup 5 --no-cpu-baseline --check 32 > gpurun_out/sweep_${cfg}_${seg}_$v.log 2>&1
   done
 done

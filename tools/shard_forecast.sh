@@ -9,7 +9,7 @@ prefix=$1; shift
 out=gpurun_out/$prefix.jsonl
 : > "$out"
 run() {
-    timeout -k 10 200 python3 bench.py --config zipf_4M --no-cpu-baseline --steps 20 --warmup 5 "$@" \
+    timeout -k 10 200 python3 bench.py --full --config zipf_4M --no-cpu-baseline --steps 20 --warmup 5 "$@" \
         > gpurun_out/${prefix}_tmp.log 2>> gpurun_out/$prefix.err
     echo "{\"args\": \"$*\", \"bench\": $(tail -1 gpurun_out/${prefix}_tmp.log)}" >> "$out"
     tail -1 gpurun_out/${prefix}_tmp.log | python3 -c 'import json,sys; d=json.load(sys.stdin); print(d["ms_per_step"], d["parity"])'

@@ -12,7 +12,7 @@ A="SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_INSTS_VALU SQ_WAVES SQ
 B="SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES GRBM_GUI_ACTIVE"
 for p in A B; do
   timeout -s KILL 120 rocprofv3 --pmc ${!p} --kernel-trace -d $out/${p}_$tag -o run --output-format csv -- \
-    python3 bench.py "$@" --steps 4 --warmup 1 --no-cpu-baseline --settle-seconds 0 \
+    python3 bench.py --full "$@" --steps 4 --warmup 1 --no-cpu-baseline --settle-seconds 0 \
     --no-kernel-timing > $out/${p}_$tag.log 2>&1 || exit $?
   echo "done $p $tag"
 done

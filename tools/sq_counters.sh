@@ -13,6 +13,6 @@ mkdir -p gpurun_out
 for c in $configs; do
     echo "== $c $(date +%T)"
     timeout -k 10 300 rocprofv3 --pmc $COUNTERS --kernel-trace -d gpurun_out/${prefix}_$c -o run --output-format csv -- \
-        python3 bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline \
+        python3 bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline \
         --settle-seconds 0 --no-kernel-timing > gpurun_out/${prefix}_$c.log 2>&1
 done

@@ -18,7 +18,7 @@ for w in "${shapes[@]}"; do
   set -- $w
   for p in A B; do
     timeout -s KILL 90 rocprofv3 --pmc ${!p} --kernel-trace -d $out/${p}_$1_$2 -o run --output-format csv -- \
-      python3 bench.py --config 1M_x_256B --msgs $1 --msg-bytes $2 --rotate 4 --steps 4 --warmup 1 \
+      python3 bench.py --full --config 1M_x_256B --msgs $1 --msg-bytes $2 --rotate 4 --steps 4 --warmup 1 \
       --no-cpu-baseline --settle-seconds 0 --no-kernel-timing > $out/${p}_$1_$2.log 2>&1 || exit $?
     echo "done $p $1 $2"
   done
