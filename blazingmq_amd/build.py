@@ -22,7 +22,7 @@ ARCH = "gfx950"
 
 PRODUCT_SOURCES = ["crc32c_kernels.hip", "bmqcrc_host.cpp", "crc32c_cpu.cpp", "bmqp_crc32c.cpp",
                    "bmqcrc_protocol.cpp"]
-PRODUCT_DEPS = ["bmqcrc_internal.h", "crc32c_consts.h"]
+PRODUCT_DEPS = ["bmqcrc_internal.h", "crc32c_consts.h", "crc32c_diag.h"]
 
 
 def _run(cmd):
@@ -70,17 +70,24 @@ def build_product(force=False, defines=(), target_name="libbmqcrc.so"):
         for leftover in os.listdir(LIB):  # hipcc offload-bundling intermediates
             if leftover.startswith(target_name + "."):
                 os.remove(os.path.join(LIB, leftover))
-    selftest = os.path.join(ROOT, "tests", "cpp", "bin", "bmqp_selftest")
-    st_src = os.path.join(ROOT, "tests", "cpp", "bmqp_crc32c_selftest.cpp")
     if target_name != "libbmqcrc.so":
         return target
+    build_selftest(target, force)
+    build_scalar_ladder(target, force)
+    return target
+
+
+def build_selftest(target, force=False):
+    """tests/cpp/bin/bmqp_selftest, the C++ drop-in's test driver, linked
+    against the product library `target`."""
+    selftest = os.path.join(ROOT, "tests", "cpp", "bin", "bmqp_selftest")
+    st_src = os.path.join(ROOT, "tests", "cpp", "bmqp_crc32c_selftest.cpp")
     if os.path.exists(st_src) and (force or _stale(selftest, [st_src, target])):
         os.makedirs(os.path.dirname(selftest), exist_ok=True)
         _run(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), st_src,
               "-o", selftest, "-L" + LIB, "-lbmqcrc", "-pthread",
               "-Wl,-rpath,$ORIGIN/../../../blazingmq_amd/lib"])
-    build_scalar_ladder(target, force)
-    return target
+    return selftest
 
 
 def build_scalar_ladder(target, force=False):

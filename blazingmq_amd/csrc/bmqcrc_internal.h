@@ -25,7 +25,7 @@ constexpr int kBuckets = 16;            // segment size classes: floor(log2(line
 // -DBMQCRC_TUNE_BITS=...); the product is built with 0.  bit0 disables the
 // non-temporal LDS-DMA loads, bit1 forces a 1-block/CU k_fold grid, bit3
 // forces 2, bit4 always builds the size-class map (no shape prediction),
-// bit5 reads one- and two-line groups non-temporally too, bit7 plans ragged
+// bit5 retired, bit7 plans ragged
 // batches with the round-2 pair k_plan<true> + k_plan_sort instead of the
 // single-pass k_plan_map, bit9 gives planner blocks whole tiles, bit10 keeps
 // two 4-wave k_fold blocks per CU with static group shares (round 3's schedule)
@@ -33,26 +33,16 @@ constexpr int kBuckets = 16;            // segment size classes: floor(log2(line
 // launches BMQCRC_F_PLAN batches as the speculative one-segment kernel instead
 // of planning them (the cost of speculating on a stream with no history),
 // bit12 plans every batch that is planned at all with k_plan_map (round 4)
-// instead of the light k_plan when nothing says it is ragged.
+// instead of the light k_plan when nothing says it is ragged.  bit8 retired.
 #ifndef BMQCRC_TUNE_BITS
 #define BMQCRC_TUNE_BITS 0u
 #endif
 constexpr uint32_t kTuneBits = BMQCRC_TUNE_BITS;
-constexpr bool kShortDefaultPolicy = (kTuneBits & 32u) == 0;
-// bit8 turns off the remainder-step skip of one-line groups (A/B).
-constexpr bool kHornerSkip = (kTuneBits & 256u) == 0;
 // Streams right-aligned at piece granularity when that saves a line or the
 // stream is at most this many lines; longer streams otherwise keep a 128-byte
 // aligned start, whose lines are whole cache lines (right-aligning every
 // stream cost Zipf's k_fold 2.3 %, one line 0.5 %: profiles/r03/ab/ab3_*).
-#ifndef BMQCRC_RIGHT_ALIGN_LINES
-#define BMQCRC_RIGHT_ALIGN_LINES 1u
-#endif
-constexpr uint32_t kRightAlignLines = BMQCRC_RIGHT_ALIGN_LINES;
-#ifndef BMQCRC_RIGHT_ALIGN
-#define BMQCRC_RIGHT_ALIGN 1
-#endif
-constexpr bool kRightAlign = BMQCRC_RIGHT_ALIGN != 0;  // 0: round 2's 128-byte aligned streams
+constexpr uint32_t kRightAlignLines = 1u;
 
 struct BatchArgs {
     const uint8_t* arena;      // device

@@ -43,6 +43,7 @@
 
 #include "bmqcrc_internal.h"
 #include "crc32c_consts.h"
+#include "crc32c_diag.h"
 
 namespace bmqcrc {
 
@@ -59,6 +60,11 @@ typedef uint64_t u64x2e __attribute__((ext_vector_type(2), aligned(8)));
 __constant__ uint32_t c_x2col[31][32] = BMQCRC_X2COL;
 __constant__ uint32_t c_xneg8[136] = BMQCRC_XNEG8;
 __constant__ uint32_t c_xbytes[4][256] = BMQCRC_XBYTES;
+// (Two table parts have no reader in the kernels since the two-word Horner and
+// the 11-bit double chain were retired: rows 4-7 of c_ty, the "times y^2"
+// slices, and words 5120-6143 of c_rtab11, the y^16 join slices.  They are
+// still generated, self-checked and copied to LDS: kTabBytes and kTab11Bytes
+// size k_fold's LDS.)
 __constant__ uint32_t c_ty[8][256] = BMQCRC_TY;
 __constant__ uint32_t c_rtab11[6144] = BMQCRC_RTAB11;
 
@@ -130,15 +136,6 @@ __device__ __forceinline__ uint32_t gmul(uint32_t v, uint32_t w)
     return acc;
 }
 
-#ifndef BMQCRC_XB_FIRST
-#define BMQCRC_XB_FIRST 1  // 0: the move factor's product starts with byte 0's factor (A/B)
-#endif
-constexpr bool kXbFirst = BMQCRC_XB_FIRST != 0;
-#ifndef BMQCRC_SPREAD
-#define BMQCRC_SPREAD 1  // 0: small batches fill 4-wave blocks on fewer CUs (A/B)
-#endif
-constexpr bool kSpread = BMQCRC_SPREAD != 0;
-
 // v * x^(8 dist) mod P: the move of a CRC past dist zero bytes, as the
 // product of the factors of dist's bytes (tables XBYTES[i][b] = x^(8 b 256^i)
 // in LDS at xb): one lookup per byte position any lane needs and one 160-VALU
@@ -152,16 +149,6 @@ __device__ __forceinline__ uint32_t mul_xbytes(uint32_t v, uint32_t dist, uint32
     // byte there is 0 looks up x^0 = 1): one 160-VALU multiply fewer than
     // starting from byte 0, whose factor is 1 in every lane when the
     // distances are multiples of 256 (uniform messages, segment moves)
-    if constexpr (!kXbFirst) {  // A/B: round 4's form
-        uint32_t f = *(const lds_u32*)(uintptr_t)(xb + 4u * (dist & 0xffu));
-#pragma unroll
-        for (int i = 1; i < 4; ++i) {
-            if (__ballot((dist >> (8 * i)) != 0) != 0) {
-                f = gmul(f, *(const lds_u32*)(uintptr_t)(xb + 1024u * i + 4u * ((dist >> (8 * i)) & 0xffu)));
-            }
-        }
-        return gmul(v, f);
-    }
     uint32_t f = 0;
     bool have = false;
 #pragma unroll
@@ -361,14 +348,12 @@ __device__ __forceinline__ void first_round(uint32_t (&q)[32], uint32_t (&p)[32]
 // Final round: the last 32 words are the remainder coefficients R_d of the
 // stream modulo m(y).  Taps that would reach this round's (non-existent)
 // quotient words are dropped.  The remainder is reduced once per segment,
-// raw = sum R_d y^(32-d), by Horner two words per step with slicing tables in
-// LDS (tab[k][b], k<4: (b<<8k)*y, k>=4: (b<<8(k-4))*y^2):
-//   c <- (c ^ R_d) * y^2  ^  R_{d+1} * y
+// raw = sum R_d y^(32-d) (tail_bytes8 below), with slicing tables in LDS
+// (byte slices tab[k][b], k<4: (b<<8k)*y, or 11-bit slices, see step11).
 __device__ __forceinline__ uint32_t tab_lookup(uint32_t tab_lds, int k, uint32_t b)
 {
     return *(const lds_u32*)(uintptr_t)(tab_lds + k * 1024u + b * 4u);
 }
-
 
 // The last round's taps into the previous round (d + k <= 31): R_d = m_d ^
 // H_d.  A pair (k, k+1) with d + k + 1 <= 31 is p[d + k].
@@ -406,41 +391,13 @@ __device__ __forceinline__ void tail_taps(const uint32_t (&q)[32], const uint32_
     }
 }
 
-// SKIP: R[0 .. 2 SKIP) is zero in every lane of the wave, so the first SKIP
-// steps would leave c = 0 and are not compiled in (one-line groups, whose
-// remainder is the line itself: right-aligned messages of at most 64 bytes
-// leave 16 leading zero words).  A compile-time count: per-step uniform
-// branches cost 2-4 % on two-line groups (profiles/r03/ab/ab2_*.jsonl).
-template <int SKIP = 0>
-__device__ __forceinline__ uint32_t tail_horner(const uint32_t (&R)[32], uint32_t tab_lds)
-{
-    uint32_t c = 0;
-#pragma unroll
-    for (int d = 2 * SKIP; d < 32; d += 2) {
-        const uint32_t v = c ^ R[d];
-        const uint32_t w = R[d + 1];
-        const uint32_t hi = xor3(tab_lookup(tab_lds, 4, v & 0xffu),
-                                 tab_lookup(tab_lds, 5, (v >> 8) & 0xffu),
-                                 tab_lookup(tab_lds, 6, (v >> 16) & 0xffu));
-        const uint32_t lo = xor3(tab_lookup(tab_lds, 0, w & 0xffu),
-                                 tab_lookup(tab_lds, 1, (w >> 8) & 0xffu),
-                                 tab_lookup(tab_lds, 2, (w >> 16) & 0xffu));
-        c = xor3(hi, lo, tab_lookup(tab_lds, 7, v >> 24) ^ tab_lookup(tab_lds, 3, w >> 24));
-    }
-    return c;
-}
-
-// The same reduction with 11-bit slices (k_fold's 8-wave blocks, which have
-// the LDS for them: 24 KiB, kTab11Bytes).  One word per step, c <- (c ^ R_d)
-// * y, in three lookups (word bits 2-12, 13-23, and 24-31 with 0-1, each
-// slice's byte offset formed by one AND, or a shift or rotate and an AND),
-// against four per word with byte slices: 100 lookups per segment instead of
-// 128, and no more VALU.  Two independent chains keep the dependent depth at
-// 16 steps: A over words 0-15, B over 16-31, raw = A * y^16 + B, the join by
-// four byte lookups.  SKIP = 8: words 0-15 are zero in every lane (chain A
-// and the join drop out).
+// One word per step, c <- (c ^ R_d) * y, with 11-bit slices (k_fold's 8-wave
+// blocks, which have the LDS for them: 24 KiB, kTab11Bytes) in three lookups
+// (word bits 2-12, 13-23, and 24-31 with 0-1, each slice's byte offset formed
+// by one AND, or a shift or rotate and an AND), against four per word with
+// byte slices (step8).
 constexpr uint32_t kTab11Bytes = 6144 * 4;
-constexpr uint32_t kT11Hi = 8192, kT11Top = 16384, kT11Join = 20480;  // slice offsets (bytes)
+constexpr uint32_t kT11Hi = 8192, kT11Top = 16384;  // slice offsets (bytes)
 
 __device__ __forceinline__ uint32_t step11(uint32_t c, uint32_t r, uint32_t tab_lds)
 {
@@ -453,30 +410,8 @@ __device__ __forceinline__ uint32_t step11(uint32_t c, uint32_t r, uint32_t tab_
                 *(const lds_u32*)(uintptr_t)(tab_lds + kT11Top + a2));
 }
 
-template <int SKIP = 0>
-__device__ __forceinline__ uint32_t tail_chains11(const uint32_t (&R)[32], uint32_t tab_lds)
-{
-    static_assert(SKIP == 0 || SKIP == 8, "chain A runs whole or not at all");
-    uint32_t ca = 0, cb = 0;
-#pragma unroll
-    for (int d = 0; d < 16; ++d) {
-        if (SKIP == 0) {
-            ca = step11(ca, R[d], tab_lds);
-        }
-        cb = step11(cb, R[16 + d], tab_lds);
-    }
-    if (SKIP != 0) {
-        return cb;
-    }
-    const uint32_t j = tab_lds + kT11Join;
-    return xor3(cb, *(const lds_u32*)(uintptr_t)(j + 4u * (ca & 0xffu)),
-                *(const lds_u32*)(uintptr_t)(j + 1024u + 4u * ((ca >> 8) & 0xffu))) ^
-           xor3(*(const lds_u32*)(uintptr_t)(j + 2048u + 4u * ((ca >> 16) & 0xffu)),
-                *(const lds_u32*)(uintptr_t)(j + 3072u + 4u * (ca >> 24)), 0u);
-}
-
 // The 32 remainder words reduced further at BYTE granularity before any
-// lookup (BMQCRC_BYTE_FOLD, A/B).  The minimal polynomial of z = x^8 is P
+// lookup.  The minimal polynomial of z = x^8 is P
 // itself (as for y = x^32: x^8 and x^32 are Frobenius conjugates of x), so the
 // remainder's 128 bytes b_i (raw = sum b_i z^(131-i)) reduce with the same 17
 // taps at byte lags 32 - k: Q_i = b_i ^ sum_k Q_(i-32+k) for the first 96
@@ -485,15 +420,18 @@ __device__ __forceinline__ uint32_t tail_chains11(const uint32_t (&R)[32], uint3
 // the Q stream at that lag (one v_alignbyte when the lag is not a multiple
 // of 4), and the seven adjacent tap pairs come from a pair stream P2_i =
 // Q_(i-1) ^ Q_i at lag 31 - k.  About 14 VALU per word; then 8 one-word
-// chain steps: 24 lookups per segment instead of 100.  SKIP16: words 0-15
-// are zero in every lane (so is their part of Q).
+// chain steps: 24 lookups per segment (one chain step per remainder word
+// took 100).  SKIP16: words 0-15 are zero in every lane (so is their part of
+// Q): right-aligned one-line groups of messages of at most 64 bytes.  A
+// compile-time choice: per-step uniform branches cost 2-4 % on two-line
+// groups (profiles/r03/ab/ab2_*.jsonl).
 __device__ __forceinline__ uint32_t alignbyte(uint32_t hi, uint32_t lo, int s)
 {
     return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)s);
 }
 
 // One word per step with the byte-sliced "times y" tables (tab[k][b], k < 4:
-// 4-wave blocks' 8 KiB tables, tail_horner's), four lookups.
+// 4-wave blocks' 8 KiB tables), four lookups.
 __device__ __forceinline__ uint32_t step8(uint32_t c, uint32_t r, uint32_t tab_lds)
 {
     const uint32_t v = c ^ r;
@@ -683,38 +621,6 @@ __device__ __forceinline__ void dma_copy_kib(uint32_t lds_dst, uint64_t src)
                      : "memory", "scc");
     }
 }
-
-#ifndef BMQCRC_ONE_EARLY
-#define BMQCRC_ONE_EARLY 1  // the one-segment kernel issues its first group's loads before its
-                            // tables (LDS-DMA'd behind them, one barrier before the first
-                            // lookup); 0: tables first, through VGPRs, and a barrier (A/B)
-#endif
-constexpr bool kOneEarly = BMQCRC_ONE_EARLY == 1;
-#ifndef BMQCRC_ROUND_WAIT
-#define BMQCRC_ROUND_WAIT 0  // a round's fold first waits for every load issued before it
-                             // (the next round landed too, the one after issued once the
-                             // line is read); 8: for its own 8 loads only, the next round
-                             // still landing while it folds (round 5; A/B)
-#endif
-constexpr bool kRoundWait0 = BMQCRC_ROUND_WAIT == 0;
-#ifndef BMQCRC_DESC_FIRST
-#define BMQCRC_DESC_FIRST 1  // the first group's descriptors before the prologue's table loads
-                             // (every k_fold); 0: after them (round 5; A/B)
-#endif
-constexpr bool kDescFirst = BMQCRC_DESC_FIRST != 0;
-
-#ifndef BMQCRC_GROUP_DESC
-#define BMQCRC_GROUP_DESC 1  // 0: every seginfo entry written (round 3; A/B)
-#endif
-constexpr bool kGroupDesc = BMQCRC_GROUP_DESC != 0;
-#ifndef BMQCRC_LONG_FLAT
-#define BMQCRC_LONG_FLAT 1  // long runs' entries and descriptors: 1 flattened over the wave, 0 run by run
-#endif
-#ifndef BMQCRC_RUN_RECORDS
-#define BMQCRC_RUN_RECORDS 1  // a long run's partial groups as per-group records, not entries
-                              // (k_plan_map, round 6); 0: entries (round 5; A/B)
-#endif
-constexpr bool kRunRecords = BMQCRC_RUN_RECORDS != 0 && kGroupDesc && BMQCRC_LONG_FLAT;
 
 // The single-pass planner's launch tag.  Normally the host's per-workspace
 // count (BatchArgs::plan_epoch, below 2^31); a batch captured into a graph
@@ -957,7 +863,7 @@ __device__ __forceinline__ SegGeom seg_geom(uint64_t mstart, uint32_t len, uint3
     const uint32_t nl_r = (uint32_t)((pe - (g.S & ~15ull) + 127u) >> 7);
     const uint64_t L0_l = g.S & ~127ull;
     const uint32_t nl_l = (uint32_t)((need_end - L0_l + 127u) >> 7);
-    if (kRightAlign && (nl_r < nl_l || nl_r <= kRightAlignLines)) {
+    if (nl_r < nl_l || nl_r <= kRightAlignLines) {
         g.nl = nl_r;
         g.L0 = pe - ((uint64_t)nl_r << 7);
     } else {
@@ -1007,24 +913,22 @@ __device__ __forceinline__ SegRef map_segment(const BatchArgs& a, const PlanLds*
             const uint32_t gsel = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg) >> 6;
             r.msg = a.seginfo[seg];
             r.k = a.firstk[gsel];
-            if (kGroupDesc) {
-                // a group of 64 full segments of one message: one tagged word
-                // instead of its 64 entries (which are then not written)
-                const unsigned long long gd = a.gdesc[gsel];
-                if ((uint32_t)(gd >> 32) == ep) {
-                    r.msg = (uint32_t)gd;
-                } else if (kRunRecords) {
-                    // a long run's tail on the group's first lanes, or its
-                    // head on the last ones: tagged records (k_plan_map,
-                    // round 6), the entries under them not written
-                    const u32x4 pre = *(const u32x4*)&a.grec[8u * gsel];
-                    const u32x4 suf = *(const u32x4*)&a.grec[8u * gsel + 4u];
-                    const uint32_t l = seg & 63u;
-                    if (pre.x == ep && l < pre.z) {
-                        r.msg = pre.y;
-                    } else if (suf.x == ep && l >= 64u - suf.z) {
-                        r.msg = suf.y;
-                    }
+            // a group of 64 full segments of one message: one tagged word
+            // instead of its 64 entries (which are then not written)
+            const unsigned long long gd = a.gdesc[gsel];
+            if ((uint32_t)(gd >> 32) == ep) {
+                r.msg = (uint32_t)gd;
+            } else {
+                // a long run's tail on the group's first lanes, or its
+                // head on the last ones: tagged records (k_plan_map,
+                // round 6), the entries under them not written
+                const u32x4 pre = *(const u32x4*)&a.grec[8u * gsel];
+                const u32x4 suf = *(const u32x4*)&a.grec[8u * gsel + 4u];
+                const uint32_t l = seg & 63u;
+                if (pre.x == ep && l < pre.z) {
+                    r.msg = pre.y;
+                } else if (suf.x == ep && l >= 64u - suf.z) {
+                    r.msg = suf.y;
                 }
             }
         }
@@ -1064,83 +968,6 @@ __device__ __forceinline__ SegDesc fetch_desc(const BatchArgs& a, SegRef r, bool
     return d;
 }
 
-#ifndef BMQCRC_FOLD_DIAG
-#define BMQCRC_FOLD_DIAG 0  // 1: per-wave wall-clock stamps of the last k_fold launch
-                            // (timing diagnostics, tools/fold_trace_diag.py); product: 0
-#endif
-#if BMQCRC_FOLD_DIAG
-// diagnostic build only: per wave (entry, prologue done, first loads issued,
-// first group folded, last group's lines folded, loop done, end), read by
-// bmqcrc_diag_fold_trace
-constexpr int kFoldTraceWaves = 4096;
-__device__ unsigned long long g_fold_trace[kFoldTraceWaves][8];
-#define FOLD_STAMP(k)                                                              \
-    if (lane == 0 && g0 < (uint32_t)kFoldTraceWaves) {                             \
-        g_fold_trace[g0][k] = wall_clock64();                                      \
-    }
-#else
-#define FOLD_STAMP(k)
-#endif
-
-#ifndef BMQCRC_ONE_DIAG
-#define BMQCRC_ONE_DIAG 0  // diagnostic builds of the ONE kernel (wrong CRCs): bit 0 skips the
-                           // remainder step, bit 1 the fold; product: 0
-#endif
-
-#ifndef BMQCRC_NT_LOADS
-#define BMQCRC_NT_LOADS 1  // 0: every data round with the default policy (A/B)
-#endif
-constexpr bool kNtLoads = BMQCRC_NT_LOADS != 0;
-
-#ifndef BMQCRC_SHORT_NT_WHOLE_LINES
-#define BMQCRC_SHORT_NT_WHOLE_LINES 1  // 0: every short group with the default policy (round 4)
-#endif
-constexpr bool kShortNtWholeLines = BMQCRC_SHORT_NT_WHOLE_LINES != 0;
-
-#ifndef BMQCRC_SNAKE
-#define BMQCRC_SNAKE 1  // 0: every round in block order (A/B)
-#endif
-constexpr bool kSnakeRounds = BMQCRC_SNAKE != 0;
-
-#ifndef BMQCRC_TWO_ENDED
-#define BMQCRC_TWO_ENDED 0  // 1: claims from both ends of each block's groups (A/B)
-#endif
-constexpr bool kTwoEnded = BMQCRC_TWO_ENDED != 0;
-
-#ifndef BMQCRC_BYTE_FOLD
-#define BMQCRC_BYTE_FOLD 1  // remainder words folded to 8 at byte granularity first (8-wave
-                            // blocks): 1 every group (product), 2 one-line groups only, 0
-                            // never: the 11-bit chains over all 32 words (A/B)
-#endif
-constexpr int kByteFold = BMQCRC_BYTE_FOLD;
-#ifndef BMQCRC_BYTE_FOLD4
-#define BMQCRC_BYTE_FOLD4 1  // 0: 4-wave blocks keep the two-word Horner over all 32 words (A/B)
-#endif
-constexpr bool kByteFold4 = BMQCRC_BYTE_FOLD4 != 0;
-
-#ifndef BMQCRC_NT_RESULTS
-#define BMQCRC_NT_RESULTS 0  // 1: result stores with the non-temporal hint (A/B)
-#endif
-constexpr bool kNtResults = BMQCRC_NT_RESULTS != 0;
-
-#ifndef BMQCRC_ONE_PRIO
-#define BMQCRC_ONE_PRIO 2  // the one-segment kernel's wave behind its SIMD partner in groups
-                           // takes issue priority: 2 in groups of two or more lines (product),
-                           // 1 in every group, 0 never (A/B)
-#endif
-constexpr int kOnePrio = BMQCRC_ONE_PRIO;
-
-#ifndef BMQCRC_ONE_CLAIMS
-#define BMQCRC_ONE_CLAIMS 0  // 1: the one-segment kernel claims its groups from the block's LDS
-                             // counter too (the claiming loop and block list; A/B)
-#endif
-constexpr bool kOneClaims = BMQCRC_ONE_CLAIMS != 0;
-
-#ifndef BMQCRC_HORNER11
-#define BMQCRC_HORNER11 1  // 0: byte-sliced remainder tables in every block shape (round 4; A/B)
-#endif
-constexpr bool kHorner11 = BMQCRC_HORNER11 != 0;
-
 // Groups whose speculative first pass skipped a message (a block's list for
 // the second pass; past this many the second pass scans the block's groups).
 constexpr uint32_t kLongListCap = 64;
@@ -1164,7 +991,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
     // 11-bit remainder slices in the 8-wave blocks (one per CU: 159 KiB of
     // LDS with them); 4-wave blocks, two of which share a CU, keep the 8 KiB
     // byte slices
-    constexpr bool H11 = kHorner11 && WPB == 8;
+    constexpr bool H11 = WPB == 8;
     constexpr int kTab = H11 ? (int)kTab11Bytes : kTabBytes;
     // remainder tables, DMA slots, move factors (not needed by ONE: no moves
     // in its first pass)
@@ -1173,9 +1000,13 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
     // from this counter; long_n / long_list: the block's groups with a message
     // its speculative first pass skipped
     __shared__ uint32_t claim_ctr, long_n;
-    __shared__ unsigned long long claim2;  // two-ended claims: front count | back count << 32
+    // (claim2 has had no reader since the two-ended claims were retired.  Its
+    // store and its 8 bytes stay: taking them out shifts the other block-shared
+    // words and, alone of that clean-up, did not stay inside the previous
+    // build's run-to-run spread, profiles/r07/retire_knobs/.)
+    [[maybe_unused]] __shared__ unsigned long long claim2;
     __shared__ uint32_t long_list[kLongListCap];
-    __shared__ uint32_t one_prog[WPB];  // BMQCRC_ONE_PRIO: groups each wave has started
+    __shared__ uint32_t one_prog[WPB];  // ONE, 8 waves: groups each wave has started
 
     const int lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1183,22 +1014,14 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
     const uint32_t wave_lds = tab_lds + kTab + wave * (kSlots * kSlotBytes);
     const uint32_t xb_lds = tab_lds + kTab + kLds;
     // a segment's raw CRC from its 32 remainder words (skip: words 0-15 are
-    // zero in every lane; one_line: the group's streams are one line; both
-    // wave-uniform, choosing between compiled copies)
-    auto remainder = [&](const uint32_t (&Rm)[32], bool skip, bool one_line) -> uint32_t {
-        if constexpr (H11 && kByteFold != 0) {
-            if (kByteFold == 1 || one_line) {
-                return skip ? tail_bytes8<true>(Rm, tab_lds) : tail_bytes8<false>(Rm, tab_lds);
-            }
-            return tail_chains11(Rm, tab_lds);  // (skip is set for one-line groups only)
-        } else if constexpr (H11) {
-            return skip ? tail_chains11<8>(Rm, tab_lds) : tail_chains11(Rm, tab_lds);
-        } else if constexpr (kByteFold4) {
-            // 4-wave blocks: the byte fold too, its last 8 steps on the byte
-            // tables (32 lookups per segment instead of 128)
-            return skip ? tail_bytes8<true, true>(Rm, tab_lds) : tail_bytes8<false, true>(Rm, tab_lds);
+    // zero in every lane; wave-uniform, choosing between compiled copies)
+    auto remainder = [&](const uint32_t (&Rm)[32], bool skip) -> uint32_t {
+        if constexpr (H11) {
+            return skip ? tail_bytes8<true>(Rm, tab_lds) : tail_bytes8<false>(Rm, tab_lds);
         } else {
-            return skip ? tail_horner<8>(Rm, tab_lds) : tail_horner(Rm, tab_lds);
+            // 4-wave blocks: the byte fold's last 8 steps on the byte tables
+            // (32 lookups per segment)
+            return skip ? tail_bytes8<true, true>(Rm, tab_lds) : tail_bytes8<false, true>(Rm, tab_lds);
         }
     };
     if (threadIdx.x < (uint32_t)WPB) {
@@ -1216,13 +1039,13 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
     // and for identity batches; discarded otherwise).
     constexpr int kTw = (kTab / 4) / (int)kThreads, kXw = 1024 / kThreads;  // table words per thread
     static_assert(kTw * (int)kThreads * 4 == kTab && kXw * kThreads == 1024, "table fill");
-    // The one-segment kernel (kOneEarly) loads no table here: its first
+    // The 4-wave one-segment kernel loads no table here: its first
     // group's descriptors go out first, then the group's data, and only then
     // the tables, LDS-DMA'd (see early_tables below), so the first data
     // load no longer waits behind 8-24 KiB of table loads and a barrier
     // (per-wave stamps, 20,000 x 256 B: prologue 0.8-1.0 us, first issue
     // 1.5 us later, profiles/r05/probe/fold_trace_small_batches.jsonl)
-    constexpr bool kEarly = ONE && kOneEarly && WPB == 4;
+    constexpr bool kEarly = ONE && WPB == 4;
     static_assert(!kEarly || kTab % (1024 * WPB) == 0, "early tables: whole KiB per wave");
     constexpr bool kNoVgprTab = kEarly;
     // the wave's first group (claim k = wave, see gid below), as if
@@ -1231,10 +1054,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
     // and every wave's first data load queued behind them)
     const uint32_t gfirst = a.spread ? wave * gridDim.x + blockIdx.x : blockIdx.x * WPB + wave;
     const uint32_t sid = gfirst * 64u + (uint32_t)lane;
-    [[maybe_unused]] SegDesc spec = {0ull, 0u, 0u, 0u, 0u};
-    if constexpr (kDescFirst) {
-        spec = fetch_desc(a, SegRef{sid, 0u}, sid < a.n);
-    }
+    const SegDesc spec = fetch_desc(a, SegRef{sid, 0u}, sid < a.n);
     uint32_t tw[kNoVgprTab ? 1 : kTw];
 #pragma unroll
     for (int i = 0; i < (kNoVgprTab ? 0 : kTw); ++i) {
@@ -1274,9 +1094,6 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
     const uint32_t xn = (!kNoVgprTab && threadIdx.x < 136u) ? c_xneg8[threadIdx.x] : 0u;
     [[maybe_unused]] const uint32_t g0 = blockIdx.x * WPB + wave;  // this wave's index in the grid
     FOLD_STAMP(0)
-    if constexpr (!kDescFirst) {
-        spec = fetch_desc(a, SegRef{sid, 0u}, sid < a.n);
-    }
     // remainder-reduction tables -> LDS (8 KiB, once per block; no DMA in
     // flight yet; plan_reduce's barriers order them before any lookup)
 #pragma unroll
@@ -1390,50 +1207,19 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
             return k * nbk + blockIdx.x;
         }
         const uint32_t r = k / (uint32_t)WPB;
-        const uint32_t b = (kSnakeRounds && !ONE && (r & 1u)) ? nbk - 1u - blockIdx.x : blockIdx.x;
+        const uint32_t b = (!ONE && (r & 1u)) ? nbk - 1u - blockIdx.x : blockIdx.x;
         return (b + nbk * r) * (uint32_t)WPB + k % (uint32_t)WPB;
     };
     // a claim in two halves: the LDS atomic (lane 0) is issued early and its
     // result read later, so its latency hides behind other LDS work
-    // Two-ended claims (BMQCRC_TWO_ENDED, A/B): the block's K claims k =
-    // 0 .. K-1 are taken from both ends at once, waves 0 .. WPB/2-1 from the
-    // front (the map's first size classes), the others from the back (its
-    // last), so that a CU folds large and small groups side by side instead
-    // of one size class after another; one 64-bit LDS counter holds both
-    // counts, and a claim is valid while they sum to less than K.
-    const bool back = kTwoEnded && wave >= (uint32_t)WPB / 2u;
-    uint32_t kb = 0;  // this block's claims (gid(k) < ngroups exactly for k < kb)
-    if (kTwoEnded && a.spread) {
-        kb = blockIdx.x < ngroups ? (ngroups - blockIdx.x - 1u) / nbk + 1u : 0u;
-    } else if (kTwoEnded) {
-        const uint32_t full = ngroups / (nbk * (uint32_t)WPB);
-        kb = full * (uint32_t)WPB;
-        const uint32_t b = (kSnakeRounds && !ONE && (full & 1u)) ? nbk - 1u - blockIdx.x : blockIdx.x;
-        const uint64_t c = (uint64_t)(b + nbk * full) * WPB;
-        if (c < ngroups) {
-            kb += (uint32_t)min((uint64_t)WPB, (uint64_t)ngroups - c);
-        }
-    }
     auto claim_issue = [&]() {
         unsigned long long k = 0;
         if (lane == 0) {
-            if (kTwoEnded) {
-                k = atomicAdd(&claim2, back ? (1ull << 32) : 1ull);
-            } else {
-                k = atomicAdd(&claim_ctr, 1u);
-            }
+            k = atomicAdd(&claim_ctr, 1u);
         }
         return k;
     };
     auto claim_take = [&](unsigned long long k) {
-        if (kTwoEnded) {
-            const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)k);
-            const uint32_t bk = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(k >> 32));
-            if ((uint64_t)f + bk >= kb) {
-                return ngroups;
-            }
-            return gid(back ? kb - 1u - bk : f);
-        }
         return gid((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)k));
     };
     auto claim = [&]() { return claim_take(claim_issue()); };
@@ -1469,7 +1255,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
         // one-line group: the remainder is the line; its leading zero word
         // pairs (before the lowest S of the wave) need no remainder step
         G.hskip = 0u;
-        if (kHornerSkip && G.R == 1u) {
+        if (G.R == 1u) {
             // every lane's S in the line's second half (one ballot: this sits
             // before the next group's loads)
             const uint32_t sl0 = G.valid ? (uint32_t)(geo.S - geo.L0) : 128u;
@@ -1527,7 +1313,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
             // the wave's second pass (below); with u = 1 an empty message is
             // folded whole (its seed)
             const bool ok = spec_u == 1u ? nseg <= 1u : nseg == spec_u;
-            if constexpr (ONE && !kOneClaims) {
+            if constexpr (ONE) {
                 long_seen |= __ballot(valid && !ok) != 0;
             } else if (__ballot(valid && !ok) != 0 && lane == 0) {  // group gg on the block's list
                 const uint32_t at = atomicAdd(&long_n, 1u);
@@ -1557,7 +1343,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
     // non-temporal (round 2).  Round 2 chose the default policy for every
     // short group from a batch the Infinity Cache held (+3 %).
     auto issue_first_rounds = [&](const Group& G) {
-        if (!NT || !kNtLoads || (kShortDefaultPolicy && G.R <= 2u && !(kShortNtWholeLines && G.whole_lines))) {
+        if (!NT || (G.R <= 2u && !G.whole_lines)) {
             dma_round<false>(wave_lds, G.pbase, G.plo, G.pcnt, zero, 0);
             if (G.R > 1) {
                 dma_round<false>(wave_lds + kSlotBytes, G.pbase, G.plo, G.pcnt, zero, 1);
@@ -1575,7 +1361,6 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
     // carried through the loop) gives the remainder words Rm.
     auto fold_rounds = [&](const Group& G, uint32_t (&Rm)[32]) {
         uint32_t q[32], p[32];
-        [[maybe_unused]] uint32_t sink = 0;  // BMQCRC_ONE_DIAG & 2: keeps the line reads
         const uint32_t R = G.R;
         auto load_line = [&](uint32_t r, uint32_t slot, uint32_t (&m)[32]) {
             // Byte edges of this round's line: the piece cut by S (first line),
@@ -1603,22 +1388,15 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
         };
         for (uint32_t r = 0; r + 1 < R; ++r) {
             const uint32_t slot = wave_lds + (r & 1u) * kSlotBytes;
-            if constexpr (kRoundWait0) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            }
+            // every load issued so far has landed: the next round's too, the
+            // one after is issued once this line is read
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             uint32_t m[32];
             load_line(r, slot, m);
             if (r + 2 < R) {
-                dma_round<NT && kNtLoads>(slot, G.pbase, G.plo, G.pcnt, zero, r + 2);
+                dma_round<NT>(slot, G.pbase, G.plo, G.pcnt, zero, r + 2);
             }
-            if (ONE && (BMQCRC_ONE_DIAG & 2)) {
-#pragma unroll
-                for (int d = 0; d < 32; ++d) {
-                    sink ^= m[d];
-                }
-            } else if (r == 0) {
+            if (r == 0) {
                 first_round(q, p, m);
             } else {
                 fold_round(q, p, m);
@@ -1639,14 +1417,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
             return;
         }
         uint32_t H[32];
-        if (ONE && (BMQCRC_ONE_DIAG & 2)) {
-#pragma unroll
-            for (int d = 0; d < 32; ++d) {
-                H[d] = d == 0 ? sink : 0u;
-            }
-        } else {
-            tail_taps(q, p, H);
-        }
+        tail_taps(q, p, H);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         uint32_t m[32];
         load_line(R - 1u, slot, m);
@@ -1694,11 +1465,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
     };
     auto commit = [&](const Pending& P) {
         if (P.mode == 1u) {
-            if (kNtResults) {
-                __builtin_nontemporal_store(P.val, &a.out[P.msg]);
-            } else {
-                a.out[P.msg] = P.val;
-            }
+            a.out[P.msg] = P.val;
         } else if (P.mode == 2u) {
             atomicXor(&a.out[P.msg], P.val);
         }
@@ -1771,7 +1538,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
         const uint32_t mpg = 64u / spec_u;  // messages per group
         const bool listed = nlong <= kLongListCap;
         for (uint32_t j = wave;; j += WPB) {
-            const uint32_t gg = (ONE && !kOneClaims) ? gfirst + (j / (uint32_t)WPB) * nbk * (uint32_t)WPB
+            const uint32_t gg = ONE ? gfirst + (j / (uint32_t)WPB) * nbk * (uint32_t)WPB
                                 : listed ? (j < nlong ? long_list[j] : ngroups) : gid(j);
             if (gg >= ngroups) {
                 break;
@@ -1796,7 +1563,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
                     issue_first_rounds(H);
                     uint32_t Rm[32];
                     fold_rounds(H, Rm);
-                    uint32_t x = contribution(H, remainder(Rm, false, H.R == 1u));
+                    uint32_t x = contribution(H, remainder(Rm, false));
 #pragma unroll
                     for (int o = 32; o > 0; o >>= 1) {
                         x ^= (uint32_t)__shfl_xor((int)x, o);
@@ -1825,7 +1592,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
     Group G;
     SegDesc nxt = {0ull, 0u, 0u, 0u, 0u};
     SegRef ref2 = {0u, 0u};
-    if constexpr (ONE && !kOneClaims) {
+    if constexpr (ONE) {
         // The speculative one-segment kernel: every group the same work, so
         // wave w of block b keeps round 3's static share, groups
         // g0 + j stride (the set its claims k = w, w + WPB, ... name, gid
@@ -1875,12 +1642,12 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
             early_tables();
             early_barrier(true);
         }
-        [[maybe_unused]] bool first = true;
+        bool first = true;
         bool meet = kEarly;  // early_barrier owed, after the first group's fold
         [[maybe_unused]] uint32_t it = 0;
         Pending pend = {0u, 0u, 0u};
         for (; g < ngroups; g += stride) {
-            if constexpr (kOnePrio != 0 && WPB == 8) {
+            if constexpr (WPB == 8) {
                 // The two waves of a SIMD (w and w ^ WPB/2) take the same
                 // number of groups, but the older one wins every issue tie:
                 // per-wave stamps put the younger four waves of every block
@@ -1893,7 +1660,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
                 // the rest unchanged (profiles/r05/ab/one_prio_ab.jsonl).
                 // 8-wave blocks only: a 4-wave block's partner wave is in
                 // another block (two per CU) or absent (one per CU).
-                if (kOnePrio == 1 || G.R >= 2u) {
+                if (G.R >= 2u) {
                     if (lane == 0) {
                         one_prog[wave] = it;
                     }
@@ -1912,7 +1679,6 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
                 early_barrier(false);
                 meet = false;
             }
-#if BMQCRC_FOLD_DIAG
             if (first) {
                 FOLD_STAMP(3)
                 first = false;
@@ -1920,7 +1686,6 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
             if (g + stride >= ngroups) {
                 FOLD_STAMP(4)
             }
-#endif
             const Group C = G;
             if (g + stride < ngroups) {
                 setup(nxt, g + stride, G);
@@ -1934,20 +1699,11 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
             }
             // the previous group's results, after the next group's loads
             commit(pend);
-            if (BMQCRC_ONE_DIAG & 1) {  // diagnostic: no remainder step (wrong CRCs)
-                uint32_t x = 0;
-#pragma unroll
-                for (int d = 0; d < 32; ++d) {
-                    x ^= Rm[d];
-                }
-                pend = finish(C, x);
-            } else {
-                pend = finish(C, remainder(Rm, C.hskip != 0u, C.R == 1u));
-            }
+            pend = finish(C, remainder(Rm, C.hskip != 0u));
         }
         commit(pend);
     } else {
-    uint32_t g = kTwoEnded ? claim() : gid(wave), g1 = ngroups, g2 = ngroups;  // (= gfirst)
+    uint32_t g = gid(wave), g1 = ngroups, g2 = ngroups;  // (= gfirst)
     if (g < ngroups) {
         g1 = claim();
         g2 = g1 < ngroups ? claim() : ngroups;
@@ -1959,11 +1715,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
                 r0 = resolve_sorted(r0, s0 < total);
             }
         }
-        // (the prologue's descriptors are gfirst's, the first claim's only
-        // with one-ended claims)
-        const SegDesc d0 = (identity && !kTwoEnded)
-                               ? spec
-                               : fetch_desc(a, identity ? SegRef{s0, 0u} : r0, s0 < total);
+        const SegDesc d0 = identity ? spec : fetch_desc(a, r0, s0 < total);
         const uint32_t s1 = g1 * 64u + (uint32_t)lane;
         const bool v1 = g1 < ngroups && s1 < total;
         SegRef r1 = map_segment(a, &pl, s1, v1, identity, uni, sorted, ep);
@@ -2011,7 +1763,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
             issue_first_rounds(G);
         }
         commit(pend);  // the previous group's results, after the next group's loads
-        pend = finish(C, remainder(Rm, C.hskip != 0u, C.R == 1u));
+        pend = finish(C, remainder(Rm, C.hskip != 0u));
         g = g1;
         g1 = g2;
         g2 = g3;
@@ -2019,7 +1771,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? 2 : 1) void k_fold(BatchArgs a
     commit(pend);
     }
     FOLD_STAMP(5)
-    if constexpr (ONE && !kOneClaims) {
+    if constexpr (ONE) {
         if (long_seen) {
             second_pass(0u);
         }
@@ -2071,7 +1823,7 @@ __device__ __forceinline__ uint32_t msg_segments(const BatchArgs& a, uint64_t of
     const uint32_t pe = (s + dn + 15u) & ~15u;
     const uint32_t nl_r = (pe - (s & ~15u) + 127u) >> 7;
     const uint32_t nl_l = (s + dn + 127u) >> 7;
-    *c_last = size_class((kRightAlign && (nl_r < nl_l || nl_r <= kRightAlignLines)) ? nl_r : nl_l);
+    *c_last = size_class((nl_r < nl_l || nl_r <= kRightAlignLines) ? nl_r : nl_l);
     return nseg;
 }
 
@@ -2533,48 +2285,7 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_sort(BatchArgs a)
 // then maps segments by searching seg_first (message order instead of
 // size-class order: exact, somewhat slower).  Arrival flags carry the
 // launch's epoch, so nothing needs resetting between launches.
-#ifndef BMQCRC_MAP_REG_TILES
-#define BMQCRC_MAP_REG_TILES 4
-#endif
-constexpr uint32_t kMapRegTiles = BMQCRC_MAP_REG_TILES;  // tiles kept in registers across the wait
-#ifndef BMQCRC_CLASS_DESC
-#define BMQCRC_CLASS_DESC 0  // size-class order in seginfo: 0 by BatchArgs::class_desc (product),
-                             // 1 always descending, 2 always ascending (A/B builds)
-#endif
-#ifndef BMQCRC_PLAN_SKIP
-#define BMQCRC_PLAN_SKIP 0  // timing diagnostics with the map voided (wrong maps, exact CRCs):
-                            // 1 no histogram atomics, 2 no last-segment claims, 4 no full-run
-                            // writes, 8 no last-segment stores, 16 no long-run writes, 32 no
-                            // short-run writes, 64 full-run slots mapped but not stored
-#endif
-#ifndef BMQCRC_PLAN_FLAGS
-#define BMQCRC_PLAN_FLAGS 0  // 1: round 3's separate arrival flags (A/B)
-#endif
-#ifndef BMQCRC_PLAN_DIAG
-#define BMQCRC_PLAN_DIAG 0  // 3: per-block phase stamps, 4: the same without seginfo stores,
-                            // 6: every block's first read of the exchanged words is stale
-                            // (timing diagnostics, tools/plan_trace_diag.py); product: 0
-#endif
-
-#if BMQCRC_PLAN_DIAG >= 3
-// diagnostic build only: per-block wall-clock stamps of the last launch
-// (start, first loads landed, first tile counted, phase 1 done, wait done,
-// deferred writes issued, class bases done, end), read by
-// bmqcrc_diag_plan_trace
-__device__ unsigned long long g_plan_trace[kPlanMaxBlocks][8];
-#define PLAN_STAMP(k)                                                        \
-    if (threadIdx.x == 0) {                                                  \
-        g_plan_trace[blockIdx.x][k] = wall_clock64();                        \
-    }
-#define PLAN_STAMP_LANDED(k)                                                 \
-    if (threadIdx.x == 0) {                                                  \
-        __builtin_amdgcn_s_waitcnt(0);                                       \
-        g_plan_trace[blockIdx.x][k] = wall_clock64();                        \
-    }
-#else
-#define PLAN_STAMP(k)
-#define PLAN_STAMP_LANDED(k)
-#endif
+constexpr uint32_t kMapRegTiles = 4;  // tiles kept in registers across the wait
 
 __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
 {
@@ -2588,10 +2299,8 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
     __shared__ uint32_t go;
     __shared__ PlanTail tail;
     __shared__ uint32_t sruns[kPlanBlock / 64][64 * kPlanV];  // per wave: short-run ends
-#if BMQCRC_LONG_FLAT
     __shared__ uint32_t slong[kPlanBlock / 64][2][64 * kPlanV];  // per wave: long runs' starts, lengths
     __shared__ uint32_t smark[kPlanBlock / 64][64];             // per wave: item-run starts in a chunk
-#endif
     const uint32_t nb = a.nblocks, ep = launch_epoch(a), bid = blockIdx.x;
     load_tail(a, min((uint64_t)bid * a.per_msg + a.per_msg, a.n), true, &tail);
     // epoch-tagged words the blocks exchange (plan_sync after the flags),
@@ -2673,7 +2382,7 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
             uint32_t c;
             const uint32_t ns = msg_segments(a, O[v], L[v], seg_shift, &c);
             full += ns ? ns - 1u : 0u;
-            if (c < (uint32_t)kBuckets && !(BMQCRC_PLAN_SKIP & 1)) {
+            if (c < (uint32_t)kBuckets) {
                 atomicAdd(&hist[c], 1u);
             }
             cls |= c << (8u * v);  // kBuckets (no segment) fits a byte
@@ -2773,17 +2482,6 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             a.block_sum[lane * nb + bid] = wv;  // for k_fold (the next launch)
         }
-#if BMQCRC_PLAN_FLAGS
-        __builtin_amdgcn_s_waitcnt(0);  // the stores above are complete (vmcnt 0)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) {
-            __hip_atomic_store(&sync[kSyncFlags + bid], (unsigned long long)ep, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        }
-        // poll the blocks' arrival flags
-        const unsigned long long* const arrive = sync + kSyncFlags;
-        constexpr int kArriveShift = 0;
-#else
         // round 4: no separate flag.  The poll reads each block's tagged
         // third block word (published beside its histogram, in no particular
         // order: the tag check below re-reads any word still stale), so the
@@ -2791,7 +2489,6 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
         // visibility latency are gone from the meeting.
         const unsigned long long* const arrive = tags + kTagWords + 2u * kPlanMaxBlocks;
         constexpr int kArriveShift = 32;
-#endif
         const uint64_t t0 = wall_clock64();
         uint32_t ok = 1u;
         static_assert(kPlanMaxBlocks <= 4 * 64, "four flags per lane");
@@ -2866,15 +2563,8 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
             stale = stale || (uint32_t)(x >> 32) != ep;
             val = (uint32_t)x;
         };
-#if BMQCRC_PLAN_DIAG == 6
-        bool forced = true;  // diagnostic: the first read counts as stale (re-read path)
-#endif
         while (true) {
             bool stale = false;
-#if BMQCRC_PLAN_DIAG == 6
-            stale = forced;
-            forced = false;
-#endif
             uint32_t hb[4], v = 0, nn = 0, u;
 #pragma unroll
             for (uint32_t k = 0; k < 4; ++k) {
@@ -2949,7 +2639,7 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
         }
         if (threadIdx.x < kBuckets) {
             uint32_t acc = 0;
-            const bool desc = BMQCRC_CLASS_DESC == 1 || (BMQCRC_CLASS_DESC == 0 && a.class_desc);
+            const bool desc = a.class_desc;
             for (uint32_t c = 0; c < (uint32_t)kBuckets; ++c) {
                 acc += (desc ? c > threadIdx.x : c < threadIdx.x) ? part[0][0][c] : 0u;
             }
@@ -2997,10 +2687,9 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
                 pos = atomicAdd(&run[c_full], ts + tl);
             }
             pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pos);
-#if BMQCRC_PLAN_DIAG != 4 && !(BMQCRC_PLAN_SKIP & 4)
             const uint32_t w = threadIdx.x >> 6;
             const uint64_t wbase = base + (uint64_t)(threadIdx.x & ~63u) * kPlanV;
-            if (ts && !(BMQCRC_PLAN_SKIP & 32)) {
+            if (ts) {
                 uint32_t e = xs - ns_all, ends[kPlanV];
 #pragma unroll
                 for (uint32_t v = 0; v < kPlanV; ++v) {
@@ -3015,13 +2704,7 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
                         q += sruns[w][q + st - 1u] <= j ? st : 0u;
                     }
                     const uint32_t k = j - (q ? sruns[w][q - 1u] : 0u);
-#if BMQCRC_PLAN_SKIP & 64
-                    if (k == 0xfffffff0u) {  // never: keeps the slot's search live
-                        a.firstk[0] = q;
-                    }
-#else
                     put_full(a, pos + j, (uint32_t)(wbase + q), k);
-#endif
                 }
             }
             uint64_t longs = 0;
@@ -3029,11 +2712,7 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
             for (uint32_t v = 0; v < kPlanV; ++v) {
                 longs |= __ballot(nf[v] > kMapShortRun);
             }
-            if (BMQCRC_PLAN_SKIP & 16) {
-                longs = 0;
-            }
             const uint32_t lpos = pos + ts + (xl - nl_all);
-#if BMQCRC_LONG_FLAT
             if (longs) {
                 // Every long run of the wave at once: its head and tail
                 // entries (the partial groups at either end) are one list of
@@ -3055,50 +2734,44 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
                 for (uint32_t v = 0; v < kPlanV; ++v) {
                     const uint32_t n = nf[v] > kMapShortRun ? nf[v] : 0u;
                     const uint32_t gf = (p + 63u) >> 6, ge = (p + n) >> 6;
-                    const bool whole = kGroupDesc && gf < ge;
+                    const bool whole = gf < ge;
                     atv[v] = p;
                     nv[v] = n;
-                    if constexpr (kRunRecords) {
-                        // entries only for a run inside one group touching
-                        // neither of its ends; a run's head (the group's
-                        // last lanes) and tail (its first lanes) are records
-                        const bool inner = n && (p >> 6) == ((p + n - 1u) >> 6) && (p & 63u) &&
-                                           ((p + n) & 63u);
-                        ni[v] = inner ? n : 0u;
-                    } else {
-                        ni[v] = whole ? (64u * gf - p) + (p + n - 64u * ge) : n;
-                    }
+                    // entries only for a run inside one group touching
+                    // neither of its ends; a run's head (the group's
+                    // last lanes) and tail (its first lanes) are records
+                    const bool inner = n && (p >> 6) == ((p + n - 1u) >> 6) && (p & 63u) &&
+                                       ((p + n) & 63u);
+                    ni[v] = inner ? n : 0u;
                     ng[v] = whole ? ge - gf : 0u;
                     p += n;
                 }
                 *(u32x4*)&slong[w][0][lane * kPlanV] = u32x4{atv[0], atv[1], atv[2], atv[3]};
                 *(u32x4*)&slong[w][1][lane * kPlanV] = u32x4{nv[0], nv[1], nv[2], nv[3]};
-                if constexpr (kRunRecords) {
-                    // Run records (round 6): a long run's partial groups
-                    // are described per group, not per slot -- its head
-                    // (lanes ho..63 of group at/64) by the group's suffix
-                    // record, its tail (lanes 0..te-1 of the last group) by
-                    // the prefix record and firstk; each side of a group has
-                    // one owner (the run covering lane 63, or lane 0).
-                    // Round 5 wrote up to 63 + 63 entries per long run, ~3 MB
-                    // on Zipf's 1/8 shard: 5.3 of its planner's 20.7 us
-                    // (profiles/r05/ab/planner/phase_stamps_fullrun_split.jsonl).
+                // Run records (round 6): a long run's partial groups
+                // are described per group, not per slot -- its head
+                // (lanes ho..63 of group at/64) by the group's suffix
+                // record, its tail (lanes 0..te-1 of the last group) by
+                // the prefix record and firstk; each side of a group has
+                // one owner (the run covering lane 63, or lane 0).
+                // Round 5 wrote up to 63 + 63 entries per long run, ~3 MB
+                // on Zipf's 1/8 shard: 5.3 of its planner's 20.7 us
+                // (profiles/r05/ab/planner/phase_stamps_fullrun_split.jsonl).
 #pragma unroll
-                    for (uint32_t v = 0; v < kPlanV; ++v) {
-                        const uint32_t at = atv[v], n = nv[v];
-                        if (n == 0u) {
-                            continue;
-                        }
-                        const uint32_t hb = at >> 6, tb = (at + n - 1u) >> 6;
-                        const uint32_t ho = at & 63u, te = (at + n) & 63u;
-                        const uint32_t msg = (uint32_t)(wbase + (uint32_t)lane * kPlanV + v);
-                        if (ho != 0u && (hb < tb || te == 0u)) {
-                            *(u32x4*)&a.grec[8u * hb + 4u] = u32x4{ep, msg, 64u - ho, 0u};
-                        }
-                        if (te != 0u && (hb < tb || ho == 0u)) {
-                            *(u32x4*)&a.grec[8u * tb] = u32x4{ep, msg, te, 0u};
-                            a.firstk[tb] = 64u * tb - at;
-                        }
+                for (uint32_t v = 0; v < kPlanV; ++v) {
+                    const uint32_t at = atv[v], n = nv[v];
+                    if (n == 0u) {
+                        continue;
+                    }
+                    const uint32_t hb = at >> 6, tb = (at + n - 1u) >> 6;
+                    const uint32_t ho = at & 63u, te = (at + n) & 63u;
+                    const uint32_t msg = (uint32_t)(wbase + (uint32_t)lane * kPlanV + v);
+                    if (ho != 0u && (hb < tb || te == 0u)) {
+                        *(u32x4*)&a.grec[8u * hb + 4u] = u32x4{ep, msg, 64u - ho, 0u};
+                    }
+                    if (te != 0u && (hb < tb || ho == 0u)) {
+                        *(u32x4*)&a.grec[8u * tb] = u32x4{ep, msg, te, 0u};
+                        a.firstk[tb] = 64u * tb - at;
                     }
                 }
                 auto flat = [&](const uint32_t (&cnt)[kPlanV], auto&& body) {
@@ -3132,59 +2805,20 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
                         }
                     }
                 };
-                if (!(BMQCRC_PLAN_SKIP & 64)) {
-                    flat(ni, [&](uint32_t q, uint32_t e) {
-                        const uint32_t at = slong[w][0][q], n = slong[w][1][q];
-                        const uint32_t gf = (at + 63u) >> 6, ge = (at + n) >> 6;
-                        const uint32_t h = kGroupDesc && gf < ge ? 64u * gf - at : n;
-                        const uint32_t slot = e < h ? at + e : 64u * ge + (e - h);
-                        put_full(a, slot, (uint32_t)(wbase + q), slot - at);
-                    });
-                    if (kGroupDesc) {
-                        flat(ng, [&](uint32_t q, uint32_t e) {
-                            const uint32_t at = slong[w][0][q];
-                            const uint32_t g = ((at + 63u) >> 6) + e;
-                            a.gdesc[g] = (unsigned long long)ep << 32 | (uint32_t)(wbase + q);
-                            a.firstk[g] = 64u * g - at;
-                        });
-                    }
-                }
+                flat(ni, [&](uint32_t q, uint32_t e) {
+                    const uint32_t at = slong[w][0][q], n = slong[w][1][q];
+                    const uint32_t gf = (at + 63u) >> 6, ge = (at + n) >> 6;
+                    const uint32_t h = gf < ge ? 64u * gf - at : n;
+                    const uint32_t slot = e < h ? at + e : 64u * ge + (e - h);
+                    put_full(a, slot, (uint32_t)(wbase + q), slot - at);
+                });
+                flat(ng, [&](uint32_t q, uint32_t e) {
+                    const uint32_t at = slong[w][0][q];
+                    const uint32_t g = ((at + 63u) >> 6) + e;
+                    a.gdesc[g] = (unsigned long long)ep << 32 | (uint32_t)(wbase + q);
+                    a.firstk[g] = 64u * g - at;
+                });
             }
-#else
-            for (; longs; longs &= longs - 1ull) {
-                const int src = __builtin_ctzll(longs);
-                uint32_t at2 = (uint32_t)__builtin_amdgcn_readlane((int)lpos, src);
-#pragma unroll
-                for (uint32_t v = 0; v < kPlanV; ++v) {
-                    const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)nf[v], src);
-                    if (n > kMapShortRun) {
-                        const uint32_t i = (uint32_t)(wbase + (uint32_t)src * kPlanV + v);
-                        // groups wholly inside [at2, at2 + n): one tagged
-                        // descriptor each (and its firstk) instead of 64
-                        // entries; the entries of the partial groups at
-                        // either end as before
-                        const uint32_t gf = (at2 + 63u) >> 6, ge = (at2 + n) >> 6;
-                        const uint32_t kh = kGroupDesc && gf < ge ? 64u * gf - at2 : n;
-                        const uint32_t kt = kGroupDesc && gf < ge ? 64u * ge - at2 : n;
-                        for (uint32_t k = (uint32_t)lane; k < kh && !(BMQCRC_PLAN_SKIP & 64); k += 64u) {
-                            put_full(a, at2 + k, i, k);
-                        }
-                        if (kGroupDesc && !(BMQCRC_PLAN_SKIP & 64)) {
-                            const unsigned long long tag = (unsigned long long)ep << 32 | i;
-                            for (uint32_t g = gf + (uint32_t)lane; g < ge; g += 64u) {
-                                a.gdesc[g] = tag;
-                                a.firstk[g] = 64u * g - at2;
-                            }
-                        }
-                        for (uint32_t k = kt + (uint32_t)lane; k < n && !(BMQCRC_PLAN_SKIP & 64); k += 64u) {
-                            put_full(a, at2 + k, i, k);
-                        }
-                        at2 += n;
-                    }
-                }
-            }
-#endif
-#endif
         }
         // last (or only) segments: one returning LDS atomic per message
 #pragma unroll
@@ -3192,17 +2826,7 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
             const uint32_t c = (cls >> (8u * v)) & 0xffu;
             if (c < (uint32_t)kBuckets) {
                 const uint64_t i = base + (uint64_t)threadIdx.x * kPlanV + v;
-#if BMQCRC_PLAN_SKIP & 2
-                const uint32_t at = run[c] + (uint32_t)threadIdx.x * kPlanV + v;
-#else
-                const uint32_t at = atomicAdd(&run[c], 1u);
-#endif
-#if BMQCRC_PLAN_DIAG != 4 && !(BMQCRC_PLAN_SKIP & 8)
-                put_last(a, at, (uint32_t)i);
-#else
-                (void)at;
-                (void)i;
-#endif
+                put_last(a, atomicAdd(&run[c], 1u), (uint32_t)i);
             }
         }
     };
@@ -3228,12 +2852,6 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_map(BatchArgs a)
     }
     __syncthreads();
     PLAN_STAMP(7)
-#if BMQCRC_PLAN_DIAG == 4 || BMQCRC_PLAN_SKIP
-    // diagnostic (timing only): no seginfo stores, so no map
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(&sync[2], (unsigned long long)ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-#endif
 }
 
 // ------------------------------------------------- verify / blob combine
@@ -3436,7 +3054,7 @@ extern "C" int bmqcrc_launch_batch(const BatchArgs* a, void* stream, int num_cus
     // few groups: one per block over every CU first (BatchArgs::spread)
     BatchArgs b = *a;
     b.spread = 0u;
-    if (kSpread && !wide && grid < cus && max_groups > grid) {
+    if (!wide && grid < cus && max_groups > grid) {
         grid = std::min<uint64_t>(max_groups, cus);
         b.spread = 1u;
     }
@@ -3474,24 +3092,6 @@ extern "C" int bmqcrc_plan_map_occupancy(int* blocks_per_cu)
     *blocks_per_cu = per;
     return 0;
 }
-
-#if BMQCRC_FOLD_DIAG
-extern "C" __attribute__((visibility("default"))) int bmqcrc_diag_fold_trace(unsigned long long* out)
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fold_trace), sizeof(g_fold_trace)) == hipSuccess
-               ? 0
-               : -5;
-}
-#endif
-
-#if BMQCRC_PLAN_DIAG >= 3
-extern "C" __attribute__((visibility("default"))) int bmqcrc_diag_plan_trace(unsigned long long* out)
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_plan_trace), sizeof(g_plan_trace)) == hipSuccess
-               ? 0
-               : -5;
-}
-#endif
 
 extern "C" int bmqcrc_launch_compare(const uint32_t* got, const uint32_t* expected, uint64_t n,
                                      uint32_t* bad_count, uint32_t* bad_idx, uint32_t bad_cap,

@@ -103,10 +103,18 @@ def test_combine():
             Crc32c.calculate(a + b)
 
 
-def test_cpp_dropin_selftest():
+def _selftest_exe():
+    """tests/cpp/bin/bmqp_selftest; a build product, so built here (one g++
+    run against the product library) when it is missing, never skipped."""
     exe = os.path.join(ROOT, "tests", "cpp", "bin", "bmqp_selftest")
     if not os.path.exists(exe):
-        pytest.skip("selftest not built")
+        from blazingmq_amd import build
+        build.build_selftest(os.path.join(build.LIB, "libbmqcrc.so"), force=True)
+    return exe
+
+
+def test_cpp_dropin_selftest():
+    exe = _selftest_exe()
     env = dict(os.environ, BMQCRC_GOLDEN_DIR=os.path.join(ROOT, "tests", "golden"))
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -119,9 +127,7 @@ def test_cpp_spellings_fall_back_without_gpu():
     PutEventCrc32c, FileStoreCrc32c, ClusterStateLedgerCrc32c) finish on the
     host, bit-exact, when no GPU is visible -- while the C-ABI batch calls
     still return BMQCRC_ENODEV (both checked inside the self-test)."""
-    exe = os.path.join(ROOT, "tests", "cpp", "bin", "bmqp_selftest")
-    if not os.path.exists(exe):
-        pytest.skip("selftest not built")
+    exe = _selftest_exe()
     env = dict(os.environ, BMQCRC_GOLDEN_DIR=os.path.join(ROOT, "tests", "golden"),
                HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)

@@ -186,8 +186,9 @@ def test_right_alignment_saves_lines():
 
 
 def horner_words(words, skip=0):
-    """k_fold's tail_horner: raw = sum R_d y^(32-d), two words per step,
-    the first `skip` steps not run."""
+    """The definition every remainder model here is checked against: raw =
+    sum R_d y^(32-d) by Horner, one "times y" per word, the first 2 * skip
+    words (zero in the callers that skip) not run."""
     c = 0
     for d in range(2 * skip, 32):
         c = mul_y(c ^ words[d])
@@ -197,44 +198,40 @@ def horner_words(words, skip=0):
 T11 = G.remainder_tables11()
 
 
-def chains11(words, skip=False):
-    """k_fold's tail_chains11 (8-wave blocks): 11/11/10-bit slices, one word
-    per step, chain A over words 0-15 and B over 16-31, raw = A * y^16 + B.
-    The slice offsets are formed as the kernel forms them: v & 0x1ffc,
-    (v >> 11) & 0x1ffc and rotr(v, 22) & 0xffc (byte offsets into the
-    tables)."""
-    def step(c, r):
-        v = c ^ r
-        rot = ((v >> 22) | (v << 10)) & 0xFFFFFFFF
-        return (T11[(v & 0x1FFC) >> 2] ^ T11[2048 + (((v >> 11) & 0x1FFC) >> 2)] ^
-                T11[4096 + ((rot & 0xFFC) >> 2)])
-    ca = cb = 0
-    for d in range(16):
-        if not skip:
-            ca = step(ca, words[d])
-        cb = step(cb, words[16 + d])
-    if skip:
-        return cb
-    j = 0
-    for k in range(4):
-        j ^= T11[5120 + 256 * k + ((ca >> (8 * k)) & 0xFF)]
-    return j ^ cb
+def step11(c, r):
+    """k_fold's step11 (8-wave blocks; tail_bytes8's last eight steps): one
+    word per step, c <- (c ^ r) * y, through the 11/11/10-bit slices
+    T11[0:5120].  The slice offsets are formed as the kernel forms them:
+    v & 0x1ffc, (v >> 11) & 0x1ffc and rotr(v, 22) & 0xffc (byte offsets into
+    the tables at 0, 8192 and 16384)."""
+    v = c ^ r
+    rot = ((v >> 22) | (v << 10)) & 0xFFFFFFFF
+    return (T11[(v & 0x1FFC) >> 2] ^ T11[2048 + (((v >> 11) & 0x1FFC) >> 2)] ^
+            T11[4096 + ((rot & 0xFFC) >> 2)])
 
 
-def test_chains11_match_horner():
+def chain11(words16):
+    c = 0
+    for r in words16:
+        c = step11(c, r)
+    return c
+
+
+def test_step11_chains_match_horner():
+    # (the y^16 join slices T11[5120:6144] have no kernel reader left; the
+    # generator self-checks them)
     rng = np.random.default_rng(11)
     for _ in range(300):
         words = [int(w) for w in rng.integers(0, 2**32, size=32, dtype=np.uint64)]
-        assert chains11(words) == horner_words(words)
-        zero_a = [0] * 16 + words[16:]
-        assert chains11(zero_a, skip=True) == chains11(zero_a) == horner_words(zero_a, 8)
+        for half in (words[:16], words[16:]):
+            zero_a = [0] * 16 + half
+            assert chain11(half) == horner_words(zero_a) == horner_words(zero_a, 8)
     for w in (0, 1, 3, 0x80000000, 0xFFFFFFFF, 0x00FFE000, 0xFF000003):
-        words = [w] * 32
-        assert chains11(words) == horner_words(words)
+        assert chain11([w] * 16) == horner_words([0] * 16 + [w] * 16)
 
 
 def bytes8(words, skip16=False):
-    """k_fold's tail_bytes8 (BMQCRC_BYTE_FOLD): the 32 remainder words folded
+    """k_fold's tail_bytes8: the 32 remainder words folded
     at byte granularity with the same taps (P(z) = 0 for z = x^8) to 8 words,
     word-parallel with v_alignbyte windows and the pair stream, then 8
     one-word chain steps."""
@@ -628,8 +625,9 @@ def test_claims_cover_every_group_once(ngroups, nbk, wpb):
 
 
 def _long_runs_flat(nf, lpos, short=16):
-    """k_plan_map's flattened long-run writes (BMQCRC_LONG_FLAT,
-    crc32c_kernels.hip phase 2): runs of more than `short` full segments laid
+    """k_plan_map's flattened long-run writes (crc32c_kernels.hip phase 2,
+    with round 5's item counts: a run's head and tail are entries here,
+    records since round 6, see _long_runs_records): runs of more than `short` full segments laid
     out from lpos in (lane, v) order; head and tail entries (the partial
     groups at either end) as one item list, whole groups as another, each
     walked 64 items at a time with a mark at each run's first item and an
@@ -689,7 +687,8 @@ def test_long_runs_flat_cover_every_segment(seed):
     entry (message, k) at its slot, or inside a whole group described by one
     descriptor whose firstk is the group's first k -- against a brute-force
     expansion; runs aligned to groups (no entries), runs inside one group and
-    runs spanning many."""
+    runs spanning many.  The item counts are round 5's (head and tail entries
+    of every run); the mark-and-max-scan walk is the kernel's."""
     rng = np.random.default_rng(seed)
     nf = rng.choice([0, 3, 17, 40, 63, 64, 65, 128, 200, 1000], size=256).tolist()
     lpos = int(rng.integers(0, 64)) if seed else 0
@@ -711,7 +710,7 @@ def test_long_runs_flat_cover_every_segment(seed):
 
 
 def _long_runs_records(nf, lpos, short=16):
-    """k_plan_map's long runs with run records (round 6, BMQCRC_RUN_RECORDS):
+    """k_plan_map's long runs with run records (round 6):
     whole groups as descriptors, a run's head (the last lanes of its first
     group) as that group's suffix record, its tail (the first lanes of its
     last group) as the prefix record with firstk, entries only for a run

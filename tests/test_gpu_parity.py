@@ -419,7 +419,6 @@ def test_shape_hint_misprediction(cuda):
         run(lens)
 
 
-@pytest.mark.perf
 def test_auto_2k_batch_every_planner_path(cuda):
     """An automatically sized 2 KiB batch (>= 512 MiB of arena) of 1.5M short
     messages with long ones mixed in -- lengths on either side of 64 KiB and

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-block phase times of k_plan_map (GPU box, diagnostic build only).
 
-Needs a library built with -DBMQCRC_PLAN_DIAG=3 or 4 (tools/build_variant.sh pd3
+Needs a library built with -DBMQCRC_PLAN_DIAG=3 (tools/build_variant.sh pd3
 -DBMQCRC_PLAN_DIAG=3), swapped in as libbmqcrc.so by the caller.  Runs the
 Zipf batch (or one shard of it) a few times, then reads the per-block
 wall-clock stamps of the last planner launch (8 per block, see g_plan_trace;
