@@ -20,6 +20,7 @@ BMQCRC_F_ASYNC = 0x2
 BMQCRC_F_TIME_KERNEL = 0x4
 BMQCRC_F_WHOLE_MESSAGES = 0x8
 BMQCRC_F_PLAN = 0x10
+BMQCRC_F_OFFSETS32 = 0x20
 
 
 class BmqCrcError(RuntimeError):
@@ -33,7 +34,7 @@ class Opts(ctypes.Structure):
                 ("stream", ctypes.c_void_p), ("flags", ctypes.c_uint32),
                 ("seg_bytes", ctypes.c_uint32), ("ndevices", ctypes.c_uint32),
                 ("devices", ctypes.c_void_p), ("max_len", ctypes.c_uint32),
-                ("min_len", ctypes.c_uint32)]
+                ("min_len", ctypes.c_uint32), ("offset_shift", ctypes.c_uint32)]
 
 
 # One HIP runtime per process: when PyTorch-ROCm is present it ships its own
@@ -83,6 +84,9 @@ lib.bmqcrc_last_plan.argtypes = [_int, _vp, ctypes.POINTER(_u32)]
 lib.bmqcrc_last_launch.restype = _int
 lib.bmqcrc_last_launch.argtypes = [_int, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
                                    ctypes.POINTER(_u32)]
+if hasattr(lib, "bmqcrc_last_offsets"):  # ABI 2.8 (an older build loads for same-box A/B)
+    lib.bmqcrc_last_offsets.restype = _int
+    lib.bmqcrc_last_offsets.argtypes = [_int, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]
 lib.bmqcrc_forget_shape.restype = _int
 lib.bmqcrc_forget_shape.argtypes = [_int, _vp]
 if hasattr(lib, "bmqcrc_plan_wait"):  # ABI 2.3 (an older build loads for same-box A/B)
@@ -136,10 +140,12 @@ def check_count(n):
 
 
 def make_opts(device=-1, stream=None, flags=0, seg_bytes=0, devices=None, max_len=0,
-              min_len=0):
+              min_len=0, offset_shift=None):
     """bmqcrc_opts; `devices` (a sequence of ordinals, repeats allowed) spreads
     the format-walk entry points over several devices (ABI 2.1); `max_len`
-    and `min_len` declare bounds on a device-resident batch's lengths (ABI 2.4)."""
+    and `min_len` declare bounds on a device-resident batch's lengths (ABI 2.4);
+    `offset_shift` (an int in 0..7, ABI 2.8) sets BMQCRC_F_OFFSETS32: the
+    offsets are uint32 in units of 1 << offset_shift bytes."""
     o = Opts()
     o.struct_size = ctypes.sizeof(Opts)
     o.device = device
@@ -148,6 +154,9 @@ def make_opts(device=-1, stream=None, flags=0, seg_bytes=0, devices=None, max_le
     o.seg_bytes = seg_bytes
     o.max_len = max_len
     o.min_len = min_len
+    if offset_shift is not None:
+        o.flags |= BMQCRC_F_OFFSETS32
+        o.offset_shift = offset_shift
     if devices is not None and len(devices) > 1:
         arr = (ctypes.c_int32 * len(devices))(*devices)
         o._devices_keep = arr  # the array lives as long as the opts

@@ -101,10 +101,10 @@ class Crc32c:
 
     @staticmethod
     def verify_batch(arena, offsets, lengths, expected, bad_cap=1 << 20, seg_bytes=0,
-                     devices=None):
+                     devices=None, offset_shift=None):
         """Batched recovery check (bmqcrc_crc32c_verify): (n_bad, bad indices)."""
         return verify_batch(arena, offsets, lengths, expected, bad_cap, seg_bytes,
-                            devices=devices)
+                            devices=devices, offset_shift=offset_shift)
 
     @staticmethod
     def calculate_blobs(blobs, seeds=None, seg_bytes=0, gather=True):
@@ -114,7 +114,8 @@ class Crc32c:
     @staticmethod
     def calculate_batch(arena, offsets, lengths, seeds=None, out=None, *, seg_bytes=0,
                         device=None, stream=None, sync=True, time_kernel=False,
-                        whole_messages=False, devices=None, plan=False, max_len=0, min_len=0):
+                        whole_messages=False, devices=None, plan=False, max_len=0, min_len=0,
+                        offset_shift=None):
         """Batched CRC32-C of messages ``arena[offsets[i] : offsets[i]+lengths[i]]``.
 
         torch CUDA tensors: ``arena`` uint8, ``offsets`` int64, ``lengths`` /
@@ -131,23 +132,63 @@ class Crc32c:
         whatever the previous batch was (a longer message stays exact);
         with ``min_len`` too, a range whose lengths all have the same u
         segments (u dividing 64) gets the uniform single launch.
+        ``offset_shift`` (BMQCRC_F_OFFSETS32): ``None`` is the 64-bit form
+        above; an int in 0..7 says the offsets are 32-bit, in units of
+        ``1 << offset_shift`` bytes -- a contiguous int32 tensor (read as
+        u32), or host offsets taken as ``uint32`` (a value that does not fit
+        is refused).  8 bytes of descriptors per message instead of 12.
         """
         try:
             import torch
         except ImportError:  # pragma: no cover
             torch = None
+        offset_shift = _check_shift(torch, offsets, offset_shift)
         if torch is not None and isinstance(arena, torch.Tensor) and arena.is_cuda:
             return _batch_torch(torch, arena, offsets, lengths, seeds, out, seg_bytes, stream,
-                                sync, time_kernel, whole_messages, plan, max_len, min_len)
+                                sync, time_kernel, whole_messages, plan, max_len, min_len,
+                                offset_shift)
         return _batch_host(arena, offsets, lengths, seeds, out, seg_bytes, device,
-                           whole_messages, devices)
+                           whole_messages, devices, offset_shift)
+
+
+def _check_shift(torch, offsets, offset_shift):
+    """Validate ``offset_shift`` (None, or an int in 0..7) against the offsets
+    it describes: torch offsets must then be int32."""
+    if offset_shift is None:
+        return None
+    if isinstance(offset_shift, bool) or not isinstance(offset_shift, (int, np.integer)) \
+            or not 0 <= offset_shift <= 7:
+        raise ValueError("offset_shift must be None or an int in 0..7")
+    if torch is not None and isinstance(offsets, torch.Tensor) and not (
+            offsets.dtype == torch.int32 and offsets.is_contiguous()):
+        raise TypeError("with offset_shift set, offsets must be a contiguous int32 tensor "
+                        "(read as u32)")
+    return int(offset_shift)
+
+
+def _host_offsets(offsets, offset_shift):
+    """Host offsets as the library takes them: uint64, or with ``offset_shift``
+    set uint32 -- refusing a value that does not fit rather than wrapping it."""
+    if offset_shift is None:
+        return np.ascontiguousarray(offsets, dtype=np.uint64)
+    off = np.asarray(offsets)
+    if off.size == 0:  # (an empty list is float64 to numpy)
+        return np.zeros(off.shape, dtype=np.uint32)
+    if off.dtype != np.uint32:
+        if off.dtype.kind not in "iu":
+            raise TypeError("with offset_shift set, offsets must be integers")
+        if off.size and (int(off.min()) < 0 or int(off.max()) > 0xFFFFFFFF):
+            raise ValueError("with offset_shift set, every offset must fit 32 bits")
+    return np.ascontiguousarray(off, dtype=np.uint32)
 
 
 def _batch_torch(torch, arena, offsets, lengths, seeds, out, seg_bytes, stream, sync,
-                 time_kernel=False, whole_messages=False, plan=False, max_len=0, min_len=0):
+                 time_kernel=False, whole_messages=False, plan=False, max_len=0, min_len=0,
+                 offset_shift=None):
     dev = arena.device
     n = offsets.numel()
-    for name, t, dt in (("offsets", offsets, torch.int64), ("lengths", lengths, torch.int32)):
+    off_dt = torch.int64 if offset_shift is None else torch.int32
+    for name, t, dt in (("offsets", offsets, off_dt), ("lengths", lengths, torch.int32)):
         if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt
                 and t.is_contiguous()):
             raise TypeError("%s must be a contiguous %s tensor on %s" % (name, dt, dev))
@@ -172,7 +213,7 @@ def _batch_torch(torch, arena, offsets, lengths, seeds, out, seg_bytes, stream, 
         flags |= _native.BMQCRC_F_PLAN
     o = _native.make_opts(device=dev.index if dev.index is not None else -1,
                           stream=stream.cuda_stream, flags=flags, seg_bytes=seg_bytes,
-                          max_len=max_len, min_len=min_len)
+                          max_len=max_len, min_len=min_len, offset_shift=offset_shift)
     _native.check(_native.lib.bmqcrc_crc32c_batch(
         arena.data_ptr(), arena.numel(), offsets.data_ptr(), lengths.data_ptr(),
         seeds.data_ptr() if seeds is not None else None, out.data_ptr(), n, ctypes.byref(o)))
@@ -193,10 +234,10 @@ def _check_host_out(out, n):
 
 
 def _batch_host(arena, offsets, lengths, seeds, out, seg_bytes, device, whole_messages=False,
-                devices=None):
+                devices=None, offset_shift=None):
     a = np.frombuffer(bytes(arena), dtype=np.uint8) if isinstance(
         arena, (bytes, bytearray, memoryview)) else np.ascontiguousarray(arena).view(np.uint8)
-    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    off = _host_offsets(offsets, offset_shift)
     ln = np.ascontiguousarray(lengths, dtype=np.uint32)
     if off.shape != ln.shape:
         raise ValueError("offsets/lengths size mismatch")
@@ -206,7 +247,7 @@ def _batch_host(arena, offsets, lengths, seeds, out, seg_bytes, device, whole_me
     res = np.empty(off.size, dtype=np.uint32) if out is None else _check_host_out(out, off.size)
     o = _native.make_opts(device=-1 if device is None else device, seg_bytes=seg_bytes,
                           flags=_native.BMQCRC_F_WHOLE_MESSAGES if whole_messages else 0,
-                          devices=devices)
+                          devices=devices, offset_shift=offset_shift)
     _native.check(_native.lib.bmqcrc_crc32c_batch(
         a.ctypes.data if a.size else None, a.size, off.ctypes.data, ln.ctypes.data,
         sd.ctypes.data if sd is not None else None, res.ctypes.data, off.size, ctypes.byref(o)))
@@ -220,12 +261,14 @@ def _u8_host(arena):
 
 
 def verify_batch(arena, offsets, lengths, expected, bad_cap=1 << 20, seg_bytes=0, device=None,
-                 devices=None):
+                 devices=None, offset_shift=None):
     """GPU batch CRC of every message compared on the device with `expected`.
 
-    Returns (n_bad, bad_index ndarray[uint64], ascending, at most bad_cap)."""
+    Returns (n_bad, bad_index ndarray[uint64], ascending, at most bad_cap).
+    ``offset_shift``: as in ``Crc32c.calculate_batch`` (host offsets)."""
     a = _u8_host(arena)
-    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    offset_shift = _check_shift(None, offsets, offset_shift)
+    off = _host_offsets(offsets, offset_shift)
     ln = np.ascontiguousarray(lengths, dtype=np.uint32)
     ex = np.ascontiguousarray(expected, dtype=np.uint32)
     if not (off.shape == ln.shape == ex.shape):
@@ -233,7 +276,7 @@ def verify_batch(arena, offsets, lengths, expected, bad_cap=1 << 20, seg_bytes=0
     nbad = ctypes.c_uint64()
     idx = np.zeros(max(int(bad_cap), 1), dtype=np.uint64)
     o = _native.make_opts(device=-1 if device is None else device, seg_bytes=seg_bytes,
-                          devices=devices)
+                          devices=devices, offset_shift=offset_shift)
     _native.check(_native.lib.bmqcrc_crc32c_verify(
         a.ctypes.data if a.size else None, a.size, off.ctypes.data, ln.ctypes.data,
         ex.ctypes.data, off.size, ctypes.byref(nbad), idx.ctypes.data, int(bad_cap),
@@ -329,18 +372,37 @@ def kernel_timing(device, stream):
     return tot.value, cnt.value
 
 
-def last_launch(device, stream):
+def last_launch(device, stream, offsets=False):
     """Launch plan of the previous batch on (device, stream)
     (bmqcrc_last_launch, bmqcrc_last_plan): dict(kernels, spec, seg_bytes,
     map) -- kernels launched
     (1 = the fold alone), segments per message a single launch assumed (0 =
-    planned), segment size, whether the planner built the size-class map."""
+    planned), segment size, whether the planner built the size-class map.
+    ``offsets=True`` adds offset_bits and offset_shift, the offset form it
+    read (``last_offsets``).  They are not in the default dict on purpose:
+    tests/test_gpu_parity.py compares that dict whole with its four keys, so
+    adding keys to it breaks callers that do the same."""
     k, u, sb = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
     _native.check(_native.lib.bmqcrc_last_launch(device, stream.cuda_stream, ctypes.byref(k),
                                                 ctypes.byref(u), ctypes.byref(sb)))
     m = ctypes.c_uint32()
     _native.check(_native.lib.bmqcrc_last_plan(device, stream.cuda_stream, ctypes.byref(m)))
-    return {"kernels": k.value, "spec": u.value, "seg_bytes": sb.value, "map": m.value}
+    plan = {"kernels": k.value, "spec": u.value, "seg_bytes": sb.value, "map": m.value}
+    if offsets:
+        plan["offset_bits"], plan["offset_shift"] = last_offsets(device, stream)
+    return plan
+
+
+def last_offsets(device, stream=None):
+    """Offset form of the previous batch on (device, stream)
+    (bmqcrc_last_offsets): (64, 0), or (32, offset_shift) for a batch with
+    ``offset_shift`` set or a format walk that chose 32-bit offsets.
+    ``stream=None`` is the device's default stream, where host-buffer calls run."""
+    bits, sh = ctypes.c_uint32(), ctypes.c_uint32()
+    _native.check(_native.lib.bmqcrc_last_offsets(
+        device, stream.cuda_stream if stream is not None else None, ctypes.byref(bits),
+        ctypes.byref(sh)))
+    return bits.value, sh.value
 
 
 def forget_shape(device, stream):
@@ -396,16 +458,18 @@ class HostRegistration:
 
 
 def calculate_batch_ptr(arena_ptr, arena_bytes, offsets, lengths, seeds=None, out=None, *,
-                        seg_bytes=0, stream=None, sync=True):
+                        seg_bytes=0, stream=None, sync=True, offset_shift=None):
     """Batch over a device-visible arena given by address (a device allocation
-    or a ``HostRegistration.dev_ptr``); offsets/lengths/seeds/out as in
-    ``Crc32c.calculate_batch``'s torch form."""
+    or a ``HostRegistration.dev_ptr``); offsets/lengths/seeds/out and
+    ``offset_shift`` as in ``Crc32c.calculate_batch``'s torch form."""
     import torch
+    offset_shift = _check_shift(torch, offsets, offset_shift)
     dev = offsets.device
     n = offsets.numel()
-    if not _is_vec(torch, offsets, dev, torch.int64, n) or \
-            not _is_vec(torch, lengths, dev, torch.int32, n):
-        raise TypeError("offsets/lengths must be contiguous int64/int32 tensors of n elements")
+    if not _is_vec(torch, offsets, dev, torch.int64 if offset_shift is None else torch.int32, n) \
+            or not _is_vec(torch, lengths, dev, torch.int32, n):
+        raise TypeError("offsets/lengths must be contiguous int64 (int32 with offset_shift) / "
+                        "int32 tensors of n elements")
     if seeds is not None and not _is_vec(torch, seeds, dev, torch.int32, n):
         raise TypeError("seeds must be a contiguous int32 tensor of %d elements on %s" % (n, dev))
     if out is None:
@@ -416,7 +480,8 @@ def calculate_batch_ptr(arena_ptr, arena_bytes, offsets, lengths, seeds=None, ou
         stream = torch.cuda.current_stream(dev)
     flags = _native.BMQCRC_F_DEVICE_PTRS | (0 if sync else _native.BMQCRC_F_ASYNC)
     o = _native.make_opts(device=dev.index if dev.index is not None else -1,
-                          stream=stream.cuda_stream, flags=flags, seg_bytes=seg_bytes)
+                          stream=stream.cuda_stream, flags=flags, seg_bytes=seg_bytes,
+                          offset_shift=offset_shift)
     _native.check(_native.lib.bmqcrc_crc32c_batch(
         arena_ptr, arena_bytes, offsets.data_ptr(), lengths.data_ptr(),
         seeds.data_ptr() if seeds is not None else None, out.data_ptr(), n, ctypes.byref(o)))

@@ -121,6 +121,8 @@ struct Workspace {
     uint32_t* hint_dev = nullptr;
     // Launch plan of the last batch (bmqcrc_last_launch).
     uint32_t last_kernels = 0, last_spec = 0, last_seg = 0, last_map = 0;
+    // Offset form of the last batch (bmqcrc_last_offsets): 64 or 32 bits, and the shift.
+    uint32_t last_off_bits = 64, last_off_shift = 0;
     // Given-up planner maps (hint_host[1], written by k_fold): the last epoch
     // seen, and how many more ragged batches take the meeting-free pair.
     uint32_t void_seen = 0, pair_left = 0;
@@ -158,7 +160,8 @@ struct DeviceState {
     // kPlanMaxBlocks): its grid never exceeds this, so on an idle GPU every
     // block is resident for the grid-wide meeting (a partitioned or smaller
     // part gets fewer, fuller blocks instead of a wait that must give up)
-    uint32_t plan_resident = kPlanMaxBlocks;
+    // ([1]: of the kernel compiled for 32-bit offsets, which is launched then)
+    uint32_t plan_resident[2] = {kPlanMaxBlocks, kPlanMaxBlocks};
 };
 
 std::mutex g_mu;
@@ -202,12 +205,14 @@ int device_state(int dev, DeviceState** st)
                                            ", this library is built for gfx950 (MI355X) only");
         }
         HIP_TRY(hipSetDevice(dev));
-        int per = 0;
-        if (bmqcrc_plan_map_occupancy(&per) != 0 || per <= 0) {
-            return fail(BMQCRC_EIO, "k_plan_map occupancy query failed");
+        for (int off32 = 0; off32 < 2; ++off32) {
+            int per = 0;
+            if (bmqcrc_plan_map_occupancy(off32, &per) != 0 || per <= 0) {
+                return fail(BMQCRC_EIO, "k_plan_map occupancy query failed");
+            }
+            s.plan_resident[off32] = (uint32_t)std::min<uint64_t>(
+                (uint64_t)per * (uint64_t)std::max(prop.multiProcessorCount, 1), kPlanMaxBlocks);
         }
-        s.plan_resident = (uint32_t)std::min<uint64_t>(
-            (uint64_t)per * (uint64_t)std::max(prop.multiProcessorCount, 1), kPlanMaxBlocks);
         s.num_cus = prop.multiProcessorCount;
     }
     *st = &s;
@@ -252,12 +257,12 @@ static void split_ranges(uint64_t items, uint64_t* per, uint32_t* blocks,
 }
 
 int plan_ws(Workspace* w, hipStream_t s, uint64_t n, uint64_t arena_bytes, uint32_t seg,
-            BatchArgs* a, const DeviceState& st)
+            BatchArgs* a, const DeviceState& st, bool off32 = false)
 {
     const int num_cus = st.num_cus;
     const uint64_t max_segs = max_segs_for(n, arena_bytes, seg);
     // k_plan_map's blocks meet grid-wide: never more than the GPU holds
-    split_ranges(n, &a->per_msg, &a->nblocks, st.plan_resident);
+    split_ranges(n, &a->per_msg, &a->nblocks, st.plan_resident[off32 ? 1 : 0]);
     int rc;
     if ((rc = w->seg_first.ensure(4 * std::max<uint64_t>(n, 1))) ||
         (rc = w->block_sum.ensure(12ull * kPlanMaxBlocks)) ||
@@ -427,6 +432,7 @@ uint64_t min_length(const uint32_t* lengths, uint64_t n)
     return m;
 }
 
+// off_shift: with BMQCRC_F_OFFSETS32 in flags, bmqcrc_opts.offset_shift.
 // host_max_len: the longest message when the lengths were seen on the host, or
 // the caller's declared bound for device lengths (bmqcrc_opts.max_len: a
 // message over it is still exact, folded by its wave's second pass)
@@ -434,12 +440,15 @@ uint64_t min_length(const uint32_t* lengths, uint64_t n)
 int run_batch(Ctx& c, uint32_t flags, uint32_t seg, const void* arena, uint64_t arena_bytes,
               const uint64_t* offsets, const uint32_t* lengths, const uint32_t* seeds,
               uint32_t* out, uint64_t n, uint64_t host_max_len = UINT64_MAX,
-              uint64_t host_min_len = 0)
+              uint64_t host_min_len = 0, uint32_t off_shift = 0)
 {
     Workspace* w = c.w;
     BatchArgs a;
     memset(&a, 0, sizeof(a));
     a.n = n;
+    // BMQCRC_F_OFFSETS32: `offsets` points at n uint32_t (device memory)
+    a.off32 = (flags & BMQCRC_F_OFFSETS32) ? 1u : 0u;
+    a.off_shift = a.off32 ? off_shift : 0u;
     auto_shape(n, arena_bytes, c.st->num_cus, &seg, &a.blocks_per_cu);
     a.seg_bytes = seg;
     a.tune = kTuneBits;
@@ -447,7 +456,7 @@ int run_batch(Ctx& c, uint32_t flags, uint32_t seg, const void* arena, uint64_t 
     if (flags & BMQCRC_F_WHOLE_MESSAGES) {
         a.whole = 1;  // identity map over messages: no planner workspace
         a.max_segs = n;
-    } else if ((rc = plan_ws(w, c.s, n, arena_bytes, seg, &a, *c.st))) {
+    } else if ((rc = plan_ws(w, c.s, n, arena_bytes, seg, &a, *c.st, a.off32 != 0))) {
         return rc;
     } else if (!(kTuneBits & 16u) && !(flags & BMQCRC_F_PLAN)) {
         const uint32_t hint = __atomic_load_n(w->hint_host, __ATOMIC_RELAXED);
@@ -563,6 +572,8 @@ int run_batch(Ctx& c, uint32_t flags, uint32_t seg, const void* arena, uint64_t 
                       : single_pass_planner(a) ? 2u
                                              : 3u;
     w->last_map = n != 0 && !a.whole && !a.spec && a.map_planned ? 1u : 0u;
+    w->last_off_bits = a.off32 ? 32u : 64u;
+    w->last_off_shift = a.off_shift;
     return 0;
 }
 
@@ -579,13 +590,19 @@ int stage(Ctx& c, DevBuf& buf, const void* host, uint64_t bytes)
     return 0;
 }
 
+// Bytes of a batch's n offsets: 32-bit ones are staged as they are, 4 bytes each.
+uint64_t offsets_bytes(uint32_t flags, uint64_t n)
+{
+    return ((flags & BMQCRC_F_OFFSETS32) ? 4 : 8) * n;
+}
+
 // declared_max / declared_min: the caller's bounds on every length of a
 // device-resident batch (bmqcrc_opts.max_len / min_len, 0 = none); host
 // batches use the lengths they hold.
 int batch_one(int dev, void* user_stream, uint32_t flags, uint32_t seg, const void* arena,
               uint64_t arena_bytes, const uint64_t* offsets, const uint32_t* lengths,
               const uint32_t* seeds, uint32_t* out, uint64_t n, uint32_t declared_max = 0,
-              uint32_t declared_min = 0)
+              uint32_t declared_min = 0, uint32_t off_shift = 0)
 {
     Ctx c;
     int rc = open_ctx(dev, user_stream, &c);
@@ -598,7 +615,8 @@ int batch_one(int dev, void* user_stream, uint32_t flags, uint32_t seg, const vo
     if (dev_ptrs) {
         if ((rc = run_batch(c, flags, seg, arena, arena_bytes, offsets, lengths, seeds, out, n,
                             declared_max ? (uint64_t)declared_max : UINT64_MAX,
-                            declared_max ? std::min(declared_min, declared_max) : 0u))) {
+                            declared_max ? std::min(declared_min, declared_max) : 0u,
+                            off_shift))) {
             return rc;
         }
         if (!(flags & BMQCRC_F_ASYNC)) {
@@ -607,14 +625,15 @@ int batch_one(int dev, void* user_stream, uint32_t flags, uint32_t seg, const vo
         return 0;
     }
     if ((rc = stage(c, w->arena, arena, arena_bytes)) ||
-        (rc = stage(c, w->offsets, offsets, 8 * n)) || (rc = stage(c, w->lengths, lengths, 4 * n)) ||
+        (rc = stage(c, w->offsets, offsets, offsets_bytes(flags, n))) ||
+        (rc = stage(c, w->lengths, lengths, 4 * n)) ||
         (seeds && (rc = stage(c, w->seeds, seeds, 4 * n))) || (rc = w->out.ensure(4 * n))) {
         return rc;
     }
     if ((rc = run_batch(c, flags, seg, w->arena.p, arena_bytes, (const uint64_t*)w->offsets.p,
                         (const uint32_t*)w->lengths.p,
                         seeds ? (const uint32_t*)w->seeds.p : nullptr, (uint32_t*)w->out.p, n,
-                        max_length(lengths, n), min_length(lengths, n)))) {
+                        max_length(lengths, n), min_length(lengths, n), off_shift))) {
         return rc;
     }
     HIP_TRY(hipMemcpyAsync(out, w->out.p, 4 * n, hipMemcpyDeviceToHost, c.s));
@@ -622,7 +641,9 @@ int batch_one(int dev, void* user_stream, uint32_t flags, uint32_t seg, const vo
     return 0;
 }
 
-int parse_opts(const bmqcrc_opts* opts, bmqcrc_opts* o, uint32_t* seg, int* dev)
+// offsets32_ok: the entry point takes BMQCRC_F_OFFSETS32 (batch and verify).
+int parse_opts(const bmqcrc_opts* opts, bmqcrc_opts* o, uint32_t* seg, int* dev,
+               bool offsets32_ok = false)
 {
     memset(o, 0, sizeof(*o));
     o->device = -1;
@@ -637,9 +658,20 @@ int parse_opts(const bmqcrc_opts* opts, bmqcrc_opts* o, uint32_t* seg, int* dev)
     }
     *seg = o->seg_bytes;
     const uint32_t known = BMQCRC_F_DEVICE_PTRS | BMQCRC_F_ASYNC | BMQCRC_F_TIME_KERNEL |
-                           BMQCRC_F_WHOLE_MESSAGES | BMQCRC_F_PLAN;
+                           BMQCRC_F_WHOLE_MESSAGES | BMQCRC_F_PLAN | BMQCRC_F_OFFSETS32;
     if (o->flags & ~known) {
         return fail(BMQCRC_EINVAL, "unknown bmqcrc_opts.flags bits");
+    }
+    // (a caller whose struct ends before offset_shift has 0 from the memset)
+    if ((o->flags & BMQCRC_F_OFFSETS32) && !offsets32_ok) {
+        return fail(BMQCRC_EINVAL,
+                    "BMQCRC_F_OFFSETS32 applies to bmqcrc_crc32c_batch and bmqcrc_crc32c_verify only");
+    }
+    if (o->offset_shift && !(o->flags & BMQCRC_F_OFFSETS32)) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_opts.offset_shift needs BMQCRC_F_OFFSETS32");
+    }
+    if (o->offset_shift > 7) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_opts.offset_shift must be in [0, 7]");
     }
     int rc;
     if ((rc = check_seg(seg)) || (rc = resolve_device(o->device, dev))) {
@@ -660,6 +692,57 @@ int check_ranges(const uint64_t* offsets, const uint32_t* lengths, uint64_t n,
     return 0;
 }
 
+// The same for 32-bit offsets, in 64 bits: (off << shift) + len <= arena_bytes.
+int check_ranges32(const uint32_t* offsets, uint32_t shift, const uint32_t* lengths, uint64_t n,
+                   uint64_t arena_bytes)
+{
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t off = (uint64_t)offsets[i] << shift;
+        if (off > arena_bytes || lengths[i] > arena_bytes - off) {
+            return fail(BMQCRC_EINVAL,
+                        "message " + std::to_string(i) + " lies outside [arena, arena+arena_bytes)");
+        }
+    }
+    return 0;
+}
+
+// A host batch's offsets in either form (BMQCRC_F_OFFSETS32: p32, shift).
+struct Offsets {
+    const uint64_t* p64;
+    const uint32_t* p32;
+    uint32_t shift;
+    uint64_t operator[](uint64_t i) const
+    {
+        return p32 ? (uint64_t)p32[i] << shift : p64[i];
+    }
+};
+
+Offsets offsets_of(const bmqcrc_opts& o, const uint64_t* offsets)
+{
+    if (o.flags & BMQCRC_F_OFFSETS32) {
+        return Offsets{nullptr, (const uint32_t*)offsets, o.offset_shift};
+    }
+    return Offsets{offsets, nullptr, 0u};
+}
+
+int check_ranges(const Offsets& of, const uint32_t* lengths, uint64_t n, uint64_t arena_bytes)
+{
+    return of.p32 ? check_ranges32(of.p32, of.shift, lengths, n, arena_bytes)
+                  : check_ranges(of.p64, lengths, n, arena_bytes);
+}
+
+int check_ranges(const bmqcrc_opts& o, const uint64_t* offsets, const uint32_t* lengths,
+                 uint64_t n, uint64_t arena_bytes)
+{
+    return (o.flags & BMQCRC_F_OFFSETS32)
+               ? check_ranges32((const uint32_t*)offsets, o.offset_shift, lengths, n, arena_bytes)
+               : check_ranges(offsets, lengths, n, arena_bytes);
+}
+
+int batch_multi(const void* arena, uint64_t arena_bytes, Offsets offsets, const uint32_t* lengths,
+                const uint32_t* seeds, uint32_t* out, uint64_t n, const int* devices, int ndev,
+                uint32_t seg_bytes);
+
 // Device mismatch-index list of a verify: 4 Mi entries (16 MiB) at most.
 constexpr uint64_t kVerifyListCap = 1ull << 22;
 
@@ -677,16 +760,18 @@ int verify_host_multi(const void* arena, uint64_t arena_bytes, bmqcrc_prepare_fn
 // an already finished "walk".
 struct GivenArrays {
     const uint64_t* off;
+    const uint32_t* off32;  // BMQCRC_F_OFFSETS32: the caller's array, `off` is null
     const uint32_t* len;
     const uint32_t* exp;
     uint64_t n;
 };
 
-int given_arrays(void* ctx, const uint64_t** off, const uint32_t** len, const uint32_t** exp,
-                 uint64_t* n)
+int given_arrays(void* ctx, const uint64_t** off, const uint32_t** off32, const uint32_t** len,
+                 const uint32_t** exp, uint64_t* n)
 {
     const GivenArrays* g = (const GivenArrays*)ctx;
     *off = g->off;
+    *off32 = g->off32;
     *len = g->len;
     *exp = g->exp;
     *n = g->n;
@@ -727,19 +812,24 @@ int bmqcrc_crc32c_batch(const void* arena, uint64_t arena_bytes, const uint64_t*
     bmqcrc_opts o;
     uint32_t seg;
     int dev, rc;
-    if ((rc = parse_opts(opts, &o, &seg, &dev))) {
+    if ((rc = parse_opts(opts, &o, &seg, &dev, true))) {
         return rc;
     }
-    if (!(o.flags & BMQCRC_F_DEVICE_PTRS) && (rc = check_ranges(offsets, lengths, n, arena_bytes))) {
+    if (!(o.flags & BMQCRC_F_DEVICE_PTRS) &&
+        (rc = check_ranges(o, offsets, lengths, n, arena_bytes))) {
         return rc;  // device arrays are trusted
     }
     if (!(o.flags & BMQCRC_F_DEVICE_PTRS) && o.ndevices > 1) {  // one byte range per device
-        return bmqcrc_crc32c_batch_multi(arena, arena_bytes, offsets, lengths, seeds, out, n,
-                                         o.devices, (int)o.ndevices, seg);
+        if (!(o.flags & BMQCRC_F_OFFSETS32)) {
+            return bmqcrc_crc32c_batch_multi(arena, arena_bytes, offsets, lengths, seeds, out, n,
+                                             o.devices, (int)o.ndevices, seg);
+        }
+        return batch_multi(arena, arena_bytes, offsets_of(o, offsets), lengths, seeds, out, n,
+                           o.devices, (int)o.ndevices, seg);
     }
     return batch_one(dev, o.stream, o.flags, seg, arena, arena_bytes, offsets, lengths, seeds,
                      out, n, (o.flags & BMQCRC_F_DEVICE_PTRS) ? o.max_len : 0u,
-                     (o.flags & BMQCRC_F_DEVICE_PTRS) ? o.min_len : 0u);
+                     (o.flags & BMQCRC_F_DEVICE_PTRS) ? o.min_len : 0u, o.offset_shift);
 }
 
 int bmqcrc_crc32c_verify(const void* arena, uint64_t arena_bytes, const uint64_t* offsets,
@@ -765,15 +855,16 @@ int bmqcrc_crc32c_verify(const void* arena, uint64_t arena_bytes, const uint64_t
     bmqcrc_opts o;
     uint32_t seg;
     int dev, rc;
-    if ((rc = parse_opts(opts, &o, &seg, &dev))) {
+    if ((rc = parse_opts(opts, &o, &seg, &dev, true))) {
         return rc;
     }
     const bool dev_ptrs = (o.flags & BMQCRC_F_DEVICE_PTRS) != 0;
-    if (!dev_ptrs && (rc = check_ranges(offsets, lengths, n, arena_bytes))) {
+    if (!dev_ptrs && (rc = check_ranges(o, offsets, lengths, n, arena_bytes))) {
         return rc;
     }
     if (!dev_ptrs && o.ndevices > 1) {  // one byte range per device, merged in index order
-        GivenArrays ga = {offsets, lengths, expected, n};
+        const Offsets of = offsets_of(o, offsets);
+        GivenArrays ga = {of.p64, of.p32, lengths, expected, n};
         std::vector<uint64_t> bad;
         uint64_t written = 0;
         if ((rc = verify_host_multi(arena, arena_bytes, given_arrays, &ga, n_bad, &bad, bad_cap, o,
@@ -799,7 +890,8 @@ namespace {
 
 // The verify pipeline after the workspace lock: stage (host buffers; the
 // arena may already be staged), fold, compare on the device, collect the
-// lowest mismatching indices.
+// lowest mismatching indices.  With BMQCRC_F_OFFSETS32 in o.flags `offsets`
+// points at n uint32_t in units of 1 << o.offset_shift bytes.
 int verify_locked(Ctx& c, Workspace* w, const bmqcrc_opts& o, uint32_t seg, bool arena_staged,
                   const void* arena, uint64_t arena_bytes, const uint64_t* offsets,
                   const uint32_t* lengths, const uint32_t* expected, uint64_t n, uint64_t* n_bad,
@@ -825,7 +917,7 @@ int verify_locked(Ctx& c, Workspace* w, const bmqcrc_opts& o, uint32_t seg, bool
     const uint32_t* d_exp = expected;
     if (!dev_ptrs) {
         if ((!arena_staged && (rc = stage(c, w->arena, arena, arena_bytes))) ||
-            (rc = stage(c, w->offsets, offsets, 8 * n)) ||
+            (rc = stage(c, w->offsets, offsets, offsets_bytes(o.flags, n))) ||
             (rc = stage(c, w->lengths, lengths, 4 * n)) ||
             (rc = stage(c, w->expected, expected, 4 * n))) {
             return rc;
@@ -837,7 +929,7 @@ int verify_locked(Ctx& c, Workspace* w, const bmqcrc_opts& o, uint32_t seg, bool
     }
     if ((rc = run_batch(c, o.flags, seg, d_arena, arena_bytes, d_off, d_len, nullptr,
                         (uint32_t*)w->out.p, n,
-                        dev_ptrs ? UINT64_MAX : max_length(lengths, n)))) {
+                        dev_ptrs ? UINT64_MAX : max_length(lengths, n), 0, o.offset_shift))) {
         return rc;
     }
     HIP_TRY(hipMemsetAsync(w->vcount.p, 0, 4, c.s));
@@ -942,13 +1034,16 @@ int verify_host_multi(const void* arena, uint64_t arena_bytes, bmqcrc_prepare_fn
             return fail(BMQCRC_EINVAL, "device ordinal out of range");
         }
     }
-    const uint64_t* off = nullptr;
+    const uint64_t* off64 = nullptr;
+    const uint32_t* off32 = nullptr;
     const uint32_t* len = nullptr;
     const uint32_t* exp = nullptr;
     uint64_t n = 0;
+    // the messages' offsets in the form `prepare` gives (both: the 32-bit one)
+    Offsets off = {nullptr, nullptr, o.offset_shift};
     if (have <= 0) {
         // no usable device: a malformed input is still reported first
-        const int prc = prepare(pctx, &off, &len, &exp, &n);
+        const int prc = prepare(pctx, &off64, &off32, &len, &exp, &n);
         if (prc || n == 0) {
             return prc;
         }
@@ -1013,6 +1108,23 @@ int verify_host_multi(const void* arena, uint64_t arena_bytes, bmqcrc_prepare_fn
                                   (const uint8_t*)arena + off[i] + len[i]);
                 }
             }
+            // The slice keeps the batch's offset form.  A range's offsets
+            // stay whole units of the shift from its cut (a multiple of 128);
+            // the gathered straddlers sit at any byte, so theirs are bytes.
+            bmqcrc_opts so = o;
+            std::vector<uint32_t> lo32;
+            if (off.p32 && (pass == 0 || packed.size() <= 0xFFFFFFFFull)) {
+                so.flags |= BMQCRC_F_OFFSETS32;
+                so.offset_shift = pass == 0 ? off.shift : 0u;
+                lo32.resize(lo.size());
+                for (size_t k = 0; k < lo.size(); ++k) {
+                    lo32[k] = (uint32_t)(lo[k] >> so.offset_shift);
+                }
+            } else {
+                so.flags &= ~BMQCRC_F_OFFSETS32;
+                so.offset_shift = 0;
+            }
+            const uint64_t* lop = lo32.empty() ? lo.data() : (const uint64_t*)lo32.data();
             if (gi.empty()) {
                 continue;
             }
@@ -1024,13 +1136,14 @@ int verify_host_multi(const void* arena, uint64_t arena_bytes, bmqcrc_prepare_fn
             if (crcs) {
                 std::vector<uint32_t> part(m);
                 if ((!staged && (rc = stage(c, c.w->arena, abase, abytes))) ||
-                    (rc = stage(c, c.w->offsets, lo.data(), 8 * m)) ||
+                    (rc = stage(c, c.w->offsets, lop, offsets_bytes(so.flags, m))) ||
                     (rc = stage(c, c.w->lengths, ll.data(), 4 * m)) ||
                     (rc = c.w->out.ensure(4 * m)) ||
-                    (rc = run_batch(c, o.flags, seg, c.w->arena.p, abytes,
+                    (rc = run_batch(c, so.flags, seg, c.w->arena.p, abytes,
                                     (const uint64_t*)c.w->offsets.p,
                                     (const uint32_t*)c.w->lengths.p, nullptr,
-                                    (uint32_t*)c.w->out.p, m, max_length(ll.data(), m)))) {
+                                    (uint32_t*)c.w->out.p, m, max_length(ll.data(), m), 0,
+                                    so.offset_shift))) {
                     break;
                 }
                 if (hipMemcpyAsync(part.data(), c.w->out.p, 4 * m, hipMemcpyDeviceToHost, c.s) !=
@@ -1046,7 +1159,7 @@ int verify_host_multi(const void* arena, uint64_t arena_bytes, bmqcrc_prepare_fn
             }
             uint64_t nbad = 0, nw = 0;
             std::vector<uint64_t> lb(std::min<uint64_t>(bad_cap, m));
-            if ((rc = verify_locked(c, c.w, o, seg, staged, abase, abytes, lo.data(), ll.data(),
+            if ((rc = verify_locked(c, c.w, so, seg, staged, abase, abytes, lop, ll.data(),
                                     le.data(), m, &nbad, lb.data(), lb.size(), &nw))) {
                 break;
             }
@@ -1062,7 +1175,9 @@ int verify_host_multi(const void* arena, uint64_t arena_bytes, bmqcrc_prepare_fn
     for (uint32_t t = 0; t < nd; ++t) {
         th.emplace_back(slice, t);
     }
-    const int prc = prepare(pctx, &off, &len, &exp, &n);
+    const int prc = prepare(pctx, &off64, &off32, &len, &exp, &n);
+    off.p64 = off64;
+    off.p32 = off32;
     int rc = prc;
     if (!rc && n > 0xFFFFFFFFull) {
         rc = fail(BMQCRC_EINVAL, "at most 2^32-1 messages per batch");
@@ -1143,6 +1258,7 @@ int bmqcrc_verify_host_overlapped(const void* arena, uint64_t arena_bytes,
     uint32_t seg;
     int dev = 0, rc;
     const uint64_t* off = nullptr;
+    const uint32_t* off32 = nullptr;
     const uint32_t* len = nullptr;
     const uint32_t* exp = nullptr;
     uint64_t n = 0;
@@ -1161,7 +1277,7 @@ int bmqcrc_verify_host_overlapped(const void* arena, uint64_t arena_bytes,
     if (rc || (rc = open_ctx(dev, o.stream, &c))) {
         // no usable device: a malformed input is still reported first
         const std::string why = t_err;
-        const int prc = prepare(pctx, &off, &len, &exp, &n);
+        const int prc = prepare(pctx, &off, &off32, &len, &exp, &n);
         if (prc || n == 0) {  // nothing to verify needs no device
             return prc;
         }
@@ -1183,7 +1299,7 @@ int bmqcrc_verify_host_overlapped(const void* arena, uint64_t arena_bytes,
             src = BMQCRC_EIO;
         }
     });
-    const int prc = prepare(pctx, &off, &len, &exp, &n);
+    const int prc = prepare(pctx, &off, &off32, &len, &exp, &n);
     copier.join();
     if (prc) {
         return prc;
@@ -1197,13 +1313,17 @@ int bmqcrc_verify_host_overlapped(const void* arena, uint64_t arena_bytes,
     if (n > 0xFFFFFFFFull) {
         return fail(BMQCRC_EINVAL, "at most 2^32-1 messages per batch");
     }
-    if ((rc = check_ranges(off, len, n, arena_bytes))) {
+    if ((rc = check_ranges(Offsets{off, off32, 0u}, len, n, arena_bytes))) {
         return rc;
+    }
+    if (off32) {  // the walk wrote its offsets in 32 bits as well: hand the device those
+        o.flags |= BMQCRC_F_OFFSETS32;
+        off = (const uint64_t*)off32;
     }
     if (crcs) {  // compute: stage the descriptors, fold, copy the CRCs back
         crcs->assign(n, 0);
-        if ((rc = stage(c, w->offsets, off, 8 * n)) || (rc = stage(c, w->lengths, len, 4 * n)) ||
-            (rc = w->out.ensure(4 * n))) {
+        if ((rc = stage(c, w->offsets, off, offsets_bytes(o.flags, n))) ||
+            (rc = stage(c, w->lengths, len, 4 * n)) || (rc = w->out.ensure(4 * n))) {
             return rc;
         }
         if ((rc = run_batch(c, o.flags, seg, w->arena.p, arena_bytes,
@@ -1468,7 +1588,24 @@ int bmqcrc_crc32c_batch_multi(const void* arena, uint64_t arena_bytes, const uin
     if (n == 0) {
         return 0;
     }
-    if (ndev < 1 || !offsets || !lengths || !out || !arena) {
+    if (!offsets) {
+        return fail(BMQCRC_EINVAL, "bad arguments");
+    }
+    return batch_multi(arena, arena_bytes, Offsets{offsets, nullptr, 0u}, lengths, seeds, out, n,
+                       devices, ndev, seg_bytes);
+}
+
+}  // extern "C"
+
+namespace {
+
+// bmqcrc_crc32c_batch_multi over offsets of either form: a slice's offsets
+// keep the batch's form (32-bit ones are rebased in whole units of the shift).
+int batch_multi(const void* arena, uint64_t arena_bytes, Offsets offsets, const uint32_t* lengths,
+                const uint32_t* seeds, uint32_t* out, uint64_t n, const int* devices, int ndev,
+                uint32_t seg_bytes)
+{
+    if (ndev < 1 || !lengths || !out || !arena) {
         return fail(BMQCRC_EINVAL, "bad arguments");
     }
     uint32_t seg = seg_bytes;
@@ -1525,6 +1662,20 @@ int bmqcrc_crc32c_batch_multi(const void* arena, uint64_t arena_bytes, const uin
             if (amin > amax) {
                 amin = amax = 0;
             }
+            if (offsets.p32) {
+                std::vector<uint32_t> rel32(hi - lo);
+                const uint32_t base = (uint32_t)(amin >> offsets.shift);  // amin is one of them
+                for (uint64_t i = lo; i < hi; ++i) {
+                    rel32[i - lo] = offsets.p32[i] - base;
+                }
+                rcs[d] = batch_one(devs[d], nullptr, BMQCRC_F_OFFSETS32, seg,
+                                   (const uint8_t*)arena + amin, amax - amin,
+                                   (const uint64_t*)rel32.data(), lengths + lo,
+                                   seeds ? seeds + lo : nullptr, out + lo, hi - lo, 0, 0,
+                                   offsets.shift);
+                errs[d] = t_err;
+                return;
+            }
             std::vector<uint64_t> rel(hi - lo);
             for (uint64_t i = lo; i < hi; ++i) {
                 rel[i - lo] = offsets[i] - amin;
@@ -1545,6 +1696,10 @@ int bmqcrc_crc32c_batch_multi(const void* arena, uint64_t arena_bytes, const uin
     }
     return 0;
 }
+
+}  // namespace
+
+extern "C" {
 
 int bmqcrc_reserve(int device, void* stream, uint64_t n_msgs, uint64_t arena_bytes,
                    uint32_t seg_bytes)
@@ -1573,6 +1728,10 @@ int bmqcrc_fill_synthetic(void* dev_dst, uint64_t nbytes, uint64_t seed, uint64_
 {
     t_err.clear();
     DeviceGuard keep_device;
+    if (opts && (opts->flags & BMQCRC_F_OFFSETS32)) {
+        return fail(BMQCRC_EINVAL,
+                    "BMQCRC_F_OFFSETS32 applies to bmqcrc_crc32c_batch and bmqcrc_crc32c_verify only");
+    }
     int dev, rc;
     if ((rc = resolve_device(opts ? opts->device : -1, &dev))) {
         return rc;
@@ -1661,6 +1820,25 @@ int bmqcrc_last_plan(int device, void* stream, uint32_t* map)
     std::lock_guard<std::mutex> g(w->mu);
     if (map) {
         *map = w->last_map;
+    }
+    return 0;
+}
+
+int bmqcrc_last_offsets(int device, void* stream, uint32_t* bits, uint32_t* shift)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    int dev, rc;
+    if ((rc = resolve_device(device, &dev))) {
+        return rc;
+    }
+    Workspace* w = workspace(dev, stream);
+    std::lock_guard<std::mutex> g(w->mu);
+    if (bits) {
+        *bits = w->last_off_bits;
+    }
+    if (shift) {
+        *shift = w->last_off_shift;
     }
     return 0;
 }
@@ -1782,7 +1960,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 7u;
+    return (2u << 16) | 8u;
 }
 
 }  // extern "C"

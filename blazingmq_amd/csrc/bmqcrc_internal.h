@@ -1,5 +1,6 @@
 // bmqcrc_internal.h -- shared between the host dispatcher and the HIP kernels.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace bmqcrc {
@@ -98,6 +99,7 @@ struct BatchArgs {
     unsigned long long* plan_sync;
     uint32_t plan_epoch;       // k_plan_map launch tag on this workspace, in [1, 2^31); 0: the
                                // tag is plan_sync[1], advanced on the device (graph capture)
+    uint32_t off32;            // 1: 32-bit offsets; the launcher picks the kernels compiled for them
     uint64_t map_wait_ticks;   // k_plan_map's grid-wide wait limit (100 MHz wall clock)
     uint32_t class_desc;       // k_plan_map: size classes in descending order (short schedules)
     // 1: plan this ragged batch with the meeting-free pair k_plan<true> +
@@ -109,7 +111,20 @@ struct BatchArgs {
     // for claim k) over every CU, instead of filling 4-wave blocks on a
     // quarter of them
     uint32_t spread;
+    // BMQCRC_F_OFFSETS32 (ABI 2.8, off32 above): `offsets` points at n
+    // uint32_t and message i starts at (uint64_t)offsets32[i] << off_shift
+    uint32_t off_shift;
 };
+
+// off_shift, appended, fills what was the struct's tail padding, and off32
+// (read by the launcher only) the padding after plan_epoch: no field moves,
+// and neither do the arguments the compiler places after the struct (grid and
+// block sizes), which a larger struct would push on in every kernel, the
+// 64-bit ones included.
+static_assert(sizeof(BatchArgs) == 200 && offsetof(BatchArgs, plan_epoch) == 168 &&
+                  offsetof(BatchArgs, off32) == 172 && offsetof(BatchArgs, map_wait_ticks) == 176 &&
+                  offsetof(BatchArgs, spread) == 192 && offsetof(BatchArgs, off_shift) == 196,
+              "BatchArgs: kernel argument offsets are fixed");
 
 // Ragged batches planned with the pair after k_fold reports a given-up map
 // on the workspace (shape_hint[1] = that launch's epoch), before the
@@ -147,8 +162,9 @@ constexpr uint32_t kHintIdentity = 3;  // one segment per message
 // Launchers (crc32c_kernels.hip).  All asynchronous on `stream`.
 extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_batch(const bmqcrc::BatchArgs* a, void* stream, int num_cus,
                                    void* ev_start, void* ev_stop);
-// k_plan_map blocks one CU holds at once (hipOccupancyMaxActiveBlocksPerMultiprocessor).
-extern "C" __attribute__((visibility("hidden"))) int bmqcrc_plan_map_occupancy(int* blocks_per_cu);
+// k_plan_map blocks one CU holds at once (hipOccupancyMaxActiveBlocksPerMultiprocessor),
+// of the kernel compiled for 64-bit (off32 = 0) or 32-bit offsets.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_plan_map_occupancy(int off32, int* blocks_per_cu);
 extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_compare(const uint32_t* got, const uint32_t* expected, uint64_t n,
                                      uint32_t* bad_count, uint32_t* bad_idx, uint32_t bad_cap,
                                      void* stream);
@@ -168,8 +184,11 @@ extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_compare_order
 // `prepare` runs on the calling thread while the arena is copied to the device
 // on a helper thread; it returns 0 and the (offset, length, expected CRC)
 // arrays of n messages, or a BMQCRC_E* code with the error already set.
-typedef int (*bmqcrc_prepare_fn)(void* ctx, const uint64_t** offsets, const uint32_t** lengths,
-                                 const uint32_t** expected, uint64_t* n);
+// *offsets32 is null, or the same offsets as uint32_t in units of
+// 1 << opts->offset_shift bytes (a walk over a buffer below 4 GiB writes
+// both, shift 0): the device is then handed those, 4 bytes per message.
+typedef int (*bmqcrc_prepare_fn)(void* ctx, const uint64_t** offsets, const uint32_t** offsets32,
+                                 const uint32_t** lengths, const uint32_t** expected, uint64_t* n);
 // `bad` receives the lowest min(*n_bad, bad_cap) mismatching indices, like
 // bmqcrc_crc32c_verify; *n_written (if non-null) = how many were written.
 // With `crcs` non-null the call computes instead of verifying: crcs = the n

@@ -46,9 +46,18 @@ struct Ranges {
     std::vector<uint32_t> len;
     std::vector<uint32_t> crc;
     std::vector<uint64_t> pos;  // CRC field position / record offset
+    // narrow: the walked buffer is below 4 GiB and its messages go to the
+    // device, which then takes their offsets as the uint32_t written here
+    // (BMQCRC_F_OFFSETS32, shift 0: 4 bytes per message less to stage and to
+    // read); the scan functions keep `off` alone
+    bool narrow = false;
+    std::vector<uint32_t> off32;
     void push(uint64_t o, uint32_t l, uint32_t c, uint64_t p)
     {
         off.push_back(o);
+        if (narrow) {
+            off32.push_back((uint32_t)o);
+        }
         len.push_back(l);
         crc.push_back(c);
         pos.push_back(p);
@@ -593,24 +602,29 @@ int64_t emit(const Ranges& r, uint64_t cap, uint64_t* off, uint32_t* len, uint32
     return (int64_t)n;
 }
 
-// Host-pointer options: the walks always hand the GPU host buffers.
+// Host-pointer options: the walks always hand the GPU host buffers.  A
+// caller's struct is read as the batch entry points read it (parse_opts):
+// struct_size bytes of it, the fields after them zero, and struct_size 0
+// the ABI 2.0 fields only -- a caller built against an earlier, shorter
+// bmqcrc_opts keeps working when the struct grows.
 int host_opts(const bmqcrc_opts* in, bmqcrc_opts* o)
 {
-    if (in && in->struct_size < sizeof(bmqcrc_opts)) {
-        return bmqcrc_set_error(BMQCRC_EINVAL, "opts->struct_size too small");
-    }
+    memset(o, 0, sizeof *o);
     if (in) {
-        *o = *in;
-    } else {
-        memset(o, 0, sizeof *o);
-        o->struct_size = sizeof *o;
+        const size_t given = in->struct_size ? in->struct_size : offsetof(bmqcrc_opts, ndevices);
+        memcpy(o, in, std::min<size_t>(sizeof *o, given));
     }
+    o->struct_size = sizeof *o;
     if (o->flags & (BMQCRC_F_DEVICE_PTRS | BMQCRC_F_ASYNC)) {
         return bmqcrc_set_error(BMQCRC_EINVAL,
                                 "protocol walks take host buffers (no DEVICE_PTRS/ASYNC)");
     }
     return 0;
 }
+
+// Buffers below this size are walked into 32-bit offsets for the device
+// (Ranges::narrow); a PUT event (at most 64 MiB) always is.
+constexpr uint64_t kNarrowBelow = 1ull << 32;
 
 // The walk of a verify call, run by bmqcrc_verify_host_overlapped while the
 // buffer is copied to the device.
@@ -620,8 +634,8 @@ struct Overlap {
     bool walked = false;  // the walk succeeded
 };
 
-int overlap_prepare(void* p, const uint64_t** off, const uint32_t** len, const uint32_t** exp,
-                    uint64_t* n)
+int overlap_prepare(void* p, const uint64_t** off, const uint32_t** off32, const uint32_t** len,
+                    const uint32_t** exp, uint64_t* n)
 {
     Overlap* o = (Overlap*)p;
     const int rc = o->walk(&o->r);
@@ -630,6 +644,7 @@ int overlap_prepare(void* p, const uint64_t** off, const uint32_t** len, const u
     }
     o->walked = true;
     *off = o->r.off.data();
+    *off32 = o->r.narrow ? o->r.off32.data() : nullptr;
     *len = o->r.len.data();
     *exp = o->r.crc.data();
     *n = o->r.off.size();
@@ -645,6 +660,7 @@ int verify_overlapped(const void* arena, uint64_t bytes, Overlap* ov, uint64_t* 
     if ((rc = host_opts(opts, &o))) {
         return rc;
     }
+    ov->r.narrow = bytes < kNarrowBelow;
     return bmqcrc_verify_host_overlapped(arena, bytes, overlap_prepare, ov, n_bad, bad, bad_cap,
                                          &o, nullptr, n_written);
 }
@@ -678,6 +694,7 @@ int64_t bmqcrc_put_event_fill_crcs(void* event, uint64_t len, const bmqcrc_opts*
     }
     Overlap ov;  // the event's copy to the device overlaps the walk
     ov.walk = [&](Ranges* r) { return walk_put_event((const uint8_t*)event, len, r); };
+    ov.r.narrow = len < kNarrowBelow;
     std::vector<uint32_t> out;
     if ((rc = bmqcrc_verify_host_overlapped(event, len, overlap_prepare, &ov, nullptr, nullptr, 0,
                                             &o, &out))) {

@@ -60,6 +60,16 @@ extern "C" {
  * (device, stream); see bmqcrc_last_launch.  What a caller whose batch shapes
  * alternate pays per batch. */
 #define BMQCRC_F_PLAN 0x10u
+/* ABI 2.8.  bmqcrc_crc32c_batch and bmqcrc_crc32c_verify only: `offsets`
+ * points at n uint32_t values instead of n uint64_t (host or device memory
+ * like the other arrays, by BMQCRC_F_DEVICE_PTRS), and message i starts at
+ * byte (uint64_t)offsets32[i] << opts->offset_shift.  8 bytes of descriptors
+ * per message instead of 12: what a PUT event (at most 64 MiB, shift 0) and
+ * a journal's DATA positions (u32 dwords, shift 2 after doubling) hold
+ * natively.  Results equal the 64-bit call's.  Every other entry point
+ * returns BMQCRC_EINVAL with this flag; the format walks of bmqcrc_protocol.h
+ * choose the form themselves (32 bits for a buffer below 4 GiB). */
+#define BMQCRC_F_OFFSETS32 0x20u
 
 typedef struct bmqcrc_opts {
     uint32_t struct_size; /* sizeof(bmqcrc_opts); 0 reads the ABI 2.0 fields only (device,
@@ -103,6 +113,14 @@ typedef struct bmqcrc_opts {
      * the batch is likewise one launch (the speculative uniform form, known
      * instead of guessed); a message outside the range stays exact. */
     uint32_t min_len;
+    /* ABI 2.8.  With BMQCRC_F_OFFSETS32: the unit of the 32-bit offsets is
+     * 1 << offset_shift bytes, offset_shift in [0, 7] (2: 4-byte aligned
+     * payloads anywhere in 16 GiB).  The shift is done in 64 bits, and a
+     * host-pointer call checks (offsets32[i] << offset_shift) + lengths[i] <=
+     * arena_bytes in 64 bits too.  Non-zero without the flag, or above 7, is
+     * BMQCRC_EINVAL.  Callers built against ABI <= 2.7 (smaller struct_size),
+     * or whose struct_size ends before this field, get 0. */
+    uint32_t offset_shift;
 } bmqcrc_opts;
 
 /* ---- scalar (host CPU) -------------------------------------------------- */
@@ -121,7 +139,7 @@ uint32_t bmqcrc_combine(uint32_t crcA, uint32_t crcB, uint64_t lenB);
 /* ---- batch (MI355X) ----------------------------------------------------- */
 
 /* out[i] = calculate(arena + offsets[i], lengths[i], seeds ? seeds[i] : 0)
- * for i < n.  Messages may sit anywhere in [arena, arena + arena_bytes) at any
+ * for i < n (with BMQCRC_F_OFFSETS32, `offsets` is n uint32_t, see the flag).  Messages may sit anywhere in [arena, arena + arena_bytes) at any
  * byte alignment and may overlap.  With BMQCRC_F_DEVICE_PTRS all five arrays
  * are device memory of opts->device (inputs "device resident"); otherwise they
  * are host memory and the library stages them through HBM.  Returns 0,
@@ -203,8 +221,17 @@ int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* sp
  * size-class map built (*map = 1: k_plan_map, or k_plan + k_plan_sort) or
  * was planned by the light k_plan alone, whose fold searches the
  * per-message segment offsets (*map = 0; also for single-launch batches).
- * A batch captured into a graph always gets the map. */
+ * A batch captured into a graph always gets the map.
+ * This is the host's planning decision at launch, not what became of it on
+ * the device: a map that k_plan_map gave up (bmqcrc_plan_wait) still reads
+ * *map = 1 here; bmqcrc_plan_wait's *voided counts those. */
 int bmqcrc_last_plan(int device, void* stream, uint32_t* map);
+
+/* ABI 2.8.  Offset form of the previous batch CRC'd on (device, stream):
+ * *bits = 64, or 32 for BMQCRC_F_OFFSETS32 (also when a format walk chose
+ * it), *shift = its offset_shift (0 with 64-bit offsets).  64 and 0 before
+ * the first batch.  Either pointer may be NULL. */
+int bmqcrc_last_offsets(int device, void* stream, uint32_t* bits, uint32_t* shift);
 
 /* ABI 2.2.  Drop the batch-shape prediction of (device, stream): the next
  * batch there is planned (k_plan runs) instead of being launched on the guess
@@ -256,7 +283,7 @@ const char* bmqcrc_last_error(void);
 void bmqcrc_note_host_fallback(int32_t rc);
 uint64_t bmqcrc_host_fallbacks(int32_t* last_rc);
 
-/* ABI version: (major << 16) | minor (2.6). */
+/* ABI version: (major << 16) | minor (2.8). */
 uint32_t bmqcrc_version(void);
 
 #ifdef __cplusplus
