@@ -87,6 +87,13 @@ lib.bmqcrc_last_launch.argtypes = [_int, _vp, ctypes.POINTER(_u32), ctypes.POINT
 if hasattr(lib, "bmqcrc_last_offsets"):  # ABI 2.8 (an older build loads for same-box A/B)
     lib.bmqcrc_last_offsets.restype = _int
     lib.bmqcrc_last_offsets.argtypes = [_int, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]
+if hasattr(lib, "bmqcrc_crc32c_copy"):  # ABI 2.9 (an older build loads for same-box A/B)
+    lib.bmqcrc_crc32c_copy.restype = _int
+    lib.bmqcrc_crc32c_copy.argtypes = [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64,
+                                       ctypes.POINTER(Opts)]
+    lib.bmqcrc_last_copy.restype = _int
+    lib.bmqcrc_last_copy.argtypes = [_int, _vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                     ctypes.POINTER(_u64)]
 lib.bmqcrc_forget_shape.restype = _int
 lib.bmqcrc_forget_shape.argtypes = [_int, _vp]
 if hasattr(lib, "bmqcrc_plan_wait"):  # ABI 2.3 (an older build loads for same-box A/B)

@@ -5,6 +5,8 @@ MI355X entry point.
     Crc32c.calculate(data, crc=Crc32c.k_NULL_CRC32C)      -> int   (CPU, like the reference)
     Crc32c.calculate_blob(blob, crc=...)                    -> int   (CPU, bmqp_crc32c.cpp:47-67)
     Crc32c.calculate_batch(arena, offsets, lengths, seeds)  -> out   (GPU only)
+    Crc32c.copy_batch(src, src_offsets, lengths, dst, dst_offsets, seeds) -> out
+                                                            (GPU only, device tensors only)
 
 ``calculate_batch`` accepts torch tensors resident on an MI355X (no copies;
 enqueued on torch's current stream) or host buffers (numpy / bytes), which the
@@ -149,6 +151,60 @@ class Crc32c:
                                 offset_shift)
         return _batch_host(arena, offsets, lengths, seeds, out, seg_bytes, device,
                            whole_messages, devices, offset_shift)
+
+    @staticmethod
+    def copy_batch(src, src_offsets, lengths, dst, dst_offsets, seeds=None, out=None, *,
+                   stream=None, sync=True):
+        """Fused copy and CRC32-C (bmqcrc_crc32c_copy): for every i, copy
+        ``lengths[i]`` bytes from ``src[src_offsets[i]:]`` to
+        ``dst[dst_offsets[i]:]`` and return ``out`` with their CRCs chained
+        from ``seeds`` -- one pass over the payload.
+
+        Device tensors only, all on one MI355X: ``src`` / ``dst`` uint8,
+        offsets int64, ``lengths`` / ``seeds`` / ``out`` int32 (read as u32),
+        contiguous.  ``dst`` may be ``src`` itself; destination ranges must
+        not overlap each other or any source range of the call.  A message
+        outside ``src`` or ``dst`` is refused on the device (not copied, its
+        ``out`` left unwritten): with ``sync=True`` that raises
+        ``BmqCrcError`` (BMQCRC_EINVAL) naming the lowest such index after
+        the other messages were copied; with ``sync=False`` ask
+        ``last_copy``.  Not meant to be captured into a graph."""
+        import torch
+        n = src_offsets.numel() if isinstance(src_offsets, torch.Tensor) else -1
+        for name, t, dt in (("src", src, torch.uint8), ("dst", dst, torch.uint8),
+                            ("src_offsets", src_offsets, torch.int64),
+                            ("dst_offsets", dst_offsets, torch.int64),
+                            ("lengths", lengths, torch.int32)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous()):
+                raise TypeError("%s must be a contiguous %s tensor" % (name, dt))
+        if lengths.numel() != n or dst_offsets.numel() != n:
+            raise ValueError("src_offsets/dst_offsets/lengths size mismatch")
+        dev = src.device
+        if seeds is not None and not _is_vec(torch, seeds, dev, torch.int32, n):
+            raise TypeError("seeds must be a contiguous int32 tensor of %d elements on %s"
+                            % (n, dev))
+        if out is not None and not _is_vec(torch, out, dev, torch.int32, n):
+            raise TypeError("out must be a contiguous int32 tensor of %d elements on %s"
+                            % (n, dev))
+        if not src.is_cuda:
+            raise TypeError("copy_batch takes device tensors only (src is on %s)" % dev)
+        for name, t in (("dst", dst), ("src_offsets", src_offsets),
+                        ("dst_offsets", dst_offsets), ("lengths", lengths)):
+            if t.device != dev:
+                raise TypeError("%s must be on %s like src" % (name, dev))
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        flags = _native.BMQCRC_F_DEVICE_PTRS | (0 if sync else _native.BMQCRC_F_ASYNC)
+        o = _native.make_opts(device=dev.index if dev.index is not None else -1,
+                              stream=stream.cuda_stream, flags=flags)
+        _native.check(_native.lib.bmqcrc_crc32c_copy(
+            src.data_ptr(), src.numel(), src_offsets.data_ptr(), lengths.data_ptr(),
+            dst.data_ptr(), dst.numel(), dst_offsets.data_ptr(),
+            seeds.data_ptr() if seeds is not None else None, out.data_ptr(), n,
+            ctypes.byref(o)))
+        return out
 
 
 def _check_shift(torch, offsets, offset_shift):
@@ -403,6 +459,18 @@ def last_offsets(device, stream=None):
         device, stream.cuda_stream if stream is not None else None, ctypes.byref(bits),
         ctypes.byref(sh)))
     return bits.value, sh.value
+
+
+def last_copy(device, stream=None):
+    """(n_msgs, n_refused, first_refused) of the previous ``Crc32c.copy_batch``
+    on (device, stream) (bmqcrc_last_copy); waits for it.  ``first_refused`` is
+    the lowest refused index, n_msgs when nothing was refused.  ``stream=None``
+    is the device's default stream."""
+    n, r, f = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    _native.check(_native.lib.bmqcrc_last_copy(
+        device, stream.cuda_stream if stream is not None else None, ctypes.byref(n),
+        ctypes.byref(r), ctypes.byref(f)))
+    return n.value, r.value, f.value
 
 
 def forget_shape(device, stream):

@@ -126,6 +126,11 @@ struct Workspace {
     // Given-up planner maps (hint_host[1], written by k_fold): the last epoch
     // seen, and how many more ragged batches take the meeting-free pair.
     uint32_t void_seen = 0, pair_left = 0;
+    // bmqcrc_crc32c_copy: its own scratch (piece prefix, block sums, counters)
+    // and the size of the last copy enqueued here (bmqcrc_last_copy)
+    DevBuf copy_first, copy_bsum, copy_ctr;
+    uint64_t copy_n = 0;
+    bool copy_any = false;
     // Pinned staging ring for gathered host buffers (bmqcrc_crc32c_gather):
     // kGatherSlots chunks of kGatherChunk bytes, each reusable once the event
     // recorded after its H2D copy has completed.
@@ -162,6 +167,7 @@ struct DeviceState {
     // part gets fewer, fuller blocks instead of a wait that must give up)
     // ([1]: of the kernel compiled for 32-bit offsets, which is launched then)
     uint32_t plan_resident[2] = {kPlanMaxBlocks, kPlanMaxBlocks};
+    uint32_t copy_blocks = 0;  // k_copy_fold's persistent grid (occupancy x CUs), set on first use
 };
 
 std::mutex g_mu;
@@ -1785,6 +1791,165 @@ int bmqcrc_kernel_timing(int device, void* stream, double* total_ms, uint32_t* c
     return 0;
 }
 
+// Counters of the copy last enqueued on c's workspace, after everything
+// enqueued on its stream (w->mu held).
+static int copy_result(Ctx& c, unsigned long long (&ctr)[kCopyCtrWords])
+{
+    HIP_TRY(hipMemcpyAsync(ctr, c.w->copy_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    return 0;
+}
+
+int bmqcrc_crc32c_copy(const void* src, uint64_t src_bytes, const uint64_t* src_offsets,
+                       const uint32_t* lengths, void* dst, uint64_t dst_bytes,
+                       const uint64_t* dst_offsets, const uint32_t* seeds, uint32_t* out,
+                       uint64_t n, const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    bmqcrc_opts o;
+    memset(&o, 0, sizeof(o));
+    o.device = -1;
+    if (opts) {
+        const size_t given = opts->struct_size ? opts->struct_size : offsetof(bmqcrc_opts, ndevices);
+        memcpy(&o, opts, std::min<size_t>(sizeof(o), given));
+    }
+    static const struct {
+        uint32_t bit;
+        const char* name;
+    } refused[] = {{BMQCRC_F_TIME_KERNEL, "BMQCRC_F_TIME_KERNEL"},
+                   {BMQCRC_F_WHOLE_MESSAGES, "BMQCRC_F_WHOLE_MESSAGES"},
+                   {BMQCRC_F_PLAN, "BMQCRC_F_PLAN"},
+                   {BMQCRC_F_OFFSETS32, "BMQCRC_F_OFFSETS32"}};
+    for (const auto& r : refused) {
+        if (o.flags & r.bit) {
+            return fail(BMQCRC_EINVAL, std::string(r.name) + " does not apply to bmqcrc_crc32c_copy");
+        }
+    }
+    if (o.flags & ~(BMQCRC_F_DEVICE_PTRS | BMQCRC_F_ASYNC)) {
+        return fail(BMQCRC_EINVAL, "unknown bmqcrc_opts.flags bits");
+    }
+    if (!(o.flags & BMQCRC_F_DEVICE_PTRS)) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_crc32c_copy takes device pointers only: "
+                                   "BMQCRC_F_DEVICE_PTRS is required");
+    }
+    if (o.ndevices > 1) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_crc32c_copy runs on one device: ndevices > 1");
+    }
+    if (n > 0xFFFFFFFFull) {
+        return fail(BMQCRC_EINVAL, "at most 2^32-1 messages per batch");
+    }
+    if (n && (!src_offsets || !lengths || !dst_offsets || !out || (!src && src_bytes) ||
+              (!dst && dst_bytes))) {
+        return fail(BMQCRC_EINVAL, "null pointer argument");
+    }
+    int dev, rc;
+    if ((rc = resolve_device(o.device, &dev))) {
+        return rc;
+    }
+    Ctx c;
+    if ((rc = open_ctx(dev, o.stream, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    std::lock_guard<std::mutex> g(w->mu);
+    if ((rc = w->copy_ctr.ensure(8 * kCopyCtrWords)) ||
+        (rc = w->copy_bsum.ensure(8ull * kCopyPlanBlocks)) ||
+        (rc = w->copy_first.ensure(4 * (n + 1)))) {
+        return rc;
+    }
+    {
+        std::lock_guard<std::mutex> gd(g_mu);  // DeviceState is shared by the device's streams
+        if (c.st->copy_blocks == 0) {
+            int per = 0;
+            if (bmqcrc_copy_occupancy(&per) != 0 || per <= 0) {
+                return fail(BMQCRC_EIO, "k_copy_fold occupancy query failed");
+            }
+            c.st->copy_blocks = (uint32_t)per * (uint32_t)std::max(c.st->num_cus, 1);
+        }
+    }
+    HIP_TRY(hipMemsetAsync(w->copy_ctr.p, 0, 8 * kCopyCtrWords, c.s));
+    w->copy_n = n;
+    w->copy_any = true;
+    if (n) {
+        CopyArgs a;
+        memset(&a, 0, sizeof(a));
+        a.src = (const uint8_t*)src;
+        a.src_bytes = src_bytes;
+        a.src_offsets = src_offsets;
+        a.lengths = lengths;
+        a.dst = (uint8_t*)dst;
+        a.dst_bytes = dst_bytes;
+        a.dst_offsets = dst_offsets;
+        a.seeds = seeds;
+        a.out = out;
+        a.n = n;
+        a.first = (uint32_t*)w->copy_first.p;
+        a.bsum = (unsigned long long*)w->copy_bsum.p;
+        a.ctr = (unsigned long long*)w->copy_ctr.p;
+        const uint64_t tiles = (n + kCopyPlanThreads - 1) / kCopyPlanThreads;
+        const uint64_t nb = std::min<uint64_t>(tiles, kCopyPlanBlocks);
+        const uint64_t tiles_per = (tiles + nb - 1) / nb;
+        a.per_block = tiles_per * kCopyPlanThreads;
+        a.nblocks = (uint32_t)((tiles + tiles_per - 1) / tiles_per);
+        if (bmqcrc_launch_copy(&a, (void*)c.s, c.st->copy_blocks)) {
+            return fail(BMQCRC_EIO, std::string("copy launch failed: ") +
+                                        hipGetErrorString(hipGetLastError()));
+        }
+    }
+    if (o.flags & BMQCRC_F_ASYNC) {
+        return 0;
+    }
+    unsigned long long ctr[kCopyCtrWords];
+    if ((rc = copy_result(c, ctr))) {
+        return rc;
+    }
+    if (ctr[kCopyCtrOverflow]) {
+        return fail(BMQCRC_EINVAL, "more than 2^32-1 16-byte pieces in one copy call: nothing copied");
+    }
+    if (ctr[kCopyCtrRefused]) {
+        return fail(BMQCRC_EINVAL,
+                    "message " + std::to_string(~ctr[kCopyCtrLowestInv]) + " lies outside [src, src+"
+                    "src_bytes) or [dst, dst+dst_bytes): refused (" +
+                        std::to_string(ctr[kCopyCtrRefused]) + " in all), the others were copied");
+    }
+    return 0;
+}
+
+int bmqcrc_last_copy(int device, void* stream, uint64_t* n_msgs, uint64_t* n_refused,
+                     uint64_t* first_refused)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    int dev, rc;
+    if ((rc = resolve_device(device, &dev))) {
+        return rc;
+    }
+    Ctx c;
+    if ((rc = open_ctx(dev, stream, &c))) {
+        return rc;
+    }
+    std::lock_guard<std::mutex> g(c.w->mu);
+    unsigned long long ctr[kCopyCtrWords] = {};
+    if (c.w->copy_any && (rc = copy_result(c, ctr))) {
+        return rc;
+    }
+    if (ctr[kCopyCtrOverflow]) {
+        return fail(BMQCRC_EINVAL, "more than 2^32-1 16-byte pieces in one copy call: nothing copied");
+    }
+    if (n_msgs) {
+        *n_msgs = c.w->copy_n;
+    }
+    if (n_refused) {
+        *n_refused = ctr[kCopyCtrRefused];
+    }
+    if (first_refused) {
+        *first_refused = ctr[kCopyCtrRefused] ? ~ctr[kCopyCtrLowestInv] : c.w->copy_n;
+    }
+    return 0;
+}
+
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,
                        uint32_t* seg_bytes)
 {
@@ -1960,7 +2125,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 8u;
+    return (2u << 16) | 9u;
 }
 
 }  // extern "C"

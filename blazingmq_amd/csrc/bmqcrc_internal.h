@@ -157,7 +157,43 @@ constexpr uint32_t kHintClosed = 1;  // uniform segment counts (> 1); | (u << 8)
 constexpr uint32_t kHintRagged = 2;
 constexpr uint32_t kHintIdentity = 3;  // one segment per message
 
+// ---- bmqcrc_crc32c_copy (crc32c_copy.hip, ABI 2.9) -------------------------
+constexpr int kCopyWaves = 4;                  // k_copy_fold: waves per block
+constexpr uint32_t kCopyChunkPieces = 4096;    // a wave's unit of work: 64 KiB of 16-byte pieces
+constexpr uint32_t kCopyChunkBytes = 16 * kCopyChunkPieces;
+constexpr int kCopyPlanThreads = 1024;         // k_copy_count / k_copy_scan block
+constexpr uint32_t kCopyPlanBlocks = 256;      // their grid: contiguous message ranges, at most
+// CopyArgs::ctr words
+constexpr int kCopyCtrRefused = 0;    // messages refused (out of [src, src+src_bytes) or dst's)
+constexpr int kCopyCtrLowestInv = 1;  // ~(lowest refused index), 0: none
+constexpr int kCopyCtrOverflow = 2;   // 1: more than 2^32-1 pieces, nothing copied
+constexpr int kCopyCtrWords = 4;
+
+struct CopyArgs {
+    const uint8_t* src;           // device
+    uint64_t src_bytes;
+    const uint64_t* src_offsets;  // device, n
+    const uint32_t* lengths;      // device, n
+    uint8_t* dst;                 // device
+    uint64_t dst_bytes;
+    const uint64_t* dst_offsets;  // device, n
+    const uint32_t* seeds;        // device, n, or nullptr (all zero)
+    uint32_t* out;                // device, n
+    uint64_t n;
+    uint32_t* first;              // workspace, n + 1: exclusive prefix of piece counts
+    unsigned long long* bsum;     // workspace, kCopyPlanBlocks: pieces per pre-kernel block
+    unsigned long long* ctr;      // workspace, kCopyCtrWords, zeroed before the launch
+    uint64_t per_block;           // messages per pre-kernel block (multiple of kCopyPlanThreads)
+    uint32_t nblocks;             // pre-kernel blocks (<= kCopyPlanBlocks)
+};
+
 }  // namespace bmqcrc
+
+// Launchers (crc32c_copy.hip).  Asynchronous on `stream`.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_copy(const bmqcrc::CopyArgs* a, void* stream,
+                                  uint32_t fold_blocks);
+// k_copy_fold blocks one CU holds at once: its persistent grid is that times the CUs.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_copy_occupancy(int* blocks_per_cu);
 
 // Launchers (crc32c_kernels.hip).  All asynchronous on `stream`.
 extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_batch(const bmqcrc::BatchArgs* a, void* stream, int num_cus,

@@ -15,6 +15,10 @@
  *                        and FileStore::recoverMessages
  *                        (src/groups/mqb/mqbs/mqbs_filestore.cpp:2603-2624);
  *                        one call CRCs a whole batch on an MI355X.
+ *   bmqcrc_crc32c_copy   the append-and-CRC of PutEventBuilder::packMessage and the
+ *                        payload copy of FileStore::writeMessageRecord
+ *                        (src/groups/mqb/mqbs/mqbs_filestore.cpp:5715-5721), for
+ *                        a device-resident batch, in one pass.
  *   bmqcrc_combine       GF(2) shift-combine crc(A||B) from crc(A), crc(B), |B|
  *                        (used to stitch segments; no reference equivalent).
  *
@@ -184,6 +188,59 @@ int bmqcrc_crc32c_gather(const void* const* bufs, const uint32_t* buf_lengths, u
                          const uint64_t* msg_first_buf, const uint32_t* seeds, uint32_t* out,
                          uint64_t n, const bmqcrc_opts* opts);
 
+/* ABI 2.9.  Fused copy and CRC.  For i < n: copy lengths[i] bytes from
+ * src + src_offsets[i] to dst + dst_offsets[i], and out[i] = calculate(those
+ * bytes, lengths[i], seeds ? seeds[i] : 0).  One pass: every payload byte is
+ * read once and written once -- what PutEventBuilder::packMessage
+ * (bmqp_puteventbuilder.cpp:302-320,400-413) and FileStore::writeMessageRecord
+ * (mqbs_filestore.cpp:5715-5721) do per message; comparing `out` with the
+ * header CRCs gives the writer "verify on write" for the price of the copy.
+ *
+ * Device pointers only.  All seven arrays are device memory of opts->device
+ *   and BMQCRC_F_DEVICE_PTRS is required; BMQCRC_F_ASYNC is allowed.  Any
+ *   other flag (BMQCRC_F_WHOLE_MESSAGES, _PLAN, _TIME_KERNEL, _OFFSETS32),
+ *   ndevices > 1 or a missing BMQCRC_F_DEVICE_PTRS is BMQCRC_EINVAL with a
+ *   message naming it, answered before the device lookup.  seg_bytes, max_len
+ *   and min_len are ignored.  Host-resident callers keep bmqcrc_crc32c_gather.
+ * Byte-exact destination.  Bytes of dst outside the n destination ranges are
+ *   never written and never read; two destination ranges may touch at any
+ *   byte position.  A message of length 0 writes nothing and out[i] is its
+ *   seed.
+ * Overlap.  Source ranges may overlap each other (one payload to two places),
+ *   and dst may be the same allocation as src (compaction in place).
+ *   Behaviour is undefined if a destination range overlaps another
+ *   destination range or any source range of the same call: the offsets live
+ *   on the device, the library cannot see them.
+ * Bounds are enforced on the device.  A message with src_offsets[i] +
+ *   lengths[i] > src_bytes or dst_offsets[i] + lengths[i] > dst_bytes (sums in
+ *   64 bits) is refused: nothing of it is read or written and out[i] is left
+ *   unwritten.  A synchronous call that refused any message returns
+ *   BMQCRC_EINVAL naming the lowest refused index; the messages in range are
+ *   still copied and checksummed.  After an asynchronous call
+ *   bmqcrc_last_copy reports the count and the lowest index.  One call holds
+ *   at most 2^32-1 16-byte pieces of destination (about 64 GiB); beyond that
+ *   nothing is copied and the call (or bmqcrc_last_copy) is BMQCRC_EINVAL.
+ * State.  The call leaves the shape prediction, bmqcrc_last_launch,
+ *   bmqcrc_last_plan and bmqcrc_last_offsets of its (device, stream) as they
+ *   were, takes that workspace's mutex like a batch call, and restores the
+ *   calling thread's current device.
+ * Limits of this version.  It allocates its own workspace on first use and
+ *   when n grows (4 bytes per message and a few counters); bmqcrc_reserve
+ *   does not cover it, and it is not meant to be captured into a hipGraph.
+ *   Results are deterministic.  n == 0 copies nothing (bmqcrc_last_copy then
+ *   reports 0 messages). */
+int bmqcrc_crc32c_copy(const void* src, uint64_t src_bytes, const uint64_t* src_offsets,
+                       const uint32_t* lengths, void* dst, uint64_t dst_bytes,
+                       const uint64_t* dst_offsets, const uint32_t* seeds, uint32_t* out,
+                       uint64_t n, const bmqcrc_opts* opts);
+
+/* ABI 2.9.  Result of the previous bmqcrc_crc32c_copy on (device, stream);
+ * waits for it.  *n_msgs = its n, *n_refused = how many messages it refused,
+ * *first_refused = the lowest refused index (n when none was refused).  All
+ * zero before the first copy there.  Any pointer may be NULL. */
+int bmqcrc_last_copy(int device, void* stream, uint64_t* n_msgs, uint64_t* n_refused,
+                     uint64_t* first_refused);
+
 /* Host-pointer batch sharded over `ndev` devices: messages are split into
  * contiguous byte-balanced slices, one per device, each on its own stream,
  * with no inter-device communication.  devices==NULL means 0..ndev-1. */
@@ -283,7 +340,7 @@ const char* bmqcrc_last_error(void);
 void bmqcrc_note_host_fallback(int32_t rc);
 uint64_t bmqcrc_host_fallbacks(int32_t* last_rc);
 
-/* ABI version: (major << 16) | minor (2.8). */
+/* ABI version: (major << 16) | minor (2.9). */
 uint32_t bmqcrc_version(void);
 
 #ifdef __cplusplus

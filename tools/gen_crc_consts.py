@@ -27,6 +27,9 @@ Constants produced:
 * ``RTAB11[6144]``: the same reduction in three 11/11/10-bit slices (one word
   per step, two 16-word chains) plus the byte tables of the join by y^16,
   for the 8-wave blocks: 3 lookups per word instead of 4.
+* ``XROW[4][256]``: byte-sliced "multiply by x^(8 * 1024)", the constant of
+  the per-lane Horner over 1 KiB rows in the fused copy kernel
+  (crc32c_copy.hip); appended after every older table.
 """
 import os
 import sys
@@ -34,6 +37,7 @@ import sys
 P_NORMAL = (1 << 32) | 0x1EDC6F41
 POLY_R = 0x82F63B78
 ORD = (1 << 31) - 1
+COPY_ROW_BYTES = 1024  # one wave-wide dwordx4 access of the fused copy kernel
 
 
 def pmod(a, m):
@@ -125,6 +129,31 @@ def remainder_tables11():
     return t11
 
 
+def xpow_r(e):
+    """x^e mod P (reflected), e >= 0."""
+    r, sq = 1 << 31, 1 << 30
+    e %= ORD
+    while e:
+        if e & 1:
+            r = mulmod_r(r, sq)
+        sq = mulmod_r(sq, sq)
+        e >>= 1
+    return r
+
+
+def row_tables():
+    """XROW[k][b] = (b << 8k) * x^(8 * COPY_ROW_BYTES): a word w of row r is
+    carried to row r + 1 by XROW[0][w & 255] ^ ... ^ XROW[3][w >> 24]."""
+    xr = xpow_r(8 * COPY_ROW_BYTES)
+    tab = [[mulmod_r(b << (8 * k), xr) for b in range(256)] for k in range(4)]
+    for v in (0, 1, 0x80000000, 0xdeadbeef, 0xffffffff):
+        got = 0
+        for k in range(4):
+            got ^= tab[k][(v >> (8 * k)) & 0xff]
+        assert got == mulmod_r(v, xr)
+    return tab
+
+
 def main(out_path):
     # P = (x+1) * Q31, Q31 primitive (2^31-1 is prime) -> ord(x) = 2^31-1.
     assert pmod(P_NORMAL, 0b11) == 0
@@ -172,6 +201,7 @@ def main(out_path):
     ty = [[mulmod_r(b << (8 * (k % 4)), x32_r if k < 4 else y2_r) for b in range(256)]
           for k in range(8)]
     t11 = remainder_tables11()
+    xrow = row_tables()
     with open(out_path, "w") as f:
         f.write("// GENERATED by tools/gen_crc_consts.py -- do not edit.\n")
         f.write("#pragma once\n#include <stdint.h>\n\n")
@@ -202,6 +232,12 @@ def main(out_path):
         for i in range(0, 6144, 8):
             f.write("  %s%s \\\n" % (", ".join("0x%08xu" % c for c in t11[i:i + 8]),
                                     "," if i + 8 < 6144 else ""))
+        f.write("}\n")
+        f.write("\n// copy kernel row step: [k][b] = (b << 8*k) * x^(8 * BMQCRC_COPY_ROW_BYTES) mod P\n")
+        f.write("#define BMQCRC_COPY_ROW_BYTES %d\n" % COPY_ROW_BYTES)
+        f.write("#define BMQCRC_XROW { \\\n")
+        for k in range(4):
+            f.write("  {%s}%s \\\n" % (", ".join("0x%08xu" % c for c in xrow[k]), "," if k < 3 else ""))
         f.write("}\n")
     print("wrote", out_path, "taps", taps)
 
