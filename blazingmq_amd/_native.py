@@ -119,6 +119,29 @@ lib.bmqcrc_put_event_fill_crcs.restype = _i64
 lib.bmqcrc_put_event_fill_crcs.argtypes = [_vp, _u64, _popts]
 lib.bmqcrc_put_event_verify.restype = _int
 lib.bmqcrc_put_event_verify.argtypes = [_vp, _u64, _pu64, _pu64, _vp, _u64, _popts]
+BMQCRC_PUT_PACK_OK = 0
+BMQCRC_PUT_PACK_SRC_RANGE = 1
+BMQCRC_PUT_PACK_EVENT_FIRST = 2
+BMQCRC_PUT_PACK_EVENT_TOO_BIG = 3
+BMQCRC_PUT_PACK_DST_TOO_SMALL = 4
+BMQCRC_PUT_PACK_TOO_MANY_PIECES = 5
+
+
+class PutPack(ctypes.Structure):
+    """bmqcrc_put_pack (include/bmqcrc_protocol.h, ABI 2.10)."""
+    _fields_ = [("struct_size", _u32), ("reserved", _u32), ("src", _vp), ("src_bytes", _u64),
+                ("src_offsets", _vp), ("lengths", _vp), ("queue_ids", _vp), ("guids", _vp),
+                ("flags", _vp), ("event_first", _vp), ("n", _u64), ("n_events", _u64),
+                ("max_event_bytes", _u64), ("dst", _vp), ("dst_bytes", _u64),
+                ("event_offsets", _vp), ("out", _vp)]
+
+
+if hasattr(lib, "bmqcrc_put_event_pack"):  # ABI 2.10 (an older build loads for same-box A/B)
+    lib.bmqcrc_put_event_pack.restype = _int
+    lib.bmqcrc_put_event_pack.argtypes = [ctypes.POINTER(PutPack), _pu64, _popts]
+    lib.bmqcrc_last_put_pack.restype = _int
+    lib.bmqcrc_last_put_pack.argtypes = [_int, _vp, _pu64, _pu64, _pu64, ctypes.POINTER(_u32),
+                                         _pu64]
 lib.bmqcrc_journal_scan.restype = _i64
 lib.bmqcrc_journal_scan.argtypes = [_vp, _u64, _vp, _u64, _vp, _pint, _pu64, _vp, _vp, _vp, _vp,
                                     _u64]

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/bmqcrc.h"
+#include "../../include/bmqcrc_protocol.h"
 #include "bmqcrc_internal.h"
 
 namespace bmqcrc {
@@ -131,6 +132,13 @@ struct Workspace {
     DevBuf copy_first, copy_bsum, copy_ctr;
     uint64_t copy_n = 0;
     bool copy_any = false;
+    // bmqcrc_put_event_pack: data offsets, the copy pass's scratch, the CRCs
+    // when the caller wants none, block sums, and the counters of the layout
+    // (kPackCtrWords) followed by the copy pass's (kCopyCtrWords); the size
+    // of the last pack enqueued here (bmqcrc_last_put_pack)
+    DevBuf pack_off, pack_first, pack_out, pack_bsum, pack_copy_bsum, pack_ctr;
+    uint64_t pack_n = 0, pack_events = 0;
+    bool pack_any = false;
     // Pinned staging ring for gathered host buffers (bmqcrc_crc32c_gather):
     // kGatherSlots chunks of kGatherChunk bytes, each reusable once the event
     // recorded after its H2D copy has completed.
@@ -1800,6 +1808,44 @@ static int copy_result(Ctx& c, unsigned long long (&ctr)[kCopyCtrWords])
     return 0;
 }
 
+// Enqueue one fused copy + CRC on c.s (caller holds c.w->mu): `a` carries the
+// caller's arrays and n; the scratch (piece prefix, block sums, kCopyCtrWords
+// counters at `ctr`, zeroed here) is the calling entry point's own, so that
+// bmqcrc_crc32c_copy and bmqcrc_put_event_pack keep separate records.
+static int enqueue_copy(Ctx& c, CopyArgs a, DevBuf& first, DevBuf& bsum, void* ctr)
+{
+    int rc;
+    if ((rc = bsum.ensure(8ull * kCopyPlanBlocks)) || (rc = first.ensure(4 * (a.n + 1)))) {
+        return rc;
+    }
+    {
+        std::lock_guard<std::mutex> gd(g_mu);  // DeviceState is shared by the device's streams
+        if (c.st->copy_blocks == 0) {
+            int per = 0;
+            if (bmqcrc_copy_occupancy(&per) != 0 || per <= 0) {
+                return fail(BMQCRC_EIO, "k_copy_fold occupancy query failed");
+            }
+            c.st->copy_blocks = (uint32_t)per * (uint32_t)std::max(c.st->num_cus, 1);
+        }
+    }
+    HIP_TRY(hipMemsetAsync(ctr, 0, 8 * kCopyCtrWords, c.s));
+    if (a.n) {
+        a.first = (uint32_t*)first.p;
+        a.bsum = (unsigned long long*)bsum.p;
+        a.ctr = (unsigned long long*)ctr;
+        const uint64_t tiles = (a.n + kCopyPlanThreads - 1) / kCopyPlanThreads;
+        const uint64_t nb = std::min<uint64_t>(tiles, kCopyPlanBlocks);
+        const uint64_t tiles_per = (tiles + nb - 1) / nb;
+        a.per_block = tiles_per * kCopyPlanThreads;
+        a.nblocks = (uint32_t)((tiles + tiles_per - 1) / tiles_per);
+        if (bmqcrc_launch_copy(&a, (void*)c.s, c.st->copy_blocks)) {
+            return fail(BMQCRC_EIO, std::string("copy launch failed: ") +
+                                        hipGetErrorString(hipGetLastError()));
+        }
+    }
+    return 0;
+}
+
 int bmqcrc_crc32c_copy(const void* src, uint64_t src_bytes, const uint64_t* src_offsets,
                        const uint32_t* lengths, void* dst, uint64_t dst_bytes,
                        const uint64_t* dst_offsets, const uint32_t* seeds, uint32_t* out,
@@ -1854,49 +1900,25 @@ int bmqcrc_crc32c_copy(const void* src, uint64_t src_bytes, const uint64_t* src_
     }
     Workspace* w = c.w;
     std::lock_guard<std::mutex> g(w->mu);
-    if ((rc = w->copy_ctr.ensure(8 * kCopyCtrWords)) ||
-        (rc = w->copy_bsum.ensure(8ull * kCopyPlanBlocks)) ||
-        (rc = w->copy_first.ensure(4 * (n + 1)))) {
+    if ((rc = w->copy_ctr.ensure(8 * kCopyCtrWords))) {
         return rc;
     }
-    {
-        std::lock_guard<std::mutex> gd(g_mu);  // DeviceState is shared by the device's streams
-        if (c.st->copy_blocks == 0) {
-            int per = 0;
-            if (bmqcrc_copy_occupancy(&per) != 0 || per <= 0) {
-                return fail(BMQCRC_EIO, "k_copy_fold occupancy query failed");
-            }
-            c.st->copy_blocks = (uint32_t)per * (uint32_t)std::max(c.st->num_cus, 1);
-        }
-    }
-    HIP_TRY(hipMemsetAsync(w->copy_ctr.p, 0, 8 * kCopyCtrWords, c.s));
+    CopyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = (const uint8_t*)src;
+    a.src_bytes = src_bytes;
+    a.src_offsets = src_offsets;
+    a.lengths = lengths;
+    a.dst = (uint8_t*)dst;
+    a.dst_bytes = dst_bytes;
+    a.dst_offsets = dst_offsets;
+    a.seeds = seeds;
+    a.out = out;
+    a.n = n;
     w->copy_n = n;
     w->copy_any = true;
-    if (n) {
-        CopyArgs a;
-        memset(&a, 0, sizeof(a));
-        a.src = (const uint8_t*)src;
-        a.src_bytes = src_bytes;
-        a.src_offsets = src_offsets;
-        a.lengths = lengths;
-        a.dst = (uint8_t*)dst;
-        a.dst_bytes = dst_bytes;
-        a.dst_offsets = dst_offsets;
-        a.seeds = seeds;
-        a.out = out;
-        a.n = n;
-        a.first = (uint32_t*)w->copy_first.p;
-        a.bsum = (unsigned long long*)w->copy_bsum.p;
-        a.ctr = (unsigned long long*)w->copy_ctr.p;
-        const uint64_t tiles = (n + kCopyPlanThreads - 1) / kCopyPlanThreads;
-        const uint64_t nb = std::min<uint64_t>(tiles, kCopyPlanBlocks);
-        const uint64_t tiles_per = (tiles + nb - 1) / nb;
-        a.per_block = tiles_per * kCopyPlanThreads;
-        a.nblocks = (uint32_t)((tiles + tiles_per - 1) / tiles_per);
-        if (bmqcrc_launch_copy(&a, (void*)c.s, c.st->copy_blocks)) {
-            return fail(BMQCRC_EIO, std::string("copy launch failed: ") +
-                                        hipGetErrorString(hipGetLastError()));
-        }
+    if ((rc = enqueue_copy(c, a, w->copy_first, w->copy_bsum, w->copy_ctr.p))) {
+        return rc;
     }
     if (o.flags & BMQCRC_F_ASYNC) {
         return 0;
@@ -1946,6 +1968,246 @@ int bmqcrc_last_copy(int device, void* stream, uint64_t* n_msgs, uint64_t* n_ref
     }
     if (first_refused) {
         *first_refused = ctr[kCopyCtrRefused] ? ~ctr[kCopyCtrLowestInv] : c.w->copy_n;
+    }
+    return 0;
+}
+
+static_assert(BMQCRC_PUT_PACK_SRC_RANGE == BMQCRC_PACK_KIND_SRC_RANGE &&
+                  BMQCRC_PUT_PACK_EVENT_FIRST == BMQCRC_PACK_KIND_EVENT_FIRST &&
+                  BMQCRC_PUT_PACK_EVENT_TOO_BIG == BMQCRC_PACK_KIND_EVENT_TOO_BIG &&
+                  BMQCRC_PUT_PACK_DST_TOO_SMALL == BMQCRC_PACK_KIND_DST_TOO_SMALL &&
+                  BMQCRC_PUT_PACK_TOO_MANY_PIECES == BMQCRC_PACK_KIND_TOO_MANY_PIECES,
+              "the kernels' refusal kinds are the public ones");
+
+constexpr uint64_t kPutMaxSizeSoft = 66ull << 20;              // PutHeader::k_MAX_SIZE_SOFT
+constexpr uint64_t kPutMaxEventBytes = ((1ull << 28) - 1) * 4;  // 28 bits of MessageWords
+
+// Counters of the pack last enqueued on c's workspace, after everything
+// enqueued on its stream (w->mu held): kind 0 = nothing refused.
+static int pack_result(Ctx& c, uint32_t* kind, uint64_t* index, uint64_t* total)
+{
+    unsigned long long ctr[kPackCtrWords + kCopyCtrWords];
+    HIP_TRY(hipMemcpyAsync(ctr, c.w->pack_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    const unsigned long long key = ctr[kPackCtrRefusal] ? ~ctr[kPackCtrRefusal] : 0;
+    *kind = (uint32_t)(key >> 56);
+    *index = key & ((1ull << 56) - 1);
+    *total = *kind ? 0 : ctr[kPackCtrTotal];
+    // the layout placed every message inside dst: the copy pass has nothing to refuse
+    const unsigned long long* cc = ctr + kPackCtrWords;
+    if (!*kind && (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow])) {
+        return fail(BMQCRC_EIO, "bmqcrc_put_event_pack: the copy pass refused a message the "
+                                "layout had placed (internal error)");
+    }
+    return 0;
+}
+
+static int pack_refusal(uint32_t kind, uint64_t index)
+{
+    static const char* const what[] = {
+        "", "BMQCRC_PUT_PACK_SRC_RANGE: message %llu lies outside [src, src+src_bytes)",
+        "BMQCRC_PUT_PACK_EVENT_FIRST: event_first[%llu] breaks 0 = first < ... < last = n",
+        "BMQCRC_PUT_PACK_EVENT_TOO_BIG: event %llu is longer than max_event_bytes",
+        "BMQCRC_PUT_PACK_DST_TOO_SMALL: event %llu ends past dst_bytes",
+        "BMQCRC_PUT_PACK_TOO_MANY_PIECES: more than 2^32-1 16-byte pieces of payload in one "
+        "call (index %llu)"};
+    char buf[192];
+    snprintf(buf, sizeof(buf), what[kind <= 5 ? kind : 0], (unsigned long long)index);
+    return fail(BMQCRC_EINVAL, std::string(buf) + ": nothing was written");
+}
+
+int bmqcrc_put_event_pack(const bmqcrc_put_pack* p, uint64_t* total_bytes, const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    if (!p || p->struct_size != sizeof(bmqcrc_put_pack)) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_put_pack.struct_size must be sizeof(bmqcrc_put_pack)");
+    }
+    if (p->reserved) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_put_pack.reserved must be 0");
+    }
+    bmqcrc_opts o;
+    memset(&o, 0, sizeof(o));
+    o.device = -1;
+    if (opts) {
+        const size_t given = opts->struct_size ? opts->struct_size : offsetof(bmqcrc_opts, ndevices);
+        memcpy(&o, opts, std::min<size_t>(sizeof(o), given));
+    }
+    static const struct {
+        uint32_t bit;
+        const char* name;
+    } refused[] = {{BMQCRC_F_TIME_KERNEL, "BMQCRC_F_TIME_KERNEL"},
+                   {BMQCRC_F_WHOLE_MESSAGES, "BMQCRC_F_WHOLE_MESSAGES"},
+                   {BMQCRC_F_PLAN, "BMQCRC_F_PLAN"},
+                   {BMQCRC_F_OFFSETS32, "BMQCRC_F_OFFSETS32"}};
+    for (const auto& r : refused) {
+        if (o.flags & r.bit) {
+            return fail(BMQCRC_EINVAL,
+                        std::string(r.name) + " does not apply to bmqcrc_put_event_pack");
+        }
+    }
+    if (o.flags & ~(BMQCRC_F_DEVICE_PTRS | BMQCRC_F_ASYNC)) {
+        return fail(BMQCRC_EINVAL, "unknown bmqcrc_opts.flags bits");
+    }
+    if (!(o.flags & BMQCRC_F_DEVICE_PTRS)) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_put_event_pack takes device pointers only: "
+                                   "BMQCRC_F_DEVICE_PTRS is required");
+    }
+    if (o.ndevices > 1) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_put_event_pack runs on one device: ndevices > 1");
+    }
+    const uint64_t n = p->n;
+    if (n > 0xFFFFFFFFull) {
+        return fail(BMQCRC_EINVAL, "at most 2^32-1 messages per call");
+    }
+    if (n) {
+        const struct {
+            bool null;
+            const char* name;
+        } arrays[] = {{!p->src_offsets, "src_offsets"}, {!p->lengths, "lengths"},
+                      {!p->queue_ids, "queue_ids"},     {!p->guids, "guids"},
+                      {!p->dst, "dst"},                 {!p->src && p->src_bytes, "src"}};
+        for (const auto& a : arrays) {
+            if (a.null) {
+                return fail(BMQCRC_EINVAL, std::string("null pointer argument: ") + a.name);
+            }
+        }
+    }
+    if ((uintptr_t)p->dst & 3u) {
+        return fail(BMQCRC_EINVAL, "dst must be 4-byte aligned");
+    }
+    {
+        const uintptr_t s0 = (uintptr_t)p->src, d0 = (uintptr_t)p->dst;
+        if (p->src_bytes && p->dst_bytes && s0 < d0 + p->dst_bytes && d0 < s0 + p->src_bytes) {
+            return fail(BMQCRC_EINVAL, "[dst, dst+dst_bytes) overlaps [src, src+src_bytes)");
+        }
+    }
+    if (p->max_event_bytes > kPutMaxEventBytes) {
+        return fail(BMQCRC_EINVAL, "max_event_bytes above (2^28-1)*4: MessageWords would overflow");
+    }
+    if (!p->event_first && p->n_events != 1) {
+        return fail(BMQCRC_EINVAL, "event_first == NULL means one event: n_events must be 1");
+    }
+    if (n && (p->n_events < 1 || p->n_events > n)) {
+        return fail(BMQCRC_EINVAL, "n_events must lie in [1, n]: no event is empty");
+    }
+    int dev, rc;
+    if ((rc = resolve_device(o.device, &dev))) {
+        return rc;
+    }
+    Ctx c;
+    if ((rc = open_ctx(dev, o.stream, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    std::lock_guard<std::mutex> g(w->mu);
+    if ((rc = w->pack_ctr.ensure(8 * (kPackCtrWords + kCopyCtrWords))) ||
+        (rc = w->pack_bsum.ensure(8ull * 2 * kPackBlocks)) ||
+        (rc = w->pack_off.ensure(8 * n)) || (!p->out && (rc = w->pack_out.ensure(4 * n)))) {
+        return rc;
+    }
+    unsigned long long* ctr = (unsigned long long*)w->pack_ctr.p;
+    HIP_TRY(hipMemsetAsync(ctr, 0, 8 * kPackCtrWords, c.s));
+    uint32_t* crcs = p->out ? p->out : (uint32_t*)w->pack_out.p;
+    PackArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src_bytes = p->src_bytes;
+    a.src_offsets = p->src_offsets;
+    a.lengths = p->lengths;
+    a.queue_ids = p->queue_ids;
+    a.guids = p->guids;
+    a.flags = p->flags;
+    a.event_first = p->event_first;
+    a.n = n;
+    a.n_events = n ? p->n_events : 0;
+    a.max_event_bytes = p->max_event_bytes ? p->max_event_bytes : kPutMaxSizeSoft;
+    a.dst = (uint8_t*)p->dst;
+    a.dst_bytes = p->dst_bytes;
+    a.event_offsets = p->event_offsets;
+    a.out = crcs;
+    a.off = (unsigned long long*)w->pack_off.p;
+    a.bsum = (unsigned long long*)w->pack_bsum.p;
+    a.ctr = ctr;
+    if (n) {
+        const uint64_t tiles = (n + kPackThreads - 1) / kPackThreads;
+        const uint64_t nb = std::min<uint64_t>(tiles, kPackBlocks);
+        const uint64_t tiles_per = (tiles + nb - 1) / nb;
+        a.per_block = tiles_per * kPackThreads;
+        a.nblocks = (uint32_t)((tiles + tiles_per - 1) / tiles_per);
+        if (bmqcrc_launch_put_layout(&a, (void*)c.s)) {
+            return fail(BMQCRC_EIO, std::string("put-pack layout launch failed: ") +
+                                        hipGetErrorString(hipGetLastError()));
+        }
+    }
+    CopyArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.src = (const uint8_t*)p->src;
+    ca.src_bytes = p->src_bytes;
+    ca.src_offsets = p->src_offsets;
+    ca.lengths = p->lengths;
+    ca.dst = (uint8_t*)p->dst;
+    ca.dst_bytes = p->dst_bytes;
+    ca.dst_offsets = (const uint64_t*)w->pack_off.p;
+    ca.out = crcs;
+    ca.n = n;
+    if ((rc = enqueue_copy(c, ca, w->pack_first, w->pack_copy_bsum, ctr + kPackCtrWords))) {
+        return rc;
+    }
+    if (n && bmqcrc_launch_put_frame(&a, (void*)c.s)) {
+        return fail(BMQCRC_EIO, std::string("put-pack frame launch failed: ") +
+                                    hipGetErrorString(hipGetLastError()));
+    }
+    w->pack_n = n;
+    w->pack_events = a.n_events;
+    w->pack_any = true;
+    if (o.flags & BMQCRC_F_ASYNC) {
+        return 0;
+    }
+    uint32_t kind;
+    uint64_t index, total;
+    if ((rc = pack_result(c, &kind, &index, &total))) {
+        return rc;
+    }
+    if (total_bytes) {
+        *total_bytes = total;
+    }
+    return kind ? pack_refusal(kind, index) : 0;
+}
+
+int bmqcrc_last_put_pack(int device, void* stream, uint64_t* n_msgs, uint64_t* n_events,
+                         uint64_t* total_bytes, uint32_t* refused_kind, uint64_t* refused_index)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    int dev, rc;
+    if ((rc = resolve_device(device, &dev))) {
+        return rc;
+    }
+    Ctx c;
+    if ((rc = open_ctx(dev, stream, &c))) {
+        return rc;
+    }
+    std::lock_guard<std::mutex> g(c.w->mu);
+    uint32_t kind = 0;
+    uint64_t index = 0, total = 0;
+    if (c.w->pack_any && (rc = pack_result(c, &kind, &index, &total))) {
+        return rc;
+    }
+    if (n_msgs) {
+        *n_msgs = c.w->pack_n;
+    }
+    if (n_events) {
+        *n_events = c.w->pack_events;
+    }
+    if (total_bytes) {
+        *total_bytes = total;
+    }
+    if (refused_kind) {
+        *refused_kind = kind;
+    }
+    if (refused_index) {
+        *refused_index = index;
     }
     return 0;
 }
@@ -2125,7 +2387,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 9u;
+    return (2u << 16) | 10u;
 }
 
 }  // extern "C"

@@ -187,7 +187,50 @@ struct CopyArgs {
     uint32_t nblocks;             // pre-kernel blocks (<= kCopyPlanBlocks)
 };
 
+// ---- bmqcrc_put_event_pack (crc32c_put_pack.hip, ABI 2.10) -----------------
+constexpr int kPackThreads = 1024;         // layout kernels' block
+constexpr uint32_t kPackBlocks = 256;      // their grid: contiguous message ranges, at most
+constexpr int kPackFrameThreads = 256;     // k_pack_frame: one header dword per thread and step
+constexpr uint32_t kPackFrameBlocks = 2048;
+// PackArgs::ctr words
+constexpr int kPackCtrRefusal = 0;  // ~((kind << 56) | index) of the refusal reported, 0: none
+constexpr int kPackCtrTotal = 1;    // bytes of all events (k_pack_check)
+constexpr int kPackCtrWords = 2;
+// BMQCRC_PUT_PACK_* of bmqcrc_protocol.h, which the kernels do not include
+#define BMQCRC_PACK_KIND_SRC_RANGE 1u
+#define BMQCRC_PACK_KIND_EVENT_FIRST 2u
+#define BMQCRC_PACK_KIND_EVENT_TOO_BIG 3u
+#define BMQCRC_PACK_KIND_DST_TOO_SMALL 4u
+#define BMQCRC_PACK_KIND_TOO_MANY_PIECES 5u
+
+struct PackArgs {
+    uint64_t src_bytes;
+    const uint64_t* src_offsets;   // device, n
+    const uint32_t* lengths;       // device, n
+    const int32_t* queue_ids;      // device, n
+    const uint8_t* guids;          // device, 16 n
+    const uint8_t* flags;          // device, n, or nullptr (all zero)
+    const uint64_t* event_first;   // device, n_events + 1, or nullptr (one event)
+    uint64_t n;
+    uint64_t n_events;
+    uint64_t max_event_bytes;
+    uint8_t* dst;                  // device, 4-byte aligned
+    uint64_t dst_bytes;
+    uint64_t* event_offsets;       // device, n_events + 1, or nullptr
+    const uint32_t* out;           // device, n: the CRCs, final after k_copy_fold
+    unsigned long long* off;       // workspace, n: block-local prefix, then data offset in dst
+    unsigned long long* bsum;      // workspace, 2 * kPackBlocks: framed bytes | pieces per block
+    unsigned long long* ctr;       // workspace, kPackCtrWords, zeroed before the launch
+    uint64_t per_block;            // messages per layout block (multiple of kPackThreads)
+    uint32_t nblocks;              // layout blocks (<= kPackBlocks)
+};
+
 }  // namespace bmqcrc
+
+// Launchers (crc32c_put_pack.hip).  Asynchronous on `stream`: the layout
+// before bmqcrc_launch_copy (it writes the copy's dst_offsets), the frame after.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_put_layout(const bmqcrc::PackArgs* a, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_put_frame(const bmqcrc::PackArgs* a, void* stream);
 
 // Launchers (crc32c_copy.hip).  Asynchronous on `stream`.
 extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_copy(const bmqcrc::CopyArgs* a, void* stream,

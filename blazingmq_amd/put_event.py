@@ -104,6 +104,102 @@ class PutEventBuilder:
         return ev
 
 
+def pack_events(src, src_offsets, lengths, queue_ids, guids, flags=None, event_first=None,
+                max_event_bytes=None, dst=None, out=None, *, stream=None, sync=True):
+    """Pack device-resident payloads into PUT events on the GPU
+    (``bmqcrc_put_event_pack``): what ``PutEventBuilder(defer_crc=False)``
+    emits with no options, one builder per event, the events back to back in
+    ``dst``.  Message i's application data is ``src[src_offsets[i]:][:lengths[i]]``.
+
+    Device tensors only, all on one MI355X, contiguous: ``src`` / ``dst``
+    uint8, ``src_offsets`` int64, ``lengths`` / ``queue_ids`` / ``out`` int32
+    (lengths and out read as u32), ``guids`` uint8 with 16 bytes per message,
+    ``flags`` uint8 (low 4 bits) or None, ``event_first`` int64 with one entry
+    more than there are events (event e holds messages ``[event_first[e],
+    event_first[e+1])``) or None for one event.  ``max_event_bytes=None`` is
+    the reference's 66 MiB.  ``dst=None`` allocates exactly the bytes needed,
+    which takes a sum of the lengths on the host and so ``sync=True``; with
+    ``sync=False`` ``dst`` is required.
+
+    Returns ``(dst, event_offsets, crcs)``: ``event_offsets`` (int64, one per
+    event and the total last) and ``crcs`` (``out``, or a new int32 tensor).
+    All or nothing: a source range outside ``src``, a malformed
+    ``event_first``, an event above the cap or a ``dst`` too small writes
+    nothing and, with ``sync=True``, raises ``BmqCrcError`` (BMQCRC_EINVAL)
+    naming the kind and the lowest index; with ``sync=False`` ask
+    ``last_put_pack``.  Not meant to be captured into a graph."""
+    import torch
+    n = src_offsets.numel() if isinstance(src_offsets, torch.Tensor) else -1
+    for name, t, dt in (("src", src, torch.uint8), ("src_offsets", src_offsets, torch.int64),
+                        ("lengths", lengths, torch.int32), ("queue_ids", queue_ids, torch.int32),
+                        ("guids", guids, torch.uint8)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous()):
+            raise TypeError("%s must be a contiguous %s tensor" % (name, dt))
+    if lengths.numel() != n or queue_ids.numel() != n or guids.numel() != 16 * n:
+        raise ValueError("src_offsets/lengths/queue_ids/guids size mismatch")
+    dev = src.device
+    for name, t, dt, want in (("flags", flags, torch.uint8, n), ("out", out, torch.int32, n)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and
+                                  t.dtype == dt and t.is_contiguous() and t.numel() == want):
+            raise TypeError("%s must be a contiguous %s tensor of %d elements on %s"
+                            % (name, dt, want, dev))
+    for name, t, dt in (("event_first", event_first, torch.int64), ("dst", dst, torch.uint8)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dt and
+                                  t.is_contiguous()):
+            raise TypeError("%s must be a contiguous %s tensor" % (name, dt))
+    if event_first is not None and event_first.numel() < 1:
+        raise ValueError("event_first needs one entry more than there are events")
+    if not src.is_cuda:
+        raise TypeError("pack_events takes device tensors only (src is on %s)" % dev)
+    for name, t in (("src_offsets", src_offsets), ("lengths", lengths), ("queue_ids", queue_ids),
+                    ("guids", guids), ("event_first", event_first), ("dst", dst)):
+        if t is not None and t.device != dev:
+            raise TypeError("%s must be on %s like src" % (name, dev))
+    n_events = event_first.numel() - 1 if event_first is not None else 1
+    if dst is None:
+        if not sync:
+            raise ValueError("dst is required when sync=False: sizing it reads the lengths back")
+        words = ((lengths.to(torch.int64) & 0xFFFFFFFF) >> 2) + 1
+        total = int((4 * words + PUT_HEADER_SIZE).sum().item()) if n else 0
+        dst = torch.empty(total + (EVENT_HEADER_SIZE * n_events if n else 0), dtype=torch.uint8,
+                          device=dev)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+    event_offsets = torch.zeros(n_events + 1, dtype=torch.int64, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    p = N.PutPack()
+    p.struct_size = ctypes.sizeof(N.PutPack)
+    p.src, p.src_bytes = src.data_ptr(), src.numel()
+    p.src_offsets, p.lengths = src_offsets.data_ptr(), lengths.data_ptr()
+    p.queue_ids, p.guids = queue_ids.data_ptr(), guids.data_ptr()
+    p.flags = flags.data_ptr() if flags is not None else None
+    p.event_first = event_first.data_ptr() if event_first is not None else None
+    p.n, p.n_events = n, n_events
+    p.max_event_bytes = int(max_event_bytes) if max_event_bytes is not None else 0
+    p.dst, p.dst_bytes = dst.data_ptr(), dst.numel()
+    p.event_offsets, p.out = event_offsets.data_ptr(), out.data_ptr()
+    o = N.make_opts(device=dev.index if dev.index is not None else -1, stream=stream.cuda_stream,
+                    flags=N.BMQCRC_F_DEVICE_PTRS | (0 if sync else N.BMQCRC_F_ASYNC))
+    N.check(N.lib.bmqcrc_put_event_pack(ctypes.byref(p), None, ctypes.byref(o)))
+    return dst, event_offsets, out
+
+
+def last_put_pack(device, stream=None):
+    """(n_msgs, n_events, total_bytes, refused_kind, refused_index) of the
+    previous ``pack_events`` on (device, stream) (bmqcrc_last_put_pack); waits
+    for it.  ``refused_kind`` is 0 (``BMQCRC_PUT_PACK_OK``) or the kind
+    refused, ``refused_index`` the lowest offending message or event, and
+    ``total_bytes`` 0 when refused.  ``stream=None`` is the device's default
+    stream."""
+    n, ne, tot, idx = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    kind = ctypes.c_uint32()
+    N.check(N.lib.bmqcrc_last_put_pack(
+        device, stream.cuda_stream if stream is not None else None, ctypes.byref(n),
+        ctypes.byref(ne), ctypes.byref(tot), ctypes.byref(kind), ctypes.byref(idx)))
+    return n.value, ne.value, tot.value, kind.value, idx.value
+
+
 class PutMessageIterator:
     """Iterate the messages of a PUT event: (put header fields, app data)."""
 

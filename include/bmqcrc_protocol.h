@@ -53,6 +53,91 @@ int64_t bmqcrc_put_event_fill_crcs(void* event, uint64_t len, const bmqcrc_opts*
 int bmqcrc_put_event_verify(const void* event, uint64_t len, uint64_t* n_msgs, uint64_t* n_bad,
                             uint64_t* bad_idx, uint64_t bad_cap, const bmqcrc_opts* opts);
 
+/* ABI 2.10.  Pack device-resident payloads into PUT events, on the device:
+ * what PutEventBuilder::packMessage does per message on the host (header,
+ * append, CRC, padding; bmqp_puteventbuilder.cpp:80-173, 302-320), for n
+ * messages in one call.  Message i's application data (properties + payload)
+ * is the lengths[i] bytes at src + src_offsets[i].
+ *
+ * Wire format: per event an 8-byte EventHeader (BE length, (1 << 6) | 2,
+ * header words 2, two zero bytes); per message a 36-byte PutHeader
+ * (flags << 28 | messageWords; optionsWords 0 | CAT 0 | headerWords 9; BE
+ * queue id; GUID; BE CRC32-C at +28; four zero bytes), the application data,
+ * and pad = 4 - len % 4 bytes each equal to pad.  Options, compression (CAT)
+ * and schema ids are out of scope for this version: those fields are zero.
+ *
+ * Layout: with B[i] = 36 + lengths[i] + pad(lengths[i]), P its 64-bit
+ * exclusive prefix and e(i) the event of message i, the events lie back to
+ * back in dst: message i's header at 8 (e(i) + 1) + P[i], event e at
+ * 8 e + P[event_first[e]].  Bytes of dst at or beyond the total are never
+ * written.  A message of length 0 is legal (four padding bytes, CRC 0).
+ *
+ * Options.  Device pointers only: BMQCRC_F_DEVICE_PTRS is required,
+ *   BMQCRC_F_ASYNC allowed; any other flag, ndevices > 1, a null required
+ *   array, dst not 4-byte aligned, [dst, dst + dst_bytes) meeting
+ *   [src, src + src_bytes), max_event_bytes above (2^28 - 1) * 4, event_first
+ *   == NULL with n_events != 1, or n_events outside [1, n] is BMQCRC_EINVAL,
+ *   answered on the host before the device lookup.
+ * All or nothing, decided on the device (all sums in 64 bits): every
+ *   src_offsets[i] + lengths[i] <= src_bytes; event_first[0] == 0, strictly
+ *   increasing, last entry == n; every event's length <= max_event_bytes;
+ *   the total <= dst_bytes; and the payload within the copy kernel's
+ *   2^32 - 1 16-byte pieces (counted as len / 16 rounded up, plus one, per
+ *   non-empty message).  On any violation nothing is written to dst, out or
+ *   event_offsets; a synchronous call returns BMQCRC_EINVAL naming the kind
+ *   and the lowest offending message (SRC_RANGE) or event index, and after
+ *   an asynchronous call bmqcrc_last_put_pack reports them.  Of several
+ *   violations the lowest kind is reported.
+ * *total_bytes (may be NULL) is written by a synchronous call only: the
+ *   bytes of all events, 0 when refused.
+ * State.  As bmqcrc_crc32c_copy: takes the workspace mutex of (device,
+ *   stream); leaves the shape prediction and every bmqcrc_last_* record of
+ *   the batch and copy calls as they were; restores the caller's current
+ *   device; allocates its own workspace on first use and when n grows (12
+ *   bytes per message, 16 without `out`), which bmqcrc_reserve does not
+ *   cover; is not meant to be captured into a hipGraph; is deterministic.
+ *   n == 0 writes nothing and reports 0 messages, 0 events, 0 bytes. */
+#define BMQCRC_PUT_PACK_OK 0
+#define BMQCRC_PUT_PACK_SRC_RANGE 1       /* index: the lowest message outside src */
+#define BMQCRC_PUT_PACK_EVENT_FIRST 2     /* index: the lowest bad entry (n_events: the last) */
+#define BMQCRC_PUT_PACK_EVENT_TOO_BIG 3   /* index: the lowest event above max_event_bytes */
+#define BMQCRC_PUT_PACK_DST_TOO_SMALL 4   /* index: the lowest event ending past dst_bytes */
+#define BMQCRC_PUT_PACK_TOO_MANY_PIECES 5 /* index 0: beyond the copy kernel's piece limit */
+
+typedef struct bmqcrc_put_pack {
+    uint32_t struct_size;          /* sizeof(bmqcrc_put_pack) */
+    uint32_t reserved;             /* 0 */
+    const void* src;               /* device: payload arena */
+    uint64_t src_bytes;
+    const uint64_t* src_offsets;   /* device, n */
+    const uint32_t* lengths;       /* device, n: application-data bytes (properties + payload) */
+    const int32_t* queue_ids;      /* device, n */
+    const uint8_t* guids;          /* device, 16 n */
+    const uint8_t* flags;          /* device, n, low 4 bits used; NULL = 0 */
+    const uint64_t* event_first;   /* device, n_events + 1: event e holds messages
+                                      [event_first[e], event_first[e+1]); NULL = one event
+                                      (n_events must then be 1) */
+    uint64_t n;
+    uint64_t n_events;
+    uint64_t max_event_bytes;      /* 0 = PutHeader::k_MAX_SIZE_SOFT (66 MiB); at most
+                                      (2^28-1)*4 so MessageWords cannot overflow */
+    void* dst;                     /* device, 4-byte aligned: events laid back to back */
+    uint64_t dst_bytes;
+    uint64_t* event_offsets;       /* device, n_events + 1, may be NULL: byte offset of each
+                                      event in dst; the last entry is the total */
+    uint32_t* out;                 /* device, n, may be NULL: the CRCs (host order) */
+} bmqcrc_put_pack;
+
+int bmqcrc_put_event_pack(const bmqcrc_put_pack* p, uint64_t* total_bytes, const bmqcrc_opts* opts);
+
+/* ABI 2.10.  Result of the previous bmqcrc_put_event_pack on (device,
+ * stream); waits for it.  *n_msgs and *n_events = its n and n_events,
+ * *total_bytes = the bytes of all events (0 when refused), *refused_kind =
+ * BMQCRC_PUT_PACK_OK or the kind refused and *refused_index its index.  All
+ * zero before the first pack there.  Any pointer may be NULL. */
+int bmqcrc_last_put_pack(int device, void* stream, uint64_t* n_msgs, uint64_t* n_events,
+                         uint64_t* total_bytes, uint32_t* refused_kind, uint64_t* refused_index);
+
 /* ---- partition recovery (mqbs_filestoreprotocol.h:306,426,483,703,953-1990) */
 
 /* mqbs::FileStore::recoverMessages result codes (mqbs_filestore.cpp:1073-1091)

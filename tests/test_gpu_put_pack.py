@@ -1,0 +1,313 @@
+"""Device-side PUT-event packer (bmqcrc_put_event_pack, ABI 2.10) on the GPU.
+The oracle throughout is the concatenated PutEventBuilder(defer_crc=False)
+bytes plus host CRCs: every check compares the packed bytes byte for byte,
+`out`, `event_offsets`, and the canary behind the total."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, last_copy, last_launch,
+                           last_put_pack, pack_events)
+from put_pack_model import host_crcs, layout, oracle_events, random_meta
+
+pytestmark = pytest.mark.gpu
+
+FILL = 0xA5
+FILL32 = 0x5A5A5A5A
+FILL64 = 0x5A5A5A5A5A5A5A5A
+CAP = 66 << 20
+
+
+def _t(cuda, a, dtype):
+    import torch
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if dtype == np.uint32:
+        a = a.view(np.int32)
+    return torch.from_numpy(a).to(cuda)
+
+
+def _inputs(cuda, src, soff, lens, qids, guids, flags, ef):
+    return dict(src=_t(cuda, src, np.uint8), src_offsets=_t(cuda, soff, np.int64),
+                lengths=_t(cuda, lens, np.uint32), queue_ids=_t(cuda, qids, np.int32),
+                guids=_t(cuda, guids, np.uint8),
+                flags=_t(cuda, flags, np.uint8) if flags is not None else None,
+                event_first=_t(cuda, ef, np.int64) if ef is not None else None)
+
+
+def _check(cuda, src, soff, lens, qids, guids, flags=None, ef=None, slack=64, **kw):
+    """One pack into a canary destination against the oracle.  Returns the
+    packed bytes (host)."""
+    import torch
+    # (n = 0 writes nothing, not even an empty event)
+    exp = np.concatenate(oracle_events(src, soff, lens, qids, guids, flags, ef)) if len(lens) \
+        else np.zeros(0, np.uint8)
+    total = exp.size
+    d = _inputs(cuda, src, soff, lens, qids, guids, flags, ef)
+    dst = torch.full((total + slack,), FILL, dtype=torch.uint8, device=cuda)
+    out = torch.full((len(lens),), FILL32, dtype=torch.int32, device=cuda)
+    rdst, evoff, rout = pack_events(dst=dst, out=out, **d, **kw)
+    assert rdst is dst and rout is out
+    stream = torch.cuda.current_stream(cuda)
+    n_events = 1 if ef is None else len(ef) - 1
+    assert last_put_pack(cuda.index, stream) == (len(lens), n_events if len(lens) else 0, total,
+                                                 N.BMQCRC_PUT_PACK_OK, 0)
+    host = dst.cpu().numpy()
+    diff = np.nonzero(host[:total] != exp)[0]
+    assert diff.size == 0, (diff.size, [int(i) for i in diff[:8]])
+    assert np.all(host[total:] == FILL)
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), host_crcs(src, soff, lens))
+    if len(lens):
+        assert np.array_equal(evoff.cpu().numpy(), layout(lens, ef)[1])
+    assert torch.equal(d["src"].cpu(), torch.from_numpy(src))  # the source is only read
+    return host[:total]
+
+
+def _raw(cuda, d, n, n_events, dst, dst_bytes, out, evoff, flags=N.BMQCRC_F_DEVICE_PTRS,
+         max_event_bytes=0, src_bytes=None):
+    import torch
+    p = N.PutPack()
+    p.struct_size = ctypes.sizeof(N.PutPack)
+    p.src = d["src"].data_ptr()
+    p.src_bytes = d["src"].numel() if src_bytes is None else src_bytes
+    p.src_offsets, p.lengths = d["src_offsets"].data_ptr(), d["lengths"].data_ptr()
+    p.queue_ids, p.guids = d["queue_ids"].data_ptr(), d["guids"].data_ptr()
+    p.flags = d["flags"].data_ptr() if d["flags"] is not None else None
+    p.event_first = d["event_first"].data_ptr() if d["event_first"] is not None else None
+    p.n, p.n_events, p.max_event_bytes = n, n_events, max_event_bytes
+    p.dst, p.dst_bytes = dst.data_ptr(), dst_bytes
+    p.event_offsets, p.out = evoff.data_ptr(), out.data_ptr()
+    stream = torch.cuda.current_stream(cuda)
+    o = N.make_opts(device=cuda.index, stream=stream.cuda_stream, flags=flags)
+    total = ctypes.c_uint64(FILL64)
+    rc = N.lib.bmqcrc_put_event_pack(ctypes.byref(p), ctypes.byref(total), ctypes.byref(o))
+    return rc, N.lib.bmqcrc_last_error(), total.value
+
+
+def _refused(cuda, kind, index, src, soff, lens, qids, guids, flags=None, ef=None,
+             dst_bytes=None, **kw):
+    """The call is refused with (kind, index), synchronously and asynchronously,
+    and the whole dst, out and event_offsets keep their canaries."""
+    import torch
+    n, n_events = len(lens), 1 if ef is None else len(ef) - 1
+    d = _inputs(cuda, src, soff, lens, qids, guids, flags, ef)
+    size = int(layout(lens, None)[1][-1]) + 8 * n_events + 64
+    stream = torch.cuda.current_stream(cuda)
+    name = {1: b"SRC_RANGE", 2: b"EVENT_FIRST", 3: b"EVENT_TOO_BIG", 4: b"DST_TOO_SMALL"}[kind]
+    for flags_ in (N.BMQCRC_F_DEVICE_PTRS, N.BMQCRC_F_DEVICE_PTRS | N.BMQCRC_F_ASYNC):
+        dst = torch.full((size,), FILL, dtype=torch.uint8, device=cuda)
+        out = torch.full((n,), FILL32, dtype=torch.int32, device=cuda)
+        evoff = torch.full((n_events + 1,), FILL64, dtype=torch.int64, device=cuda)
+        rc, err, total = _raw(cuda, d, n, n_events, dst, size if dst_bytes is None else dst_bytes,
+                              out, evoff, flags_, **kw)
+        if flags_ & N.BMQCRC_F_ASYNC:
+            assert rc == 0 and total == FILL64, (rc, err)
+        else:
+            assert rc == N.BMQCRC_EINVAL and name in err and total == 0, (rc, err)
+            assert (" %d " % index).encode() in err or ("[%d]" % index).encode() in err, err
+        assert last_put_pack(cuda.index, stream) == (n, n_events, 0, kind, index)
+        assert bool((dst == FILL).all()) and bool((out == FILL32).all())
+        assert bool((evoff == FILL64).all())
+
+
+def _short(rng, n, lo=1, hi=41, src_size=1 << 16):
+    src = rng.integers(0, 256, size=src_size, dtype=np.uint8)
+    lens = rng.integers(lo, hi, size=n)
+    soff = rng.integers(0, src_size - hi, size=n)
+    return (src, soff, lens) + random_meta(rng, n)
+
+
+def test_every_length_at_every_source_misalignment(cuda):
+    # lengths 0..67 in one event: every padding count, and (the 36-byte header
+    # shifts a payload by 4 mod 16 per message) every destination alignment
+    rng = np.random.default_rng(1)
+    lens = np.arange(68)
+    src = rng.integers(0, 256, size=68 * 96 + 64, dtype=np.uint8)
+    for mis in range(16):
+        soff = 96 * np.arange(68) + mis + 16 * rng.integers(0, 2, size=68)
+        assert np.all(soff % 16 == mis)
+        qids, guids, flags = random_meta(rng, 68)
+        _check(cuda, src, soff, rng.permutation(lens), qids, guids, flags)
+    assert set((36 + layout(lens)[0]) % 16) == {0, 4, 8, 12}
+
+
+def test_smallest_cases(cuda):
+    rng = np.random.default_rng(2)
+    src = rng.integers(0, 256, size=256, dtype=np.uint8)
+    for ln in (0, 1):
+        qids, guids, flags = random_meta(rng, 1)
+        got = _check(cuda, src, [7], [ln], qids, guids, flags)
+        assert got.size == 8 + 36 + 4 and list(got[44 + ln:]) == [4 - ln] * (4 - ln)
+    # flags=None is zero flags; event_first given for one event
+    qids, guids, _ = random_meta(rng, 1)
+    _check(cuda, src, [3], [5], qids, guids, None, [0, 1])
+    # n = 0: nothing is written
+    got = _check(cuda, src, np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int32),
+                 np.zeros((0, 16), np.uint8))
+    assert got.size == 0
+
+
+def test_wrapper_allocates_the_exact_destination(cuda):
+    rng = np.random.default_rng(3)
+    src, soff, lens, qids, guids, flags = _short(rng, 77, 0, 30)
+    ef = [0, 10, 77]
+    d = _inputs(cuda, src, soff, lens, qids, guids, flags, ef)
+    dst, evoff, out = pack_events(**d)
+    exp = np.concatenate(oracle_events(src, soff, lens, qids, guids, flags, ef))
+    assert dst.numel() == exp.size and np.array_equal(dst.cpu().numpy(), exp)
+    assert int(evoff[-1]) == exp.size
+    with pytest.raises(ValueError, match="dst is required"):
+        pack_events(sync=False, **d)
+
+
+@pytest.mark.parametrize("n", [1025, 3 * 1024 + 1])
+def test_more_than_one_layout_block(cuda, n):
+    rng = np.random.default_rng(4)
+    case = _short(rng, n)
+    ef = sorted(set([0, 1, 1024, 1025, n]))
+    assert [b - a for a, b in zip(ef, ef[1:])].count(1) >= 2  # single-message events
+    _check(cuda, *case, ef=ef)
+    _check(cuda, *case)  # and as one event
+
+
+@pytest.mark.parametrize("own_event", [False, True])
+def test_a_long_message_among_short_ones(cuda, own_event):
+    rng = np.random.default_rng(5)
+    src, soff, lens, qids, guids, flags = _short(rng, 41, 0, 200, src_size=1 << 19)
+    lens[20], soff[20] = 300000, 13  # longer than a 64 KiB chunk of the copy pass
+    ef = [0, 20, 21, 41] if own_event else None
+    first = _check(cuda, src, soff, lens, qids, guids, flags, ef)
+    again = _check(cuda, src, soff, lens, qids, guids, flags, ef)
+    assert np.array_equal(first, again)
+
+
+def _cap_case(rng, last_len):
+    # event 1 = 40 messages of 100 framed bytes and one of 36 + last_len + pad
+    lens = np.array([5, 6] + [60] * 40 + [last_len])
+    src = rng.integers(0, 256, size=4096, dtype=np.uint8)
+    soff = rng.integers(0, 4000, size=lens.size)
+    return (src, soff, lens) + random_meta(rng, lens.size), [0, 2, lens.size]
+
+
+def test_event_size_cap(cuda):
+    rng = np.random.default_rng(6)
+    case, ef = _cap_case(rng, 48)
+    assert np.diff(layout(case[2], ef)[1])[1] == 4096
+    _check(cuda, *case, ef=ef, max_event_bytes=4096)          # exactly at the cap
+    case, ef = _cap_case(rng, 52)
+    assert np.diff(layout(case[2], ef)[1])[1] == 4100          # one word over
+    _refused(cuda, N.BMQCRC_PUT_PACK_EVENT_TOO_BIG, 1, *case, ef=ef, max_event_bytes=4096)
+    _check(cuda, *case, ef=ef, max_event_bytes=4100)
+    with pytest.raises(BmqCrcError, match="EVENT_TOO_BIG: event 1 "):
+        pack_events(**_inputs(cuda, *case, ef), max_event_bytes=4096)
+
+
+def test_destination_size(cuda):
+    rng = np.random.default_rng(7)
+    case = _short(rng, 300)
+    ef = [0, 100, 299, 300]
+    total = int(layout(case[2], ef)[1][-1])
+    _check(cuda, *case, ef=ef, slack=0)                        # dst_bytes == total
+    _refused(cuda, N.BMQCRC_PUT_PACK_DST_TOO_SMALL, 2, *case, ef=ef, dst_bytes=total - 4)
+    _refused(cuda, N.BMQCRC_PUT_PACK_DST_TOO_SMALL, 0, *case, ef=ef, dst_bytes=64)
+
+
+def test_source_range(cuda):
+    rng = np.random.default_rng(8)
+    src, soff, lens, qids, guids, flags = _short(rng, 1500, src_size=1 << 15)
+    src_bytes = 20000  # declared smaller than the tensor: a broken check stays inside it
+    soff = soff % (src_bytes - 64)
+    soff[1200], lens[1200] = src_bytes - 10, 11               # one byte past
+    soff[1300] = (1 << 63) - 8                                 # the sum needs 64 bits
+    soff[77], lens[77] = src_bytes, 0                          # empty at the very end: legal
+    _refused(cuda, N.BMQCRC_PUT_PACK_SRC_RANGE, 1200, src, soff, lens, qids, guids, flags,
+             src_bytes=src_bytes)
+
+
+@pytest.mark.parametrize("ef,index", [
+    ([1, 5, 20], 0),        # not starting at 0
+    ([0, 5, 5, 20], 1),     # not increasing
+    ([0, 9, 5, 20], 1),     # decreasing
+    ([0, 5, 19], 2),        # not ending at n
+    ([0, 5, 21], 2)])       # ending past n
+def test_bad_event_first(cuda, ef, index):
+    rng = np.random.default_rng(9)
+    _refused(cuda, N.BMQCRC_PUT_PACK_EVENT_FIRST, index, *_short(rng, 20), ef=ef)
+
+
+def test_asynchronous_call(cuda):
+    import torch
+    rng = np.random.default_rng(10)
+    src, soff, lens, qids, guids, flags = _short(rng, 2000, 0, 300)
+    ef = [0, 500, 2000]
+    got = _check(cuda, src, soff, lens, qids, guids, flags, ef, sync=False)
+    s = torch.cuda.Stream(cuda)
+    with torch.cuda.stream(s):
+        again = _check(cuda, src, soff, lens, qids, guids, flags, ef, sync=False, stream=s)
+    assert np.array_equal(got, again)
+
+
+def test_state_untouched(cuda):
+    import torch
+    rng = np.random.default_rng(11)
+    host = rng.integers(0, 256, size=1 << 20, dtype=np.uint8)
+    arena = torch.from_numpy(host).to(cuda)
+    lens = rng.integers(1, 1025, size=5001).astype(np.uint32)
+    offs = (rng.random(lens.size) * (host.size - 1100)).astype(np.int64)
+    d_off, d_len = _t(cuda, offs, np.int64), _t(cuda, lens, np.uint32)
+    copy_dst = torch.zeros(int(lens.sum()) + 16, dtype=torch.uint8, device=cuda)
+    doff = _t(cuda, np.concatenate([[0], np.cumsum(lens)[:-1]]), np.int64)
+    qids, guids, flags = random_meta(rng, lens.size)
+    pack = _inputs(cuda, host, offs, lens, qids, guids, flags, None)
+    pack["src"] = arena
+    plans = []
+    for with_pack in (False, True):
+        s = torch.cuda.Stream(cuda)
+        with torch.cuda.stream(s):
+            Crc32c.copy_batch(arena, d_off[:40], d_len[:40], copy_dst, doff[:40], stream=s)
+            Crc32c.calculate_batch(arena, d_off, d_len, stream=s, seg_bytes=1024)
+            before = last_launch(cuda.index, s, offsets=True)
+            assert last_copy(cuda.index, s) == (40, 0, 40)
+            if with_pack:
+                pack_events(stream=s, **pack)
+                pack_events(stream=s, sync=False, dst=torch.zeros(64, dtype=torch.uint8,
+                                                                  device=cuda), **pack)
+                assert last_put_pack(cuda.index, s)[3] == N.BMQCRC_PUT_PACK_DST_TOO_SMALL
+                assert last_launch(cuda.index, s, offsets=True) == before
+                assert last_copy(cuda.index, s) == (40, 0, 40)
+            out = Crc32c.calculate_batch(arena, d_off, d_len, stream=s, seg_bytes=1024)
+            plans.append(last_launch(cuda.index, s, offsets=True))
+        s.synchronize()
+        assert np.array_equal(out.cpu().numpy().view(np.uint32),
+                              host_crcs(host, offs, lens))
+    assert plans[0] == plans[1], plans
+
+
+def test_crossing_4_gib(cuda):
+    # 70 events of 66 messages of 2^20 - 4 framed bytes: 8 bytes under the
+    # 66 MiB cap each, 4.5 GiB in all -- what a 32-bit prefix gets wrong.
+    # Every payload lies in one 1 MiB source region (source ranges overlap).
+    import torch
+    rng = np.random.default_rng(12)
+    per, n_events, ln = 66, 70, (1 << 20) - 44
+    n = per * n_events
+    src = rng.integers(0, 256, size=1 << 20, dtype=np.uint8)
+    soff = 4 * (np.arange(n) % 11)
+    lens = np.full(n, ln)
+    qids, guids, flags = random_meta(rng, n)
+    ef = per * np.arange(n_events + 1)
+    hdr, ev = layout(lens, ef)
+    total = int(ev[-1])
+    assert total > (1 << 32) + (1 << 28) and int(np.diff(ev).max()) == CAP - 256 <= CAP
+    dst = torch.empty(total + 64, dtype=torch.uint8, device=cuda)
+    dst[total:] = FILL
+    d = _inputs(cuda, src, soff, lens, qids, guids, flags, ef)
+    _, evoff, out = pack_events(dst=dst, **d)
+    assert np.array_equal(evoff.cpu().numpy(), ev)
+    assert last_put_pack(cuda.index, torch.cuda.current_stream(cuda)) == (n, n_events, total, 0, 0)
+    first, last = oracle_events(src, soff, lens, qids, guids, flags, ef, events=[0, n_events - 1])
+    assert torch.equal(dst[:first.size].cpu(), torch.from_numpy(first))
+    assert torch.equal(dst[int(ev[-2]):total].cpu(), torch.from_numpy(last))
+    assert bool((dst[total:] == FILL).all())
+    crc11 = host_crcs(src, soff[:11], lens[:11])
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), crc11[np.arange(n) % 11])
