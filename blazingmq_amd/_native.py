@@ -142,6 +142,42 @@ if hasattr(lib, "bmqcrc_put_event_pack"):  # ABI 2.10 (an older build loads for 
     lib.bmqcrc_last_put_pack.restype = _int
     lib.bmqcrc_last_put_pack.argtypes = [_int, _vp, _pu64, _pu64, _pu64, ctypes.POINTER(_u32),
                                          _pu64]
+BMQCRC_REC_PACK_OK = 0
+BMQCRC_REC_PACK_RECORD_TOO_BIG = 1
+BMQCRC_REC_PACK_SRC_RANGE = 2
+BMQCRC_REC_PACK_DST_TOO_SMALL = 3
+BMQCRC_REC_PACK_DATA_FILE_FULL = 4
+BMQCRC_REC_PACK_TOO_MANY_PIECES = 5
+
+
+class RecordsPack(ctypes.Structure):
+    """bmqcrc_records_pack (include/bmqcrc_protocol.h, ABI 2.11)."""
+    _fields_ = [("struct_size", _u32), ("reserved", _u32), ("src", _vp), ("src_bytes", _u64),
+                ("src_offsets", _vp), ("lengths", _vp), ("queue_keys", _vp), ("guids", _vp),
+                ("data_flags", _vp), ("ref_counts", _vp), ("timestamps", _vp), ("expected", _vp),
+                ("file_key", ctypes.c_uint8 * 5), ("reserved2", ctypes.c_uint8 * 3),
+                ("lease_id", _u32), ("first_seq", _u64), ("timestamp", _u64),
+                ("data_file_pos", _u64), ("n", _u64), ("dst", _vp), ("dst_bytes", _u64),
+                ("journal_dst", _vp), ("journal_bytes", _u64), ("record_offsets", _vp),
+                ("out", _vp)]
+
+
+class RecordsResult(ctypes.Structure):
+    """bmqcrc_records_result (include/bmqcrc_protocol.h, ABI 2.11)."""
+    _fields_ = [("n_msgs", _u64), ("data_bytes", _u64), ("journal_bytes", _u64), ("n_bad", _u64),
+                ("first_bad", _u64), ("refused_kind", _u32), ("reserved", _u32),
+                ("refused_index", _u64)]
+
+    def as_dict(self):
+        return {f[0]: int(getattr(self, f[0])) for f in self._fields_ if f[0] != "reserved"}
+
+
+if hasattr(lib, "bmqcrc_message_records_pack"):  # ABI 2.11 (an older build loads for same-box A/B)
+    lib.bmqcrc_message_records_pack.restype = _int
+    lib.bmqcrc_message_records_pack.argtypes = [ctypes.POINTER(RecordsPack),
+                                                ctypes.POINTER(RecordsResult), _popts]
+    lib.bmqcrc_last_records_pack.restype = _int
+    lib.bmqcrc_last_records_pack.argtypes = [_int, _vp, ctypes.POINTER(RecordsResult)]
 lib.bmqcrc_journal_scan.restype = _i64
 lib.bmqcrc_journal_scan.argtypes = [_vp, _u64, _vp, _u64, _vp, _pint, _pu64, _vp, _vp, _vp, _vp,
                                     _u64]

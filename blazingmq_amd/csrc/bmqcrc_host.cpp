@@ -139,6 +139,12 @@ struct Workspace {
     DevBuf pack_off, pack_first, pack_out, pack_bsum, pack_copy_bsum, pack_ctr;
     uint64_t pack_n = 0, pack_events = 0;
     bool pack_any = false;
+    // bmqcrc_message_records_pack: the same set of its own (the counters are
+    // kRecCtrWords followed by the copy pass's kCopyCtrWords) and the size of
+    // the last pack enqueued here (bmqcrc_last_records_pack)
+    DevBuf rec_off, rec_first, rec_out, rec_bsum, rec_copy_bsum, rec_ctr;
+    uint64_t rec_n = 0;
+    bool rec_any = false;
     // Pinned staging ring for gathered host buffers (bmqcrc_crc32c_gather):
     // kGatherSlots chunks of kGatherChunk bytes, each reusable once the event
     // recorded after its H2D copy has completed.
@@ -2212,6 +2218,277 @@ int bmqcrc_last_put_pack(int device, void* stream, uint64_t* n_msgs, uint64_t* n
     return 0;
 }
 
+static_assert(BMQCRC_REC_PACK_RECORD_TOO_BIG == BMQCRC_REC_KIND_RECORD_TOO_BIG &&
+                  BMQCRC_REC_PACK_SRC_RANGE == BMQCRC_REC_KIND_SRC_RANGE &&
+                  BMQCRC_REC_PACK_DST_TOO_SMALL == BMQCRC_REC_KIND_DST_TOO_SMALL &&
+                  BMQCRC_REC_PACK_DATA_FILE_FULL == BMQCRC_REC_KIND_DATA_FILE_FULL &&
+                  BMQCRC_REC_PACK_TOO_MANY_PIECES == BMQCRC_REC_KIND_TOO_MANY_PIECES,
+              "the kernels' refusal kinds are the public ones");
+
+constexpr uint64_t kJournalRecordBytes = 60;       // FileStoreProtocol::k_JOURNAL_RECORD_SIZE
+constexpr uint64_t kMaxSeqNum = (1ull << 48) - 1;  // RecordHeader: 48 bits of sequence number
+
+// Result of the records pack last enqueued on c's workspace, after everything
+// enqueued on its stream (w->mu held); zeros when there was none.
+static int records_result(Ctx& c, bmqcrc_records_result* r)
+{
+    memset(r, 0, sizeof(*r));
+    if (!c.w->rec_any) {
+        return 0;
+    }
+    unsigned long long ctr[kRecCtrWords + kCopyCtrWords];
+    HIP_TRY(hipMemcpyAsync(ctr, c.w->rec_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    const unsigned long long key = ctr[kRecCtrRefusal] ? ~ctr[kRecCtrRefusal] : 0;
+    r->n_msgs = c.w->rec_n;
+    r->refused_kind = (uint32_t)(key >> 56);
+    r->refused_index = key & ((1ull << 56) - 1);
+    r->first_bad = r->n_msgs;
+    if (r->refused_kind) {
+        return 0;
+    }
+    r->data_bytes = r->n_msgs ? ctr[kRecCtrTotal] : 0;
+    r->journal_bytes = kJournalRecordBytes * r->n_msgs;
+    r->n_bad = ctr[kRecCtrBad];
+    if (r->n_bad) {
+        r->first_bad = ~ctr[kRecCtrFirstBad];
+    }
+    // the layout placed every message inside dst: the copy pass has nothing to refuse
+    const unsigned long long* cc = ctr + kRecCtrWords;
+    if (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow]) {
+        return fail(BMQCRC_EIO, "bmqcrc_message_records_pack: the copy pass refused a message "
+                                "the layout had placed (internal error)");
+    }
+    return 0;
+}
+
+static int records_refusal(uint32_t kind, uint64_t index)
+{
+    static const char* const what[] = {
+        "", "BMQCRC_REC_PACK_RECORD_TOO_BIG: message %llu makes a record above 2^29-1 words",
+        "BMQCRC_REC_PACK_SRC_RANGE: message %llu lies outside [src, src+src_bytes)",
+        "BMQCRC_REC_PACK_DST_TOO_SMALL: the record of message %llu ends past dst_bytes",
+        "BMQCRC_REC_PACK_DATA_FILE_FULL: the record of message %llu ends past 8*(2^32-1) bytes "
+        "of DATA file, where MessageOffsetDwords stops",
+        "BMQCRC_REC_PACK_TOO_MANY_PIECES: more than 2^32-1 16-byte pieces of payload in one "
+        "call (index %llu)"};
+    char buf[192];
+    snprintf(buf, sizeof(buf), what[kind <= 5 ? kind : 0], (unsigned long long)index);
+    return fail(BMQCRC_EINVAL, std::string(buf) + ": nothing was written");
+}
+
+int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_result* result,
+                                const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    if (!p || p->struct_size != sizeof(bmqcrc_records_pack)) {
+        return fail(BMQCRC_EINVAL,
+                    "bmqcrc_records_pack.struct_size must be sizeof(bmqcrc_records_pack)");
+    }
+    if (p->reserved) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_records_pack.reserved must be 0");
+    }
+    bmqcrc_opts o;
+    memset(&o, 0, sizeof(o));
+    o.device = -1;
+    if (opts) {
+        const size_t given = opts->struct_size ? opts->struct_size : offsetof(bmqcrc_opts, ndevices);
+        memcpy(&o, opts, std::min<size_t>(sizeof(o), given));
+    }
+    static const struct {
+        uint32_t bit;
+        const char* name;
+    } refused[] = {{BMQCRC_F_TIME_KERNEL, "BMQCRC_F_TIME_KERNEL"},
+                   {BMQCRC_F_WHOLE_MESSAGES, "BMQCRC_F_WHOLE_MESSAGES"},
+                   {BMQCRC_F_PLAN, "BMQCRC_F_PLAN"},
+                   {BMQCRC_F_OFFSETS32, "BMQCRC_F_OFFSETS32"}};
+    for (const auto& r : refused) {
+        if (o.flags & r.bit) {
+            return fail(BMQCRC_EINVAL,
+                        std::string(r.name) + " does not apply to bmqcrc_message_records_pack");
+        }
+    }
+    if (o.flags & ~(BMQCRC_F_DEVICE_PTRS | BMQCRC_F_ASYNC)) {
+        return fail(BMQCRC_EINVAL, "unknown bmqcrc_opts.flags bits");
+    }
+    if (!(o.flags & BMQCRC_F_DEVICE_PTRS)) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_message_records_pack takes device pointers only: "
+                                   "BMQCRC_F_DEVICE_PTRS is required");
+    }
+    if (o.ndevices > 1) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_message_records_pack runs on one device: ndevices > 1");
+    }
+    const uint64_t n = p->n;
+    if (n > 0xFFFFFFFFull) {
+        return fail(BMQCRC_EINVAL, "at most 2^32-1 messages per call");
+    }
+    if (n) {
+        const struct {
+            bool null;
+            const char* name;
+        } arrays[] = {{!p->src_offsets, "src_offsets"}, {!p->lengths, "lengths"},
+                      {!p->queue_keys, "queue_keys"},   {!p->guids, "guids"},
+                      {!p->dst, "dst"},                 {!p->journal_dst, "journal_dst"},
+                      {!p->src && p->src_bytes, "src"}};
+        for (const auto& a : arrays) {
+            if (a.null) {
+                return fail(BMQCRC_EINVAL, std::string("null pointer argument: ") + a.name);
+            }
+        }
+    }
+    if ((uintptr_t)p->dst & 7u) {
+        return fail(BMQCRC_EINVAL, "dst must be 8-byte aligned");
+    }
+    if ((uintptr_t)p->journal_dst & 3u) {
+        return fail(BMQCRC_EINVAL, "journal_dst must be 4-byte aligned");
+    }
+    if (p->data_file_pos == 0 || (p->data_file_pos & 7u)) {
+        return fail(BMQCRC_EINVAL, "data_file_pos must be a multiple of 8 and not 0 (recovery "
+                                   "treats a MessageOffsetDwords of 0 as invalid)");
+    }
+    if (p->lease_id == 0) {
+        return fail(BMQCRC_EINVAL, "lease_id must not be 0");
+    }
+    if (p->first_seq == 0 || p->first_seq > kMaxSeqNum ||
+        (n && n - 1 > kMaxSeqNum - p->first_seq)) {
+        return fail(BMQCRC_EINVAL, "first_seq must not be 0, and first_seq + n - 1 at most 2^48-1");
+    }
+    if (kJournalRecordBytes * n > p->journal_bytes) {
+        return fail(BMQCRC_EINVAL, "journal_bytes is below 60 n");
+    }
+    {
+        const struct {
+            uintptr_t at;
+            uint64_t bytes;
+            const char* name;
+        } r[] = {{(uintptr_t)p->src, p->src_bytes, "[src, src+src_bytes)"},
+                 {(uintptr_t)p->dst, p->dst_bytes, "[dst, dst+dst_bytes)"},
+                 {(uintptr_t)p->journal_dst, p->journal_bytes,
+                  "[journal_dst, journal_dst+journal_bytes)"}};
+        for (int i = 1; i < 3; ++i) {
+            for (int j = 0; j < i; ++j) {
+                if (r[i].bytes && r[j].bytes && r[i].at < r[j].at + r[j].bytes &&
+                    r[j].at < r[i].at + r[i].bytes) {
+                    return fail(BMQCRC_EINVAL, std::string(r[i].name) + " overlaps " + r[j].name);
+                }
+            }
+        }
+    }
+    int dev, rc;
+    if ((rc = resolve_device(o.device, &dev))) {
+        return rc;
+    }
+    Ctx c;
+    if ((rc = open_ctx(dev, o.stream, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    std::lock_guard<std::mutex> g(w->mu);
+    if ((rc = w->rec_ctr.ensure(8 * (kRecCtrWords + kCopyCtrWords))) ||
+        (rc = w->rec_bsum.ensure(8ull * 2 * kPackBlocks)) || (rc = w->rec_off.ensure(8 * n)) ||
+        (!p->out && (rc = w->rec_out.ensure(4 * n)))) {
+        return rc;
+    }
+    unsigned long long* ctr = (unsigned long long*)w->rec_ctr.p;
+    HIP_TRY(hipMemsetAsync(ctr, 0, 8 * kRecCtrWords, c.s));
+    uint32_t* crcs = p->out ? p->out : (uint32_t*)w->rec_out.p;
+    RecArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src_bytes = p->src_bytes;
+    a.src_offsets = p->src_offsets;
+    a.lengths = p->lengths;
+    a.queue_keys = p->queue_keys;
+    a.guids = p->guids;
+    a.data_flags = p->data_flags;
+    a.ref_counts = p->ref_counts;
+    a.timestamps = p->timestamps;
+    a.expected = p->expected;
+    a.n = n;
+    a.first_seq = p->first_seq;
+    a.timestamp = p->timestamp;
+    a.data_file_pos = p->data_file_pos;
+    a.lease_id = p->lease_id;
+    const uint8_t* fk = p->file_key;
+    a.key_lo = (uint32_t)fk[0] << 24;
+    a.key_hi = (uint32_t)fk[1] | ((uint32_t)fk[2] << 8) | ((uint32_t)fk[3] << 16) |
+               ((uint32_t)fk[4] << 24);
+    a.dst = (uint8_t*)p->dst;
+    a.dst_bytes = p->dst_bytes;
+    a.journal = (uint8_t*)p->journal_dst;
+    a.record_offsets = p->record_offsets;
+    a.out = crcs;
+    a.off = (unsigned long long*)w->rec_off.p;
+    a.bsum = (unsigned long long*)w->rec_bsum.p;
+    a.ctr = ctr;
+    if (n) {
+        const uint64_t tiles = (n + kPackThreads - 1) / kPackThreads;
+        const uint64_t nb = std::min<uint64_t>(tiles, kPackBlocks);
+        const uint64_t tiles_per = (tiles + nb - 1) / nb;
+        a.per_block = tiles_per * kPackThreads;
+        a.nblocks = (uint32_t)((tiles + tiles_per - 1) / tiles_per);
+        if (bmqcrc_launch_records_layout(&a, (void*)c.s)) {
+            return fail(BMQCRC_EIO, std::string("records-pack layout launch failed: ") +
+                                        hipGetErrorString(hipGetLastError()));
+        }
+    }
+    CopyArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.src = (const uint8_t*)p->src;
+    ca.src_bytes = p->src_bytes;
+    ca.src_offsets = p->src_offsets;
+    ca.lengths = p->lengths;
+    ca.dst = (uint8_t*)p->dst;
+    ca.dst_bytes = p->dst_bytes;
+    ca.dst_offsets = (const uint64_t*)w->rec_off.p;
+    ca.out = crcs;
+    ca.n = n;
+    if ((rc = enqueue_copy(c, ca, w->rec_first, w->rec_copy_bsum, ctr + kRecCtrWords))) {
+        return rc;
+    }
+    if (n && bmqcrc_launch_records_frame(&a, (void*)c.s)) {
+        return fail(BMQCRC_EIO, std::string("records-pack frame launch failed: ") +
+                                    hipGetErrorString(hipGetLastError()));
+    }
+    w->rec_n = n;
+    w->rec_any = true;
+    if (o.flags & BMQCRC_F_ASYNC) {
+        return 0;
+    }
+    bmqcrc_records_result r;
+    if ((rc = records_result(c, &r))) {
+        return rc;
+    }
+    if (result) {
+        *result = r;
+    }
+    return r.refused_kind ? records_refusal(r.refused_kind, r.refused_index) : 0;
+}
+
+int bmqcrc_last_records_pack(int device, void* stream, bmqcrc_records_result* result)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    int dev, rc;
+    if ((rc = resolve_device(device, &dev))) {
+        return rc;
+    }
+    Ctx c;
+    if ((rc = open_ctx(dev, stream, &c))) {
+        return rc;
+    }
+    std::lock_guard<std::mutex> g(c.w->mu);
+    bmqcrc_records_result r;
+    if ((rc = records_result(c, &r))) {
+        return rc;
+    }
+    if (result) {
+        *result = r;
+    }
+    return 0;
+}
+
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,
                        uint32_t* seg_bytes)
 {
@@ -2387,7 +2664,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 10u;
+    return (2u << 16) | 11u;
 }
 
 }  // extern "C"

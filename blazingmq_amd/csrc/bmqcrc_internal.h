@@ -225,7 +225,57 @@ struct PackArgs {
     uint32_t nblocks;              // layout blocks (<= kPackBlocks)
 };
 
+// ---- bmqcrc_message_records_pack (crc32c_records_pack.hip, ABI 2.11) -------
+// The layout grid and block are kPackBlocks x kPackThreads, the frame kernel's
+// kPackFrameBlocks x kPackFrameThreads.  RecArgs::ctr words
+constexpr int kRecCtrRefusal = 0;   // ~((kind << 56) | index) of the refusal reported, 0: none
+constexpr int kRecCtrTotal = 1;     // bytes of all DATA records (k_rec_place)
+constexpr int kRecCtrBad = 2;       // messages whose CRC differs from expected[]
+constexpr int kRecCtrFirstBad = 3;  // ~(lowest such message), 0: none
+constexpr int kRecCtrWords = 4;
+// BMQCRC_REC_PACK_* of bmqcrc_protocol.h, which the kernels do not include
+#define BMQCRC_REC_KIND_RECORD_TOO_BIG 1u
+#define BMQCRC_REC_KIND_SRC_RANGE 2u
+#define BMQCRC_REC_KIND_DST_TOO_SMALL 3u
+#define BMQCRC_REC_KIND_DATA_FILE_FULL 4u
+#define BMQCRC_REC_KIND_TOO_MANY_PIECES 5u
+constexpr uint64_t kRecMaxFileBytes = 8ull * 0xFFFFFFFFull;  // where MessageOffsetDwords stops
+
+struct RecArgs {
+    uint64_t src_bytes;
+    const uint64_t* src_offsets;   // device, n
+    const uint32_t* lengths;       // device, n
+    const uint8_t* queue_keys;     // device, 5 n
+    const uint8_t* guids;          // device, 16 n
+    const uint8_t* data_flags;     // device, n, or nullptr (all zero)
+    const uint32_t* ref_counts;    // device, n, or nullptr (all 1)
+    const uint64_t* timestamps;    // device, n, or nullptr (all `timestamp`)
+    const uint32_t* expected;      // device, n, or nullptr (store the computed CRC)
+    uint64_t n;
+    uint64_t first_seq;
+    uint64_t timestamp;
+    uint64_t data_file_pos;        // multiple of 8, > 0
+    uint32_t lease_id;
+    uint32_t key_lo;               // record bytes 24..27 carry file_key[0] in the top byte
+    uint32_t key_hi;               // record bytes 28..31: file_key[1..4], as stored
+    uint8_t* dst;                  // device, 8-byte aligned
+    uint64_t dst_bytes;
+    uint8_t* journal;              // device, 4-byte aligned, 60 n bytes at least
+    uint64_t* record_offsets;      // device, n + 1, or nullptr
+    const uint32_t* out;           // device, n: the CRCs, final after k_copy_fold
+    unsigned long long* off;       // workspace, n: block-local prefix, then data offset in dst
+    unsigned long long* bsum;      // workspace, 2 * kPackBlocks: record bytes | pieces per block
+    unsigned long long* ctr;       // workspace, kRecCtrWords, zeroed before the launch
+    uint64_t per_block;            // messages per layout block (multiple of kPackThreads)
+    uint32_t nblocks;              // layout blocks (<= kPackBlocks)
+};
+
 }  // namespace bmqcrc
+
+// Launchers (crc32c_records_pack.hip).  Asynchronous on `stream`: the layout
+// before bmqcrc_launch_copy (it writes the copy's dst_offsets), the frame after.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_records_layout(const bmqcrc::RecArgs* a, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_records_frame(const bmqcrc::RecArgs* a, void* stream);
 
 // Launchers (crc32c_put_pack.hip).  Asynchronous on `stream`: the layout
 // before bmqcrc_launch_copy (it writes the copy's dst_offsets), the frame after.

@@ -442,24 +442,34 @@ class PartitionWriter:
             (22, bytes(queue_key)), (27, bytes(app_key)), (32, int(op).to_bytes(4, "big")),
             (36, (9 if op in (OP_CREATION, OP_ADDITION) else 0).to_bytes(4, "big"))])
 
-    def message(self, app, queue_key, crc=None, guid=None, data_header=None):
+    def message(self, app, queue_key, crc=None, guid=None, data_header=None, file_key=NULL_KEY,
+                ref_count=1, data_flags=0, timestamp=None):
         """MESSAGE record + its DATA record (12-byte DataHeader, no options,
         1..8 padding bytes).  `crc` overrides the stored CRC (default: the
-        CRC32C of `app`); `data_header` overrides the DataHeader bytes."""
+        CRC32C of `app`); `data_header` overrides the DataHeader bytes.
+        `file_key` is the DATA file's key, `ref_count` the 20-bit reference
+        count (low 12 bits in the RecordHeader's flags, the rest at @20),
+        `data_flags` the DataHeader's flags byte and `timestamp` this
+        record's own (default: the writer's)."""
         app = bytes(app)
         rem = (12 + len(app)) % DWORD
         pad = DWORD - rem if rem else DWORD
         total = 12 + len(app) + pad
         hdr = data_header if data_header is not None else \
-            ((3 << 29) | (total // WORD)).to_bytes(4, "big") + bytes(8)
+            ((3 << 29) | (total // WORD)).to_bytes(4, "big") + \
+            (int(data_flags) & 0xFF).to_bytes(4, "big") + bytes(4)
         self.data.append(bytes(hdr) + app + bytes([pad]) * pad)
         if guid is None:
             self._guid += 1
             guid = (0x40000000000000000000000000000000 | self._guid).to_bytes(16, "big")
         crc = Crc32c.calculate(app) if crc is None else int(crc)
-        off = self._record(REC_MESSAGE, [
-            (22, bytes(queue_key)), (32, (self.dpos // DWORD).to_bytes(4, "big")),
-            (36, bytes(guid)), (52, crc.to_bytes(4, "big"))], flags=1)
+        ref_count = int(ref_count) & 0xFFFFF
+        body = [(20, bytes([ref_count >> 12])), (22, bytes(queue_key)), (27, bytes(file_key)),
+                (32, (self.dpos // DWORD).to_bytes(4, "big")), (36, bytes(guid)),
+                (52, crc.to_bytes(4, "big"))]
+        if timestamp is not None:
+            body.append((12, int(timestamp).to_bytes(8, "big")))
+        off = self._record(REC_MESSAGE, body, flags=ref_count & 0xFFF)
         self.dpos += total
         return off, bytes(guid)
 
@@ -491,3 +501,119 @@ def write_partition(app_datas, crcs=None, lease_id=1, timestamp=0x6720EAB4,
     for i, app in enumerate(app_datas):
         w.message(app, queue_key, crc=None if crcs is None else crcs[i])
     return w.files()
+
+
+# ----------------------------------------------------------------------------
+# Device-side writer: DATA records and journal MessageRecords in one call.
+# ----------------------------------------------------------------------------
+def pack_records(src, src_offsets, lengths, queue_keys, guids, *, file_key, lease_id, first_seq,
+                 data_file_pos, timestamp=0, timestamps=None, ref_counts=None, data_flags=None,
+                 expected=None, dst=None, journal_dst=None, out=None, stream=None, sync=True):
+    """Pack device-resident payloads into DATA-file records and their journal
+    MessageRecords on the GPU (``bmqcrc_message_records_pack``): the bytes
+    ``PartitionWriter.message`` appends to both files for n messages, what
+    ``FileStore::writeMessageRecord`` writes with no options.  Message i's
+    application data is ``src[src_offsets[i]:][:lengths[i]]``; its DATA record
+    stands for byte ``data_file_pos + record_offsets[i]`` of the DATA file and
+    its sequence number is ``first_seq + i``.
+
+    Device tensors only, all on one MI355X, contiguous: ``src`` / ``dst`` /
+    ``journal_dst`` uint8, ``src_offsets`` / ``timestamps`` int64, ``lengths``
+    / ``ref_counts`` / ``expected`` / ``out`` int32 (read as u32),
+    ``queue_keys`` uint8 with 5 and ``guids`` uint8 with 16 bytes per message,
+    ``data_flags`` uint8.  ``file_key`` is 5 bytes.  With ``expected`` the
+    journal stores those CRCs, as the broker stores the one that arrived with
+    the message, and the result counts the messages whose computed CRC
+    differs.  ``dst=None`` allocates exactly the bytes needed, which takes a
+    sum of the lengths on the host and so ``sync=True``; ``journal_dst=None``
+    allocates 60 n bytes.
+
+    Returns ``(dst, journal_dst, record_offsets, crcs, result)``:
+    ``record_offsets`` (int64, one per record and the total last), ``crcs``
+    the computed CRCs (``out``, or a new int32 tensor) and ``result`` the
+    dict of ``last_records_pack`` (None with ``sync=False``).  All or nothing:
+    a record above the DataHeader's size field, a source range outside
+    ``src``, a ``dst`` too small or a DATA file position past what
+    MessageOffsetDwords addresses writes nothing and, with ``sync=True``,
+    raises ``BmqCrcError`` (BMQCRC_EINVAL) naming the kind and the lowest
+    message; with ``sync=False`` ask ``last_records_pack``.  Not meant to be
+    captured into a graph."""
+    import torch
+    n = src_offsets.numel() if isinstance(src_offsets, torch.Tensor) else -1
+    for name, t, dt in (("src", src, torch.uint8), ("src_offsets", src_offsets, torch.int64),
+                        ("lengths", lengths, torch.int32), ("queue_keys", queue_keys, torch.uint8),
+                        ("guids", guids, torch.uint8)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous()):
+            raise TypeError("%s must be a contiguous %s tensor" % (name, dt))
+    if lengths.numel() != n or queue_keys.numel() != 5 * n or guids.numel() != 16 * n:
+        raise ValueError("src_offsets/lengths/queue_keys/guids size mismatch")
+    dev = src.device
+    for name, t, dt in (("data_flags", data_flags, torch.uint8),
+                        ("ref_counts", ref_counts, torch.int32),
+                        ("timestamps", timestamps, torch.int64),
+                        ("expected", expected, torch.int32), ("out", out, torch.int32)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and
+                                  t.dtype == dt and t.is_contiguous() and t.numel() == n):
+            raise TypeError("%s must be a contiguous %s tensor of %d elements on %s"
+                            % (name, dt, n, dev))
+    for name, t in (("dst", dst), ("journal_dst", journal_dst)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and
+                                  t.is_contiguous()):
+            raise TypeError("%s must be a contiguous %s tensor" % (name, torch.uint8))
+    file_key = bytes(file_key)
+    if len(file_key) != 5:
+        raise ValueError("file_key is 5 bytes")
+    if not src.is_cuda:
+        raise TypeError("pack_records takes device tensors only (src is on %s)" % dev)
+    for name, t in (("src_offsets", src_offsets), ("lengths", lengths),
+                    ("queue_keys", queue_keys), ("guids", guids), ("dst", dst),
+                    ("journal_dst", journal_dst)):
+        if t is not None and t.device != dev:
+            raise TypeError("%s must be on %s like src" % (name, dev))
+    if dst is None:
+        if not sync:
+            raise ValueError("dst is required when sync=False: sizing it reads the lengths back")
+        dwords = (((lengths.to(torch.int64) & 0xFFFFFFFF) + 12) >> 3) + 1
+        dst = torch.empty(int((8 * dwords).sum().item()) if n else 0, dtype=torch.uint8,
+                          device=dev)
+    if journal_dst is None:
+        journal_dst = torch.empty(JOURNAL_RECORD_SIZE * n, dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+    record_offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    p = N.RecordsPack()
+    p.struct_size = ctypes.sizeof(N.RecordsPack)
+    p.src, p.src_bytes = src.data_ptr(), src.numel()
+    p.src_offsets, p.lengths = src_offsets.data_ptr(), lengths.data_ptr()
+    p.queue_keys, p.guids = queue_keys.data_ptr(), guids.data_ptr()
+    for name, t in (("data_flags", data_flags), ("ref_counts", ref_counts),
+                    ("timestamps", timestamps), ("expected", expected)):
+        setattr(p, name, t.data_ptr() if t is not None else None)
+    p.file_key = (ctypes.c_uint8 * 5)(*file_key)
+    p.lease_id, p.first_seq, p.timestamp = int(lease_id), int(first_seq), int(timestamp)
+    p.data_file_pos, p.n = int(data_file_pos), n
+    p.dst, p.dst_bytes = dst.data_ptr(), dst.numel()
+    p.journal_dst, p.journal_bytes = journal_dst.data_ptr(), journal_dst.numel()
+    p.record_offsets, p.out = record_offsets.data_ptr(), out.data_ptr()
+    o = N.make_opts(device=dev.index if dev.index is not None else -1, stream=stream.cuda_stream,
+                    flags=N.BMQCRC_F_DEVICE_PTRS | (0 if sync else N.BMQCRC_F_ASYNC))
+    res = N.RecordsResult()
+    N.check(N.lib.bmqcrc_message_records_pack(ctypes.byref(p), ctypes.byref(res), ctypes.byref(o)))
+    return dst, journal_dst, record_offsets, out, res.as_dict() if sync else None
+
+
+def last_records_pack(device, stream=None):
+    """Result of the previous ``pack_records`` on (device, stream)
+    (bmqcrc_last_records_pack); waits for it.  A dict: ``n_msgs``,
+    ``data_bytes`` and ``journal_bytes`` (both 0 when refused), ``n_bad`` and
+    ``first_bad`` (the messages whose computed CRC differs from ``expected``
+    and the lowest of them, ``n_msgs`` when none), ``refused_kind`` (0,
+    ``BMQCRC_REC_PACK_OK``, or the kind refused) and ``refused_index`` (the
+    lowest offending message).  ``stream=None`` is the device's default
+    stream."""
+    res = N.RecordsResult()
+    N.check(N.lib.bmqcrc_last_records_pack(
+        device, stream.cuda_stream if stream is not None else None, ctypes.byref(res)))
+    return res.as_dict()

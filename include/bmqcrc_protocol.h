@@ -138,6 +138,122 @@ int bmqcrc_put_event_pack(const bmqcrc_put_pack* p, uint64_t* total_bytes, const
 int bmqcrc_last_put_pack(int device, void* stream, uint64_t* n_msgs, uint64_t* n_events,
                          uint64_t* total_bytes, uint32_t* refused_kind, uint64_t* refused_index);
 
+/* ABI 2.11.  Pack device-resident payloads into DATA-file records and their
+ * journal MessageRecords, on the device: what FileStore::writeMessageRecord
+ * does per accepted message on the host (mqbs_filestore.cpp:5634-5747:
+ * DataHeader, payload, dword padding, then the journal record pointing at
+ * it), for n messages in one call.  Message i's application data is the
+ * lengths[i] bytes at src + src_offsets[i].
+ *
+ * DATA records (dst).  R[i] = 12 + lengths[i] + pad with pad = 8 - (12 +
+ *   lengths[i]) % 8, that is 1..8 bytes each equal to pad; Q = the 64-bit
+ *   exclusive prefix of R.  Record i lies at dst + Q[i]: a 12-byte DataHeader
+ *   (mqbs_filestoreprotocol.h:703) of three big-endian words, (3 << 29) |
+ *   R[i] / 4; optionsWords 0 | flags (data_flags[i], else 0); schema id 0;
+ *   then the application data and the padding.  Bytes of dst at or beyond
+ *   Q[n] are never written.  A length of 0 is legal (12 + 4 padding bytes,
+ *   CRC 0).  Options, compression (CAT) and schema ids are out of scope for
+ *   this version: those fields are zero.
+ * Journal records (journal_dst).  Record i occupies [60 i, 60 i + 60), a
+ *   MessageRecord (:1125) as writeMessageRecord fills it: @0 BE u16 (1 << 12)
+ *   | (refcount & 0xFFF); @2 the 6-byte BE sequence number first_seq + i; @8
+ *   BE lease_id; @12 BE u64 timestamps[i], else `timestamp`; @20 refcount >>
+ *   12 (refcount = the low 20 bits of ref_counts[i], else 1); @21 0 (CAT);
+ *   @22 queue_keys[5 i ..]; @27 file_key; @32 BE u32 MessageOffsetDwords =
+ *   (data_file_pos + Q[i]) / 8; @36 guids[16 i ..]; @52 the BE stored CRC;
+ *   @56 the magic 0x2A724563.
+ * CRC and verify on write.  out[i] (may be NULL) always receives the CRC32-C
+ *   computed from the bytes copied, seed 0.  Without `expected` that is the
+ *   stored CRC.  With `expected` (device, n, host order) the stored CRC is
+ *   expected[i] -- the broker stores the value that arrived in the PutHeader,
+ *   so a corrupt payload stays detectable at recovery -- and the call counts
+ *   the messages with out[i] != expected[i] (n_bad) and reports the lowest
+ *   (first_bad; n when none).  Mismatches do not fail the call.
+ * record_offsets (may be NULL): device, n + 1, receives Q; the last entry is
+ *   the total.
+ *
+ * Options.  Device pointers only: BMQCRC_F_DEVICE_PTRS is required,
+ *   BMQCRC_F_ASYNC allowed; any other flag, ndevices > 1, a wrong struct_size
+ *   or reserved, a null required array, dst not 8-byte or journal_dst not
+ *   4-byte aligned, data_file_pos zero or no multiple of 8 (recovery treats
+ *   offset 0 as invalid), lease_id 0, first_seq 0 or first_seq + n - 1 above
+ *   2^48 - 1, 60 n > journal_bytes, or any two of [src, +src_bytes), [dst,
+ *   +dst_bytes), [journal_dst, +journal_bytes) meeting is BMQCRC_EINVAL,
+ *   answered on the host before the device lookup.
+ * All or nothing, decided on the device (all sums in 64 bits): every R[i] / 4
+ *   within the DataHeader's 29 bits; every src_offsets[i] + lengths[i] <=
+ *   src_bytes; Q[n] <= dst_bytes; data_file_pos + Q[n] <= 8 (2^32 - 1), where
+ *   MessageOffsetDwords stops; and the payload within the copy kernel's
+ *   2^32 - 1 16-byte pieces (counted as len / 16 rounded up, plus one, per
+ *   non-empty message).  On any violation nothing is written to dst,
+ *   journal_dst, out or record_offsets; a synchronous call returns
+ *   BMQCRC_EINVAL naming the kind and the lowest offending message, and after
+ *   an asynchronous call bmqcrc_last_records_pack reports them.  Of several
+ *   violations the lowest kind is reported.
+ * *result (may be NULL) is written by a synchronous call only.
+ * State.  As bmqcrc_put_event_pack: takes the workspace mutex of (device,
+ *   stream); leaves the shape prediction and every bmqcrc_last_* record of
+ *   the batch, copy and PUT-pack calls as they were; restores the caller's
+ *   current device; allocates its own workspace on first use and when n grows
+ *   (12 bytes per message, 16 without `out`), which bmqcrc_reserve does not
+ *   cover; is not meant to be captured into a hipGraph; is deterministic.
+ *   n == 0 writes nothing and reports zeros. */
+#define BMQCRC_REC_PACK_OK 0
+#define BMQCRC_REC_PACK_RECORD_TOO_BIG 1  /* index: the lowest message with R/4 > 2^29-1 */
+#define BMQCRC_REC_PACK_SRC_RANGE 2       /* index: the lowest message outside src */
+#define BMQCRC_REC_PACK_DST_TOO_SMALL 3   /* index: the lowest message ending past dst_bytes */
+#define BMQCRC_REC_PACK_DATA_FILE_FULL 4  /* index: the lowest message ending past 8 (2^32-1) */
+#define BMQCRC_REC_PACK_TOO_MANY_PIECES 5 /* index 0: beyond the copy kernel's piece limit */
+
+typedef struct bmqcrc_records_pack {
+    uint32_t struct_size;          /* sizeof(bmqcrc_records_pack) */
+    uint32_t reserved;             /* 0 */
+    const void* src;               /* device: payload arena */
+    uint64_t src_bytes;
+    const uint64_t* src_offsets;   /* device, n */
+    const uint32_t* lengths;       /* device, n: application-data bytes */
+    const uint8_t* queue_keys;     /* device, 5 n */
+    const uint8_t* guids;          /* device, 16 n */
+    const uint8_t* data_flags;     /* device, n: DataHeader flags; NULL = 0 */
+    const uint32_t* ref_counts;    /* device, n, low 20 bits used; NULL = 1 */
+    const uint64_t* timestamps;    /* device, n; NULL = `timestamp` for all */
+    const uint32_t* expected;      /* device, n, host order: the CRCs to store and to check
+                                      against; NULL = store the computed ones */
+    uint8_t file_key[5];           /* the DATA file's key, into every record */
+    uint8_t reserved2[3];          /* ignored */
+    uint32_t lease_id;             /* primary lease id, not 0 */
+    uint64_t first_seq;            /* sequence number of message 0, not 0 */
+    uint64_t timestamp;
+    uint64_t data_file_pos;        /* byte position in the DATA file that dst stands for:
+                                      a multiple of 8, not 0 */
+    uint64_t n;
+    void* dst;                     /* device, 8-byte aligned: DATA records back to back */
+    uint64_t dst_bytes;
+    void* journal_dst;             /* device, 4-byte aligned: 60-byte records back to back */
+    uint64_t journal_bytes;        /* at least 60 n */
+    uint64_t* record_offsets;      /* device, n + 1, may be NULL: Q, the total last */
+    uint32_t* out;                 /* device, n, may be NULL: the computed CRCs (host order) */
+} bmqcrc_records_pack;
+
+/* All fields zero before the first call on (device, stream). */
+typedef struct bmqcrc_records_result {
+    uint64_t n_msgs;
+    uint64_t data_bytes;           /* Q[n]; 0 when refused */
+    uint64_t journal_bytes;        /* 60 n; 0 when refused */
+    uint64_t n_bad;                /* messages whose computed CRC differs from expected[] */
+    uint64_t first_bad;            /* the lowest of them; n_msgs when none */
+    uint32_t refused_kind;         /* BMQCRC_REC_PACK_OK or the kind refused */
+    uint32_t reserved;             /* 0 */
+    uint64_t refused_index;
+} bmqcrc_records_result;
+
+int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_result* result,
+                                const bmqcrc_opts* opts);
+
+/* ABI 2.11.  Result of the previous bmqcrc_message_records_pack on (device,
+ * stream); waits for it.  `result` may be NULL. */
+int bmqcrc_last_records_pack(int device, void* stream, bmqcrc_records_result* result);
+
 /* ---- partition recovery (mqbs_filestoreprotocol.h:306,426,483,703,953-1990) */
 
 /* mqbs::FileStore::recoverMessages result codes (mqbs_filestore.cpp:1073-1091)

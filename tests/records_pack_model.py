@@ -1,0 +1,136 @@
+"""The DATA-record and journal-record layout of bmqcrc_message_records_pack
+(ABI 2.11) restated in numpy, and its oracle (shared by
+test_records_pack_model.py and test_gpu_records_pack.py; not a test module).
+
+R[i] = 12 + lengths[i] + pad, pad = 8 - (12 + lengths[i]) % 8 (1..8), Q = the
+64-bit exclusive prefix of R:
+
+    DATA record i      at Q[i]: DataHeader (12), application data, padding
+    journal record i   at 60 i, MessageOffsetDwords = (data_file_pos + Q[i]) / 8
+"""
+import os
+
+import numpy as np
+
+from blazingmq_amd import Crc32c
+from blazingmq_amd import storage as S
+
+DH, REC = 12, 60
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def pad_of(lens):
+    return 8 - (DH + np.asarray(lens, np.int64)) % 8
+
+
+def layout(lens):
+    """(R, Q with the total last)."""
+    lens = np.asarray(lens, np.int64)
+    R = DH + lens + pad_of(lens)
+    return R, np.concatenate([[0], np.cumsum(R)]).astype(np.int64)
+
+
+def _opt(a, i, default):
+    return default if a is None else int(a[i])
+
+
+def model_bytes(src, soff, lens, qkeys, guids, stored_crcs, *, file_key, lease_id, first_seq,
+                data_file_pos, timestamp=0, timestamps=None, ref_counts=None, data_flags=None):
+    """(DATA bytes, journal bytes) from the formulas alone (no PartitionWriter).
+    `stored_crcs` is what the journal holds: the computed CRCs, or `expected`."""
+    lens = np.asarray(lens, np.int64)
+    R, Q = layout(lens)
+    n = lens.size
+    data = np.zeros(int(Q[-1]), np.uint8)
+    jour = np.zeros(REC * n, np.uint8)
+    for i in range(n):
+        q, ln, r = int(Q[i]), int(lens[i]), int(R[i])
+        pad = r - DH - ln
+        head = ((3 << 29) | (r // 4)).to_bytes(4, "big") + \
+            (_opt(data_flags, i, 0) & 0xFF).to_bytes(4, "big") + bytes(4)
+        data[q:q + DH] = np.frombuffer(head, np.uint8)
+        data[q + DH:q + DH + ln] = src[int(soff[i]):int(soff[i]) + ln]
+        data[q + DH + ln:q + r] = pad
+        rc = _opt(ref_counts, i, 1) & 0xFFFFF
+        rec = ((1 << 12) | (rc & 0xFFF)).to_bytes(2, "big") + \
+            (int(first_seq) + i).to_bytes(6, "big") + int(lease_id).to_bytes(4, "big") + \
+            _opt(timestamps, i, int(timestamp)).to_bytes(8, "big") + bytes([rc >> 12, 0]) + \
+            bytes(qkeys[i]) + bytes(file_key) + \
+            ((int(data_file_pos) + q) // 8).to_bytes(4, "big") + bytes(guids[i]) + \
+            int(stored_crcs[i]).to_bytes(4, "big") + (0x2A724563).to_bytes(4, "big")
+        assert len(rec) == REC
+        jour[REC * i:REC * (i + 1)] = np.frombuffer(rec, np.uint8)
+    return data, jour
+
+
+def _writer(lease_id, first_seq, data_file_pos, timestamp):
+    """A PartitionWriter about to write sequence number `first_seq` of
+    `lease_id` at byte `data_file_pos` of its DATA file."""
+    w = S.PartitionWriter(lease_id=int(lease_id), timestamp=int(timestamp))
+    w.seq = int(first_seq) - 1
+    w.dpos = int(data_file_pos)
+    return w
+
+
+def oracle_bytes(src, soff, lens, qkeys, guids, stored_crcs, *, file_key, lease_id, first_seq,
+                 data_file_pos, timestamp=0, timestamps=None, ref_counts=None, data_flags=None):
+    """(DATA bytes, journal bytes) as PartitionWriter.message appends them."""
+    w = _writer(lease_id, first_seq, data_file_pos, timestamp)
+    n_data = len(w.data)
+    for i in range(len(lens)):
+        so, ln = int(soff[i]), int(lens[i])
+        w.message(src[so:so + ln].tobytes(), bytes(qkeys[i]), crc=int(stored_crcs[i]),
+                  guid=bytes(guids[i]), file_key=bytes(file_key),
+                  ref_count=_opt(ref_counts, i, 1), data_flags=_opt(data_flags, i, 0),
+                  timestamp=None if timestamps is None else int(timestamps[i]))
+    return (np.frombuffer(b"".join(w.data[n_data:]), np.uint8).copy(),
+            np.frombuffer(b"".join(w.recs), np.uint8).copy())
+
+
+def wrap_partition(data, jour, queue_key, lease_id=1):
+    """(journal file, DATA file): the packed bytes behind the file headers and
+    one QueueOp CREATION record of `queue_key` with sequence number 1, so the
+    pack's first_seq is 2 and its data_file_pos 40."""
+    w = S.PartitionWriter(lease_id=int(lease_id))
+    w.queue_op(S.OP_CREATION, bytes(queue_key))
+    j, d = w.files()
+    return (np.concatenate([j, np.asarray(jour, np.uint8)]),
+            np.concatenate([d, np.asarray(data, np.uint8)]))
+
+
+def host_crcs(src, soff, lens):
+    return np.array([Crc32c.calculate(src[int(s):int(s) + int(l)].tobytes())
+                     for s, l in zip(soff, lens)], np.uint32)
+
+
+def random_meta(rng, n):
+    """(queue keys (n, 5), guids (n, 16), both never all zero)."""
+    qkeys = rng.integers(1, 256, size=(n, 5), dtype=np.uint8)
+    guids = rng.integers(1, 256, size=(n, 16), dtype=np.uint8)
+    return qkeys, guids
+
+
+# The two MESSAGE records of the reference's fixture partition: (journal
+# offset, DATA bytes [a, b)); every field of the pack comes from the records.
+GOLDEN_RECORDS = ((44 + 60 * 3, 40, 64), (44 + 60 * 10, 64, 88))
+
+
+def golden_case(k):
+    """Arguments that reproduce fixture record k as an n = 1 pack: (src, soff,
+    lens, qkeys, guids, stored crc, keywords, expected DATA bytes, expected
+    journal bytes)."""
+    j = np.fromfile(os.path.join(GOLDEN, "test.bmq_journal"), np.uint8)
+    d = np.fromfile(os.path.join(GOLDEN, "test.bmq_data"), np.uint8)
+    at, a, b = GOLDEN_RECORDS[k]
+    r = j[at:at + REC]
+    be = lambda lo, hi: int.from_bytes(r[lo:hi].tobytes(), "big")  # noqa: E731
+    assert r[0] >> 4 == S.REC_MESSAGE and be(32, 36) * 8 == a
+    pad = int(d[b - 1])
+    app = d[a + DH:b - pad].copy()
+    assert d[a:a + DH].tobytes() == (((3 << 29) | ((b - a) // 4)).to_bytes(4, "big") + bytes(8))
+    kw = dict(file_key=r[27:32].tobytes(), lease_id=be(8, 12), first_seq=be(2, 8),
+              data_file_pos=a, timestamp=be(12, 20),
+              ref_counts=np.array([(int(r[20]) << 12) | (be(0, 2) & 0xFFF)], np.uint32))
+    return (app, np.array([0]), np.array([app.size]), r[22:27].reshape(1, 5).copy(),
+            r[36:52].reshape(1, 16).copy(), np.array([be(52, 56)], np.uint32), kw,
+            d[a:b].copy(), r.copy())
