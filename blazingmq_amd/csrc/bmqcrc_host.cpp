@@ -101,6 +101,27 @@ struct DevBuf {
     }
 };
 
+// Scratch of one device packer (bmqcrc_put_event_pack,
+// bmqcrc_message_records_pack): data offsets, the copy pass's piece prefix,
+// the CRCs when the caller wants none, the layout's and the copy pass's block
+// sums, and the counters of the layout (ctr_words) followed by the copy
+// pass's (kCopyCtrWords); the size of the last pack enqueued (bmqcrc_last_*).
+struct PackScratch {
+    DevBuf off, first, out, bsum, copy_bsum, ctr;
+    uint64_t n = 0;
+    bool any = false;
+    // (first and copy_bsum are sized by enqueue_copy)
+    int ensure(uint64_t n_msgs, int ctr_words, bool need_out)
+    {
+        int rc;
+        if ((rc = ctr.ensure(8 * (ctr_words + kCopyCtrWords))) ||
+            (rc = bsum.ensure(8ull * 2 * kPackBlocks)) || (rc = off.ensure(8 * n_msgs))) {
+            return rc;
+        }
+        return need_out ? out.ensure(4 * n_msgs) : 0;
+    }
+};
+
 // Planner + staging scratch for one (device, stream).
 struct Workspace {
     std::mutex mu;
@@ -132,19 +153,11 @@ struct Workspace {
     DevBuf copy_first, copy_bsum, copy_ctr;
     uint64_t copy_n = 0;
     bool copy_any = false;
-    // bmqcrc_put_event_pack: data offsets, the copy pass's scratch, the CRCs
-    // when the caller wants none, block sums, and the counters of the layout
-    // (kPackCtrWords) followed by the copy pass's (kCopyCtrWords); the size
-    // of the last pack enqueued here (bmqcrc_last_put_pack)
-    DevBuf pack_off, pack_first, pack_out, pack_bsum, pack_copy_bsum, pack_ctr;
-    uint64_t pack_n = 0, pack_events = 0;
-    bool pack_any = false;
-    // bmqcrc_message_records_pack: the same set of its own (the counters are
-    // kRecCtrWords followed by the copy pass's kCopyCtrWords) and the size of
-    // the last pack enqueued here (bmqcrc_last_records_pack)
-    DevBuf rec_off, rec_first, rec_out, rec_bsum, rec_copy_bsum, rec_ctr;
-    uint64_t rec_n = 0;
-    bool rec_any = false;
+    // bmqcrc_put_event_pack and bmqcrc_message_records_pack: a set each,
+    // because bmqcrc_last_put_pack and bmqcrc_last_records_pack report
+    // independently; the events of the last PUT pack
+    PackScratch pack, rec;
+    uint64_t pack_events = 0;
     // Pinned staging ring for gathered host buffers (bmqcrc_crc32c_gather):
     // kGatherSlots chunks of kGatherChunk bytes, each reusable once the event
     // recorded after its H2D copy has completed.
@@ -1805,6 +1818,69 @@ int bmqcrc_kernel_timing(int device, void* stream, double* total_ms, uint32_t* c
     return 0;
 }
 
+}  // extern "C"
+
+// ---- the calls that take device pointers only: the fused copy, the packers --
+namespace {
+
+// Their bmqcrc_opts, with `call` naming the entry point in the refusals.
+// Answers without a device: the call's own argument checks follow it, and
+// only then the device lookup.
+int device_call_opts(const bmqcrc_opts* opts, const std::string& call, bmqcrc_opts* o)
+{
+    memset(o, 0, sizeof(*o));
+    o->device = -1;
+    if (opts) {
+        const size_t given = opts->struct_size ? opts->struct_size : offsetof(bmqcrc_opts, ndevices);
+        memcpy(o, opts, std::min<size_t>(sizeof(*o), given));
+    }
+    static const struct {
+        uint32_t bit;
+        const char* name;
+    } refused[] = {{BMQCRC_F_TIME_KERNEL, "BMQCRC_F_TIME_KERNEL"},
+                   {BMQCRC_F_WHOLE_MESSAGES, "BMQCRC_F_WHOLE_MESSAGES"},
+                   {BMQCRC_F_PLAN, "BMQCRC_F_PLAN"},
+                   {BMQCRC_F_OFFSETS32, "BMQCRC_F_OFFSETS32"}};
+    for (const auto& r : refused) {
+        if (o->flags & r.bit) {
+            return fail(BMQCRC_EINVAL, std::string(r.name) + " does not apply to " + call);
+        }
+    }
+    if (o->flags & ~(BMQCRC_F_DEVICE_PTRS | BMQCRC_F_ASYNC)) {
+        return fail(BMQCRC_EINVAL, "unknown bmqcrc_opts.flags bits");
+    }
+    if (!(o->flags & BMQCRC_F_DEVICE_PTRS)) {
+        return fail(BMQCRC_EINVAL,
+                    call + " takes device pointers only: BMQCRC_F_DEVICE_PTRS is required");
+    }
+    if (o->ndevices > 1) {
+        return fail(BMQCRC_EINVAL, call + " runs on one device: ndevices > 1");
+    }
+    return 0;
+}
+
+// The context of (device, stream) as a call or a bmqcrc_last_* query names it.
+int open_on(int device, void* stream, Ctx* c)
+{
+    int dev;
+    const int rc = resolve_device(device, &dev);
+    return rc ? rc : open_ctx(dev, stream, c);
+}
+
+static_assert(kCopyPlanThreads == kPackThreads && kCopyPlanBlocks == kPackBlocks,
+              "layout_split: the copy's and the packers' pre-kernels share one grid split");
+
+// Contiguous message ranges of whole kPackThreads tiles for at most
+// kPackBlocks blocks (n > 0).
+void layout_split(uint64_t n, uint64_t* per_block, uint32_t* nblocks)
+{
+    const uint64_t tiles = (n + kPackThreads - 1) / kPackThreads;
+    const uint64_t nb = std::min<uint64_t>(tiles, kPackBlocks);
+    const uint64_t tiles_per = (tiles + nb - 1) / nb;
+    *per_block = tiles_per * kPackThreads;
+    *nblocks = (uint32_t)((tiles + tiles_per - 1) / tiles_per);
+}
+
 // Counters of the copy last enqueued on c's workspace, after everything
 // enqueued on its stream (w->mu held).
 static int copy_result(Ctx& c, unsigned long long (&ctr)[kCopyCtrWords])
@@ -1839,11 +1915,7 @@ static int enqueue_copy(Ctx& c, CopyArgs a, DevBuf& first, DevBuf& bsum, void* c
         a.first = (uint32_t*)first.p;
         a.bsum = (unsigned long long*)bsum.p;
         a.ctr = (unsigned long long*)ctr;
-        const uint64_t tiles = (a.n + kCopyPlanThreads - 1) / kCopyPlanThreads;
-        const uint64_t nb = std::min<uint64_t>(tiles, kCopyPlanBlocks);
-        const uint64_t tiles_per = (tiles + nb - 1) / nb;
-        a.per_block = tiles_per * kCopyPlanThreads;
-        a.nblocks = (uint32_t)((tiles + tiles_per - 1) / tiles_per);
+        layout_split(a.n, &a.per_block, &a.nblocks);
         if (bmqcrc_launch_copy(&a, (void*)c.s, c.st->copy_blocks)) {
             return fail(BMQCRC_EIO, std::string("copy launch failed: ") +
                                         hipGetErrorString(hipGetLastError()));
@@ -1851,6 +1923,51 @@ static int enqueue_copy(Ctx& c, CopyArgs a, DevBuf& first, DevBuf& bsum, void* c
     }
     return 0;
 }
+
+// The payload pass of a packer: the messages of `a` (PackArgs or RecArgs)
+// copied from `src` to where the layout placed them (a.off), their CRCs to
+// a.out, the copy's counters behind the layout's ctr_words.
+template <class Args>
+int enqueue_payload(Ctx& c, PackScratch& s, int ctr_words, const void* src, const Args& a)
+{
+    CopyArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.src = (const uint8_t*)src;
+    ca.src_bytes = a.src_bytes;
+    ca.src_offsets = a.src_offsets;
+    ca.lengths = a.lengths;
+    ca.dst = a.dst;
+    ca.dst_bytes = a.dst_bytes;
+    ca.dst_offsets = (const uint64_t*)a.off;
+    ca.out = (uint32_t*)a.out;
+    ca.n = a.n;
+    return enqueue_copy(c, ca, s.first, s.copy_bsum, a.ctr + ctr_words);
+}
+
+// Counters of the pack last enqueued on `s`, after everything enqueued on c's
+// stream (w->mu held): ctr[] receives the layout's ctr_words and the copy
+// pass's kCopyCtrWords, kind and index the refusal (kind 0: nothing refused).
+int pack_counters(Ctx& c, const PackScratch& s, int ctr_words, const char* call,
+                  unsigned long long* ctr, uint32_t* kind, uint64_t* index)
+{
+    HIP_TRY(hipMemcpyAsync(ctr, s.ctr.p, 8 * (ctr_words + kCopyCtrWords), hipMemcpyDeviceToHost,
+                           c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    const unsigned long long key = ctr[kLayoutCtrRefusal] ? ~ctr[kLayoutCtrRefusal] : 0;
+    *kind = (uint32_t)(key >> 56);
+    *index = key & ((1ull << 56) - 1);
+    // the layout placed every message inside dst: the copy pass has nothing to refuse
+    const unsigned long long* cc = ctr + ctr_words;
+    if (!*kind && (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow])) {
+        return fail(BMQCRC_EIO, std::string(call) + ": the copy pass refused a message the "
+                                                    "layout had placed (internal error)");
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
 
 int bmqcrc_crc32c_copy(const void* src, uint64_t src_bytes, const uint64_t* src_offsets,
                        const uint32_t* lengths, void* dst, uint64_t dst_bytes,
@@ -1861,33 +1978,9 @@ int bmqcrc_crc32c_copy(const void* src, uint64_t src_bytes, const uint64_t* src_
     DeviceGuard keep_device;
     // every refusal below answers before the device lookup (no GPU needed)
     bmqcrc_opts o;
-    memset(&o, 0, sizeof(o));
-    o.device = -1;
-    if (opts) {
-        const size_t given = opts->struct_size ? opts->struct_size : offsetof(bmqcrc_opts, ndevices);
-        memcpy(&o, opts, std::min<size_t>(sizeof(o), given));
-    }
-    static const struct {
-        uint32_t bit;
-        const char* name;
-    } refused[] = {{BMQCRC_F_TIME_KERNEL, "BMQCRC_F_TIME_KERNEL"},
-                   {BMQCRC_F_WHOLE_MESSAGES, "BMQCRC_F_WHOLE_MESSAGES"},
-                   {BMQCRC_F_PLAN, "BMQCRC_F_PLAN"},
-                   {BMQCRC_F_OFFSETS32, "BMQCRC_F_OFFSETS32"}};
-    for (const auto& r : refused) {
-        if (o.flags & r.bit) {
-            return fail(BMQCRC_EINVAL, std::string(r.name) + " does not apply to bmqcrc_crc32c_copy");
-        }
-    }
-    if (o.flags & ~(BMQCRC_F_DEVICE_PTRS | BMQCRC_F_ASYNC)) {
-        return fail(BMQCRC_EINVAL, "unknown bmqcrc_opts.flags bits");
-    }
-    if (!(o.flags & BMQCRC_F_DEVICE_PTRS)) {
-        return fail(BMQCRC_EINVAL, "bmqcrc_crc32c_copy takes device pointers only: "
-                                   "BMQCRC_F_DEVICE_PTRS is required");
-    }
-    if (o.ndevices > 1) {
-        return fail(BMQCRC_EINVAL, "bmqcrc_crc32c_copy runs on one device: ndevices > 1");
+    int rc;
+    if ((rc = device_call_opts(opts, "bmqcrc_crc32c_copy", &o))) {
+        return rc;
     }
     if (n > 0xFFFFFFFFull) {
         return fail(BMQCRC_EINVAL, "at most 2^32-1 messages per batch");
@@ -1896,12 +1989,8 @@ int bmqcrc_crc32c_copy(const void* src, uint64_t src_bytes, const uint64_t* src_
               (!dst && dst_bytes))) {
         return fail(BMQCRC_EINVAL, "null pointer argument");
     }
-    int dev, rc;
-    if ((rc = resolve_device(o.device, &dev))) {
-        return rc;
-    }
     Ctx c;
-    if ((rc = open_ctx(dev, o.stream, &c))) {
+    if ((rc = open_on(o.device, o.stream, &c))) {
         return rc;
     }
     Workspace* w = c.w;
@@ -1950,12 +2039,9 @@ int bmqcrc_last_copy(int device, void* stream, uint64_t* n_msgs, uint64_t* n_ref
 {
     t_err.clear();
     DeviceGuard keep_device;
-    int dev, rc;
-    if ((rc = resolve_device(device, &dev))) {
-        return rc;
-    }
     Ctx c;
-    if ((rc = open_ctx(dev, stream, &c))) {
+    int rc;
+    if ((rc = open_on(device, stream, &c))) {
         return rc;
     }
     std::lock_guard<std::mutex> g(c.w->mu);
@@ -1993,19 +2079,10 @@ constexpr uint64_t kPutMaxEventBytes = ((1ull << 28) - 1) * 4;  // 28 bits of Me
 static int pack_result(Ctx& c, uint32_t* kind, uint64_t* index, uint64_t* total)
 {
     unsigned long long ctr[kPackCtrWords + kCopyCtrWords];
-    HIP_TRY(hipMemcpyAsync(ctr, c.w->pack_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
-    HIP_TRY(hipStreamSynchronize(c.s));
-    const unsigned long long key = ctr[kPackCtrRefusal] ? ~ctr[kPackCtrRefusal] : 0;
-    *kind = (uint32_t)(key >> 56);
-    *index = key & ((1ull << 56) - 1);
-    *total = *kind ? 0 : ctr[kPackCtrTotal];
-    // the layout placed every message inside dst: the copy pass has nothing to refuse
-    const unsigned long long* cc = ctr + kPackCtrWords;
-    if (!*kind && (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow])) {
-        return fail(BMQCRC_EIO, "bmqcrc_put_event_pack: the copy pass refused a message the "
-                                "layout had placed (internal error)");
-    }
-    return 0;
+    const int rc =
+        pack_counters(c, c.w->pack, kPackCtrWords, "bmqcrc_put_event_pack", ctr, kind, index);
+    *total = rc || *kind ? 0 : ctr[kPackCtrTotal];
+    return rc;
 }
 
 static int pack_refusal(uint32_t kind, uint64_t index)
@@ -2034,34 +2111,9 @@ int bmqcrc_put_event_pack(const bmqcrc_put_pack* p, uint64_t* total_bytes, const
         return fail(BMQCRC_EINVAL, "bmqcrc_put_pack.reserved must be 0");
     }
     bmqcrc_opts o;
-    memset(&o, 0, sizeof(o));
-    o.device = -1;
-    if (opts) {
-        const size_t given = opts->struct_size ? opts->struct_size : offsetof(bmqcrc_opts, ndevices);
-        memcpy(&o, opts, std::min<size_t>(sizeof(o), given));
-    }
-    static const struct {
-        uint32_t bit;
-        const char* name;
-    } refused[] = {{BMQCRC_F_TIME_KERNEL, "BMQCRC_F_TIME_KERNEL"},
-                   {BMQCRC_F_WHOLE_MESSAGES, "BMQCRC_F_WHOLE_MESSAGES"},
-                   {BMQCRC_F_PLAN, "BMQCRC_F_PLAN"},
-                   {BMQCRC_F_OFFSETS32, "BMQCRC_F_OFFSETS32"}};
-    for (const auto& r : refused) {
-        if (o.flags & r.bit) {
-            return fail(BMQCRC_EINVAL,
-                        std::string(r.name) + " does not apply to bmqcrc_put_event_pack");
-        }
-    }
-    if (o.flags & ~(BMQCRC_F_DEVICE_PTRS | BMQCRC_F_ASYNC)) {
-        return fail(BMQCRC_EINVAL, "unknown bmqcrc_opts.flags bits");
-    }
-    if (!(o.flags & BMQCRC_F_DEVICE_PTRS)) {
-        return fail(BMQCRC_EINVAL, "bmqcrc_put_event_pack takes device pointers only: "
-                                   "BMQCRC_F_DEVICE_PTRS is required");
-    }
-    if (o.ndevices > 1) {
-        return fail(BMQCRC_EINVAL, "bmqcrc_put_event_pack runs on one device: ndevices > 1");
+    int rc;
+    if ((rc = device_call_opts(opts, "bmqcrc_put_event_pack", &o))) {
+        return rc;
     }
     const uint64_t n = p->n;
     if (n > 0xFFFFFFFFull) {
@@ -2098,24 +2150,16 @@ int bmqcrc_put_event_pack(const bmqcrc_put_pack* p, uint64_t* total_bytes, const
     if (n && (p->n_events < 1 || p->n_events > n)) {
         return fail(BMQCRC_EINVAL, "n_events must lie in [1, n]: no event is empty");
     }
-    int dev, rc;
-    if ((rc = resolve_device(o.device, &dev))) {
-        return rc;
-    }
     Ctx c;
-    if ((rc = open_ctx(dev, o.stream, &c))) {
+    if ((rc = open_on(o.device, o.stream, &c))) {
         return rc;
     }
     Workspace* w = c.w;
     std::lock_guard<std::mutex> g(w->mu);
-    if ((rc = w->pack_ctr.ensure(8 * (kPackCtrWords + kCopyCtrWords))) ||
-        (rc = w->pack_bsum.ensure(8ull * 2 * kPackBlocks)) ||
-        (rc = w->pack_off.ensure(8 * n)) || (!p->out && (rc = w->pack_out.ensure(4 * n)))) {
+    if ((rc = w->pack.ensure(n, kPackCtrWords, !p->out))) {
         return rc;
     }
-    unsigned long long* ctr = (unsigned long long*)w->pack_ctr.p;
-    HIP_TRY(hipMemsetAsync(ctr, 0, 8 * kPackCtrWords, c.s));
-    uint32_t* crcs = p->out ? p->out : (uint32_t*)w->pack_out.p;
+    HIP_TRY(hipMemsetAsync(w->pack.ctr.p, 0, 8 * kPackCtrWords, c.s));
     PackArgs a;
     memset(&a, 0, sizeof(a));
     a.src_bytes = p->src_bytes;
@@ -2131,42 +2175,27 @@ int bmqcrc_put_event_pack(const bmqcrc_put_pack* p, uint64_t* total_bytes, const
     a.dst = (uint8_t*)p->dst;
     a.dst_bytes = p->dst_bytes;
     a.event_offsets = p->event_offsets;
-    a.out = crcs;
-    a.off = (unsigned long long*)w->pack_off.p;
-    a.bsum = (unsigned long long*)w->pack_bsum.p;
-    a.ctr = ctr;
+    a.out = p->out ? p->out : (uint32_t*)w->pack.out.p;
+    a.off = (unsigned long long*)w->pack.off.p;
+    a.bsum = (unsigned long long*)w->pack.bsum.p;
+    a.ctr = (unsigned long long*)w->pack.ctr.p;
     if (n) {
-        const uint64_t tiles = (n + kPackThreads - 1) / kPackThreads;
-        const uint64_t nb = std::min<uint64_t>(tiles, kPackBlocks);
-        const uint64_t tiles_per = (tiles + nb - 1) / nb;
-        a.per_block = tiles_per * kPackThreads;
-        a.nblocks = (uint32_t)((tiles + tiles_per - 1) / tiles_per);
+        layout_split(n, &a.per_block, &a.nblocks);
         if (bmqcrc_launch_put_layout(&a, (void*)c.s)) {
             return fail(BMQCRC_EIO, std::string("put-pack layout launch failed: ") +
                                         hipGetErrorString(hipGetLastError()));
         }
     }
-    CopyArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.src = (const uint8_t*)p->src;
-    ca.src_bytes = p->src_bytes;
-    ca.src_offsets = p->src_offsets;
-    ca.lengths = p->lengths;
-    ca.dst = (uint8_t*)p->dst;
-    ca.dst_bytes = p->dst_bytes;
-    ca.dst_offsets = (const uint64_t*)w->pack_off.p;
-    ca.out = crcs;
-    ca.n = n;
-    if ((rc = enqueue_copy(c, ca, w->pack_first, w->pack_copy_bsum, ctr + kPackCtrWords))) {
+    if ((rc = enqueue_payload(c, w->pack, kPackCtrWords, p->src, a))) {
         return rc;
     }
     if (n && bmqcrc_launch_put_frame(&a, (void*)c.s)) {
         return fail(BMQCRC_EIO, std::string("put-pack frame launch failed: ") +
                                     hipGetErrorString(hipGetLastError()));
     }
-    w->pack_n = n;
+    w->pack.n = n;
     w->pack_events = a.n_events;
-    w->pack_any = true;
+    w->pack.any = true;
     if (o.flags & BMQCRC_F_ASYNC) {
         return 0;
     }
@@ -2186,22 +2215,19 @@ int bmqcrc_last_put_pack(int device, void* stream, uint64_t* n_msgs, uint64_t* n
 {
     t_err.clear();
     DeviceGuard keep_device;
-    int dev, rc;
-    if ((rc = resolve_device(device, &dev))) {
-        return rc;
-    }
     Ctx c;
-    if ((rc = open_ctx(dev, stream, &c))) {
+    int rc;
+    if ((rc = open_on(device, stream, &c))) {
         return rc;
     }
     std::lock_guard<std::mutex> g(c.w->mu);
     uint32_t kind = 0;
     uint64_t index = 0, total = 0;
-    if (c.w->pack_any && (rc = pack_result(c, &kind, &index, &total))) {
+    if (c.w->pack.any && (rc = pack_result(c, &kind, &index, &total))) {
         return rc;
     }
     if (n_msgs) {
-        *n_msgs = c.w->pack_n;
+        *n_msgs = c.w->pack.n;
     }
     if (n_events) {
         *n_events = c.w->pack_events;
@@ -2233,16 +2259,16 @@ constexpr uint64_t kMaxSeqNum = (1ull << 48) - 1;  // RecordHeader: 48 bits of s
 static int records_result(Ctx& c, bmqcrc_records_result* r)
 {
     memset(r, 0, sizeof(*r));
-    if (!c.w->rec_any) {
+    if (!c.w->rec.any) {
         return 0;
     }
     unsigned long long ctr[kRecCtrWords + kCopyCtrWords];
-    HIP_TRY(hipMemcpyAsync(ctr, c.w->rec_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
-    HIP_TRY(hipStreamSynchronize(c.s));
-    const unsigned long long key = ctr[kRecCtrRefusal] ? ~ctr[kRecCtrRefusal] : 0;
-    r->n_msgs = c.w->rec_n;
-    r->refused_kind = (uint32_t)(key >> 56);
-    r->refused_index = key & ((1ull << 56) - 1);
+    const int rc = pack_counters(c, c.w->rec, kRecCtrWords, "bmqcrc_message_records_pack", ctr,
+                                 &r->refused_kind, &r->refused_index);
+    if (rc) {
+        return rc;
+    }
+    r->n_msgs = c.w->rec.n;
     r->first_bad = r->n_msgs;
     if (r->refused_kind) {
         return 0;
@@ -2252,12 +2278,6 @@ static int records_result(Ctx& c, bmqcrc_records_result* r)
     r->n_bad = ctr[kRecCtrBad];
     if (r->n_bad) {
         r->first_bad = ~ctr[kRecCtrFirstBad];
-    }
-    // the layout placed every message inside dst: the copy pass has nothing to refuse
-    const unsigned long long* cc = ctr + kRecCtrWords;
-    if (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow]) {
-        return fail(BMQCRC_EIO, "bmqcrc_message_records_pack: the copy pass refused a message "
-                                "the layout had placed (internal error)");
     }
     return 0;
 }
@@ -2291,34 +2311,9 @@ int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_res
         return fail(BMQCRC_EINVAL, "bmqcrc_records_pack.reserved must be 0");
     }
     bmqcrc_opts o;
-    memset(&o, 0, sizeof(o));
-    o.device = -1;
-    if (opts) {
-        const size_t given = opts->struct_size ? opts->struct_size : offsetof(bmqcrc_opts, ndevices);
-        memcpy(&o, opts, std::min<size_t>(sizeof(o), given));
-    }
-    static const struct {
-        uint32_t bit;
-        const char* name;
-    } refused[] = {{BMQCRC_F_TIME_KERNEL, "BMQCRC_F_TIME_KERNEL"},
-                   {BMQCRC_F_WHOLE_MESSAGES, "BMQCRC_F_WHOLE_MESSAGES"},
-                   {BMQCRC_F_PLAN, "BMQCRC_F_PLAN"},
-                   {BMQCRC_F_OFFSETS32, "BMQCRC_F_OFFSETS32"}};
-    for (const auto& r : refused) {
-        if (o.flags & r.bit) {
-            return fail(BMQCRC_EINVAL,
-                        std::string(r.name) + " does not apply to bmqcrc_message_records_pack");
-        }
-    }
-    if (o.flags & ~(BMQCRC_F_DEVICE_PTRS | BMQCRC_F_ASYNC)) {
-        return fail(BMQCRC_EINVAL, "unknown bmqcrc_opts.flags bits");
-    }
-    if (!(o.flags & BMQCRC_F_DEVICE_PTRS)) {
-        return fail(BMQCRC_EINVAL, "bmqcrc_message_records_pack takes device pointers only: "
-                                   "BMQCRC_F_DEVICE_PTRS is required");
-    }
-    if (o.ndevices > 1) {
-        return fail(BMQCRC_EINVAL, "bmqcrc_message_records_pack runs on one device: ndevices > 1");
+    int rc;
+    if ((rc = device_call_opts(opts, "bmqcrc_message_records_pack", &o))) {
+        return rc;
     }
     const uint64_t n = p->n;
     if (n > 0xFFFFFFFFull) {
@@ -2376,24 +2371,16 @@ int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_res
             }
         }
     }
-    int dev, rc;
-    if ((rc = resolve_device(o.device, &dev))) {
-        return rc;
-    }
     Ctx c;
-    if ((rc = open_ctx(dev, o.stream, &c))) {
+    if ((rc = open_on(o.device, o.stream, &c))) {
         return rc;
     }
     Workspace* w = c.w;
     std::lock_guard<std::mutex> g(w->mu);
-    if ((rc = w->rec_ctr.ensure(8 * (kRecCtrWords + kCopyCtrWords))) ||
-        (rc = w->rec_bsum.ensure(8ull * 2 * kPackBlocks)) || (rc = w->rec_off.ensure(8 * n)) ||
-        (!p->out && (rc = w->rec_out.ensure(4 * n)))) {
+    if ((rc = w->rec.ensure(n, kRecCtrWords, !p->out))) {
         return rc;
     }
-    unsigned long long* ctr = (unsigned long long*)w->rec_ctr.p;
-    HIP_TRY(hipMemsetAsync(ctr, 0, 8 * kRecCtrWords, c.s));
-    uint32_t* crcs = p->out ? p->out : (uint32_t*)w->rec_out.p;
+    HIP_TRY(hipMemsetAsync(w->rec.ctr.p, 0, 8 * kRecCtrWords, c.s));
     RecArgs a;
     memset(&a, 0, sizeof(a));
     a.src_bytes = p->src_bytes;
@@ -2418,41 +2405,26 @@ int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_res
     a.dst_bytes = p->dst_bytes;
     a.journal = (uint8_t*)p->journal_dst;
     a.record_offsets = p->record_offsets;
-    a.out = crcs;
-    a.off = (unsigned long long*)w->rec_off.p;
-    a.bsum = (unsigned long long*)w->rec_bsum.p;
-    a.ctr = ctr;
+    a.out = p->out ? p->out : (uint32_t*)w->rec.out.p;
+    a.off = (unsigned long long*)w->rec.off.p;
+    a.bsum = (unsigned long long*)w->rec.bsum.p;
+    a.ctr = (unsigned long long*)w->rec.ctr.p;
     if (n) {
-        const uint64_t tiles = (n + kPackThreads - 1) / kPackThreads;
-        const uint64_t nb = std::min<uint64_t>(tiles, kPackBlocks);
-        const uint64_t tiles_per = (tiles + nb - 1) / nb;
-        a.per_block = tiles_per * kPackThreads;
-        a.nblocks = (uint32_t)((tiles + tiles_per - 1) / tiles_per);
+        layout_split(n, &a.per_block, &a.nblocks);
         if (bmqcrc_launch_records_layout(&a, (void*)c.s)) {
             return fail(BMQCRC_EIO, std::string("records-pack layout launch failed: ") +
                                         hipGetErrorString(hipGetLastError()));
         }
     }
-    CopyArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.src = (const uint8_t*)p->src;
-    ca.src_bytes = p->src_bytes;
-    ca.src_offsets = p->src_offsets;
-    ca.lengths = p->lengths;
-    ca.dst = (uint8_t*)p->dst;
-    ca.dst_bytes = p->dst_bytes;
-    ca.dst_offsets = (const uint64_t*)w->rec_off.p;
-    ca.out = crcs;
-    ca.n = n;
-    if ((rc = enqueue_copy(c, ca, w->rec_first, w->rec_copy_bsum, ctr + kRecCtrWords))) {
+    if ((rc = enqueue_payload(c, w->rec, kRecCtrWords, p->src, a))) {
         return rc;
     }
     if (n && bmqcrc_launch_records_frame(&a, (void*)c.s)) {
         return fail(BMQCRC_EIO, std::string("records-pack frame launch failed: ") +
                                     hipGetErrorString(hipGetLastError()));
     }
-    w->rec_n = n;
-    w->rec_any = true;
+    w->rec.n = n;
+    w->rec.any = true;
     if (o.flags & BMQCRC_F_ASYNC) {
         return 0;
     }
@@ -2470,12 +2442,9 @@ int bmqcrc_last_records_pack(int device, void* stream, bmqcrc_records_result* re
 {
     t_err.clear();
     DeviceGuard keep_device;
-    int dev, rc;
-    if ((rc = resolve_device(device, &dev))) {
-        return rc;
-    }
     Ctx c;
-    if ((rc = open_ctx(dev, stream, &c))) {
+    int rc;
+    if ((rc = open_on(device, stream, &c))) {
         return rc;
     }
     std::lock_guard<std::mutex> g(c.w->mu);

@@ -192,8 +192,11 @@ constexpr int kPackThreads = 1024;         // layout kernels' block
 constexpr uint32_t kPackBlocks = 256;      // their grid: contiguous message ranges, at most
 constexpr int kPackFrameThreads = 256;     // k_pack_frame: one header dword per thread and step
 constexpr uint32_t kPackFrameBlocks = 2048;
+// ctr[] word 0 of both packers (crc32c_pack_layout.h raises it):
+// ~((kind << 56) | index) of the refusal reported, 0: none
+constexpr int kLayoutCtrRefusal = 0;
 // PackArgs::ctr words
-constexpr int kPackCtrRefusal = 0;  // ~((kind << 56) | index) of the refusal reported, 0: none
+constexpr int kPackCtrRefusal = kLayoutCtrRefusal;
 constexpr int kPackCtrTotal = 1;    // bytes of all events (k_pack_check)
 constexpr int kPackCtrWords = 2;
 // BMQCRC_PUT_PACK_* of bmqcrc_protocol.h, which the kernels do not include
@@ -228,7 +231,7 @@ struct PackArgs {
 // ---- bmqcrc_message_records_pack (crc32c_records_pack.hip, ABI 2.11) -------
 // The layout grid and block are kPackBlocks x kPackThreads, the frame kernel's
 // kPackFrameBlocks x kPackFrameThreads.  RecArgs::ctr words
-constexpr int kRecCtrRefusal = 0;   // ~((kind << 56) | index) of the refusal reported, 0: none
+constexpr int kRecCtrRefusal = kLayoutCtrRefusal;
 constexpr int kRecCtrTotal = 1;     // bytes of all DATA records (k_rec_place)
 constexpr int kRecCtrBad = 2;       // messages whose CRC differs from expected[]
 constexpr int kRecCtrFirstBad = 3;  // ~(lowest such message), 0: none

@@ -10,9 +10,8 @@
 // prefix, message i's header lies at 8 (e(i) + 1) + P[i] and event e starts at
 // 8 e + P[event_first[e]].  Three steps on one stream:
 //
-//   1. Layout.  k_pack_count: contiguous message ranges per block; checks
-//      every source range, writes the BLOCK-LOCAL exclusive prefix of B into
-//      off[i] and the block's sum into bsum[]; checks event_first's shape.
+//   1. Layout.  k_pack_count: pass 1 of crc32c_pack_layout.h over B, with
+//      every source range checked; then event_first's shape.
 //      k_pack_check (only when pass 1 refused nothing, so every event_first
 //      entry is a valid index): P[j] = off[j] + the sum of the blocks before
 //      j's; every event's length against the cap and its end against
@@ -26,13 +25,13 @@
 //      adjacent lanes store adjacent dwords; the padding bytes as byte stores;
 //      the EventHeaders and event_offsets.  It leaves at once on a refusal.
 //
-// A refusal is one 64-bit word: ~((kind << 56) | index), raised with
-// atomicMax, so the lowest kind and within it the lowest index wins whatever
-// the order the blocks run in.
+// The refusal word, pass 1's scan and the prefix of the block sums are shared
+// with crc32c_records_pack.hip and described in crc32c_pack_layout.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "bmqcrc_internal.h"
+#include "crc32c_pack_layout.h"
 
 namespace bmqcrc {
 namespace {
@@ -42,83 +41,22 @@ typedef uint32_t u32u __attribute__((aligned(1)));
 
 constexpr uint32_t kPutHeaderBytes = 36, kEventHeaderBytes = 8;
 
-__device__ __forceinline__ void refuse(const PackArgs& a, uint32_t kind, uint64_t index)
-{
-    atomicMax(&a.ctr[kPackCtrRefusal], ~(((unsigned long long)kind << 56) | index));
-}
-
 // PutHeader + application data + padding (calcNumWordsAndPadding: 1..4 bytes)
 __device__ __forceinline__ uint64_t framed_bytes(uint32_t len)
 {
     return (uint64_t)kPutHeaderBytes + (((uint64_t)len >> 2) + 1) * 4;
 }
 
-__device__ __forceinline__ unsigned long long pack_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        v += __shfl_down(v, d);
-    }
-    return v;  // lane 0
-}
-
-// Pass 1.
+// Pass 1: the shared scan, then event_first's shape.
 __global__ __launch_bounds__(kPackThreads) void k_pack_count(PackArgs a)
 {
-    __shared__ unsigned long long wtot[kPackThreads / 64];
-    __shared__ unsigned long long wpieces[kPackThreads / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    const uint64_t lo = (uint64_t)blockIdx.x * a.per_block;
-    const uint64_t hi = min(lo + a.per_block, a.n);
-    unsigned long long carry = 0, pieces = 0;
-    for (uint64_t base = lo; base < hi; base += kPackThreads) {
-        const uint64_t i = base + tid;
-        const bool valid = i < hi;
-        unsigned long long b = 0;
-        if (valid) {
-            const uint64_t so = a.src_offsets[i];
-            const uint32_t len = a.lengths[i];
-            if (!(so <= a.src_bytes && len <= a.src_bytes - so)) {
-                refuse(a, BMQCRC_PACK_KIND_SRC_RANGE, i);
-            }
-            b = framed_bytes(len);
-            // at most this many 16-byte pieces of destination, wherever it lies
-            pieces += len ? (((uint64_t)len + 15u) >> 4) + 1u : 0u;
+    layout_count(a, [&a](uint64_t i, uint64_t so, uint32_t len) {
+        if (!(so <= a.src_bytes && len <= a.src_bytes - so)) {
+            refuse(a, BMQCRC_PACK_KIND_SRC_RANGE, i);
         }
-        unsigned long long incl = b;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long o = __shfl_up(incl, d);
-            incl += lane >= (uint32_t)d ? o : 0ull;
-        }
-        if (lane == 63) {
-            wtot[wv] = incl;
-        }
-        __syncthreads();
-        unsigned long long woff = 0, tot = 0;
-        for (uint32_t w = 0; w < kPackThreads / 64; ++w) {
-            woff += w < wv ? wtot[w] : 0ull;
-            tot += wtot[w];
-        }
-        __syncthreads();
-        if (valid) {
-            a.off[i] = carry + woff + incl - b;
-        }
-        carry += tot;
-    }
-    pieces = pack_wave_sum(pieces);
-    if (lane == 0) {
-        wpieces[wv] = pieces;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < kPackThreads / 64; ++w) {
-            t += wpieces[w];
-        }
-        a.bsum[blockIdx.x] = carry;
-        a.bsum[kPackBlocks + blockIdx.x] = t;
-    }
+        return framed_bytes(len);
+    });
+    const uint32_t tid = threadIdx.x;
     // event_first: starts at 0, strictly increasing, ends at n
     if (a.event_first) {
         const uint64_t stride = (uint64_t)gridDim.x * kPackThreads;
@@ -131,52 +69,6 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_count(PackArgs a)
             }
         }
     }
-}
-
-static_assert(kPackBlocks == 256 && kPackThreads >= (int)kPackBlocks, "block_prefix: 4 waves");
-
-// bpre[b] = framed bytes of the blocks before b, bpre[nblocks] = of all; the
-// return value is the pieces of all blocks.  One load per thread (a serial
-// walk of 256 dependent loads by one thread took 30 us), scanned by
-// shuffles in the block's first four waves.  Called by the whole block.
-__device__ __forceinline__ unsigned long long block_prefix(const PackArgs& a,
-                                                           unsigned long long* bpre)
-{
-    __shared__ unsigned long long wsum[2][kPackBlocks / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    unsigned long long incl = 0, v = 0, pieces = 0;
-    if (tid < kPackBlocks) {
-        v = tid < a.nblocks ? a.bsum[tid] : 0ull;
-        pieces = tid < a.nblocks ? a.bsum[kPackBlocks + tid] : 0ull;
-        incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long o = __shfl_up(incl, d);
-            incl += lane >= (uint32_t)d ? o : 0ull;
-        }
-        pieces = pack_wave_sum(pieces);
-        if (lane == 63) {
-            wsum[0][wv] = incl;
-        }
-        if (lane == 0) {
-            wsum[1][wv] = pieces;
-        }
-    }
-    __syncthreads();
-    if (tid < kPackBlocks) {
-        unsigned long long before = 0;
-        for (uint32_t w = 0; w < wv; ++w) {
-            before += wsum[0][w];
-        }
-        if (tid < a.nblocks) {
-            bpre[tid] = before + incl - v;
-        }
-        if (tid + 1 == a.nblocks) {
-            bpre[a.nblocks] = before + incl;
-        }
-    }
-    __syncthreads();
-    return wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
 }
 
 // Pass 2: the events, one per thread.  Runs only on a clean pass 1: every

@@ -11,9 +11,8 @@
 // record i lies at dst + Q[i] and journal record i at journal + 60 i.  Three
 // steps on one stream:
 //
-//   1. Layout.  k_rec_count: contiguous message ranges per block; checks every
-//      record's size and source range, writes the BLOCK-LOCAL exclusive prefix
-//      of R into off[i] and the block's sum into bsum[].  k_rec_place: every
+//   1. Layout.  k_rec_count: pass 1 of crc32c_pack_layout.h over R, with every
+//      record's size and source range checked.  k_rec_place: every
 //      block scans the block sums; the block in whose range the records first
 //      end past dst_bytes, or past the last byte MessageOffsetDwords can
 //      address, finds that message by bisection and raises the refusal; off[i]
@@ -30,13 +29,13 @@
 //      only (no read-modify-write of a word that holds payload).  It leaves at
 //      once on a refusal.
 //
-// A refusal is one 64-bit word: ~((kind << 56) | index), raised with
-// atomicMax, so the lowest kind and within it the lowest index wins whatever
-// the order the blocks run in.
+// The refusal word, pass 1's scan and the prefix of the block sums are shared
+// with crc32c_put_pack.hip and described in crc32c_pack_layout.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "bmqcrc_internal.h"
+#include "crc32c_pack_layout.h"
 
 namespace bmqcrc {
 namespace {
@@ -46,135 +45,28 @@ typedef uint32_t u32u __attribute__((aligned(1)));
 
 constexpr uint32_t kDataHeaderBytes = 12, kJournalDwords = 15;
 
-__device__ __forceinline__ void refuse(const RecArgs& a, uint32_t kind, uint64_t index)
-{
-    atomicMax(&a.ctr[kRecCtrRefusal], ~(((unsigned long long)kind << 56) | index));
-}
-
 // DataHeader + application data + padding (calcNumDwordsAndPadding: 1..8 bytes)
 __device__ __forceinline__ uint64_t record_bytes(uint32_t len)
 {
     return ((((uint64_t)len + kDataHeaderBytes) >> 3) + 1) << 3;
 }
 
-__device__ __forceinline__ unsigned long long rec_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        v += __shfl_down(v, d);
-    }
-    return v;  // lane 0
-}
-
-// Pass 1.
+// Pass 1: the shared scan.
 __global__ __launch_bounds__(kPackThreads) void k_rec_count(RecArgs a)
 {
-    __shared__ unsigned long long wtot[kPackThreads / 64];
-    __shared__ unsigned long long wpieces[kPackThreads / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    const uint64_t lo = (uint64_t)blockIdx.x * a.per_block;
-    const uint64_t hi = min(lo + a.per_block, a.n);
-    unsigned long long carry = 0, pieces = 0;
-    for (uint64_t base = lo; base < hi; base += kPackThreads) {
-        const uint64_t i = base + tid;
-        const bool valid = i < hi;
-        unsigned long long b = 0;
-        if (valid) {
-            const uint64_t so = a.src_offsets[i];
-            const uint32_t len = a.lengths[i];
-            b = record_bytes(len);
-            if ((b >> 2) > 0x1FFFFFFFull) {
-                // 29 bits of DataHeader::messageWords; the record counts for
-                // nothing, so that no sum below can pass 2^64
-                refuse(a, BMQCRC_REC_KIND_RECORD_TOO_BIG, i);
-                b = 0;
-            }
-            if (!(so <= a.src_bytes && len <= a.src_bytes - so)) {
-                refuse(a, BMQCRC_REC_KIND_SRC_RANGE, i);
-            }
-            // at most this many 16-byte pieces of destination, wherever it lies
-            pieces += len ? (((uint64_t)len + 15u) >> 4) + 1u : 0u;
+    layout_count(a, [&a](uint64_t i, uint64_t so, uint32_t len) {
+        unsigned long long b = record_bytes(len);
+        if ((b >> 2) > 0x1FFFFFFFull) {
+            // 29 bits of DataHeader::messageWords; the record counts for
+            // nothing, so that no sum of the scan can pass 2^64
+            refuse(a, BMQCRC_REC_KIND_RECORD_TOO_BIG, i);
+            b = 0;
         }
-        unsigned long long incl = b;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long o = __shfl_up(incl, d);
-            incl += lane >= (uint32_t)d ? o : 0ull;
+        if (!(so <= a.src_bytes && len <= a.src_bytes - so)) {
+            refuse(a, BMQCRC_REC_KIND_SRC_RANGE, i);
         }
-        if (lane == 63) {
-            wtot[wv] = incl;
-        }
-        __syncthreads();
-        unsigned long long woff = 0, tot = 0;
-        for (uint32_t w = 0; w < kPackThreads / 64; ++w) {
-            woff += w < wv ? wtot[w] : 0ull;
-            tot += wtot[w];
-        }
-        __syncthreads();
-        if (valid) {
-            a.off[i] = carry + woff + incl - b;
-        }
-        carry += tot;
-    }
-    pieces = rec_wave_sum(pieces);
-    if (lane == 0) {
-        wpieces[wv] = pieces;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < kPackThreads / 64; ++w) {
-            t += wpieces[w];
-        }
-        a.bsum[blockIdx.x] = carry;
-        a.bsum[kPackBlocks + blockIdx.x] = t;
-    }
-}
-
-static_assert(kPackBlocks == 256 && kPackThreads >= (int)kPackBlocks, "block_prefix: 4 waves");
-
-// bpre[b] = record bytes of the blocks before b, bpre[nblocks] = of all; the
-// return value is the pieces of all blocks.  One load per thread, scanned by
-// shuffles in the block's first four waves (section 12: a serial walk of the
-// 256 sums by one thread took 30 us).  Called by the whole block.
-__device__ __forceinline__ unsigned long long block_prefix(const RecArgs& a,
-                                                           unsigned long long* bpre)
-{
-    __shared__ unsigned long long wsum[2][kPackBlocks / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    unsigned long long incl = 0, v = 0, pieces = 0;
-    if (tid < kPackBlocks) {
-        v = tid < a.nblocks ? a.bsum[tid] : 0ull;
-        pieces = tid < a.nblocks ? a.bsum[kPackBlocks + tid] : 0ull;
-        incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long o = __shfl_up(incl, d);
-            incl += lane >= (uint32_t)d ? o : 0ull;
-        }
-        pieces = rec_wave_sum(pieces);
-        if (lane == 63) {
-            wsum[0][wv] = incl;
-        }
-        if (lane == 0) {
-            wsum[1][wv] = pieces;
-        }
-    }
-    __syncthreads();
-    if (tid < kPackBlocks) {
-        unsigned long long before = 0;
-        for (uint32_t w = 0; w < wv; ++w) {
-            before += wsum[0][w];
-        }
-        if (tid < a.nblocks) {
-            bpre[tid] = before + incl - v;
-        }
-        if (tid + 1 == a.nblocks) {
-            bpre[a.nblocks] = before + incl;
-        }
-    }
-    __syncthreads();
-    return wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
+        return b;
+    });
 }
 
 // Pass 2: the checks on the totals, then off[i] = where message i's

@@ -9,7 +9,7 @@ import pytest
 
 from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, last_copy, last_launch,
                            last_put_pack, pack_events)
-from put_pack_model import host_crcs, layout, oracle_events, random_meta
+from put_pack_model import host_crcs, layout, model_bytes, oracle_events, random_meta
 
 pytestmark = pytest.mark.gpu
 
@@ -281,6 +281,41 @@ def test_state_untouched(cuda):
         assert np.array_equal(out.cpu().numpy().view(np.uint32),
                               host_crcs(host, offs, lens))
     assert plans[0] == plans[1], plans
+
+
+def test_a_layout_block_of_two_tiles(cuda):
+    # 258 tiles of 1,024 messages for at most 256 blocks: per_block is 2,048
+    # and each of the 129 blocks scans two tiles, the second on top of the
+    # first's carry -- the smallest n at which a block loops.  Events meet the
+    # first block seam from both sides; lengths 0..7 keep it at some 11 MB.
+    import torch
+    rng = np.random.default_rng(13)
+    n = 256 * 1024 + 1025
+    src, soff, lens, qids, guids, flags = _short(rng, n, 0, 8)
+    ef = [0, 2047, 2048, 2049, n - 1, n]
+    ev = layout(lens, ef)[1]
+    total = int(ev[-1])
+    assert int(np.diff(ev).max()) <= CAP  # the long event fits the cap given below
+    d = _inputs(cuda, src, soff, lens, qids, guids, flags, ef)
+    dst = torch.full((total + 64,), FILL, dtype=torch.uint8, device=cuda)
+    out = torch.full((n,), FILL32, dtype=torch.int32, device=cuda)
+    _, evoff, _ = pack_events(dst=dst, out=out, max_event_bytes=CAP, **d)
+    assert last_put_pack(cuda.index, torch.cuda.current_stream(cuda)) == (n, 5, total, 0, 0)
+    assert np.array_equal(evoff.cpu().numpy(), ev)
+    crcs = host_crcs(src, soff, lens)
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), crcs)
+    host = dst.cpu().numpy()
+    assert np.all(host[total:] == FILL)
+    # every byte against the numpy model, which test_put_pack_model.py holds to
+    # PutEventBuilder; the four short events against PutEventBuilder itself
+    diff = np.nonzero(host[:total] != model_bytes(src, soff, lens, qids, guids, flags, ef, crcs))[0]
+    assert diff.size == 0, (diff.size, [int(i) for i in diff[:8]])
+    short = [0, 1, 2, 4]
+    for e, exp in zip(short, oracle_events(src, soff, lens, qids, guids, flags, ef, events=short)):
+        assert np.array_equal(host[int(ev[e]):int(ev[e + 1])], exp), e
+    # the same inputs with message 2048, the first of the second block, out of range
+    soff[2048] = src.size - int(lens[2048]) + 1
+    _refused(cuda, N.BMQCRC_PUT_PACK_SRC_RANGE, 2048, src, soff, lens, qids, guids, flags, ef)
 
 
 def test_crossing_4_gib(cuda):

@@ -218,6 +218,20 @@ def test_more_than_one_layout_block(cuda, n):
     _check(cuda, *case)
 
 
+def test_a_layout_block_of_two_tiles(cuda):
+    # 258 tiles of 1,024 messages for at most 256 blocks: per_block is 2,048
+    # and each of the 129 blocks scans two tiles, the second on top of the
+    # first's carry -- the smallest n at which a block loops.  Lengths 0..7
+    # keep both destinations below 20 MB; every byte is checked.
+    rng = np.random.default_rng(16)
+    n = 256 * 1024 + 1025
+    src, soff, lens, qkeys, guids = _short(rng, n, 0, 8)
+    _check(cuda, src, soff, lens, qkeys, guids)
+    # the same inputs with message 2048, the first of the second block, out of range
+    soff[2048] = src.size - int(lens[2048]) + 1
+    _refused(cuda, N.BMQCRC_REC_PACK_SRC_RANGE, 2048, src, soff, lens, qkeys, guids)
+
+
 def test_a_long_message_among_short_ones(cuda):
     rng = np.random.default_rng(5)
     src, soff, lens, qkeys, guids = _short(rng, 41, 1, 41, src_size=1 << 19)
