@@ -178,6 +178,38 @@ if hasattr(lib, "bmqcrc_message_records_pack"):  # ABI 2.11 (an older build load
                                                 ctypes.POINTER(RecordsResult), _popts]
     lib.bmqcrc_last_records_pack.restype = _int
     lib.bmqcrc_last_records_pack.argtypes = [_int, _vp, ctypes.POINTER(RecordsResult)]
+BMQCRC_PUT_UNPACK_OK = 0
+BMQCRC_PUT_UNPACK_EVENT_OFFSETS = 1
+BMQCRC_PUT_UNPACK_EVENT_HEADER = 2
+BMQCRC_PUT_UNPACK_PUT_HEADER = 3
+BMQCRC_PUT_UNPACK_PADDING = 4
+BMQCRC_PUT_UNPACK_TOO_MANY_MESSAGES = 5
+
+
+class PutUnpack(ctypes.Structure):
+    """bmqcrc_put_unpack (include/bmqcrc_protocol.h, ABI 2.12)."""
+    _fields_ = [("struct_size", _u32), ("reserved", _u32), ("events", _vp), ("events_bytes", _u64),
+                ("event_offsets", _vp), ("n_events", _u64), ("msg_cap", _u64),
+                ("app_offsets", _vp), ("lengths", _vp), ("queue_ids", _vp), ("guids", _vp),
+                ("flags", _vp), ("expected", _vp), ("out", _vp), ("event_first", _vp)]
+
+
+class PutUnpackResult(ctypes.Structure):
+    """bmqcrc_put_unpack_result (include/bmqcrc_protocol.h, ABI 2.12)."""
+    _fields_ = [("n_events", _u64), ("n_msgs", _u64), ("n_bad", _u64), ("first_bad", _u64),
+                ("refused_kind", _u32), ("reserved", _u32), ("refused_event", _u64),
+                ("refused_offset", _u64)]
+
+    def as_dict(self):
+        return {f[0]: int(getattr(self, f[0])) for f in self._fields_ if f[0] != "reserved"}
+
+
+if hasattr(lib, "bmqcrc_put_event_unpack"):  # ABI 2.12 (an older build loads for same-box A/B)
+    lib.bmqcrc_put_event_unpack.restype = _int
+    lib.bmqcrc_put_event_unpack.argtypes = [ctypes.POINTER(PutUnpack),
+                                            ctypes.POINTER(PutUnpackResult), _popts]
+    lib.bmqcrc_last_put_unpack.restype = _int
+    lib.bmqcrc_last_put_unpack.argtypes = [_int, _vp, ctypes.POINTER(PutUnpackResult)]
 lib.bmqcrc_journal_scan.restype = _i64
 lib.bmqcrc_journal_scan.argtypes = [_vp, _u64, _vp, _u64, _vp, _pint, _pu64, _vp, _vp, _vp, _vp,
                                     _u64]

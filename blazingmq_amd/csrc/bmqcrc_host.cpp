@@ -158,6 +158,13 @@ struct Workspace {
     // independently; the events of the last PUT pack
     PackScratch pack, rec;
     uint64_t pack_events = 0;
+    // bmqcrc_put_event_unpack: the descriptors its fold reads (offset 8,
+    // length 4), the header and the computed CRCs (4 each) per slot; the
+    // counts / their prefix and the refusal offset (8 each) per event; the
+    // counters; the events of the last unpack enqueued (bmqcrc_last_put_unpack)
+    DevBuf unp_off, unp_len, unp_exp, unp_out, unp_first, unp_bad, unp_ctr;
+    uint64_t unp_events = 0;
+    bool unp_any = false;
     // Pinned staging ring for gathered host buffers (bmqcrc_crc32c_gather):
     // kGatherSlots chunks of kGatherChunk bytes, each reusable once the event
     // recorded after its H2D copy has completed.
@@ -2458,6 +2465,209 @@ int bmqcrc_last_records_pack(int device, void* stream, bmqcrc_records_result* re
     return 0;
 }
 
+static_assert(BMQCRC_PUT_UNPACK_EVENT_OFFSETS == BMQCRC_UNPACK_KIND_EVENT_OFFSETS &&
+                  BMQCRC_PUT_UNPACK_EVENT_HEADER == BMQCRC_UNPACK_KIND_EVENT_HEADER &&
+                  BMQCRC_PUT_UNPACK_PUT_HEADER == BMQCRC_UNPACK_KIND_PUT_HEADER &&
+                  BMQCRC_PUT_UNPACK_PADDING == BMQCRC_UNPACK_KIND_PADDING &&
+                  BMQCRC_PUT_UNPACK_TOO_MANY_MESSAGES == BMQCRC_UNPACK_KIND_TOO_MANY_MESSAGES,
+              "the kernels' refusal kinds are the public ones");
+
+// Result of the unpack last enqueued on c's workspace, after everything
+// enqueued on its stream (w->mu held); zeros when there was none.
+static int unpack_result(Ctx& c, bmqcrc_put_unpack_result* r)
+{
+    memset(r, 0, sizeof(*r));
+    if (!c.w->unp_any) {
+        return 0;
+    }
+    unsigned long long ctr[kUnpCtrWords];
+    HIP_TRY(hipMemcpyAsync(ctr, c.w->unp_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    r->n_events = c.w->unp_events;
+    if (ctr[kUnpCtrRefusal]) {
+        const unsigned long long key = ~ctr[kUnpCtrRefusal];
+        r->refused_kind = (uint32_t)(key >> 56);
+        r->refused_event = key & ((1ull << 56) - 1);
+        r->refused_offset = ctr[kUnpCtrOffset];
+        return 0;
+    }
+    r->n_msgs = ctr[kUnpCtrMsgs];
+    r->n_bad = ctr[kUnpCtrBad];
+    r->first_bad = r->n_bad ? ~ctr[kUnpCtrFirstBad] : r->n_msgs;
+    return 0;
+}
+
+static int unpack_refusal(const bmqcrc_put_unpack_result& r)
+{
+    static const char* const what[] = {
+        "", "BMQCRC_PUT_UNPACK_EVENT_OFFSETS: event_offsets[%llu] is above its successor, no "
+            "multiple of 4, or the event ends past events_bytes (offset %llu)",
+        "BMQCRC_PUT_UNPACK_EVENT_HEADER: event %llu has a malformed EventHeader (offset %llu)",
+        "BMQCRC_PUT_UNPACK_PUT_HEADER: event %llu has a truncated or inconsistent PutHeader "
+        "(offset %llu)",
+        "BMQCRC_PUT_UNPACK_PADDING: event %llu has invalid PUT message padding (offset %llu)",
+        "BMQCRC_PUT_UNPACK_TOO_MANY_MESSAGES: the messages of event %llu do not fit msg_cap "
+        "(offset %llu)"};
+    char buf[256];
+    snprintf(buf, sizeof(buf), what[r.refused_kind <= 5 ? r.refused_kind : 0],
+             (unsigned long long)r.refused_event, (unsigned long long)r.refused_offset);
+    return fail(BMQCRC_EINVAL, std::string(buf) + ": nothing was written");
+}
+
+int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result* result,
+                            const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    if (!p || p->struct_size != sizeof(bmqcrc_put_unpack)) {
+        return fail(BMQCRC_EINVAL,
+                    "bmqcrc_put_unpack.struct_size must be sizeof(bmqcrc_put_unpack)");
+    }
+    if (p->reserved) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_put_unpack.reserved must be 0");
+    }
+    bmqcrc_opts o;
+    int rc;
+    if ((rc = device_call_opts(opts, "bmqcrc_put_event_unpack", &o))) {
+        return rc;
+    }
+    {
+        const struct {
+            bool null;
+            const char* name;
+        } arrays[] = {{!p->events, "events"},
+                      {!p->app_offsets, "app_offsets"},
+                      {!p->lengths, "lengths"}};
+        for (const auto& a : arrays) {
+            if (a.null) {
+                return fail(BMQCRC_EINVAL, std::string("null pointer argument: ") + a.name);
+            }
+        }
+    }
+    if ((uintptr_t)p->events & 3u) {
+        return fail(BMQCRC_EINVAL, "events must be 4-byte aligned");
+    }
+    if (!p->event_offsets && p->n_events != 1) {
+        return fail(BMQCRC_EINVAL, "event_offsets == NULL means one event: n_events must be 1");
+    }
+    if (p->n_events > 0xFFFFFFFFull || p->msg_cap > 0xFFFFFFFFull) {
+        return fail(BMQCRC_EINVAL, "n_events and msg_cap must be below 2^32");
+    }
+    {
+        const uint64_t cap = p->msg_cap;
+        const struct {
+            const void* at;
+            uint64_t bytes;
+            const char* name;
+        } outs[] = {{p->app_offsets, 8 * cap, "app_offsets"},
+                    {p->lengths, 4 * cap, "lengths"},
+                    {p->queue_ids, 4 * cap, "queue_ids"},
+                    {p->guids, 16 * cap, "guids"},
+                    {p->flags, cap, "flags"},
+                    {p->expected, 4 * cap, "expected"},
+                    {p->out, 4 * cap, "out"},
+                    {p->event_first, 8 * (p->n_events + 1), "event_first"}};
+        const uintptr_t e0 = (uintptr_t)p->events;
+        for (const auto& a : outs) {
+            const uintptr_t a0 = (uintptr_t)a.at;
+            if (a.at && a.bytes && p->events_bytes && a0 < e0 + p->events_bytes &&
+                e0 < a0 + a.bytes) {
+                return fail(BMQCRC_EINVAL,
+                            std::string(a.name) + " overlaps [events, events+events_bytes)");
+            }
+        }
+    }
+    Ctx c;
+    if ((rc = open_on(o.device, o.stream, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    std::lock_guard<std::mutex> g(w->mu);
+    const uint64_t cap = p->msg_cap, slots = std::max<uint64_t>(cap, 1);
+    if ((rc = w->unp_ctr.ensure(8 * kUnpCtrWords)) || (rc = w->unp_off.ensure(8 * slots)) ||
+        (rc = w->unp_len.ensure(4 * slots)) || (rc = w->unp_exp.ensure(4 * slots)) ||
+        (p->out && (rc = w->unp_out.ensure(4 * slots))) ||
+        (rc = w->unp_first.ensure(8 * (p->n_events + 1))) ||
+        (rc = w->unp_bad.ensure(8 * std::max<uint64_t>(p->n_events, 1)))) {
+        return rc;
+    }
+    HIP_TRY(hipMemsetAsync(w->unp_ctr.p, 0, 8 * kUnpCtrWords, c.s));
+    w->unp_events = p->n_events;
+    w->unp_any = true;
+    if (p->n_events) {
+        UnpackArgs a;
+        memset(&a, 0, sizeof(a));
+        a.events = (const uint8_t*)p->events;
+        a.events_bytes = p->events_bytes;
+        a.event_offsets = p->event_offsets;
+        a.n_events = p->n_events;
+        a.msg_cap = cap;
+        a.app_offsets = p->app_offsets;
+        a.lengths = p->lengths;
+        a.queue_ids = p->queue_ids;
+        a.guids = p->guids;
+        a.flags = p->flags;
+        a.expected = p->expected;
+        a.out = p->out;
+        a.event_first = p->event_first;
+        a.ws_off = (unsigned long long*)w->unp_off.p;
+        a.ws_len = (uint32_t*)w->unp_len.p;
+        a.ws_exp = (uint32_t*)w->unp_exp.p;
+        a.ws_out = (const uint32_t*)w->unp_out.p;
+        a.first = (unsigned long long*)w->unp_first.p;
+        a.bad_off = (unsigned long long*)w->unp_bad.p;
+        a.ctr = (unsigned long long*)w->unp_ctr.p;
+        if (bmqcrc_launch_unpack_walk(&a, (void*)c.s)) {
+            return fail(BMQCRC_EIO, std::string("put-unpack walk launch failed: ") +
+                                        hipGetErrorString(hipGetLastError()));
+        }
+        // the fold over the workspace's descriptors, which the placing kernel
+        // filled for every slot: never over the caller's arrays
+        if (p->out && (rc = run_batch(c, BMQCRC_F_DEVICE_PTRS | BMQCRC_F_PLAN, 0, p->events,
+                                      p->events_bytes, (const uint64_t*)w->unp_off.p,
+                                      (const uint32_t*)w->unp_len.p, nullptr,
+                                      (uint32_t*)w->unp_out.p, cap))) {
+            return rc;
+        }
+        if (bmqcrc_launch_unpack_publish(&a, (void*)c.s)) {
+            return fail(BMQCRC_EIO, std::string("put-unpack publish launch failed: ") +
+                                        hipGetErrorString(hipGetLastError()));
+        }
+    }
+    if (o.flags & BMQCRC_F_ASYNC) {
+        return 0;
+    }
+    bmqcrc_put_unpack_result r;
+    if ((rc = unpack_result(c, &r))) {
+        return rc;
+    }
+    if (result) {
+        *result = r;
+    }
+    return r.refused_kind ? unpack_refusal(r) : 0;
+}
+
+int bmqcrc_last_put_unpack(int device, void* stream, bmqcrc_put_unpack_result* result)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    Ctx c;
+    int rc;
+    if ((rc = open_on(device, stream, &c))) {
+        return rc;
+    }
+    std::lock_guard<std::mutex> g(c.w->mu);
+    bmqcrc_put_unpack_result r;
+    if ((rc = unpack_result(c, &r))) {
+        return rc;
+    }
+    if (result) {
+        *result = r;
+    }
+    return 0;
+}
+
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,
                        uint32_t* seg_bytes)
 {
@@ -2633,7 +2843,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 11u;
+    return (2u << 16) | 12u;
 }
 
 }  // extern "C"

@@ -273,7 +273,56 @@ struct RecArgs {
     uint32_t nblocks;              // layout blocks (<= kPackBlocks)
 };
 
+// ---- bmqcrc_put_event_unpack (crc32c_put_unpack.hip, ABI 2.12) -------------
+constexpr int kUnpackWalkThreads = 64;        // the walks: one wave per block, one event at a time
+constexpr uint32_t kUnpackWalkBlocks = 4096;  // their grid, at most: 16 waves per CU
+constexpr uint32_t kUnpackWindowBytes = 1024; // a chunk of a wave's window of its event (two in LDS)
+constexpr int kUnpackThreads = 1024;          // k_unpack_scan: one block
+constexpr int kUnpackPublishThreads = 256;    // k_unpack_publish: one message per thread and step
+constexpr uint32_t kUnpackPublishBlocks = 2048;
+// UnpackArgs::ctr words
+constexpr int kUnpCtrRefusal = kLayoutCtrRefusal;
+constexpr int kUnpCtrMsgs = 1;       // messages of all events (k_unpack_publish; 0 when refused)
+constexpr int kUnpCtrBad = 2;        // messages whose computed CRC differs from the header's
+constexpr int kUnpCtrFirstBad = 3;   // ~(lowest such message), 0: none
+constexpr int kUnpCtrOffset = 4;     // the refused event's bad_off (k_unpack_publish)
+constexpr int kUnpCtrWords = 5;
+// BMQCRC_PUT_UNPACK_* of bmqcrc_protocol.h, which the kernels do not include
+#define BMQCRC_UNPACK_KIND_EVENT_OFFSETS 1u
+#define BMQCRC_UNPACK_KIND_EVENT_HEADER 2u
+#define BMQCRC_UNPACK_KIND_PUT_HEADER 3u
+#define BMQCRC_UNPACK_KIND_PADDING 4u
+#define BMQCRC_UNPACK_KIND_TOO_MANY_MESSAGES 5u
+
+struct UnpackArgs {
+    const uint8_t* events;          // device, 4-byte aligned
+    uint64_t events_bytes;
+    const uint64_t* event_offsets;  // device, n_events + 1, or nullptr (one event, the buffer)
+    uint64_t n_events;
+    uint64_t msg_cap;
+    uint64_t* app_offsets;          // the caller's arrays (device, msg_cap; event_first n_events
+    uint32_t* lengths;              // + 1): written when nothing was refused, and only by
+    int32_t* queue_ids;             // k_unpack_place (queue_ids, guids, flags) and
+    uint8_t* guids;                 // k_unpack_publish (the others); all but the first two
+    uint8_t* flags;                 // may be nullptr
+    uint32_t* expected;
+    uint32_t* out;                  // nullptr: walk only, ws_out is then unused
+    uint64_t* event_first;
+    unsigned long long* ws_off;     // workspace, msg_cap: what the fold reads, every slot filled
+    uint32_t* ws_len;               // workspace, msg_cap  by k_unpack_place (empty when unused)
+    uint32_t* ws_exp;               // workspace, msg_cap: the PutHeader CRCs
+    const uint32_t* ws_out;         // workspace, msg_cap: the fold's CRCs
+    unsigned long long* first;      // workspace, n_events + 1: counts, then their exclusive prefix
+    unsigned long long* bad_off;    // workspace, n_events: the offset an event's refusal names
+    unsigned long long* ctr;        // workspace, kUnpCtrWords, zeroed before the launch
+};
+
 }  // namespace bmqcrc
+
+// Launchers (crc32c_put_unpack.hip).  Asynchronous on `stream`: the walk fills
+// ws_off / ws_len for the fold (bmqcrc_launch_batch), the publish runs after it.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_unpack_walk(const bmqcrc::UnpackArgs* a, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_unpack_publish(const bmqcrc::UnpackArgs* a, void* stream);
 
 // Launchers (crc32c_records_pack.hip).  Asynchronous on `stream`: the layout
 // before bmqcrc_launch_copy (it writes the copy's dst_offsets), the frame after.

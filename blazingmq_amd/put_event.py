@@ -23,6 +23,7 @@ with one batched GPU call before the event is posted
 ``PutMessageIterator.verify_crcs()`` is the batched form of the iterator's
 recompute (bmqp_putmessageiterator.cpp:670-679): ``bmqcrc_put_event_verify``.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -198,6 +199,100 @@ def last_put_pack(device, stream=None):
         device, stream.cuda_stream if stream is not None else None, ctypes.byref(n),
         ctypes.byref(ne), ctypes.byref(tot), ctypes.byref(kind), ctypes.byref(idx)))
     return n.value, ne.value, tot.value, kind.value, idx.value
+
+
+Unpacked = collections.namedtuple(
+    "Unpacked", "app_offsets lengths queue_ids guids flags expected crcs event_first")
+
+
+def unpack_events(events, event_offsets=None, msg_cap=None, verify=True, *, stream=None,
+                  sync=True):
+    """Walk device-resident PUT events on the GPU (``bmqcrc_put_event_unpack``),
+    the inverse of ``pack_events``: what ``PutMessageIterator`` reports for
+    every message of every event, as device tensors, with no payload byte and
+    no descriptor crossing PCIe.
+
+    ``events`` is a contiguous uint8 device tensor (4-byte aligned),
+    ``event_offsets`` int64 with one entry more than there are events (event e
+    is ``events[event_offsets[e]:event_offsets[e+1]]``) or None for one event,
+    the whole buffer.  ``msg_cap`` is the capacity of the per-message arrays;
+    None is ``events.numel() // 40``, the most a buffer can hold.  With
+    ``verify`` every message's application data is CRC'd and compared with its
+    PutHeader CRC (ask ``last_put_unpack`` for n_bad / first_bad); the CRC
+    pass runs over all ``msg_cap`` slots, so a tight ``msg_cap`` is cheaper.
+
+    Returns the named tuple ``(app_offsets, lengths, queue_ids, guids, flags,
+    expected, crcs, event_first)``: int64 offsets in ``events`` of the
+    application data, int32 lengths and queue ids, uint8 GUIDs (16 per
+    message) and PutHeader flags, the PutHeader CRCs and the computed ones
+    (int32; ``crcs`` is None when ``verify=False``), and the first message of
+    each event with the message count last (int64).  With ``sync=True`` the
+    per-message tensors are sliced to the messages found, and a malformed
+    event, bad ``event_offsets`` or more than ``msg_cap`` messages raises
+    ``BmqCrcError`` (BMQCRC_EINVAL) naming kind, event and offset: nothing is
+    written then.  With ``sync=False`` the tensors keep their full capacity
+    and ``last_put_unpack`` reports the outcome.  Not meant to be captured
+    into a graph."""
+    import torch
+    for name, t, dt in (("events", events, torch.uint8),
+                        ("event_offsets", event_offsets, torch.int64)):
+        if name == "event_offsets" and t is None:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous()):
+            raise TypeError("%s must be a contiguous %s tensor" % (name, dt))
+    dev = events.device
+    if not events.is_cuda:
+        raise TypeError("unpack_events takes device tensors only (events is on %s)" % dev)
+    if event_offsets is not None and event_offsets.device != dev:
+        raise TypeError("event_offsets must be on %s like events" % dev)
+    if event_offsets is not None and event_offsets.numel() < 1:
+        raise ValueError("event_offsets needs one entry more than there are events")
+    n_events = event_offsets.numel() - 1 if event_offsets is not None else 1
+    cap = events.numel() // (PUT_HEADER_SIZE + WORD) if msg_cap is None else int(msg_cap)
+    if cap < 0:
+        raise ValueError("msg_cap must not be negative")
+
+    def new(shape, dt):
+        return torch.empty(shape, dtype=dt, device=dev)
+    u = Unpacked(new(cap, torch.int64), new(cap, torch.int32), new(cap, torch.int32),
+                 new((cap, 16), torch.uint8), new(cap, torch.uint8), new(cap, torch.int32),
+                 new(cap, torch.int32) if verify else None, new(n_events + 1, torch.int64))
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    p = N.PutUnpack()
+    p.struct_size = ctypes.sizeof(N.PutUnpack)
+    p.events, p.events_bytes = events.data_ptr(), events.numel()
+    p.event_offsets = event_offsets.data_ptr() if event_offsets is not None else None
+    p.n_events, p.msg_cap = n_events, cap
+    # (an empty tensor has no address: the call wants one for the required arrays)
+    p.app_offsets = u.app_offsets.data_ptr() or u.event_first.data_ptr()
+    p.lengths = u.lengths.data_ptr() or u.event_first.data_ptr()
+    p.queue_ids, p.guids, p.flags = u.queue_ids.data_ptr(), u.guids.data_ptr(), u.flags.data_ptr()
+    p.expected = u.expected.data_ptr()
+    p.out = u.crcs.data_ptr() if verify else None
+    p.event_first = u.event_first.data_ptr()
+    o = N.make_opts(device=dev.index if dev.index is not None else -1, stream=stream.cuda_stream,
+                    flags=N.BMQCRC_F_DEVICE_PTRS | (0 if sync else N.BMQCRC_F_ASYNC))
+    r = N.PutUnpackResult()
+    N.check(N.lib.bmqcrc_put_event_unpack(ctypes.byref(p), ctypes.byref(r), ctypes.byref(o)))
+    if not sync:
+        return u
+    n = int(r.n_msgs)
+    return Unpacked(*[t[:n] if t is not None else None for t in u[:7]], u.event_first)
+
+
+def last_put_unpack(device, stream=None):
+    """The result of the previous ``unpack_events`` on (device, stream)
+    (bmqcrc_last_put_unpack), as a dict; waits for it.  ``n_events``,
+    ``n_msgs`` (0 when refused), ``n_bad`` and ``first_bad`` (messages whose
+    computed CRC differs from the PutHeader's, and the lowest; ``n_msgs`` when
+    none), ``refused_kind`` (0, ``BMQCRC_PUT_UNPACK_OK``, or the kind),
+    ``refused_event`` and ``refused_offset`` (the byte in ``events`` the host
+    walk would name).  ``stream=None`` is the device's default stream."""
+    r = N.PutUnpackResult()
+    N.check(N.lib.bmqcrc_last_put_unpack(
+        device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
+    return r.as_dict()
 
 
 class PutMessageIterator:

@@ -254,6 +254,112 @@ int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_res
  * stream); waits for it.  `result` may be NULL. */
 int bmqcrc_last_records_pack(int device, void* stream, bmqcrc_records_result* result);
 
+/* ABI 2.12.  The inverse of bmqcrc_put_event_pack: PUT events in device
+ * memory are walked ON THE DEVICE, and every message's descriptors come back
+ * as the arrays the packers take.  It is PutMessageIterator::next with its
+ * recompute (bmqp_putmessageiterator.cpp:670-679) for a batch of events in
+ * one asynchronous call: with `out` every PutHeader CRC is checked against
+ * its application data.  No payload byte and no descriptor crosses PCIe.
+ *
+ * Events.  Event e is bytes [event_offsets[e], event_offsets[e + 1]) of
+ *   `events`; event_offsets == NULL means one event, the whole buffer.
+ * Messages are numbered event by event in walk order; event_first (may be
+ *   NULL) receives the exclusive prefix of the per-event counts, n_msgs last.
+ *   Message i yields app_offsets[i] (byte offset in `events` of its
+ *   application data), lengths[i], queue_ids[i], guids[16 i ..], flags[i] (the
+ *   PutHeader's 4 flag bits) and expected[i] (the PutHeader CRC, host order):
+ *   exactly what bmqcrc_put_event_scan reports for the event, with the
+ *   event's offset added to positions.
+ * What it accepts.  Message options, the compression type (CAT) and schema
+ *   ids are not interpreted, but events that carry them are accepted: PutHeader
+ *   headerWords may be 8..31, optionsWords is skipped as the host walk skips
+ *   it, an EventHeader longer than 8 bytes is honoured, and an event of 8
+ *   bytes with no message is legal.
+ * Options.  Device pointers only: BMQCRC_F_DEVICE_PTRS is required,
+ *   BMQCRC_F_ASYNC allowed; any other flag, ndevices > 1, a wrong struct_size
+ *   or reserved, `events`, app_offsets or lengths null, `events` not 4-byte
+ *   aligned, event_offsets == NULL with n_events != 1, n_events or msg_cap at
+ *   or above 2^32, or any given output array meeting [events, events +
+ *   events_bytes) is BMQCRC_EINVAL, answered on the host before the device
+ *   lookup.  n_events == 0 writes nothing and reports zeros.
+ * All or nothing, decided on the device.  One violation anywhere refuses the
+ *   call, and a refused call writes nothing to any output array.  Within an
+ *   event the violation reported is the first in walk order: the checks of
+ *   bmqcrc_put_event_scan in its order, refused_offset being the event's
+ *   offset plus the offset its error text names.  Across events the lowest
+ *   kind wins and within it the lowest event.  For EVENT_OFFSETS
+ *   refused_offset is event_offsets[refused_event], for TOO_MANY_MESSAGES the
+ *   event's start.  A synchronous call returns BMQCRC_EINVAL naming kind,
+ *   event and offset; after an asynchronous call bmqcrc_last_put_unpack
+ *   reports them.  The walk never loads a byte it has not first shown to lie
+ *   inside its event, and event_offsets is checked against events_bytes
+ *   before any event byte is read.
+ * CRC pass.  With out != NULL the application data of every message is CRC'd
+ *   (seed 0) by the batch kernels, planned, on the call's own stream; n_bad
+ *   and first_bad count the messages whose out[i] differs from the PutHeader
+ *   CRC.  Mismatches do not fail the call.  The call never synchronises under
+ *   BMQCRC_F_ASYNC and the device alone knows n_msgs, so the pass always runs
+ *   over msg_cap slots (the unused ones are empty messages): a tight msg_cap
+ *   is the caller's job.  The pass reads its descriptors from the call's own
+ *   workspace, never from the caller's arrays.
+ * After a successful call entries [n_msgs, msg_cap) of app_offsets, lengths,
+ *   expected and out are unspecified and the other arrays untouched there;
+ *   nothing at or beyond msg_cap is ever written.
+ * *result (may be NULL) is written by a synchronous call only.
+ * State.  Takes the workspace mutex of (device, stream); restores the
+ *   caller's current device; allocates its own workspace on first use and
+ *   when msg_cap or n_events grows (20 bytes per slot of msg_cap, 16 per
+ *   event), which bmqcrc_reserve does not cover; is not meant to be captured
+ *   into a hipGraph; is deterministic.  With out != NULL it counts as a
+ *   BMQCRC_F_DEVICE_PTRS | BMQCRC_F_PLAN batch of msg_cap messages for
+ *   bmqcrc_last_launch, bmqcrc_last_plan, bmqcrc_last_offsets and the shape
+ *   prediction; with out == NULL those stay untouched.  The records of
+ *   bmqcrc_last_copy, bmqcrc_last_put_pack and bmqcrc_last_records_pack are
+ *   never touched. */
+#define BMQCRC_PUT_UNPACK_OK 0
+#define BMQCRC_PUT_UNPACK_EVENT_OFFSETS 1     /* event_offsets[e] > event_offsets[e+1], event_offsets[e+1] >
+                                                 events_bytes, or event_offsets[e] not a multiple of 4 */
+#define BMQCRC_PUT_UNPACK_EVENT_HEADER 2      /* shorter than 8; length field != event size; type != PUT;
+                                                 headerWords * 4 outside [8, size] */
+#define BMQCRC_PUT_UNPACK_PUT_HEADER 3        /* truncated PutHeader; headerWords * 4 < 32; messageWords 0,
+                                                 past the event, or <= header + options */
+#define BMQCRC_PUT_UNPACK_PADDING 4           /* last byte of the message not in 1..4 or larger than the data */
+#define BMQCRC_PUT_UNPACK_TOO_MANY_MESSAGES 5 /* more than msg_cap messages; index: the lowest event whose
+                                                 last message does not fit */
+
+typedef struct bmqcrc_put_unpack {
+    uint32_t struct_size, reserved;       /* sizeof, 0 */
+    const void* events;                   /* device, 4-byte aligned */
+    uint64_t events_bytes;
+    const uint64_t* event_offsets;        /* device, n_events + 1: event e is [event_offsets[e], event_offsets[e+1]);
+                                             NULL = one event, the whole buffer (n_events must be 1) */
+    uint64_t n_events;
+    uint64_t msg_cap;                     /* capacity of the per-message arrays, < 2^32 */
+    uint64_t* app_offsets;                /* device, msg_cap: byte offset in `events` of the application data */
+    uint32_t* lengths;                    /* device, msg_cap */
+    int32_t* queue_ids;                   /* device, msg_cap, may be NULL */
+    uint8_t* guids;                       /* device, 16 msg_cap, may be NULL */
+    uint8_t* flags;                       /* device, msg_cap, may be NULL: PutHeader flags (4 bits) */
+    uint32_t* expected;                   /* device, msg_cap, may be NULL: the PutHeader CRCs, host order */
+    uint32_t* out;                        /* device, msg_cap, may be NULL: the computed CRCs; NULL = walk only */
+    uint64_t* event_first;                /* device, n_events + 1, may be NULL: first message of each event, n last */
+} bmqcrc_put_unpack;
+
+/* All fields zero before the first call on (device, stream). */
+typedef struct bmqcrc_put_unpack_result {
+    uint64_t n_events, n_msgs;            /* n_msgs 0 when refused */
+    uint64_t n_bad, first_bad;            /* header CRC != computed CRC; first_bad = n_msgs when none */
+    uint32_t refused_kind, reserved;
+    uint64_t refused_event, refused_offset; /* offset: byte in `events` that the host walk would name */
+} bmqcrc_put_unpack_result;
+
+int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result* result,
+                            const bmqcrc_opts* opts);
+
+/* ABI 2.12.  Result of the previous bmqcrc_put_event_unpack on (device,
+ * stream); waits for it.  `result` may be NULL. */
+int bmqcrc_last_put_unpack(int device, void* stream, bmqcrc_put_unpack_result* result);
+
 /* ---- partition recovery (mqbs_filestoreprotocol.h:306,426,483,703,953-1990) */
 
 /* mqbs::FileStore::recoverMessages result codes (mqbs_filestore.cpp:1073-1091)

@@ -1,0 +1,271 @@
+"""What bmqcrc_put_event_unpack (ABI 2.12) promises, restated in numpy and
+Python, and the inputs its tests share (test_put_unpack_model.py,
+test_gpu_put_unpack.py; not a test module).
+
+The outputs of a well-formed batch come from the host's own walks, run per
+event: the native bmqcrc_put_event_scan (offsets, lengths, CRC positions) and
+PutMessageIterator (queue id, GUID, flags, header CRC), with the event's offset
+added to positions.  The refusal (kind, event, offset) comes from `walk`, a
+Python restatement of walk_put_event's checks in its order;
+test_put_unpack_model.py holds it against the offset the native walk's error
+text names.  Across events the lowest kind wins, within it the lowest event.
+"""
+import re
+
+import numpy as np
+
+from blazingmq_amd import BmqCrcError, Crc32c
+from blazingmq_amd.put_event import PutEventBuilder, PutMessageIterator
+
+K_OFFSETS, K_EVENT, K_PUT, K_PAD, K_MANY = 1, 2, 3, 4, 5
+
+
+def be32(ev, at):
+    return int.from_bytes(bytes(ev[at:at + 4]), "big")
+
+
+def put32(ev, at, v):
+    ev[at:at + 4] = np.frombuffer(int(v).to_bytes(4, "big"), np.uint8)
+
+
+def walk(ev):
+    """walk_put_event in Python: (header positions, None) of a well-formed
+    event, or (None, (kind, offset)) with its first violation."""
+    n = len(ev)
+    if n < 8:
+        return None, (K_EVENT, 0)
+    if be32(ev, 0) & 0x7FFFFFFF != n:
+        return None, (K_EVENT, 0)
+    if int(ev[4]) & 0x3F != 2:
+        return None, (K_EVENT, 4)
+    pos = int(ev[5]) * 4
+    if pos < 8 or pos > n:
+        return None, (K_EVENT, 5)
+    hdrs = []
+    while pos < n:
+        if pos + 8 > n:
+            return None, (K_PUT, pos)
+        msg = (be32(ev, pos) & 0x0FFFFFFF) * 4
+        w1 = be32(ev, pos + 4)
+        hdr, opt = (w1 & 0x1F) * 4, (w1 >> 8) * 4
+        if hdr < 32:
+            return None, (K_PUT, pos)
+        if msg == 0 or pos + msg > n or hdr + opt >= msg:
+            return None, (K_PUT, pos)
+        pad = int(ev[pos + msg - 1])
+        if pad < 1 or pad > 4 or hdr + opt + pad > msg:
+            return None, (K_PAD, pos + msg - 1)
+        hdrs.append(pos)
+        pos += msg
+    return hdrs, None
+
+
+def native_error(ev):
+    """(error text, the offset it names) of the native walk, or None when it
+    accepts the event."""
+    try:
+        PutMessageIterator.scan(_Raw(ev))
+    except BmqCrcError as e:
+        m = re.search(r"\(offset (\d+)\)", str(e))
+        return str(e), int(m.group(1))
+    return None
+
+
+class _Raw:
+    """An event as PutMessageIterator.scan takes it, without the constructor's
+    own checks (the native walk is what is asked)."""
+
+    def __init__(self, ev):
+        self.ev = np.ascontiguousarray(ev, np.uint8)
+
+
+def model(buf, event_offsets=None, msg_cap=None):
+    """The call's outcome on the events in `buf`: a dict with `refused` =
+    (kind, event, offset) and nothing else, or `refused` None and the arrays
+    (crcs = the host CRCs of the application data, expected = the headers')."""
+    buf = np.ascontiguousarray(buf, np.uint8)
+    offs = [0, buf.size] if event_offsets is None else [int(x) for x in event_offsets]
+    refusals, events = [], []
+    for e in range(len(offs) - 1):
+        b, t = offs[e], offs[e + 1]
+        if b > t or t > buf.size or b % 4:
+            refusals.append((K_OFFSETS, e, b))
+            continue
+        ev = buf[b:t]
+        hdrs, bad = walk(ev)
+        if bad:
+            refusals.append((bad[0], e, b + bad[1]))
+        events.append((e, b, ev, hdrs))
+    if refusals:
+        return {"refused": min(refusals)}
+    out = {k: [] for k in ("app_offsets", "lengths", "queue_ids", "guids", "flags", "expected",
+                           "crcs")}
+    first = [0]
+    for e, b, ev, hdrs in events:
+        off, ln, pos = PutMessageIterator.scan(_Raw(ev))
+        assert len(off) == len(hdrs) and [int(p) - 28 for p in pos] == hdrs
+        msgs = list(PutMessageIterator(ev)) if len(off) else []
+        assert [m["app_offset"] for m in msgs] == [int(o) for o in off]
+        assert [len(m["app_data"]) for m in msgs] == [int(x) for x in ln]
+        for m in msgs:
+            out["app_offsets"].append(b + m["app_offset"])
+            out["lengths"].append(len(m["app_data"]))
+            out["queue_ids"].append(m["queue_id"])
+            out["guids"].append(np.frombuffer(m["guid"], np.uint8))
+            out["flags"].append(m["flags"])
+            out["expected"].append(m["crc32c"])
+            out["crcs"].append(Crc32c.calculate(m["app_data"]))
+        first.append(len(out["lengths"]))
+    n = first[-1]
+    if msg_cap is not None and n > msg_cap:
+        e = min(e for e in range(len(first) - 1) if first[e + 1] > msg_cap)
+        return {"refused": (K_MANY, e, offs[e] if event_offsets is not None else 0)}
+    return {"refused": None, "n": n,
+            "app_offsets": np.array(out["app_offsets"], np.int64),
+            "lengths": np.array(out["lengths"], np.uint32),
+            "queue_ids": np.array(out["queue_ids"], np.int32),
+            "guids": np.array(out["guids"], np.uint8).reshape(n, 16),
+            "flags": np.array(out["flags"], np.uint8),
+            "expected": np.array(out["expected"], np.uint32),
+            "crcs": np.array(out["crcs"], np.uint32),
+            "event_first": np.array(first, np.int64)}
+
+
+# ---- inputs ------------------------------------------------------------------
+
+def payload(rng, n):
+    return rng.integers(0, 256, size=n, dtype=np.uint8).tobytes()
+
+
+def build_event(rng, lens, options=None):
+    """One finalized event of len(lens) messages with random queue ids
+    (negative ones included), GUIDs and flags; options[i] (bytes, a multiple
+    of 4) when given."""
+    b = PutEventBuilder(defer_crc=False)
+    for i, ln in enumerate(lens):
+        b.pack_message(payload(rng, int(ln)), queue_id=int(rng.integers(-2**31, 2**31)),
+                       guid=payload(rng, 16), flags=int(rng.integers(0, 16)),
+                       options=options[i] if options is not None else b"")
+    return b.finalize()
+
+
+def concat(events):
+    """(buffer, event offsets) of events back to back."""
+    offs = np.concatenate([[0], np.cumsum([len(e) for e in events])]).astype(np.int64)
+    buf = np.concatenate([np.asarray(e, np.uint8) for e in events]) if events \
+        else np.zeros(0, np.uint8)
+    return buf, offs
+
+
+def ramp_event(rng):
+    """One event of 1,024 messages with application lengths 0..1023: its
+    headers stand at all 256 word positions modulo 1 KiB and so do its padding
+    bytes (test_put_unpack_model.py asserts both)."""
+    return build_event(rng, range(1024))
+
+
+def long_event_header(ev, words=3):
+    """`ev` with an EventHeader of 4 * words bytes (the extra ones zero)."""
+    extra = 4 * words - 8
+    out = np.concatenate([ev[:8], np.zeros(extra, np.uint8), ev[8:]])
+    put32(out, 0, out.size)
+    out[5] = words
+    return out
+
+
+def long_put_headers(ev, words=10):
+    """`ev` with every PutHeader grown to 4 * words bytes (the extra ones zero)."""
+    hdrs, bad = walk(ev)
+    assert bad is None
+    parts = [ev[:int(ev[5]) * 4].copy()]
+    for h in hdrs:
+        msg = (be32(ev, h) & 0x0FFFFFFF) * 4
+        w0, w1 = be32(ev, h), be32(ev, h + 4)
+        hw = (w1 & 0x1F) * 4
+        m = np.concatenate([ev[h:h + hw], np.zeros(4 * words - hw, np.uint8), ev[h + hw:h + msg]])
+        put32(m, 0, (w0 & 0xF0000000) | (m.size // 4))
+        put32(m, 4, (w1 & 0xFFFFFFE0) | words)
+        parts.append(m)
+    out = np.concatenate(parts)
+    put32(out, 0, out.size)
+    return out
+
+
+def with_cat_bits(ev, cat=5):
+    """`ev` with nonzero CompressionAlgorithmType bits in every PutHeader."""
+    out = ev.copy()
+    for h in walk(ev)[0]:
+        out[h + 7] |= (cat & 7) << 5
+    return out
+
+
+def _second_header(ev):
+    return walk(ev)[0][1]
+
+
+def _mutate(name, ev):
+    """Event `ev` (three messages at least, below 1,020 bytes) made malformed."""
+    ev = ev.copy()
+    h = _second_header(ev)
+    msg = (be32(ev, h) & 0x0FFFFFFF) * 4
+    if name == "length_off_by_4":
+        put32(ev, 0, ev.size + 4)
+    elif name == "type_3":
+        ev[4] = (1 << 6) | 3
+    elif name == "event_header_words_1":
+        ev[5] = 1
+    elif name == "event_header_words_past":
+        ev[5] = 255
+    elif name == "truncated_put_header":
+        ev = np.concatenate([ev, np.zeros(4, np.uint8)])
+        put32(ev, 0, ev.size)
+    elif name == "put_header_words_7":
+        ev[h + 7] = (int(ev[h + 7]) & 0xE0) | 7
+    elif name == "message_words_0":
+        put32(ev, h, be32(ev, h) & 0xF0000000)
+    elif name == "message_words_past":
+        put32(ev, h, (be32(ev, h) & 0xF0000000) | (ev.size // 4))
+    elif name == "message_words_le_header":
+        put32(ev, h, (be32(ev, h) & 0xF0000000) | 9)
+    elif name == "padding_0":
+        ev[h + msg - 1] = 0
+    elif name == "padding_5":
+        ev[h + msg - 1] = 5
+    else:
+        raise KeyError(name)
+    return ev
+
+
+EVENT_VARIANTS = ("length_off_by_4", "type_3", "event_header_words_1", "event_header_words_past",
+                  "truncated_put_header", "put_header_words_7", "message_words_0",
+                  "message_words_past", "message_words_le_header", "padding_0", "padding_5")
+OFFSET_VARIANTS = ("offsets_decreasing", "offsets_past_end", "offsets_unaligned", "event_short")
+VARIANTS = OFFSET_VARIANTS + EVENT_VARIANTS
+# (A padding byte "larger than the data" with a count in 1..4 cannot be built:
+# header, options and message sizes are multiples of 4 and header + options <
+# message, so four bytes of data and padding at least remain.  padding_5 is
+# the case that clause of the host walk can meet.)
+
+
+def malformed(name, seed=7):
+    """(buffer, event offsets) of three events of which the middle one, or
+    the offsets around it, are malformed as `name` says.  Every event is
+    malformed inside the buffer; only offsets_past_end names a byte behind it."""
+    rng = np.random.default_rng(seed)
+    good = [build_event(rng, ln) for ln in ([5, 0, 17], [9, 33, 2, 64], [1, 70])]
+    if name in EVENT_VARIANTS:
+        good[1] = _mutate(name, good[1])
+        return concat(good)
+    if name == "event_short":
+        good.insert(1, np.zeros(4, np.uint8))
+        return concat(good)
+    buf, offs = concat(good)
+    if name == "offsets_decreasing":
+        offs[1], offs[2] = offs[2], offs[1]
+    elif name == "offsets_past_end":
+        offs[3] = buf.size + 4  # (the GPU test keeps slack behind the buffer)
+    elif name == "offsets_unaligned":
+        offs[1] += 2
+    else:
+        raise KeyError(name)
+    return buf, offs

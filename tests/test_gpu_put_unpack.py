@@ -1,0 +1,458 @@
+"""Device-side PUT-event walk (bmqcrc_put_event_unpack, ABI 2.12) on the GPU.
+The oracle throughout is tests/put_unpack_model.py (the host's own walks plus
+host CRCs).  Every raw call hands the library canary-filled output arrays with
+guard elements behind msg_cap: the guards are checked after every call, the
+slots the call leaves untouched after a successful one, and every element
+after a refused one."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, last_copy, last_launch,
+                           last_put_pack, last_put_unpack, last_records_pack, pack_events,
+                           pack_records, unpack_events)
+from blazingmq_amd import storage as S
+import put_pack_model as P
+import put_unpack_model as M
+from records_pack_model import REC, wrap_partition
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 8
+SLACK = 64   # bytes kept behind every events buffer (offsets_past_end points into them)
+CANARY = {"app_offsets": 0x5A5A5A5A5A5A5A5A, "lengths": 0x5A5A5A5A, "queue_ids": 0x5A5A5A5A,
+          "guids": 0xA5, "flags": 0xA5, "expected": 0x5A5A5A5A, "out": 0x5A5A5A5A,
+          "event_first": 0x5A5A5A5A5A5A5A5A}
+PER = {"app_offsets": 1, "lengths": 1, "queue_ids": 1, "guids": 16, "flags": 1, "expected": 1,
+       "out": 1}
+KIND_NAME = {1: b"EVENT_OFFSETS", 2: b"EVENT_HEADER", 3: b"PUT_HEADER", 4: b"PADDING",
+             5: b"TOO_MANY_MESSAGES"}
+
+
+def _side_stream(cuda):
+    """A stream of its own from the high-priority pool (the default pool's
+    streams carry planner history that tests elsewhere rely on)."""
+    import torch
+    return torch.cuda.Stream(cuda, priority=-1)
+
+
+def _t(cuda, a, dtype):
+    import torch
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if dtype == np.uint32:
+        a = a.view(np.int32)
+    return torch.from_numpy(a).to(cuda)
+
+
+def _device_events(cuda, buf):
+    """`buf` on the device as a view of a longer allocation."""
+    import torch
+    back = torch.full((buf.size + SLACK,), 0xEE, dtype=torch.uint8, device=cuda)
+    back[:buf.size] = torch.from_numpy(np.ascontiguousarray(buf)).to(cuda)
+    return back[:buf.size]
+
+
+def _raw(cuda, events, offs, cap, verify=True, sync=True, stream=None, skip=()):
+    """One bmqcrc_put_event_unpack into canary-filled arrays.  Returns (rc,
+    error text, result of the call or of bmqcrc_last_put_unpack, the arrays
+    on the host with their guards)."""
+    import torch
+    stream = stream or torch.cuda.current_stream(cuda)
+    n_events = 1 if offs is None else len(offs) - 1
+    dt = {"app_offsets": torch.int64, "lengths": torch.int32, "queue_ids": torch.int32,
+          "guids": torch.uint8, "flags": torch.uint8, "expected": torch.int32,
+          "out": torch.int32, "event_first": torch.int64}
+    with torch.cuda.stream(stream):
+        d_offs = _t(cuda, offs, np.int64) if offs is not None else None
+        arr = {}
+        for name, t in dt.items():
+            if name in skip or (name == "out" and not verify):
+                continue
+            size = n_events + 1 + GUARD if name == "event_first" else (cap + GUARD) * PER[name]
+            fill = CANARY[name] - (1 << 64 if t == torch.int64 and CANARY[name] >> 63 else 0)
+            arr[name] = torch.full((size,), fill, dtype=t, device=cuda)
+        p = N.PutUnpack()
+        p.struct_size = ctypes.sizeof(N.PutUnpack)
+        p.events, p.events_bytes = events.data_ptr(), events.numel()
+        p.event_offsets = d_offs.data_ptr() if d_offs is not None else None
+        p.n_events, p.msg_cap = n_events, cap
+        for name, t in arr.items():
+            setattr(p, name, t.data_ptr())
+        o = N.make_opts(device=cuda.index, stream=stream.cuda_stream,
+                        flags=N.BMQCRC_F_DEVICE_PTRS | (0 if sync else N.BMQCRC_F_ASYNC))
+        r = N.PutUnpackResult()
+        rc = N.lib.bmqcrc_put_event_unpack(ctypes.byref(p), ctypes.byref(r), ctypes.byref(o))
+        err = N.lib.bmqcrc_last_error()
+        res = r.as_dict() if sync else None
+        if not sync:
+            assert rc == 0, (rc, err)
+            assert r.as_dict() == N.PutUnpackResult().as_dict()  # written by a synchronous call only
+            res = last_put_unpack(cuda.index, stream)
+        host = {}
+        for name, t in arr.items():
+            a = t.cpu().numpy()
+            host[name] = a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.itemsize]) \
+                if name != "queue_ids" else a
+    return rc, err, res, host
+
+
+def _canary(name, a):
+    want = CANARY[name] if name != "queue_ids" else np.int32(CANARY[name])
+    return bool(np.all(a == want))
+
+
+def _guards_intact(host, cap, n_events):
+    for name, a in host.items():
+        at = n_events + 1 if name == "event_first" else cap * PER[name]
+        assert a.size == at + GUARD * PER.get(name, 1) and _canary(name, a[at:]), name
+
+
+def _ok(cuda, buf, offs, cap=None, verify=True, sync=True, stream=None, model=None, n_bad=0,
+        first_bad=None, skip=()):
+    """A call that must succeed, against the model.  Returns (model, arrays)."""
+    m = model or M.model(buf, offs)
+    assert m["refused"] is None
+    n = m["n"]
+    cap = n + 5 if cap is None else cap
+    n_events = 1 if offs is None else len(offs) - 1
+    rc, err, res, host = _raw(cuda, _device_events(cuda, buf), offs, cap, verify, sync, stream,
+                              skip)
+    assert rc == 0, (rc, err)
+    assert res == dict(n_events=n_events, n_msgs=n, n_bad=n_bad,
+                       first_bad=n if first_bad is None else first_bad, refused_kind=0,
+                       refused_event=0, refused_offset=0), res
+    _guards_intact(host, cap, n_events)
+    for name in ("app_offsets", "lengths", "queue_ids", "flags", "expected", "event_first"):
+        if name in host:
+            k = len(m[name])
+            assert np.array_equal(host[name][:k].astype(np.int64), m[name].astype(np.int64)), name
+    if "guids" in host:
+        assert np.array_equal(host["guids"][:16 * n].reshape(n, 16), m["guids"])
+    for name in ("queue_ids", "guids", "flags"):  # untouched where no message is
+        if name in host:
+            assert _canary(name, host[name][n * PER[name]:]), name
+    return m, host
+
+
+def _refused(cuda, buf, offs, cap, want=None, verify=True):
+    """A call that must be refused, synchronously and asynchronously: the
+    model's (kind, event, offset), and not one element written."""
+    kind, event, offset = want or M.model(buf, offs, cap)["refused"]
+    events = _device_events(cuda, buf)
+    n_events = 1 if offs is None else len(offs) - 1
+    for sync in (True, False):
+        rc, err, res, host = _raw(cuda, events, offs, cap, verify, sync)
+        if sync:
+            assert rc == N.BMQCRC_EINVAL and KIND_NAME[kind] in err and \
+                b"nothing was written" in err, (rc, err)
+            assert (b"%d" % event) in err and (b"offset %d" % offset) in err, err
+        assert res == dict(n_events=n_events, n_msgs=0, n_bad=0, first_bad=0, refused_kind=kind,
+                           refused_event=event, refused_offset=offset), (sync, res)
+        for name, a in host.items():
+            assert _canary(name, a), (sync, name)
+    return kind, event, offset
+
+
+# ---- round trip --------------------------------------------------------------
+
+def test_round_trip_with_the_packer(cuda):
+    import torch
+    rng = np.random.default_rng(21)
+    lens = np.arange(71, dtype=np.uint32)
+    rng.shuffle(lens)
+    soff = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    src = rng.integers(0, 256, size=int(lens.sum()), dtype=np.uint8)
+    qids, guids, flags = P.random_meta(rng, 71)
+    qids[:3] = [-1, -2**31, 2**31 - 1]
+    ef = np.array([0, 1, 12, 13, 30, 45, 64, 71], np.int64)
+    events, evoff, crcs = pack_events(
+        _t(cuda, src, np.uint8), _t(cuda, soff, np.int64), _t(cuda, lens, np.uint32),
+        _t(cuda, qids, np.int32), _t(cuda, guids, np.uint8), _t(cuda, flags, np.uint8),
+        _t(cuda, ef, np.int64))
+    want = P.host_crcs(src, soff, lens)
+    u = unpack_events(events, evoff)
+    res = last_put_unpack(cuda.index, torch.cuda.current_stream(cuda))
+    assert (res["n_events"], res["n_msgs"], res["n_bad"], res["first_bad"],
+            res["refused_kind"]) == (7, 71, 0, 71, 0)
+    assert np.array_equal(u.lengths.cpu().numpy().view(np.uint32), lens)
+    assert np.array_equal(u.queue_ids.cpu().numpy(), qids)
+    assert np.array_equal(u.guids.cpu().numpy(), guids) and u.guids.shape == (71, 16)
+    assert np.array_equal(u.flags.cpu().numpy(), flags)
+    assert np.array_equal(u.event_first.cpu().numpy(), ef)
+    assert np.array_equal(u.expected.cpu().numpy().view(np.uint32), want)
+    assert np.array_equal(u.crcs.cpu().numpy().view(np.uint32), want)
+    assert np.array_equal(crcs.cpu().numpy().view(np.uint32), want)
+    again, evoff2, _ = pack_events(events, u.app_offsets, u.lengths, u.queue_ids, u.guids, u.flags,
+                                   u.event_first)
+    assert torch.equal(again, events) and torch.equal(evoff2, evoff)
+    # and the canary form of the same call, against the model
+    _ok(cuda, events.cpu().numpy(), evoff.cpu().numpy())
+
+
+# ---- window and lane edges ---------------------------------------------------
+
+def test_every_window_position(cuda):
+    ev = M.ramp_event(np.random.default_rng(1))
+    m, host = _ok(cuda, ev, None)
+    assert m["n"] == 1024
+    assert np.array_equal(host["out"][:1024], m["crcs"])
+
+
+@pytest.mark.parametrize("count", [1, 63, 64, 65, 128, 129])
+def test_lane_edges(cuda, count):
+    rng = np.random.default_rng(count)
+    ev = M.build_event(rng, rng.integers(0, 40, size=count))
+    m, host = _ok(cuda, ev, np.array([0, ev.size]), cap=count)
+    assert np.array_equal(host["out"][:count], m["crcs"])
+
+
+def test_long_messages_among_short_ones(cuda):
+    rng = np.random.default_rng(22)
+    ev = M.build_event(rng, [3, 5000, 0, 70000, 17, 5000, 70001, 1, 2])
+    m, host = _ok(cuda, ev, None)
+    assert np.array_equal(host["out"][:9], m["crcs"])
+
+
+def test_an_event_with_no_message_between_two_others(cuda):
+    rng = np.random.default_rng(23)
+    buf, offs = M.concat([M.build_event(rng, [4, 9]), M.build_event(rng, []),
+                          M.build_event(rng, [0, 1, 2])])
+    assert offs[2] - offs[1] == 8
+    m, host = _ok(cuda, buf, offs)
+    assert list(m["event_first"]) == [0, 2, 2, 5]
+    assert np.array_equal(host["out"][:5], m["crcs"])
+    # nothing but empty events: no message, and msg_cap 0 is legal
+    buf, offs = M.concat([M.build_event(rng, [])] * 3)
+    _ok(cuda, buf, offs, cap=0)
+
+
+def test_more_events_than_the_walk_grid(cuda):
+    rng = np.random.default_rng(24)
+    buf, offs = M.concat([M.build_event(rng, [int(k)]) for k in rng.integers(0, 24, size=5000)])
+    m, host = _ok(cuda, buf, offs)
+    assert m["n"] == 5000 and np.array_equal(host["out"][:5000], m["crcs"])
+
+
+def test_one_event_without_offsets_and_optional_arrays_left_out(cuda):
+    rng = np.random.default_rng(25)
+    ev = M.build_event(rng, rng.integers(0, 200, size=150))
+    m = M.model(ev)
+    _ok(cuda, ev, None, model=m)
+    _ok(cuda, ev, None, model=m, skip=("queue_ids", "guids", "flags", "expected", "event_first"))
+    _ok(cuda, ev, None, model=m, verify=False, skip=("guids",))
+    u = unpack_events(_device_events(cuda, ev))  # msg_cap None: the most the buffer can hold
+    assert u.lengths.numel() == 150 and u.event_first.tolist() == [0, 150]
+    assert np.array_equal(u.crcs.cpu().numpy().view(np.uint32), m["crcs"])
+
+
+def test_events_beyond_4_gib_of_buffer(cuda):
+    # positions with bits 31 and 32 set: nothing in the walk, the placing or
+    # the refusal may hold a byte position in 32 bits or sign-extend one
+    import torch
+    base = (1 << 32) + (1 << 31) + 64
+    rng = np.random.default_rng(33)
+    buf, offs = M.concat([M.build_event(rng, rng.integers(0, 3000, size=k)) for k in (70, 3, 0)])
+    m = M.model(buf, offs)
+    back = torch.empty(base + buf.size + SLACK, dtype=torch.uint8, device=cuda)
+    back[base:base + buf.size] = torch.from_numpy(buf).to(cuda)
+    events, cap = back[:base + buf.size], m["n"] + 3
+    rc, err, res, host = _raw(cuda, events, offs + base, cap)
+    assert rc == 0, (rc, err)
+    assert res == dict(n_events=3, n_msgs=73, n_bad=0, first_bad=73, refused_kind=0,
+                       refused_event=0, refused_offset=0), res
+    _guards_intact(host, cap, 3)
+    assert np.array_equal(host["app_offsets"][:73].astype(np.int64), m["app_offsets"] + base)
+    for name in ("lengths", "queue_ids", "flags", "expected"):
+        assert np.array_equal(host[name][:73].astype(np.int64), m[name].astype(np.int64)), name
+    assert np.array_equal(host["out"][:73], m["crcs"])
+    assert np.array_equal(host["guids"][:16 * 73].reshape(73, 16), m["guids"])
+    assert list(host["event_first"][:4]) == [0, 70, 73, 73]
+    # and a refusal there names a byte beyond 4 GiB
+    bad, offs = M.malformed("padding_5")
+    kind, event, offset = M.model(bad, offs)["refused"]
+    back[base:base + bad.size] = torch.from_numpy(bad).to(cuda)
+    for sync in (True, False):
+        rc, err, res, host = _raw(cuda, back[:base + bad.size], offs + base, 64, sync=sync)
+        assert (res["refused_kind"], res["refused_event"], res["refused_offset"]) == \
+            (kind, event, offset + base), res
+        assert all(_canary(name, a) for name, a in host.items())
+    del back, events
+    torch.cuda.empty_cache()
+
+
+# ---- header variants ---------------------------------------------------------
+
+def test_header_variants(cuda):
+    rng = np.random.default_rng(26)
+    n = 70
+    lens = rng.integers(0, 90, size=n)
+    options = [M.payload(rng, 4 * int(k)) for k in rng.integers(0, 6, size=n)]
+    plain = M.build_event(rng, lens)
+    buf, offs = M.concat([M.long_event_header(plain), M.long_put_headers(plain),
+                          M.build_event(rng, lens, options), M.with_cat_bits(plain)])
+    m, host = _ok(cuda, buf, offs)
+    assert m["n"] == 4 * n and np.array_equal(host["out"][:4 * n], m["crcs"])
+    assert np.array_equal(m["expected"], m["crcs"])
+
+
+# ---- verify ------------------------------------------------------------------
+
+def test_verify_counts_corrupt_payloads_and_corrupt_header_crcs(cuda):
+    rng = np.random.default_rng(27)
+    n = 200
+    buf, offs = M.concat([M.build_event(rng, rng.integers(1, 120, size=100)) for _ in range(2)])
+    good = M.model(buf, offs)
+    victims = [0, 64, n - 1]
+    for what in ("payload", "header"):
+        bad = buf.copy()
+        for v in victims:
+            at = int(good["app_offsets"][v])
+            if what == "payload":
+                bad[at] ^= 0x10
+            else:
+                hdr = [o + h for o, ev in ((offs[0], buf[:offs[1]]), (offs[1], buf[offs[1]:]))
+                       for h in M.walk(ev)[0]][v]
+                bad[hdr + 28] ^= 0x01
+        m, host = _ok(cuda, bad, offs, n_bad=3, first_bad=0)
+        differ = np.nonzero(host["out"][:n] != host["expected"][:n])[0]
+        assert list(differ) == victims
+        assert np.array_equal(host["out"][:n], m["crcs"])
+        assert np.array_equal(host["expected"][:n], m["expected"])
+
+
+def test_walk_only_leaves_the_launch_record(cuda):
+    import torch
+    rng = np.random.default_rng(28)
+    buf, offs = M.concat([M.build_event(rng, rng.integers(1, 120, size=60)) for _ in range(3)])
+    bad = buf.copy()
+    bad[int(M.model(buf, offs)["app_offsets"][5])] ^= 1
+    s = _side_stream(cuda)
+    with torch.cuda.stream(s):
+        arena = _t(cuda, buf, np.uint8)
+        Crc32c.calculate_batch(arena, _t(cuda, [0, 64], np.int64), _t(cuda, [64, 100], np.uint32),
+                               stream=s, seg_bytes=1024)
+        before = last_launch(cuda.index, s, offsets=True)
+        _ok(cuda, bad, offs, verify=False, stream=s)  # n_bad == 0: nothing was compared
+        assert last_launch(cuda.index, s, offsets=True) == before
+
+
+# ---- refusals ----------------------------------------------------------------
+
+@pytest.mark.parametrize("name", M.VARIANTS)
+def test_malformed_input_is_refused_like_the_host_walk(cuda, name):
+    buf, offs = M.malformed(name)
+    kind, event, _ = _refused(cuda, buf, offs, 64)
+    assert event == (2 if name == "offsets_past_end" else 1)
+    assert kind == M.model(buf, offs)["refused"][0]
+
+
+def test_msg_cap_edge(cuda):
+    rng = np.random.default_rng(29)
+    buf, offs = M.concat([M.build_event(rng, ln) for ln in ([1, 2], [], [3, 4, 5], [])])
+    _ok(cuda, buf, offs, cap=5)
+    assert _refused(cuda, buf, offs, 4) == (M.K_MANY, 2, int(offs[2]))
+    assert _refused(cuda, buf, offs, 0, verify=False) == (M.K_MANY, 0, 0)
+    ev = M.build_event(rng, range(130))
+    assert _refused(cuda, ev, None, 129) == (M.K_MANY, 0, 0)
+
+
+def test_refusal_precedence(cuda):
+    rng = np.random.default_rng(30)
+    good = M.build_event(rng, [4, 5, 6])
+    pad, typ = M._mutate("padding_0", good), M._mutate("type_3", good)
+    buf, offs = M.concat([good, pad, typ, typ])
+    assert _refused(cuda, buf, offs, 64)[:2] == (M.K_EVENT, 2)    # the lower kind
+    buf, offs = M.concat([pad, good, pad] + [good] * 40 + [pad])
+    assert _refused(cuda, buf, offs, 256)[:2] == (M.K_PAD, 0)     # the lower event
+    buf, offs = M.concat([good, pad, good])
+    assert _refused(cuda, buf, offs, 2)[:2] == (M.K_PAD, 1)       # before TOO_MANY_MESSAGES
+
+
+def test_python_wrapper_raises_and_reports(cuda):
+    import torch
+    buf, offs = M.malformed("padding_5")
+    kind, event, offset = M.model(buf, offs)["refused"]
+    events, d_offs = _device_events(cuda, buf), _t(cuda, offs, np.int64)
+    with pytest.raises(BmqCrcError, match="BMQCRC_PUT_UNPACK_PADDING") as e:
+        unpack_events(events, d_offs)
+    assert e.value.rc == N.BMQCRC_EINVAL
+    s = _side_stream(cuda)
+    with torch.cuda.stream(s):
+        u = unpack_events(events, d_offs, msg_cap=32, stream=s, sync=False)
+        assert u.lengths.numel() == 32 and u.guids.shape == (32, 16)
+        res = last_put_unpack(cuda.index, s)
+    assert (res["refused_kind"], res["refused_event"], res["refused_offset"]) == \
+        (kind, event, offset)
+
+
+# ---- state -------------------------------------------------------------------
+
+def test_state(cuda):
+    import torch
+    rng = np.random.default_rng(31)
+    host = rng.integers(0, 256, size=1 << 18, dtype=np.uint8)
+    arena = torch.from_numpy(host).to(cuda)
+    lens = rng.integers(1, 1025, size=3001).astype(np.uint32)
+    offs = (rng.random(lens.size) * (host.size - 1100)).astype(np.int64)
+    d_off, d_len = _t(cuda, offs, np.int64), _t(cuda, lens, np.uint32)
+    doff = _t(cuda, np.concatenate([[0], np.cumsum(lens[:40])[:-1]]), np.int64)
+    copy_dst = torch.zeros(int(lens[:40].sum()) + 16, dtype=torch.uint8, device=cuda)
+    qids, guids, flags = P.random_meta(rng, 30)
+    buf, evoffs = M.concat([M.build_event(rng, rng.integers(0, 300, size=50)) for _ in range(4)])
+    s = _side_stream(cuda)
+    with torch.cuda.stream(s):
+        Crc32c.copy_batch(arena, d_off[:40], d_len[:40], copy_dst, doff, stream=s)
+        pack_events(arena, d_off[:30], d_len[:30], _t(cuda, qids, np.int32),
+                    _t(cuda, guids, np.uint8), _t(cuda, flags, np.uint8), stream=s)
+        pack_records(arena, d_off[:30], d_len[:30],
+                     _t(cuda, np.full((30, 5), 7), np.uint8), _t(cuda, guids, np.uint8),
+                     file_key=b"\x11\x22\x33\x44\x55", lease_id=3, first_seq=2,
+                     data_file_pos=40, stream=s)
+        put, rec = last_put_pack(cuda.index, s), last_records_pack(cuda.index, s)
+        assert last_put_unpack(cuda.index, s) == N.PutUnpackResult().as_dict()  # none yet on s
+        _ok(cuda, buf, evoffs, stream=s)
+        _ok(cuda, buf, evoffs, stream=s, sync=False)
+        assert last_copy(cuda.index, s) == (40, 0, 40)
+        assert last_put_pack(cuda.index, s) == put
+        assert last_records_pack(cuda.index, s) == rec
+        plan = last_launch(cuda.index, s, offsets=True)
+        # a planned batch: planner and fold, nothing speculated, 64-bit offsets
+        assert plan["kernels"] >= 2 and plan["spec"] == 0 and plan["offset_bits"] == 64, plan
+        out = Crc32c.calculate_batch(arena, d_off, d_len, stream=s)
+    s.synchronize()
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), P.host_crcs(host, offs, lens))
+
+
+# ---- the loop closed ---------------------------------------------------------
+
+def test_put_events_to_verified_partition_without_host_descriptors(cuda):
+    rng = np.random.default_rng(32)
+    n = 300
+    key = bytes([9, 8, 7, 6, 5])
+    buf, evoffs = M.concat([M.build_event(rng, rng.integers(0, 120, size=100)) for _ in range(3)])
+    m = M.model(buf, evoffs)
+    victim = next(i for i in range(100, n) if m["lengths"][i] > 0)
+    kw = dict(file_key=b"\x11\x22\x33\x44\x55", lease_id=1, first_seq=2, data_file_pos=40,
+              timestamp=0x6720EAB4)
+    import torch
+    for corrupt in (False, True):
+        ev = buf.copy()
+        if corrupt:
+            ev[int(m["app_offsets"][victim])] ^= 0x40
+        events = _device_events(cuda, ev)
+        u = unpack_events(events, _t(cuda, evoffs, np.int64), msg_cap=n)
+        res = last_put_unpack(cuda.index, torch.cuda.current_stream(cuda))
+        assert (res["n_msgs"], res["n_bad"]) == (n, int(corrupt))
+        qkeys = torch.from_numpy(np.frombuffer(key, np.uint8).copy()).to(cuda).repeat(n, 1)
+        dst, jour, roff, crcs, rres = pack_records(events, u.app_offsets, u.lengths, qkeys,
+                                                   u.guids, expected=u.expected, **kw)
+        assert (rres["n_msgs"], rres["n_bad"], rres["refused_kind"]) == (n, int(corrupt), 0)
+        if corrupt:
+            assert res["first_bad"] == rres["first_bad"] == victim
+        jf, df = wrap_partition(dst.cpu().numpy(), jour.cpu().numpy(),
+                                np.frombuffer(key, np.uint8))
+        got = S.verify_partition(jf, df)
+        assert (got["recovery_rc"], got["n_messages"], got["n_bad"]) == (0, n, int(corrupt))
+        if corrupt:
+            assert list(got["bad_record_offsets"]) == [44 + 60 + REC * victim]

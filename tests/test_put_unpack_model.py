@@ -1,0 +1,124 @@
+"""The outputs and refusals bmqcrc_put_event_unpack (ABI 2.12) promises,
+restated in tests/put_unpack_model.py, held against the host's own walk
+(bmqcrc_put_event_scan); and the inputs the GPU tests rely on."""
+import numpy as np
+import pytest
+
+from blazingmq_amd import unpack_events  # noqa: F401  (ABI 2.12: absent before it)
+from blazingmq_amd.put_event import PutMessageIterator
+import put_unpack_model as M
+
+
+def _options(rng, n):
+    return [M.payload(rng, 4 * int(k)) for k in rng.integers(0, 5, size=n)]
+
+
+@pytest.mark.parametrize("with_options", [False, True])
+def test_model_agrees_with_the_native_scan(with_options):
+    rng = np.random.default_rng(11)
+    lens = [list(rng.integers(0, 300, size=k)) for k in (1, 7, 0, 70)]
+    events = [M.build_event(rng, ln, _options(rng, len(ln)) if with_options else None)
+              for ln in lens]
+    buf, offs = M.concat(events)
+    m = M.model(buf, offs)
+    assert m["refused"] is None and m["n"] == 78
+    assert list(m["event_first"]) == [0, 1, 8, 8, 78]
+    i = 0
+    for e, ev in enumerate(events):
+        hdrs, bad = M.walk(ev)
+        assert bad is None and len(hdrs) == len(lens[e])
+        off, ln, pos = PutMessageIterator(ev).scan()
+        for j in range(len(off)):
+            assert m["app_offsets"][i] == offs[e] + off[j] and m["lengths"][i] == ln[j]
+            assert m["lengths"][i] == lens[e][j]
+            assert m["expected"][i] == M.be32(ev, int(pos[j])) == m["crcs"][i]
+            assert pos[j] == hdrs[j] + 28
+            i += 1
+    assert i == 78
+    if with_options:
+        assert np.any(m["app_offsets"][1:8] - offs[1] !=
+                      np.array(M.walk(events[1])[0]) + 36)  # options were skipped
+
+
+@pytest.mark.parametrize("name", M.EVENT_VARIANTS + ("event_short",))
+def test_model_names_the_offset_of_the_native_error(name):
+    buf, offs = M.malformed(name)
+    ev = buf[offs[1]:offs[2]]
+    err = M.native_error(ev)
+    assert err is not None, name
+    hdrs, bad = M.walk(ev)
+    assert hdrs is None and bad[1] == err[1], (name, bad, err)
+    want = {"event_short": M.K_EVENT, "length_off_by_4": M.K_EVENT, "type_3": M.K_EVENT,
+            "event_header_words_1": M.K_EVENT, "event_header_words_past": M.K_EVENT,
+            "padding_0": M.K_PAD, "padding_5": M.K_PAD}.get(name, M.K_PUT)
+    assert M.model(buf, offs)["refused"] == (want, 1, int(offs[1]) + err[1])
+    # the events around it are well formed
+    assert M.native_error(buf[offs[0]:offs[1]]) is None
+    assert M.native_error(buf[offs[2]:offs[3]]) is None
+
+
+def test_malformed_variants_hit_every_check_of_the_host_walk():
+    texts = set()
+    for name in M.EVENT_VARIANTS + ("event_short",):
+        buf, offs = M.malformed(name)
+        texts.add(M.native_error(buf[offs[1]:offs[2]])[0].split(": ", 1)[1].split(" (offset")[0])
+    assert texts == {"PUT event shorter than its EventHeader",
+                     "EventHeader length differs from the event size", "not a PUT event",
+                     "EventHeader headerWords out of range", "truncated PutHeader",
+                     "PutHeader headerWords too small for the CRC field",
+                     "PutHeader messageWords inconsistent with the event",
+                     "invalid PUT message padding"}
+
+
+def test_offset_refusals_and_precedence():
+    buf, offs = M.malformed("offsets_decreasing")
+    assert M.model(buf, offs)["refused"] == (M.K_OFFSETS, 1, int(offs[1]))
+    buf, offs = M.malformed("offsets_past_end")
+    assert offs[3] > buf.size and M.model(buf, offs)["refused"] == (M.K_OFFSETS, 2, int(offs[2]))
+    buf, offs = M.malformed("offsets_unaligned")
+    assert M.model(buf, offs)["refused"] == (M.K_OFFSETS, 1, int(offs[1]))
+    # lower kind first, then lower event
+    rng = np.random.default_rng(3)
+    good = M.build_event(rng, [4, 5, 6])
+    a, b = M._mutate("padding_0", good), M._mutate("type_3", good)
+    buf, offs = M.concat([good, a, b, b])
+    assert M.model(buf, offs)["refused"] == (M.K_EVENT, 2, int(offs[2]) + 4)
+    buf, offs = M.concat([a, good, a])
+    assert M.model(buf, offs)["refused"][:2] == (M.K_PAD, 0)
+
+
+def test_msg_cap():
+    rng = np.random.default_rng(5)
+    buf, offs = M.concat([M.build_event(rng, ln) for ln in ([1, 2], [], [3, 4, 5], [])])
+    assert M.model(buf, offs, 5)["refused"] is None
+    assert M.model(buf, offs, 4)["refused"] == (M.K_MANY, 2, int(offs[2]))
+    assert M.model(buf, offs, 1)["refused"] == (M.K_MANY, 0, 0)
+
+
+def test_ramp_event_covers_every_window_position():
+    ev = M.ramp_event(np.random.default_rng(1))
+    assert ev.size == 563208
+    hdrs, bad = M.walk(ev)
+    assert bad is None and len(hdrs) == 1024
+    ends = hdrs[1:] + [ev.size]
+    assert len({h % 1024 // 4 for h in hdrs}) == 256
+    assert len({(e - 1) % 1024 // 4 for e in ends}) == 256
+    m = M.model(ev)
+    assert list(m["lengths"]) == list(range(1024))
+
+
+def test_header_variants_are_well_formed():
+    rng = np.random.default_rng(2)
+    ev = M.build_event(rng, [0, 5, 130, 64])
+    base = M.model(ev)
+    for var, shift in ((M.long_event_header(ev), 4), (M.long_put_headers(ev), None),
+                       (M.with_cat_bits(ev), 0)):
+        assert M.native_error(var) is None
+        m = M.model(var)
+        for k in ("lengths", "queue_ids", "guids", "flags", "expected", "crcs"):
+            assert np.array_equal(m[k], base[k]), k
+        if shift is not None:
+            assert np.array_equal(m["app_offsets"], base["app_offsets"] + shift)
+        else:
+            assert np.array_equal(m["app_offsets"],
+                                  base["app_offsets"] + 4 * np.arange(1, 5))
