@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -398,6 +399,33 @@ int open_ctx(int dev, void* user_stream, Ctx* c)
     return 0;
 }
 
+// The context of (device, stream) as a device call or a query names it, its
+// workspace locked until the LockedCtx goes.  with_state false is for the
+// queries that only read or set workspace fields: no DeviceState (no gfx950
+// check, no occupancy query) and no hipSetDevice, and c->st stays null.
+struct LockedCtx : Ctx {
+    std::unique_lock<std::mutex> lock;
+};
+
+int lock_on(int device, void* stream, bool with_state, LockedCtx* c)
+{
+    int dev, rc;
+    if ((rc = resolve_device(device, &dev))) {
+        return rc;
+    }
+    if (with_state) {
+        if ((rc = open_ctx(dev, stream, c))) {
+            return rc;
+        }
+    } else {
+        c->dev = dev;
+        c->s = (hipStream_t)stream;
+        c->w = workspace(dev, stream);
+    }
+    c->lock = std::unique_lock<std::mutex>(c->w->mu);
+    return 0;
+}
+
 // A speculative single launch (BatchArgs::spec) is used only when every
 // k_fold wave owns at least one group of 64 messages: a message longer than
 // one segment is then folded by the wave that met it, and no wave is idle
@@ -636,6 +664,61 @@ uint64_t offsets_bytes(uint32_t flags, uint64_t n)
     return ((flags & BMQCRC_F_OFFSETS32) ? 4 : 8) * n;
 }
 
+// Where a batch's arrays lie on the device.
+struct DevArrays {
+    const void* arena;
+    const uint64_t* offsets;
+    const uint32_t* lengths;
+    const uint32_t* seeds;
+};
+
+// Stage a host batch's arrays into the workspace (async on c.s; caller holds
+// c.w->mu).  arena_staged: the arena's bytes are in c.w->arena already, and
+// `arena` is not read.  seeds may be null.
+int stage_batch(Ctx& c, uint32_t flags, bool arena_staged, const void* arena,
+                uint64_t arena_bytes, const void* offsets, const uint32_t* lengths,
+                const uint32_t* seeds, uint64_t n, DevArrays* d)
+{
+    Workspace* w = c.w;
+    int rc;
+    if ((!arena_staged && (rc = stage(c, w->arena, arena, arena_bytes))) ||
+        (rc = stage(c, w->offsets, offsets, offsets_bytes(flags, n))) ||
+        (rc = stage(c, w->lengths, lengths, 4 * n)) ||
+        (seeds && (rc = stage(c, w->seeds, seeds, 4 * n)))) {
+        return rc;
+    }
+    d->arena = w->arena.p;
+    d->offsets = (const uint64_t*)w->offsets.p;
+    d->lengths = (const uint32_t*)w->lengths.p;
+    d->seeds = seeds ? (const uint32_t*)w->seeds.p : nullptr;
+    return 0;
+}
+
+// One fold over host arrays (caller holds c.w->mu): stage them, run_batch,
+// copy the n CRCs back to `out` (host) and synchronise.  run_batch is told the
+// longest message and, with min_too, the shortest: the two bounds together
+// select its speculative uniform launch, so min_too changes which kernel runs.
+// (The bounds are taken after the copies are enqueued, while those run.)
+int fold_staged(Ctx& c, uint32_t flags, uint32_t seg, bool arena_staged, const void* arena,
+                uint64_t arena_bytes, const void* offsets, const uint32_t* lengths,
+                const uint32_t* seeds, uint64_t n, bool min_too, uint32_t off_shift,
+                uint32_t* out)
+{
+    DevArrays d;
+    int rc;
+    if ((rc = stage_batch(c, flags, arena_staged, arena, arena_bytes, offsets, lengths, seeds, n,
+                          &d)) ||
+        (rc = c.w->out.ensure(4 * n)) ||
+        (rc = run_batch(c, flags, seg, d.arena, arena_bytes, d.offsets, d.lengths, d.seeds,
+                        (uint32_t*)c.w->out.p, n, max_length(lengths, n),
+                        min_too ? min_length(lengths, n) : 0, off_shift))) {
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out, c.w->out.p, 4 * n, hipMemcpyDeviceToHost, c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    return 0;
+}
+
 // declared_max / declared_min: the caller's bounds on every length of a
 // device-resident batch (bmqcrc_opts.max_len / min_len, 0 = none); host
 // batches use the lengths they hold.
@@ -664,26 +747,13 @@ int batch_one(int dev, void* user_stream, uint32_t flags, uint32_t seg, const vo
         }
         return 0;
     }
-    if ((rc = stage(c, w->arena, arena, arena_bytes)) ||
-        (rc = stage(c, w->offsets, offsets, offsets_bytes(flags, n))) ||
-        (rc = stage(c, w->lengths, lengths, 4 * n)) ||
-        (seeds && (rc = stage(c, w->seeds, seeds, 4 * n))) || (rc = w->out.ensure(4 * n))) {
-        return rc;
-    }
-    if ((rc = run_batch(c, flags, seg, w->arena.p, arena_bytes, (const uint64_t*)w->offsets.p,
-                        (const uint32_t*)w->lengths.p,
-                        seeds ? (const uint32_t*)w->seeds.p : nullptr, (uint32_t*)w->out.p, n,
-                        max_length(lengths, n), min_length(lengths, n), off_shift))) {
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out, w->out.p, 4 * n, hipMemcpyDeviceToHost, c.s));
-    HIP_TRY(hipStreamSynchronize(c.s));
-    return 0;
+    return fold_staged(c, flags, seg, false, arena, arena_bytes, offsets, lengths, seeds, n, true,
+                       off_shift, out);
 }
 
-// offsets32_ok: the entry point takes BMQCRC_F_OFFSETS32 (batch and verify).
-int parse_opts(const bmqcrc_opts* opts, bmqcrc_opts* o, uint32_t* seg, int* dev,
-               bool offsets32_ok = false)
+// The caller's bmqcrc_opts (null: the defaults) as the current layout, read
+// by its struct_size.
+void read_opts(const bmqcrc_opts* opts, bmqcrc_opts* o)
 {
     memset(o, 0, sizeof(*o));
     o->device = -1;
@@ -696,6 +766,13 @@ int parse_opts(const bmqcrc_opts* opts, bmqcrc_opts* o, uint32_t* seg, int* dev,
         memcpy(o, opts, std::min<size_t>(sizeof(*o), given));
         o->struct_size = sizeof(*o);
     }
+}
+
+// offsets32_ok: the entry point takes BMQCRC_F_OFFSETS32 (batch and verify).
+int parse_opts(const bmqcrc_opts* opts, bmqcrc_opts* o, uint32_t* seg, int* dev,
+               bool offsets32_ok = false)
+{
+    read_opts(opts, o);
     *seg = o->seg_bytes;
     const uint32_t known = BMQCRC_F_DEVICE_PTRS | BMQCRC_F_ASYNC | BMQCRC_F_TIME_KERNEL |
                            BMQCRC_F_WHOLE_MESSAGES | BMQCRC_F_PLAN | BMQCRC_F_OFFSETS32;
@@ -720,33 +797,8 @@ int parse_opts(const bmqcrc_opts* opts, bmqcrc_opts* o, uint32_t* seg, int* dev,
     return 0;
 }
 
-int check_ranges(const uint64_t* offsets, const uint32_t* lengths, uint64_t n,
-                 uint64_t arena_bytes)
-{
-    for (uint64_t i = 0; i < n; ++i) {
-        if (offsets[i] > arena_bytes || lengths[i] > arena_bytes - offsets[i]) {
-            return fail(BMQCRC_EINVAL,
-                        "message " + std::to_string(i) + " lies outside [arena, arena+arena_bytes)");
-        }
-    }
-    return 0;
-}
-
-// The same for 32-bit offsets, in 64 bits: (off << shift) + len <= arena_bytes.
-int check_ranges32(const uint32_t* offsets, uint32_t shift, const uint32_t* lengths, uint64_t n,
-                   uint64_t arena_bytes)
-{
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint64_t off = (uint64_t)offsets[i] << shift;
-        if (off > arena_bytes || lengths[i] > arena_bytes - off) {
-            return fail(BMQCRC_EINVAL,
-                        "message " + std::to_string(i) + " lies outside [arena, arena+arena_bytes)");
-        }
-    }
-    return 0;
-}
-
-// A host batch's offsets in either form (BMQCRC_F_OFFSETS32: p32, shift).
+// A host batch's offsets in either form (BMQCRC_F_OFFSETS32: p32, shift),
+// read in 64 bits: off << shift.
 struct Offsets {
     const uint64_t* p64;
     const uint32_t* p32;
@@ -765,36 +817,25 @@ Offsets offsets_of(const bmqcrc_opts& o, const uint64_t* offsets)
     return Offsets{offsets, nullptr, 0u};
 }
 
+// Bytes [off, off+len) do not lie inside an arena of arena_bytes.
+bool outside(uint64_t off, uint32_t len, uint64_t arena_bytes)
+{
+    return off > arena_bytes || len > arena_bytes - off;
+}
+
 int check_ranges(const Offsets& of, const uint32_t* lengths, uint64_t n, uint64_t arena_bytes)
 {
-    return of.p32 ? check_ranges32(of.p32, of.shift, lengths, n, arena_bytes)
-                  : check_ranges(of.p64, lengths, n, arena_bytes);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (outside(of[i], lengths[i], arena_bytes)) {
+            return fail(BMQCRC_EINVAL,
+                        "message " + std::to_string(i) + " lies outside [arena, arena+arena_bytes)");
+        }
+    }
+    return 0;
 }
-
-int check_ranges(const bmqcrc_opts& o, const uint64_t* offsets, const uint32_t* lengths,
-                 uint64_t n, uint64_t arena_bytes)
-{
-    return (o.flags & BMQCRC_F_OFFSETS32)
-               ? check_ranges32((const uint32_t*)offsets, o.offset_shift, lengths, n, arena_bytes)
-               : check_ranges(offsets, lengths, n, arena_bytes);
-}
-
-int batch_multi(const void* arena, uint64_t arena_bytes, Offsets offsets, const uint32_t* lengths,
-                const uint32_t* seeds, uint32_t* out, uint64_t n, const int* devices, int ndev,
-                uint32_t seg_bytes);
 
 // Device mismatch-index list of a verify: 4 Mi entries (16 MiB) at most.
 constexpr uint64_t kVerifyListCap = 1ull << 22;
-
-int verify_locked(Ctx& c, Workspace* w, const bmqcrc_opts& o, uint32_t seg, bool arena_staged,
-                  const void* arena, uint64_t arena_bytes, const uint64_t* offsets,
-                  const uint32_t* lengths, const uint32_t* expected, uint64_t n, uint64_t* n_bad,
-                  uint64_t* bad_idx, uint64_t bad_cap, uint64_t* n_written);
-
-int verify_host_multi(const void* arena, uint64_t arena_bytes, bmqcrc_prepare_fn prepare,
-                      void* pctx, uint64_t* n_bad, std::vector<uint64_t>* bad, uint64_t bad_cap,
-                      const bmqcrc_opts& o, uint32_t seg, std::vector<uint32_t>* crcs,
-                      uint64_t* n_written);
 
 // The message arrays of a plain verify call, handed to verify_host_multi as
 // an already finished "walk".
@@ -817,116 +858,6 @@ int given_arrays(void* ctx, const uint64_t** off, const uint32_t** off32, const 
     *n = g->n;
     return 0;
 }
-
-}  // namespace
-
-extern "C" int bmqcrc_set_error(int rc, const char* msg)
-{
-    return fail(rc, msg ? msg : "");
-}
-
-extern "C" void bmqcrc_clear_error(void)
-{
-    t_err.clear();
-}
-
-extern "C" {
-
-// bmqcrc_crc32c, bmqcrc_crc32c_blob and bmqcrc_combine: crc32c_cpu.cpp
-
-int bmqcrc_crc32c_batch(const void* arena, uint64_t arena_bytes, const uint64_t* offsets,
-                        const uint32_t* lengths, const uint32_t* seeds, uint32_t* out,
-                        uint64_t n, const bmqcrc_opts* opts)
-{
-    t_err.clear();
-    DeviceGuard keep_device;
-    if (n == 0) {
-        return 0;
-    }
-    if (!offsets || !lengths || !out || (!arena && arena_bytes)) {
-        return fail(BMQCRC_EINVAL, "null pointer argument");
-    }
-    if (n > 0xFFFFFFFFull) {
-        return fail(BMQCRC_EINVAL, "at most 2^32-1 messages per batch");
-    }
-    bmqcrc_opts o;
-    uint32_t seg;
-    int dev, rc;
-    if ((rc = parse_opts(opts, &o, &seg, &dev, true))) {
-        return rc;
-    }
-    if (!(o.flags & BMQCRC_F_DEVICE_PTRS) &&
-        (rc = check_ranges(o, offsets, lengths, n, arena_bytes))) {
-        return rc;  // device arrays are trusted
-    }
-    if (!(o.flags & BMQCRC_F_DEVICE_PTRS) && o.ndevices > 1) {  // one byte range per device
-        if (!(o.flags & BMQCRC_F_OFFSETS32)) {
-            return bmqcrc_crc32c_batch_multi(arena, arena_bytes, offsets, lengths, seeds, out, n,
-                                             o.devices, (int)o.ndevices, seg);
-        }
-        return batch_multi(arena, arena_bytes, offsets_of(o, offsets), lengths, seeds, out, n,
-                           o.devices, (int)o.ndevices, seg);
-    }
-    return batch_one(dev, o.stream, o.flags, seg, arena, arena_bytes, offsets, lengths, seeds,
-                     out, n, (o.flags & BMQCRC_F_DEVICE_PTRS) ? o.max_len : 0u,
-                     (o.flags & BMQCRC_F_DEVICE_PTRS) ? o.min_len : 0u, o.offset_shift);
-}
-
-int bmqcrc_crc32c_verify(const void* arena, uint64_t arena_bytes, const uint64_t* offsets,
-                         const uint32_t* lengths, const uint32_t* expected, uint64_t n,
-                         uint64_t* n_bad, uint64_t* bad_idx, uint64_t bad_cap,
-                         const bmqcrc_opts* opts)
-{
-    t_err.clear();
-    DeviceGuard keep_device;
-    if (!n_bad) {
-        return fail(BMQCRC_EINVAL, "n_bad is required");
-    }
-    *n_bad = 0;
-    if (n == 0) {
-        return 0;
-    }
-    if (!offsets || !lengths || !expected || (!arena && arena_bytes) || (bad_cap && !bad_idx)) {
-        return fail(BMQCRC_EINVAL, "null pointer argument");
-    }
-    if (n > 0xFFFFFFFFull) {
-        return fail(BMQCRC_EINVAL, "at most 2^32-1 messages per batch");
-    }
-    bmqcrc_opts o;
-    uint32_t seg;
-    int dev, rc;
-    if ((rc = parse_opts(opts, &o, &seg, &dev, true))) {
-        return rc;
-    }
-    const bool dev_ptrs = (o.flags & BMQCRC_F_DEVICE_PTRS) != 0;
-    if (!dev_ptrs && (rc = check_ranges(o, offsets, lengths, n, arena_bytes))) {
-        return rc;
-    }
-    if (!dev_ptrs && o.ndevices > 1) {  // one byte range per device, merged in index order
-        const Offsets of = offsets_of(o, offsets);
-        GivenArrays ga = {of.p64, of.p32, lengths, expected, n};
-        std::vector<uint64_t> bad;
-        uint64_t written = 0;
-        if ((rc = verify_host_multi(arena, arena_bytes, given_arrays, &ga, n_bad, &bad, bad_cap, o,
-                                    seg, nullptr, &written))) {
-            return rc;
-        }
-        std::copy(bad.begin(), bad.begin() + written, bad_idx);
-        return 0;
-    }
-    Ctx c;
-    if ((rc = open_ctx(dev, o.stream, &c))) {
-        return rc;
-    }
-    Workspace* w = c.w;
-    std::lock_guard<std::mutex> g(w->mu);
-    return verify_locked(c, w, o, seg, false, arena, arena_bytes, offsets, lengths, expected, n,
-                         n_bad, bad_idx, bad_cap, nullptr);
-}
-
-}  // extern "C"
-
-namespace {
 
 // The verify pipeline after the workspace lock: stage (host buffers; the
 // arena may already be staged), fold, compare on the device, collect the
@@ -951,23 +882,17 @@ int verify_locked(Ctx& c, Workspace* w, const bmqcrc_opts& o, uint32_t seg, bool
         (rc = w->vidx.ensure(4ull * std::max<uint32_t>(cap, 1)))) {
         return rc;
     }
-    const void* d_arena = arena;
-    const uint64_t* d_off = offsets;
-    const uint32_t* d_len = lengths;
+    DevArrays d = {arena, offsets, lengths, nullptr};
     const uint32_t* d_exp = expected;
     if (!dev_ptrs) {
-        if ((!arena_staged && (rc = stage(c, w->arena, arena, arena_bytes))) ||
-            (rc = stage(c, w->offsets, offsets, offsets_bytes(o.flags, n))) ||
-            (rc = stage(c, w->lengths, lengths, 4 * n)) ||
+        if ((rc = stage_batch(c, o.flags, arena_staged, arena, arena_bytes, offsets, lengths,
+                              nullptr, n, &d)) ||
             (rc = stage(c, w->expected, expected, 4 * n))) {
             return rc;
         }
-        d_arena = w->arena.p;
-        d_off = (const uint64_t*)w->offsets.p;
-        d_len = (const uint32_t*)w->lengths.p;
         d_exp = (const uint32_t*)w->expected.p;
     }
-    if ((rc = run_batch(c, o.flags, seg, d_arena, arena_bytes, d_off, d_len, nullptr,
+    if ((rc = run_batch(c, o.flags, seg, d.arena, arena_bytes, d.offsets, d.lengths, nullptr,
                         (uint32_t*)w->out.p, n,
                         dev_ptrs ? UINT64_MAX : max_length(lengths, n), 0, o.offset_shift))) {
         return rc;
@@ -1049,6 +974,22 @@ int internal_stream(int dev, int k, hipStream_t* out)
     return 0;
 }
 
+// The device ordinals of a multi-device call, one per entry of `devs`
+// (devices == NULL: 0, 1, ...), each below `have`; with no device (have <= 0)
+// only their sign is checked, and the caller decides what a missing device
+// means.
+int device_list(const int* devices, int have, std::vector<int>* devs)
+{
+    for (size_t d = 0; d < devs->size(); ++d) {
+        const int dev = devices ? devices[d] : (int)d;
+        if (dev < 0 || (have > 0 && dev >= have)) {
+            return fail(BMQCRC_EINVAL, "device ordinal out of range");
+        }
+        (*devs)[d] = dev;
+    }
+    return 0;
+}
+
 // bmqcrc_verify_host_overlapped over several devices (bmqcrc_opts.ndevices >
 // 1): the arena is cut into ndevices contiguous byte ranges; one thread per
 // range copies it to its device over that device's PCIe link while the
@@ -1068,11 +1009,8 @@ int verify_host_multi(const void* arena, uint64_t arena_bytes, bmqcrc_prepare_fn
     }
     const int have = device_count_raw();
     std::vector<int> devs(nd);
-    for (uint32_t d = 0; d < nd; ++d) {
-        devs[d] = o.devices ? o.devices[d] : (int)d;
-        if (devs[d] < 0 || (have > 0 && devs[d] >= have)) {
-            return fail(BMQCRC_EINVAL, "device ordinal out of range");
-        }
+    if (const int drc = device_list(o.devices, have, &devs)) {
+        return drc;
     }
     const uint64_t* off64 = nullptr;
     const uint32_t* off32 = nullptr;
@@ -1175,21 +1113,8 @@ int verify_host_multi(const void* arena, uint64_t arena_bytes, bmqcrc_prepare_fn
             const uint64_t abytes = staged ? cut[t + 1] - cut[t] : packed.size();
             if (crcs) {
                 std::vector<uint32_t> part(m);
-                if ((!staged && (rc = stage(c, c.w->arena, abase, abytes))) ||
-                    (rc = stage(c, c.w->offsets, lop, offsets_bytes(so.flags, m))) ||
-                    (rc = stage(c, c.w->lengths, ll.data(), 4 * m)) ||
-                    (rc = c.w->out.ensure(4 * m)) ||
-                    (rc = run_batch(c, so.flags, seg, c.w->arena.p, abytes,
-                                    (const uint64_t*)c.w->offsets.p,
-                                    (const uint32_t*)c.w->lengths.p, nullptr,
-                                    (uint32_t*)c.w->out.p, m, max_length(ll.data(), m), 0,
-                                    so.offset_shift))) {
-                    break;
-                }
-                if (hipMemcpyAsync(part.data(), c.w->out.p, 4 * m, hipMemcpyDeviceToHost, c.s) !=
-                        hipSuccess ||
-                    hipStreamSynchronize(c.s) != hipSuccess) {
-                    rc = fail(BMQCRC_EIO, "copying the CRCs back failed");
+                if ((rc = fold_staged(c, so.flags, seg, staged, abase, abytes, lop, ll.data(),
+                                      nullptr, m, false, so.offset_shift, part.data()))) {
                     break;
                 }
                 for (uint64_t k = 0; k < m; ++k) {
@@ -1275,7 +1200,113 @@ int verify_host_multi(const void* arena, uint64_t arena_bytes, bmqcrc_prepare_fn
     return 0;
 }
 
+// bmqcrc_crc32c_batch_multi over offsets of either form: a slice's offsets
+// keep the batch's form (32-bit ones are rebased in whole units of the shift).
+int batch_multi(const void* arena, uint64_t arena_bytes, Offsets offsets, const uint32_t* lengths,
+                const uint32_t* seeds, uint32_t* out, uint64_t n, const int* devices, int ndev,
+                uint32_t seg_bytes)
+{
+    if (ndev < 1 || !lengths || !out || !arena) {
+        return fail(BMQCRC_EINVAL, "bad arguments");
+    }
+    uint32_t seg = seg_bytes;
+    int rc = check_seg(&seg);
+    if (rc) {
+        return rc;
+    }
+    const int have = device_count_raw();
+    if (have <= 0) {
+        return fail(BMQCRC_ENODEV, "no HIP device available");
+    }
+    std::vector<int> devs(ndev);
+    if ((rc = device_list(devices, have, &devs))) {
+        return rc;
+    }
+    // (its own text and the byte total: not check_ranges)
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (outside(offsets[i], lengths[i], arena_bytes)) {
+            return fail(BMQCRC_EINVAL, "message outside arena");
+        }
+        total += lengths[i];
+    }
+    // Contiguous byte-balanced message slices; each device gets its own
+    // copy of the arena range its slice touches.
+    std::vector<uint64_t> cut(ndev + 1, n);
+    cut[0] = 0;
+    {
+        uint64_t acc = 0, i = 0;
+        for (int d = 1; d < ndev; ++d) {
+            const uint64_t target = total * (uint64_t)d / (uint64_t)ndev;
+            while (i < n && acc < target) {
+                acc += lengths[i++];
+            }
+            cut[d] = i;
+        }
+    }
+    std::vector<int> rcs(ndev, 0);
+    std::vector<std::string> errs(ndev);
+    std::vector<std::thread> th;
+    for (int d = 0; d < ndev; ++d) {
+        th.emplace_back([&, d]() {
+            const uint64_t lo = cut[d], hi = cut[d + 1];
+            if (lo >= hi) {
+                return;
+            }
+            uint64_t amin = UINT64_MAX, amax = 0;
+            for (uint64_t i = lo; i < hi; ++i) {
+                amin = std::min(amin, offsets[i]);
+                amax = std::max(amax, offsets[i] + lengths[i]);
+            }
+            if (amin > amax) {
+                amin = amax = 0;
+            }
+            if (offsets.p32) {
+                std::vector<uint32_t> rel32(hi - lo);
+                const uint32_t base = (uint32_t)(amin >> offsets.shift);  // amin is one of them
+                for (uint64_t i = lo; i < hi; ++i) {
+                    rel32[i - lo] = offsets.p32[i] - base;
+                }
+                rcs[d] = batch_one(devs[d], nullptr, BMQCRC_F_OFFSETS32, seg,
+                                   (const uint8_t*)arena + amin, amax - amin,
+                                   (const uint64_t*)rel32.data(), lengths + lo,
+                                   seeds ? seeds + lo : nullptr, out + lo, hi - lo, 0, 0,
+                                   offsets.shift);
+                errs[d] = t_err;
+                return;
+            }
+            std::vector<uint64_t> rel(hi - lo);
+            for (uint64_t i = lo; i < hi; ++i) {
+                rel[i - lo] = offsets[i] - amin;
+            }
+            rcs[d] = batch_one(devs[d], nullptr, 0, seg, (const uint8_t*)arena + amin, amax - amin,
+                               rel.data(), lengths + lo, seeds ? seeds + lo : nullptr, out + lo,
+                               hi - lo);
+            errs[d] = t_err;
+        });
+    }
+    for (auto& t : th) {
+        t.join();
+    }
+    for (int d = 0; d < ndev; ++d) {
+        if (rcs[d]) {
+            return fail(rcs[d], "device " + std::to_string(devs[d]) + ": " + errs[d]);
+        }
+    }
+    return 0;
+}
+
 }  // namespace
+
+extern "C" int bmqcrc_set_error(int rc, const char* msg)
+{
+    return fail(rc, msg ? msg : "");
+}
+
+extern "C" void bmqcrc_clear_error(void)
+{
+    t_err.clear();
+}
 
 int bmqcrc_verify_host_overlapped(const void* arena, uint64_t arena_bytes,
                                   bmqcrc_prepare_fn prepare, void* pctx, uint64_t* n_bad,
@@ -1362,18 +1393,8 @@ int bmqcrc_verify_host_overlapped(const void* arena, uint64_t arena_bytes,
     }
     if (crcs) {  // compute: stage the descriptors, fold, copy the CRCs back
         crcs->assign(n, 0);
-        if ((rc = stage(c, w->offsets, off, offsets_bytes(o.flags, n))) ||
-            (rc = stage(c, w->lengths, len, 4 * n)) || (rc = w->out.ensure(4 * n))) {
-            return rc;
-        }
-        if ((rc = run_batch(c, o.flags, seg, w->arena.p, arena_bytes,
-                            (const uint64_t*)w->offsets.p, (const uint32_t*)w->lengths.p, nullptr,
-                            (uint32_t*)w->out.p, n, max_length(len, n)))) {
-            return rc;
-        }
-        HIP_TRY(hipMemcpyAsync(crcs->data(), w->out.p, 4 * n, hipMemcpyDeviceToHost, c.s));
-        HIP_TRY(hipStreamSynchronize(c.s));
-        return 0;
+        return fold_staged(c, o.flags, seg, true, arena, arena_bytes, off, len, nullptr, n, false,
+                           0, crcs->data());
     }
     bad->assign(std::min<uint64_t>(bad_cap, n), 0);
     return verify_locked(c, w, o, seg, true, arena, arena_bytes, off, len, exp, n, n_bad,
@@ -1381,6 +1402,98 @@ int bmqcrc_verify_host_overlapped(const void* arena, uint64_t arena_bytes,
 }
 
 extern "C" {
+
+// bmqcrc_crc32c, bmqcrc_crc32c_blob and bmqcrc_combine: crc32c_cpu.cpp
+
+int bmqcrc_crc32c_batch(const void* arena, uint64_t arena_bytes, const uint64_t* offsets,
+                        const uint32_t* lengths, const uint32_t* seeds, uint32_t* out,
+                        uint64_t n, const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    if (n == 0) {
+        return 0;
+    }
+    if (!offsets || !lengths || !out || (!arena && arena_bytes)) {
+        return fail(BMQCRC_EINVAL, "null pointer argument");
+    }
+    if (n > 0xFFFFFFFFull) {
+        return fail(BMQCRC_EINVAL, "at most 2^32-1 messages per batch");
+    }
+    bmqcrc_opts o;
+    uint32_t seg;
+    int dev, rc;
+    if ((rc = parse_opts(opts, &o, &seg, &dev, true))) {
+        return rc;
+    }
+    if (!(o.flags & BMQCRC_F_DEVICE_PTRS) &&
+        (rc = check_ranges(offsets_of(o, offsets), lengths, n, arena_bytes))) {
+        return rc;  // device arrays are trusted
+    }
+    if (!(o.flags & BMQCRC_F_DEVICE_PTRS) && o.ndevices > 1) {  // one byte range per device
+        if (!(o.flags & BMQCRC_F_OFFSETS32)) {
+            return bmqcrc_crc32c_batch_multi(arena, arena_bytes, offsets, lengths, seeds, out, n,
+                                             o.devices, (int)o.ndevices, seg);
+        }
+        return batch_multi(arena, arena_bytes, offsets_of(o, offsets), lengths, seeds, out, n,
+                           o.devices, (int)o.ndevices, seg);
+    }
+    return batch_one(dev, o.stream, o.flags, seg, arena, arena_bytes, offsets, lengths, seeds,
+                     out, n, (o.flags & BMQCRC_F_DEVICE_PTRS) ? o.max_len : 0u,
+                     (o.flags & BMQCRC_F_DEVICE_PTRS) ? o.min_len : 0u, o.offset_shift);
+}
+
+int bmqcrc_crc32c_verify(const void* arena, uint64_t arena_bytes, const uint64_t* offsets,
+                         const uint32_t* lengths, const uint32_t* expected, uint64_t n,
+                         uint64_t* n_bad, uint64_t* bad_idx, uint64_t bad_cap,
+                         const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    if (!n_bad) {
+        return fail(BMQCRC_EINVAL, "n_bad is required");
+    }
+    *n_bad = 0;
+    if (n == 0) {
+        return 0;
+    }
+    if (!offsets || !lengths || !expected || (!arena && arena_bytes) || (bad_cap && !bad_idx)) {
+        return fail(BMQCRC_EINVAL, "null pointer argument");
+    }
+    if (n > 0xFFFFFFFFull) {
+        return fail(BMQCRC_EINVAL, "at most 2^32-1 messages per batch");
+    }
+    bmqcrc_opts o;
+    uint32_t seg;
+    int dev, rc;
+    if ((rc = parse_opts(opts, &o, &seg, &dev, true))) {
+        return rc;
+    }
+    const bool dev_ptrs = (o.flags & BMQCRC_F_DEVICE_PTRS) != 0;
+    const Offsets of = offsets_of(o, offsets);
+    if (!dev_ptrs && (rc = check_ranges(of, lengths, n, arena_bytes))) {
+        return rc;
+    }
+    if (!dev_ptrs && o.ndevices > 1) {  // one byte range per device, merged in index order
+        GivenArrays ga = {of.p64, of.p32, lengths, expected, n};
+        std::vector<uint64_t> bad;
+        uint64_t written = 0;
+        if ((rc = verify_host_multi(arena, arena_bytes, given_arrays, &ga, n_bad, &bad, bad_cap, o,
+                                    seg, nullptr, &written))) {
+            return rc;
+        }
+        std::copy(bad.begin(), bad.begin() + written, bad_idx);
+        return 0;
+    }
+    Ctx c;
+    if ((rc = open_ctx(dev, o.stream, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    std::lock_guard<std::mutex> g(w->mu);
+    return verify_locked(c, w, o, seg, false, arena, arena_bytes, offsets, lengths, expected, n,
+                         n_bad, bad_idx, bad_cap, nullptr);
+}
 
 int bmqcrc_crc32c_blobs(const void* arena, uint64_t arena_bytes, const uint64_t* buf_offsets,
                         const uint32_t* buf_lengths, uint64_t nbuf,
@@ -1407,7 +1520,8 @@ int bmqcrc_crc32c_blobs(const void* arena, uint64_t arena_bytes, const uint64_t*
     }
     const bool dev_ptrs = (o.flags & BMQCRC_F_DEVICE_PTRS) != 0;
     if (!dev_ptrs) {
-        if ((rc = check_ranges(buf_offsets, buf_lengths, nbuf, arena_bytes))) {
+        if ((rc = check_ranges(Offsets{buf_offsets, nullptr, 0u}, buf_lengths, nbuf,
+                               arena_bytes))) {
             return rc;
         }
         for (uint64_t m = 0; m < n; ++m) {
@@ -1425,34 +1539,29 @@ int bmqcrc_crc32c_blobs(const void* arena, uint64_t arena_bytes, const uint64_t*
     if ((rc = w->buf_crc.ensure(4 * std::max<uint64_t>(nbuf, 1)))) {
         return rc;
     }
-    const void* d_arena = arena;
-    const uint64_t* d_off = buf_offsets;
-    const uint32_t* d_len = buf_lengths;
+    // the batch is the nbuf buffers; the seeds are the n blobs', staged apart
+    DevArrays d = {arena, buf_offsets, buf_lengths, nullptr};
     const uint64_t* d_first = msg_first_buf;
     const uint32_t* d_seeds = seeds;
     uint32_t* d_out = out;
     if (!dev_ptrs) {
-        if ((rc = stage(c, w->arena, arena, arena_bytes)) ||
-            (rc = stage(c, w->offsets, buf_offsets, 8 * nbuf)) ||
-            (rc = stage(c, w->lengths, buf_lengths, 4 * nbuf)) ||
+        if ((rc = stage_batch(c, o.flags, false, arena, arena_bytes, buf_offsets, buf_lengths,
+                              nullptr, nbuf, &d)) ||
             (rc = stage(c, w->first_buf, msg_first_buf, 8 * (n + 1))) ||
             (seeds && (rc = stage(c, w->seeds, seeds, 4 * n))) || (rc = w->out.ensure(4 * n))) {
             return rc;
         }
-        d_arena = w->arena.p;
-        d_off = (const uint64_t*)w->offsets.p;
-        d_len = (const uint32_t*)w->lengths.p;
         d_first = (const uint64_t*)w->first_buf.p;
         d_seeds = seeds ? (const uint32_t*)w->seeds.p : nullptr;
         d_out = (uint32_t*)w->out.p;
     }
-    if (nbuf && (rc = run_batch(c, o.flags, seg, d_arena, arena_bytes, d_off, d_len, nullptr,
-                                (uint32_t*)w->buf_crc.p, nbuf,
+    if (nbuf && (rc = run_batch(c, o.flags, seg, d.arena, arena_bytes, d.offsets, d.lengths,
+                                nullptr, (uint32_t*)w->buf_crc.p, nbuf,
                                 dev_ptrs ? UINT64_MAX : max_length(buf_lengths, nbuf)))) {
         return rc;
     }
-    if (bmqcrc_launch_blob_combine((const uint32_t*)w->buf_crc.p, d_len, d_first, d_seeds, d_out,
-                                   n, (void*)c.s)) {
+    if (bmqcrc_launch_blob_combine((const uint32_t*)w->buf_crc.p, d.lengths, d_first, d_seeds,
+                                   d_out, n, (void*)c.s)) {
         return fail(BMQCRC_EIO, "blob combine launch failed");
     }
     if (!dev_ptrs) {
@@ -1506,7 +1615,6 @@ int bmqcrc_crc32c_gather(const void* const* bufs, const uint32_t* buf_lengths, u
     const uint64_t total = boff.back();
     std::vector<uint64_t> moff(n);
     std::vector<uint32_t> mlen(n);
-    uint64_t maxlen = 0;
     for (uint64_t m = 0; m < n; ++m) {
         moff[m] = boff[msg_first_buf[m] - b0];
         const uint64_t len = boff[msg_first_buf[m + 1] - b0] - moff[m];
@@ -1514,7 +1622,6 @@ int bmqcrc_crc32c_gather(const void* const* bufs, const uint32_t* buf_lengths, u
             return fail(BMQCRC_EINVAL, "message " + std::to_string(m) + " is longer than 2^32-1");
         }
         mlen[m] = (uint32_t)len;
-        maxlen = std::max(maxlen, len);
     }
     // argument errors above are reported before a missing device
     bmqcrc_opts o;
@@ -1604,20 +1711,9 @@ int bmqcrc_crc32c_gather(const void* const* bufs, const uint32_t* buf_lengths, u
             return fail(trc[t], terr[t]);
         }
     }
-    if ((rc = stage(c, w->offsets, moff.data(), 8 * n)) ||
-        (rc = stage(c, w->lengths, mlen.data(), 4 * n)) ||
-        (seeds && (rc = stage(c, w->seeds, seeds, 4 * n))) || (rc = w->out.ensure(4 * n))) {
-        return rc;
-    }
-    if ((rc = run_batch(c, o.flags, seg, w->arena.p, total, (const uint64_t*)w->offsets.p,
-                        (const uint32_t*)w->lengths.p,
-                        seeds ? (const uint32_t*)w->seeds.p : nullptr, (uint32_t*)w->out.p, n,
-                        maxlen))) {
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out, w->out.p, 4 * n, hipMemcpyDeviceToHost, c.s));
-    HIP_TRY(hipStreamSynchronize(c.s));
-    return 0;
+    // the ring has put the arena on the device
+    return fold_staged(c, o.flags, seg, true, nullptr, total, moff.data(), mlen.data(), seeds, n,
+                       false, 0, out);
 }
 
 int bmqcrc_crc32c_batch_multi(const void* arena, uint64_t arena_bytes, const uint64_t* offsets,
@@ -1635,132 +1731,20 @@ int bmqcrc_crc32c_batch_multi(const void* arena, uint64_t arena_bytes, const uin
                        devices, ndev, seg_bytes);
 }
 
-}  // extern "C"
-
-namespace {
-
-// bmqcrc_crc32c_batch_multi over offsets of either form: a slice's offsets
-// keep the batch's form (32-bit ones are rebased in whole units of the shift).
-int batch_multi(const void* arena, uint64_t arena_bytes, Offsets offsets, const uint32_t* lengths,
-                const uint32_t* seeds, uint32_t* out, uint64_t n, const int* devices, int ndev,
-                uint32_t seg_bytes)
-{
-    if (ndev < 1 || !lengths || !out || !arena) {
-        return fail(BMQCRC_EINVAL, "bad arguments");
-    }
-    uint32_t seg = seg_bytes;
-    int rc = check_seg(&seg);
-    if (rc) {
-        return rc;
-    }
-    const int have = device_count_raw();
-    if (have <= 0) {
-        return fail(BMQCRC_ENODEV, "no HIP device available");
-    }
-    std::vector<int> devs(ndev);
-    for (int d = 0; d < ndev; ++d) {
-        devs[d] = devices ? devices[d] : d;
-        if (devs[d] < 0 || devs[d] >= have) {
-            return fail(BMQCRC_EINVAL, "device ordinal out of range");
-        }
-    }
-    uint64_t total = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (offsets[i] > arena_bytes || lengths[i] > arena_bytes - offsets[i]) {
-            return fail(BMQCRC_EINVAL, "message outside arena");
-        }
-        total += lengths[i];
-    }
-    // Contiguous byte-balanced message slices; each device gets its own
-    // copy of the arena range its slice touches.
-    std::vector<uint64_t> cut(ndev + 1, n);
-    cut[0] = 0;
-    {
-        uint64_t acc = 0, i = 0;
-        for (int d = 1; d < ndev; ++d) {
-            const uint64_t target = total * (uint64_t)d / (uint64_t)ndev;
-            while (i < n && acc < target) {
-                acc += lengths[i++];
-            }
-            cut[d] = i;
-        }
-    }
-    std::vector<int> rcs(ndev, 0);
-    std::vector<std::string> errs(ndev);
-    std::vector<std::thread> th;
-    for (int d = 0; d < ndev; ++d) {
-        th.emplace_back([&, d]() {
-            const uint64_t lo = cut[d], hi = cut[d + 1];
-            if (lo >= hi) {
-                return;
-            }
-            uint64_t amin = UINT64_MAX, amax = 0;
-            for (uint64_t i = lo; i < hi; ++i) {
-                amin = std::min(amin, offsets[i]);
-                amax = std::max(amax, offsets[i] + lengths[i]);
-            }
-            if (amin > amax) {
-                amin = amax = 0;
-            }
-            if (offsets.p32) {
-                std::vector<uint32_t> rel32(hi - lo);
-                const uint32_t base = (uint32_t)(amin >> offsets.shift);  // amin is one of them
-                for (uint64_t i = lo; i < hi; ++i) {
-                    rel32[i - lo] = offsets.p32[i] - base;
-                }
-                rcs[d] = batch_one(devs[d], nullptr, BMQCRC_F_OFFSETS32, seg,
-                                   (const uint8_t*)arena + amin, amax - amin,
-                                   (const uint64_t*)rel32.data(), lengths + lo,
-                                   seeds ? seeds + lo : nullptr, out + lo, hi - lo, 0, 0,
-                                   offsets.shift);
-                errs[d] = t_err;
-                return;
-            }
-            std::vector<uint64_t> rel(hi - lo);
-            for (uint64_t i = lo; i < hi; ++i) {
-                rel[i - lo] = offsets[i] - amin;
-            }
-            rcs[d] = batch_one(devs[d], nullptr, 0, seg, (const uint8_t*)arena + amin, amax - amin,
-                               rel.data(), lengths + lo, seeds ? seeds + lo : nullptr, out + lo,
-                               hi - lo);
-            errs[d] = t_err;
-        });
-    }
-    for (auto& t : th) {
-        t.join();
-    }
-    for (int d = 0; d < ndev; ++d) {
-        if (rcs[d]) {
-            return fail(rcs[d], "device " + std::to_string(devs[d]) + ": " + errs[d]);
-        }
-    }
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
 int bmqcrc_reserve(int device, void* stream, uint64_t n_msgs, uint64_t arena_bytes,
                    uint32_t seg_bytes)
 {
     t_err.clear();
     DeviceGuard keep_device;
-    int dev, rc;
-    if ((rc = check_seg(&seg_bytes)) || (rc = resolve_device(device, &dev))) {
+    LockedCtx c;
+    int rc;
+    if ((rc = check_seg(&seg_bytes)) || (rc = lock_on(device, stream, true, &c))) {
         return rc;
     }
-    DeviceState* st = nullptr;
-    if ((rc = device_state(dev, &st))) {
-        return rc;
-    }
-    HIP_TRY(hipSetDevice(dev));
-    Workspace* w = workspace(dev, stream);
-    std::lock_guard<std::mutex> g(w->mu);
     BatchArgs a;
     memset(&a, 0, sizeof(a));
-    auto_shape(n_msgs, arena_bytes, st->num_cus, &seg_bytes, &a.blocks_per_cu);  // as the batch call will
-    return plan_ws(w, (hipStream_t)stream, n_msgs, arena_bytes, seg_bytes, &a, *st);
+    auto_shape(n_msgs, arena_bytes, c.st->num_cus, &seg_bytes, &a.blocks_per_cu);  // as the batch call will
+    return plan_ws(c.w, c.s, n_msgs, arena_bytes, seg_bytes, &a, *c.st);
 }
 
 int bmqcrc_fill_synthetic(void* dev_dst, uint64_t nbytes, uint64_t seed, uint64_t begin,
@@ -1798,13 +1782,13 @@ int bmqcrc_kernel_timing(int device, void* stream, double* total_ms, uint32_t* c
 {
     t_err.clear();
     DeviceGuard keep_device;
-    int dev, rc;
-    if ((rc = resolve_device(device, &dev))) {
+    LockedCtx c;
+    int rc;
+    if ((rc = lock_on(device, stream, false, &c))) {
         return rc;
     }
-    HIP_TRY(hipSetDevice(dev));
-    Workspace* w = workspace(dev, stream);
-    std::lock_guard<std::mutex> g(w->mu);
+    HIP_TRY(hipSetDevice(c.dev));  // for the event calls below
+    Workspace* w = c.w;
     double tot = 0;
     uint32_t cnt = 0;
     for (auto& e : w->timing) {
@@ -1835,12 +1819,7 @@ namespace {
 // only then the device lookup.
 int device_call_opts(const bmqcrc_opts* opts, const std::string& call, bmqcrc_opts* o)
 {
-    memset(o, 0, sizeof(*o));
-    o->device = -1;
-    if (opts) {
-        const size_t given = opts->struct_size ? opts->struct_size : offsetof(bmqcrc_opts, ndevices);
-        memcpy(o, opts, std::min<size_t>(sizeof(*o), given));
-    }
+    read_opts(opts, o);
     static const struct {
         uint32_t bit;
         const char* name;
@@ -1866,12 +1845,52 @@ int device_call_opts(const bmqcrc_opts* opts, const std::string& call, bmqcrc_op
     return 0;
 }
 
-// The context of (device, stream) as a call or a bmqcrc_last_* query names it.
-int open_on(int device, void* stream, Ctx* c)
+// `what` names the kernel ("copy", "put-pack layout") whose launch call failed.
+int launch_failed(const char* what)
 {
-    int dev;
-    const int rc = resolve_device(device, &dev);
-    return rc ? rc : open_ctx(dev, stream, c);
+    return fail(BMQCRC_EIO, std::string(what) + " launch failed: " +
+                                hipGetErrorString(hipGetLastError()));
+}
+
+// The first required pointer that is null, by its name in the call's struct.
+struct NamedNull {
+    bool null;
+    const char* name;
+};
+
+int refuse_null(std::initializer_list<NamedNull> args)
+{
+    for (const NamedNull& a : args) {
+        if (a.null) {
+            return fail(BMQCRC_EINVAL, std::string("null pointer argument: ") + a.name);
+        }
+    }
+    return 0;
+}
+
+// Two byte ranges, neither empty, share a byte.
+bool overlaps(uintptr_t a, uint64_t a_bytes, uintptr_t b, uint64_t b_bytes)
+{
+    return a_bytes && b_bytes && a < b + b_bytes && b < a + a_bytes;
+}
+
+// A refusal counter as the kernels leave it: 0 when nothing was refused,
+// otherwise the complement of (kind << 56 | index).
+void refusal_of(unsigned long long ctr, uint32_t* kind, uint64_t* index)
+{
+    const unsigned long long key = ctr ? ~ctr : 0;
+    *kind = (uint32_t)(key >> 56);
+    *index = key & ((1ull << 56) - 1);
+}
+
+// The refusal `kind` of a device call in words: what[kind] is its text,
+// with %llu for the index and, where the text has a second, for the offset.
+int refused(const char* const (&what)[6], uint32_t kind, uint64_t index, uint64_t offset = 0)
+{
+    char buf[256];
+    snprintf(buf, sizeof(buf), what[kind <= 5 ? kind : 0], (unsigned long long)index,
+             (unsigned long long)offset);
+    return fail(BMQCRC_EINVAL, std::string(buf) + ": nothing was written");
 }
 
 static_assert(kCopyPlanThreads == kPackThreads && kCopyPlanBlocks == kPackBlocks,
@@ -1924,8 +1943,7 @@ static int enqueue_copy(Ctx& c, CopyArgs a, DevBuf& first, DevBuf& bsum, void* c
         a.ctr = (unsigned long long*)ctr;
         layout_split(a.n, &a.per_block, &a.nblocks);
         if (bmqcrc_launch_copy(&a, (void*)c.s, c.st->copy_blocks)) {
-            return fail(BMQCRC_EIO, std::string("copy launch failed: ") +
-                                        hipGetErrorString(hipGetLastError()));
+            return launch_failed("copy");
         }
     }
     return 0;
@@ -1960,9 +1978,7 @@ int pack_counters(Ctx& c, const PackScratch& s, int ctr_words, const char* call,
     HIP_TRY(hipMemcpyAsync(ctr, s.ctr.p, 8 * (ctr_words + kCopyCtrWords), hipMemcpyDeviceToHost,
                            c.s));
     HIP_TRY(hipStreamSynchronize(c.s));
-    const unsigned long long key = ctr[kLayoutCtrRefusal] ? ~ctr[kLayoutCtrRefusal] : 0;
-    *kind = (uint32_t)(key >> 56);
-    *index = key & ((1ull << 56) - 1);
+    refusal_of(ctr[kLayoutCtrRefusal], kind, index);
     // the layout placed every message inside dst: the copy pass has nothing to refuse
     const unsigned long long* cc = ctr + ctr_words;
     if (!*kind && (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow])) {
@@ -1996,12 +2012,11 @@ int bmqcrc_crc32c_copy(const void* src, uint64_t src_bytes, const uint64_t* src_
               (!dst && dst_bytes))) {
         return fail(BMQCRC_EINVAL, "null pointer argument");
     }
-    Ctx c;
-    if ((rc = open_on(o.device, o.stream, &c))) {
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
         return rc;
     }
     Workspace* w = c.w;
-    std::lock_guard<std::mutex> g(w->mu);
     if ((rc = w->copy_ctr.ensure(8 * kCopyCtrWords))) {
         return rc;
     }
@@ -2046,12 +2061,11 @@ int bmqcrc_last_copy(int device, void* stream, uint64_t* n_msgs, uint64_t* n_ref
 {
     t_err.clear();
     DeviceGuard keep_device;
-    Ctx c;
+    LockedCtx c;
     int rc;
-    if ((rc = open_on(device, stream, &c))) {
+    if ((rc = lock_on(device, stream, true, &c))) {
         return rc;
     }
-    std::lock_guard<std::mutex> g(c.w->mu);
     unsigned long long ctr[kCopyCtrWords] = {};
     if (c.w->copy_any && (rc = copy_result(c, ctr))) {
         return rc;
@@ -2092,19 +2106,13 @@ static int pack_result(Ctx& c, uint32_t* kind, uint64_t* index, uint64_t* total)
     return rc;
 }
 
-static int pack_refusal(uint32_t kind, uint64_t index)
-{
-    static const char* const what[] = {
-        "", "BMQCRC_PUT_PACK_SRC_RANGE: message %llu lies outside [src, src+src_bytes)",
-        "BMQCRC_PUT_PACK_EVENT_FIRST: event_first[%llu] breaks 0 = first < ... < last = n",
-        "BMQCRC_PUT_PACK_EVENT_TOO_BIG: event %llu is longer than max_event_bytes",
-        "BMQCRC_PUT_PACK_DST_TOO_SMALL: event %llu ends past dst_bytes",
-        "BMQCRC_PUT_PACK_TOO_MANY_PIECES: more than 2^32-1 16-byte pieces of payload in one "
-        "call (index %llu)"};
-    char buf[192];
-    snprintf(buf, sizeof(buf), what[kind <= 5 ? kind : 0], (unsigned long long)index);
-    return fail(BMQCRC_EINVAL, std::string(buf) + ": nothing was written");
-}
+static const char* const kPackRefusals[6] = {
+    "", "BMQCRC_PUT_PACK_SRC_RANGE: message %llu lies outside [src, src+src_bytes)",
+    "BMQCRC_PUT_PACK_EVENT_FIRST: event_first[%llu] breaks 0 = first < ... < last = n",
+    "BMQCRC_PUT_PACK_EVENT_TOO_BIG: event %llu is longer than max_event_bytes",
+    "BMQCRC_PUT_PACK_DST_TOO_SMALL: event %llu ends past dst_bytes",
+    "BMQCRC_PUT_PACK_TOO_MANY_PIECES: more than 2^32-1 16-byte pieces of payload in one "
+    "call (index %llu)"};
 
 int bmqcrc_put_event_pack(const bmqcrc_put_pack* p, uint64_t* total_bytes, const bmqcrc_opts* opts)
 {
@@ -2126,27 +2134,19 @@ int bmqcrc_put_event_pack(const bmqcrc_put_pack* p, uint64_t* total_bytes, const
     if (n > 0xFFFFFFFFull) {
         return fail(BMQCRC_EINVAL, "at most 2^32-1 messages per call");
     }
-    if (n) {
-        const struct {
-            bool null;
-            const char* name;
-        } arrays[] = {{!p->src_offsets, "src_offsets"}, {!p->lengths, "lengths"},
-                      {!p->queue_ids, "queue_ids"},     {!p->guids, "guids"},
-                      {!p->dst, "dst"},                 {!p->src && p->src_bytes, "src"}};
-        for (const auto& a : arrays) {
-            if (a.null) {
-                return fail(BMQCRC_EINVAL, std::string("null pointer argument: ") + a.name);
-            }
-        }
+    if (n && (rc = refuse_null({{!p->src_offsets, "src_offsets"},
+                                {!p->lengths, "lengths"},
+                                {!p->queue_ids, "queue_ids"},
+                                {!p->guids, "guids"},
+                                {!p->dst, "dst"},
+                                {!p->src && p->src_bytes, "src"}}))) {
+        return rc;
     }
     if ((uintptr_t)p->dst & 3u) {
         return fail(BMQCRC_EINVAL, "dst must be 4-byte aligned");
     }
-    {
-        const uintptr_t s0 = (uintptr_t)p->src, d0 = (uintptr_t)p->dst;
-        if (p->src_bytes && p->dst_bytes && s0 < d0 + p->dst_bytes && d0 < s0 + p->src_bytes) {
-            return fail(BMQCRC_EINVAL, "[dst, dst+dst_bytes) overlaps [src, src+src_bytes)");
-        }
+    if (overlaps((uintptr_t)p->src, p->src_bytes, (uintptr_t)p->dst, p->dst_bytes)) {
+        return fail(BMQCRC_EINVAL, "[dst, dst+dst_bytes) overlaps [src, src+src_bytes)");
     }
     if (p->max_event_bytes > kPutMaxEventBytes) {
         return fail(BMQCRC_EINVAL, "max_event_bytes above (2^28-1)*4: MessageWords would overflow");
@@ -2157,12 +2157,11 @@ int bmqcrc_put_event_pack(const bmqcrc_put_pack* p, uint64_t* total_bytes, const
     if (n && (p->n_events < 1 || p->n_events > n)) {
         return fail(BMQCRC_EINVAL, "n_events must lie in [1, n]: no event is empty");
     }
-    Ctx c;
-    if ((rc = open_on(o.device, o.stream, &c))) {
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
         return rc;
     }
     Workspace* w = c.w;
-    std::lock_guard<std::mutex> g(w->mu);
     if ((rc = w->pack.ensure(n, kPackCtrWords, !p->out))) {
         return rc;
     }
@@ -2189,16 +2188,14 @@ int bmqcrc_put_event_pack(const bmqcrc_put_pack* p, uint64_t* total_bytes, const
     if (n) {
         layout_split(n, &a.per_block, &a.nblocks);
         if (bmqcrc_launch_put_layout(&a, (void*)c.s)) {
-            return fail(BMQCRC_EIO, std::string("put-pack layout launch failed: ") +
-                                        hipGetErrorString(hipGetLastError()));
+            return launch_failed("put-pack layout");
         }
     }
     if ((rc = enqueue_payload(c, w->pack, kPackCtrWords, p->src, a))) {
         return rc;
     }
     if (n && bmqcrc_launch_put_frame(&a, (void*)c.s)) {
-        return fail(BMQCRC_EIO, std::string("put-pack frame launch failed: ") +
-                                    hipGetErrorString(hipGetLastError()));
+        return launch_failed("put-pack frame");
     }
     w->pack.n = n;
     w->pack_events = a.n_events;
@@ -2214,7 +2211,7 @@ int bmqcrc_put_event_pack(const bmqcrc_put_pack* p, uint64_t* total_bytes, const
     if (total_bytes) {
         *total_bytes = total;
     }
-    return kind ? pack_refusal(kind, index) : 0;
+    return kind ? refused(kPackRefusals, kind, index) : 0;
 }
 
 int bmqcrc_last_put_pack(int device, void* stream, uint64_t* n_msgs, uint64_t* n_events,
@@ -2222,15 +2219,12 @@ int bmqcrc_last_put_pack(int device, void* stream, uint64_t* n_msgs, uint64_t* n
 {
     t_err.clear();
     DeviceGuard keep_device;
-    Ctx c;
+    LockedCtx c;
     int rc;
-    if ((rc = open_on(device, stream, &c))) {
-        return rc;
-    }
-    std::lock_guard<std::mutex> g(c.w->mu);
     uint32_t kind = 0;
     uint64_t index = 0, total = 0;
-    if (c.w->pack.any && (rc = pack_result(c, &kind, &index, &total))) {
+    if ((rc = lock_on(device, stream, true, &c)) ||
+        (c.w->pack.any && (rc = pack_result(c, &kind, &index, &total)))) {
         return rc;
     }
     if (n_msgs) {
@@ -2289,20 +2283,14 @@ static int records_result(Ctx& c, bmqcrc_records_result* r)
     return 0;
 }
 
-static int records_refusal(uint32_t kind, uint64_t index)
-{
-    static const char* const what[] = {
-        "", "BMQCRC_REC_PACK_RECORD_TOO_BIG: message %llu makes a record above 2^29-1 words",
-        "BMQCRC_REC_PACK_SRC_RANGE: message %llu lies outside [src, src+src_bytes)",
-        "BMQCRC_REC_PACK_DST_TOO_SMALL: the record of message %llu ends past dst_bytes",
-        "BMQCRC_REC_PACK_DATA_FILE_FULL: the record of message %llu ends past 8*(2^32-1) bytes "
-        "of DATA file, where MessageOffsetDwords stops",
-        "BMQCRC_REC_PACK_TOO_MANY_PIECES: more than 2^32-1 16-byte pieces of payload in one "
-        "call (index %llu)"};
-    char buf[192];
-    snprintf(buf, sizeof(buf), what[kind <= 5 ? kind : 0], (unsigned long long)index);
-    return fail(BMQCRC_EINVAL, std::string(buf) + ": nothing was written");
-}
+static const char* const kRecordsRefusals[6] = {
+    "", "BMQCRC_REC_PACK_RECORD_TOO_BIG: message %llu makes a record above 2^29-1 words",
+    "BMQCRC_REC_PACK_SRC_RANGE: message %llu lies outside [src, src+src_bytes)",
+    "BMQCRC_REC_PACK_DST_TOO_SMALL: the record of message %llu ends past dst_bytes",
+    "BMQCRC_REC_PACK_DATA_FILE_FULL: the record of message %llu ends past 8*(2^32-1) bytes "
+    "of DATA file, where MessageOffsetDwords stops",
+    "BMQCRC_REC_PACK_TOO_MANY_PIECES: more than 2^32-1 16-byte pieces of payload in one "
+    "call (index %llu)"};
 
 int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_result* result,
                                 const bmqcrc_opts* opts)
@@ -2326,19 +2314,14 @@ int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_res
     if (n > 0xFFFFFFFFull) {
         return fail(BMQCRC_EINVAL, "at most 2^32-1 messages per call");
     }
-    if (n) {
-        const struct {
-            bool null;
-            const char* name;
-        } arrays[] = {{!p->src_offsets, "src_offsets"}, {!p->lengths, "lengths"},
-                      {!p->queue_keys, "queue_keys"},   {!p->guids, "guids"},
-                      {!p->dst, "dst"},                 {!p->journal_dst, "journal_dst"},
-                      {!p->src && p->src_bytes, "src"}};
-        for (const auto& a : arrays) {
-            if (a.null) {
-                return fail(BMQCRC_EINVAL, std::string("null pointer argument: ") + a.name);
-            }
-        }
+    if (n && (rc = refuse_null({{!p->src_offsets, "src_offsets"},
+                                {!p->lengths, "lengths"},
+                                {!p->queue_keys, "queue_keys"},
+                                {!p->guids, "guids"},
+                                {!p->dst, "dst"},
+                                {!p->journal_dst, "journal_dst"},
+                                {!p->src && p->src_bytes, "src"}}))) {
+        return rc;
     }
     if ((uintptr_t)p->dst & 7u) {
         return fail(BMQCRC_EINVAL, "dst must be 8-byte aligned");
@@ -2371,19 +2354,17 @@ int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_res
                   "[journal_dst, journal_dst+journal_bytes)"}};
         for (int i = 1; i < 3; ++i) {
             for (int j = 0; j < i; ++j) {
-                if (r[i].bytes && r[j].bytes && r[i].at < r[j].at + r[j].bytes &&
-                    r[j].at < r[i].at + r[i].bytes) {
+                if (overlaps(r[i].at, r[i].bytes, r[j].at, r[j].bytes)) {
                     return fail(BMQCRC_EINVAL, std::string(r[i].name) + " overlaps " + r[j].name);
                 }
             }
         }
     }
-    Ctx c;
-    if ((rc = open_on(o.device, o.stream, &c))) {
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
         return rc;
     }
     Workspace* w = c.w;
-    std::lock_guard<std::mutex> g(w->mu);
     if ((rc = w->rec.ensure(n, kRecCtrWords, !p->out))) {
         return rc;
     }
@@ -2419,16 +2400,14 @@ int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_res
     if (n) {
         layout_split(n, &a.per_block, &a.nblocks);
         if (bmqcrc_launch_records_layout(&a, (void*)c.s)) {
-            return fail(BMQCRC_EIO, std::string("records-pack layout launch failed: ") +
-                                        hipGetErrorString(hipGetLastError()));
+            return launch_failed("records-pack layout");
         }
     }
     if ((rc = enqueue_payload(c, w->rec, kRecCtrWords, p->src, a))) {
         return rc;
     }
     if (n && bmqcrc_launch_records_frame(&a, (void*)c.s)) {
-        return fail(BMQCRC_EIO, std::string("records-pack frame launch failed: ") +
-                                    hipGetErrorString(hipGetLastError()));
+        return launch_failed("records-pack frame");
     }
     w->rec.n = n;
     w->rec.any = true;
@@ -2442,21 +2421,17 @@ int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_res
     if (result) {
         *result = r;
     }
-    return r.refused_kind ? records_refusal(r.refused_kind, r.refused_index) : 0;
+    return r.refused_kind ? refused(kRecordsRefusals, r.refused_kind, r.refused_index) : 0;
 }
 
 int bmqcrc_last_records_pack(int device, void* stream, bmqcrc_records_result* result)
 {
     t_err.clear();
     DeviceGuard keep_device;
-    Ctx c;
+    LockedCtx c;
     int rc;
-    if ((rc = open_on(device, stream, &c))) {
-        return rc;
-    }
-    std::lock_guard<std::mutex> g(c.w->mu);
     bmqcrc_records_result r;
-    if ((rc = records_result(c, &r))) {
+    if ((rc = lock_on(device, stream, true, &c)) || (rc = records_result(c, &r))) {
         return rc;
     }
     if (result) {
@@ -2485,9 +2460,7 @@ static int unpack_result(Ctx& c, bmqcrc_put_unpack_result* r)
     HIP_TRY(hipStreamSynchronize(c.s));
     r->n_events = c.w->unp_events;
     if (ctr[kUnpCtrRefusal]) {
-        const unsigned long long key = ~ctr[kUnpCtrRefusal];
-        r->refused_kind = (uint32_t)(key >> 56);
-        r->refused_event = key & ((1ull << 56) - 1);
+        refusal_of(ctr[kUnpCtrRefusal], &r->refused_kind, &r->refused_event);
         r->refused_offset = ctr[kUnpCtrOffset];
         return 0;
     }
@@ -2497,22 +2470,15 @@ static int unpack_result(Ctx& c, bmqcrc_put_unpack_result* r)
     return 0;
 }
 
-static int unpack_refusal(const bmqcrc_put_unpack_result& r)
-{
-    static const char* const what[] = {
-        "", "BMQCRC_PUT_UNPACK_EVENT_OFFSETS: event_offsets[%llu] is above its successor, no "
-            "multiple of 4, or the event ends past events_bytes (offset %llu)",
-        "BMQCRC_PUT_UNPACK_EVENT_HEADER: event %llu has a malformed EventHeader (offset %llu)",
-        "BMQCRC_PUT_UNPACK_PUT_HEADER: event %llu has a truncated or inconsistent PutHeader "
-        "(offset %llu)",
-        "BMQCRC_PUT_UNPACK_PADDING: event %llu has invalid PUT message padding (offset %llu)",
-        "BMQCRC_PUT_UNPACK_TOO_MANY_MESSAGES: the messages of event %llu do not fit msg_cap "
-        "(offset %llu)"};
-    char buf[256];
-    snprintf(buf, sizeof(buf), what[r.refused_kind <= 5 ? r.refused_kind : 0],
-             (unsigned long long)r.refused_event, (unsigned long long)r.refused_offset);
-    return fail(BMQCRC_EINVAL, std::string(buf) + ": nothing was written");
-}
+static const char* const kUnpackRefusals[6] = {
+    "", "BMQCRC_PUT_UNPACK_EVENT_OFFSETS: event_offsets[%llu] is above its successor, no "
+        "multiple of 4, or the event ends past events_bytes (offset %llu)",
+    "BMQCRC_PUT_UNPACK_EVENT_HEADER: event %llu has a malformed EventHeader (offset %llu)",
+    "BMQCRC_PUT_UNPACK_PUT_HEADER: event %llu has a truncated or inconsistent PutHeader "
+    "(offset %llu)",
+    "BMQCRC_PUT_UNPACK_PADDING: event %llu has invalid PUT message padding (offset %llu)",
+    "BMQCRC_PUT_UNPACK_TOO_MANY_MESSAGES: the messages of event %llu do not fit msg_cap "
+    "(offset %llu)"};
 
 int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result* result,
                             const bmqcrc_opts* opts)
@@ -2532,18 +2498,10 @@ int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result
     if ((rc = device_call_opts(opts, "bmqcrc_put_event_unpack", &o))) {
         return rc;
     }
-    {
-        const struct {
-            bool null;
-            const char* name;
-        } arrays[] = {{!p->events, "events"},
-                      {!p->app_offsets, "app_offsets"},
-                      {!p->lengths, "lengths"}};
-        for (const auto& a : arrays) {
-            if (a.null) {
-                return fail(BMQCRC_EINVAL, std::string("null pointer argument: ") + a.name);
-            }
-        }
+    if ((rc = refuse_null({{!p->events, "events"},
+                           {!p->app_offsets, "app_offsets"},
+                           {!p->lengths, "lengths"}}))) {
+        return rc;
     }
     if ((uintptr_t)p->events & 3u) {
         return fail(BMQCRC_EINVAL, "events must be 4-byte aligned");
@@ -2568,22 +2526,18 @@ int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result
                     {p->expected, 4 * cap, "expected"},
                     {p->out, 4 * cap, "out"},
                     {p->event_first, 8 * (p->n_events + 1), "event_first"}};
-        const uintptr_t e0 = (uintptr_t)p->events;
         for (const auto& a : outs) {
-            const uintptr_t a0 = (uintptr_t)a.at;
-            if (a.at && a.bytes && p->events_bytes && a0 < e0 + p->events_bytes &&
-                e0 < a0 + a.bytes) {
+            if (a.at && overlaps((uintptr_t)a.at, a.bytes, (uintptr_t)p->events, p->events_bytes)) {
                 return fail(BMQCRC_EINVAL,
                             std::string(a.name) + " overlaps [events, events+events_bytes)");
             }
         }
     }
-    Ctx c;
-    if ((rc = open_on(o.device, o.stream, &c))) {
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
         return rc;
     }
     Workspace* w = c.w;
-    std::lock_guard<std::mutex> g(w->mu);
     const uint64_t cap = p->msg_cap, slots = std::max<uint64_t>(cap, 1);
     if ((rc = w->unp_ctr.ensure(8 * kUnpCtrWords)) || (rc = w->unp_off.ensure(8 * slots)) ||
         (rc = w->unp_len.ensure(4 * slots)) || (rc = w->unp_exp.ensure(4 * slots)) ||
@@ -2619,8 +2573,7 @@ int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result
         a.bad_off = (unsigned long long*)w->unp_bad.p;
         a.ctr = (unsigned long long*)w->unp_ctr.p;
         if (bmqcrc_launch_unpack_walk(&a, (void*)c.s)) {
-            return fail(BMQCRC_EIO, std::string("put-unpack walk launch failed: ") +
-                                        hipGetErrorString(hipGetLastError()));
+            return launch_failed("put-unpack walk");
         }
         // the fold over the workspace's descriptors, which the placing kernel
         // filled for every slot: never over the caller's arrays
@@ -2631,8 +2584,7 @@ int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result
             return rc;
         }
         if (bmqcrc_launch_unpack_publish(&a, (void*)c.s)) {
-            return fail(BMQCRC_EIO, std::string("put-unpack publish launch failed: ") +
-                                        hipGetErrorString(hipGetLastError()));
+            return launch_failed("put-unpack publish");
         }
     }
     if (o.flags & BMQCRC_F_ASYNC) {
@@ -2645,21 +2597,19 @@ int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result
     if (result) {
         *result = r;
     }
-    return r.refused_kind ? unpack_refusal(r) : 0;
+    return r.refused_kind
+               ? refused(kUnpackRefusals, r.refused_kind, r.refused_event, r.refused_offset)
+               : 0;
 }
 
 int bmqcrc_last_put_unpack(int device, void* stream, bmqcrc_put_unpack_result* result)
 {
     t_err.clear();
     DeviceGuard keep_device;
-    Ctx c;
+    LockedCtx c;
     int rc;
-    if ((rc = open_on(device, stream, &c))) {
-        return rc;
-    }
-    std::lock_guard<std::mutex> g(c.w->mu);
     bmqcrc_put_unpack_result r;
-    if ((rc = unpack_result(c, &r))) {
+    if ((rc = lock_on(device, stream, true, &c)) || (rc = unpack_result(c, &r))) {
         return rc;
     }
     if (result) {
@@ -2673,12 +2623,12 @@ int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* sp
 {
     t_err.clear();
     DeviceGuard keep_device;
-    int dev, rc;
-    if ((rc = resolve_device(device, &dev))) {
+    LockedCtx c;
+    int rc;
+    if ((rc = lock_on(device, stream, false, &c))) {
         return rc;
     }
-    Workspace* w = workspace(dev, stream);
-    std::lock_guard<std::mutex> g(w->mu);
+    Workspace* w = c.w;
     if (kernels) {
         *kernels = w->last_kernels;
     }
@@ -2695,12 +2645,12 @@ int bmqcrc_last_plan(int device, void* stream, uint32_t* map)
 {
     t_err.clear();
     DeviceGuard keep_device;
-    int dev, rc;
-    if ((rc = resolve_device(device, &dev))) {
+    LockedCtx c;
+    int rc;
+    if ((rc = lock_on(device, stream, false, &c))) {
         return rc;
     }
-    Workspace* w = workspace(dev, stream);
-    std::lock_guard<std::mutex> g(w->mu);
+    Workspace* w = c.w;
     if (map) {
         *map = w->last_map;
     }
@@ -2711,12 +2661,12 @@ int bmqcrc_last_offsets(int device, void* stream, uint32_t* bits, uint32_t* shif
 {
     t_err.clear();
     DeviceGuard keep_device;
-    int dev, rc;
-    if ((rc = resolve_device(device, &dev))) {
+    LockedCtx c;
+    int rc;
+    if ((rc = lock_on(device, stream, false, &c))) {
         return rc;
     }
-    Workspace* w = workspace(dev, stream);
-    std::lock_guard<std::mutex> g(w->mu);
+    Workspace* w = c.w;
     if (bits) {
         *bits = w->last_off_bits;
     }
@@ -2730,12 +2680,12 @@ int bmqcrc_forget_shape(int device, void* stream)
 {
     t_err.clear();
     DeviceGuard keep_device;
-    int dev, rc;
-    if ((rc = resolve_device(device, &dev))) {
+    LockedCtx c;
+    int rc;
+    if ((rc = lock_on(device, stream, false, &c))) {
         return rc;
     }
-    Workspace* w = workspace(dev, stream);
-    std::lock_guard<std::mutex> g(w->mu);
+    Workspace* w = c.w;
     if (w->hint_host) {
         __atomic_store_n(w->hint_host, kHintUnknown, __ATOMIC_RELAXED);
     }
@@ -2746,14 +2696,12 @@ int bmqcrc_plan_wait(int device, void* stream, uint64_t wait_us, uint64_t* voide
 {
     t_err.clear();
     DeviceGuard keep_device;
-    int dev, rc;
-    DeviceState* st = nullptr;
-    if ((rc = resolve_device(device, &dev)) || (rc = device_state(dev, &st))) {
+    LockedCtx c;
+    int rc;
+    if ((rc = lock_on(device, stream, true, &c))) {
         return rc;
     }
-    HIP_TRY(hipSetDevice(dev));
-    Workspace* w = workspace(dev, stream);
-    std::lock_guard<std::mutex> g(w->mu);
+    Workspace* w = c.w;
     w->map_wait_ticks = wait_us > (UINT64_MAX / 100) ? UINT64_MAX : wait_us * 100;
     if (voided) {
         // k_plan_map counts its launches that gave up their map (plan_sync[3])
