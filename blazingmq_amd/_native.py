@@ -210,6 +210,40 @@ if hasattr(lib, "bmqcrc_put_event_unpack"):  # ABI 2.12 (an older build loads fo
                                             ctypes.POINTER(PutUnpackResult), _popts]
     lib.bmqcrc_last_put_unpack.restype = _int
     lib.bmqcrc_last_put_unpack.argtypes = [_int, _vp, ctypes.POINTER(PutUnpackResult)]
+BMQCRC_REC_UNPACK_OK = 0
+BMQCRC_REC_UNPACK_RECORD_HEADER = 1
+BMQCRC_REC_UNPACK_MESSAGE_RECORD = 2
+BMQCRC_REC_UNPACK_DATA_OFFSET = 3
+BMQCRC_REC_UNPACK_DATA_RECORD = 4
+BMQCRC_REC_UNPACK_TOO_MANY_MESSAGES = 5
+
+
+class RecordsUnpack(ctypes.Structure):
+    """bmqcrc_records_unpack (include/bmqcrc_protocol.h, ABI 2.13)."""
+    _fields_ = [("struct_size", _u32), ("reserved", _u32), ("journal", _vp),
+                ("journal_bytes", _u64), ("n_records", _u64), ("data", _vp), ("data_bytes", _u64),
+                ("data_file_pos", _u64), ("select", _vp), ("msg_cap", _u64),
+                ("record_index", _vp), ("app_offsets", _vp), ("lengths", _vp),
+                ("queue_keys", _vp), ("guids", _vp), ("data_flags", _vp), ("ref_counts", _vp),
+                ("timestamps", _vp), ("expected", _vp), ("out", _vp)]
+
+
+class RecordsUnpackResult(ctypes.Structure):
+    """bmqcrc_records_unpack_result (include/bmqcrc_protocol.h, ABI 2.13)."""
+    _fields_ = [("n_records", _u64), ("n_msgs", _u64), ("n_skipped", _u64), ("n_bad", _u64),
+                ("first_bad", _u64), ("refused_kind", _u32), ("reserved", _u32),
+                ("refused_index", _u64)]
+
+    def as_dict(self):
+        return {f[0]: int(getattr(self, f[0])) for f in self._fields_ if f[0] != "reserved"}
+
+
+if hasattr(lib, "bmqcrc_message_records_unpack"):  # ABI 2.13 (an older build loads for same-box A/B)
+    lib.bmqcrc_message_records_unpack.restype = _int
+    lib.bmqcrc_message_records_unpack.argtypes = [ctypes.POINTER(RecordsUnpack),
+                                                  ctypes.POINTER(RecordsUnpackResult), _popts]
+    lib.bmqcrc_last_records_unpack.restype = _int
+    lib.bmqcrc_last_records_unpack.argtypes = [_int, _vp, ctypes.POINTER(RecordsUnpackResult)]
 lib.bmqcrc_journal_scan.restype = _i64
 lib.bmqcrc_journal_scan.argtypes = [_vp, _u64, _vp, _u64, _vp, _pint, _pu64, _vp, _vp, _vp, _vp,
                                     _u64]

@@ -166,6 +166,15 @@ struct Workspace {
     DevBuf unp_off, unp_len, unp_exp, unp_out, unp_first, unp_bad, unp_ctr;
     uint64_t unp_events = 0;
     bool unp_any = false;
+    // bmqcrc_message_records_unpack: the same four per slot; per record the
+    // message flag with the block-local prefix (4), the application data's
+    // offset (8), length (4) and DataHeader flags (1); the block sums; the
+    // counters; the records of the last unpack enqueued
+    // (bmqcrc_last_records_unpack)
+    DevBuf runp_off, runp_len, runp_exp, runp_out, runp_pre, runp_roff, runp_rlen, runp_rflags,
+        runp_bsum, runp_ctr;
+    uint64_t runp_records = 0;
+    bool runp_any = false;
     // Pinned staging ring for gathered host buffers (bmqcrc_crc32c_gather):
     // kGatherSlots chunks of kGatherChunk bytes, each reusable once the event
     // recorded after its H2D copy has completed.
@@ -2618,6 +2627,207 @@ int bmqcrc_last_put_unpack(int device, void* stream, bmqcrc_put_unpack_result* r
     return 0;
 }
 
+static_assert(BMQCRC_REC_UNPACK_RECORD_HEADER == BMQCRC_RECUNP_KIND_RECORD_HEADER &&
+                  BMQCRC_REC_UNPACK_MESSAGE_RECORD == BMQCRC_RECUNP_KIND_MESSAGE_RECORD &&
+                  BMQCRC_REC_UNPACK_DATA_OFFSET == BMQCRC_RECUNP_KIND_DATA_OFFSET &&
+                  BMQCRC_REC_UNPACK_DATA_RECORD == BMQCRC_RECUNP_KIND_DATA_RECORD &&
+                  BMQCRC_REC_UNPACK_TOO_MANY_MESSAGES == BMQCRC_RECUNP_KIND_TOO_MANY_MESSAGES,
+              "the kernels' refusal kinds are the public ones");
+static_assert(kJournalRecordBytes == 4 * kJournalRecordDwords, "a journal record is 15 dwords");
+
+// Result of the records unpack last enqueued on c's workspace, after
+// everything enqueued on its stream (w->mu held); zeros when there was none.
+static int records_unpack_result(Ctx& c, bmqcrc_records_unpack_result* r)
+{
+    memset(r, 0, sizeof(*r));
+    if (!c.w->runp_any) {
+        return 0;
+    }
+    unsigned long long ctr[kRecUnpCtrWords];
+    HIP_TRY(hipMemcpyAsync(ctr, c.w->runp_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    r->n_records = c.w->runp_records;
+    if (ctr[kRecUnpCtrRefusal]) {
+        refusal_of(ctr[kRecUnpCtrRefusal], &r->refused_kind, &r->refused_index);
+        return 0;
+    }
+    r->n_msgs = ctr[kRecUnpCtrMsgs];
+    r->n_skipped = ctr[kRecUnpCtrSkipped];
+    r->n_bad = ctr[kRecUnpCtrBad];
+    r->first_bad = r->n_bad ? ~ctr[kRecUnpCtrFirstBad] : r->n_msgs;
+    return 0;
+}
+
+static const char* const kRecordsUnpackRefusals[6] = {
+    "", "BMQCRC_REC_UNPACK_RECORD_HEADER: record %llu has type 0, lease id 0, sequence number 0 "
+        "or a wrong magic",
+    "BMQCRC_REC_UNPACK_MESSAGE_RECORD: MESSAGE record %llu has a null GUID or queue key",
+    "BMQCRC_REC_UNPACK_DATA_OFFSET: MESSAGE record %llu points at offset 0 or outside "
+    "[data_file_pos, data_file_pos+data_bytes]",
+    "BMQCRC_REC_UNPACK_DATA_RECORD: MESSAGE record %llu points at a malformed DATA record",
+    "BMQCRC_REC_UNPACK_TOO_MANY_MESSAGES: the message of record %llu does not fit msg_cap"};
+
+int bmqcrc_message_records_unpack(const bmqcrc_records_unpack* p,
+                                  bmqcrc_records_unpack_result* result, const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    if (!p || p->struct_size != sizeof(bmqcrc_records_unpack)) {
+        return fail(BMQCRC_EINVAL,
+                    "bmqcrc_records_unpack.struct_size must be sizeof(bmqcrc_records_unpack)");
+    }
+    if (p->reserved) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_records_unpack.reserved must be 0");
+    }
+    bmqcrc_opts o;
+    int rc;
+    if ((rc = device_call_opts(opts, "bmqcrc_message_records_unpack", &o))) {
+        return rc;
+    }
+    if ((rc = refuse_null({{!p->journal, "journal"},
+                           {!p->data, "data"},
+                           {!p->app_offsets, "app_offsets"},
+                           {!p->lengths, "lengths"}}))) {
+        return rc;
+    }
+    if ((uintptr_t)p->journal & 3u) {
+        return fail(BMQCRC_EINVAL, "journal must be 4-byte aligned");
+    }
+    if ((uintptr_t)p->data & 7u) {
+        return fail(BMQCRC_EINVAL, "data must be 8-byte aligned");
+    }
+    if (p->data_file_pos & 7u) {
+        return fail(BMQCRC_EINVAL, "data_file_pos must be a multiple of 8");
+    }
+    if (p->n_records > 0xFFFFFFFFull || p->msg_cap > 0xFFFFFFFFull) {
+        return fail(BMQCRC_EINVAL, "n_records and msg_cap must be below 2^32");
+    }
+    if (kJournalRecordBytes * p->n_records > p->journal_bytes) {
+        return fail(BMQCRC_EINVAL, "journal_bytes is below 60 n_records");
+    }
+    {
+        const uint64_t cap = p->msg_cap;
+        const struct {
+            const void* at;
+            uint64_t bytes;
+            const char* name;
+        } outs[] = {{p->record_index, 4 * cap, "record_index"},
+                    {p->app_offsets, 8 * cap, "app_offsets"},
+                    {p->lengths, 4 * cap, "lengths"},
+                    {p->queue_keys, 5 * cap, "queue_keys"},
+                    {p->guids, 16 * cap, "guids"},
+                    {p->data_flags, cap, "data_flags"},
+                    {p->ref_counts, 4 * cap, "ref_counts"},
+                    {p->timestamps, 8 * cap, "timestamps"},
+                    {p->expected, 4 * cap, "expected"},
+                    {p->out, 4 * cap, "out"}};
+        for (const auto& a : outs) {
+            if (!a.at) {
+                continue;
+            }
+            if (overlaps((uintptr_t)a.at, a.bytes, (uintptr_t)p->journal, p->journal_bytes)) {
+                return fail(BMQCRC_EINVAL,
+                            std::string(a.name) + " overlaps [journal, journal+journal_bytes)");
+            }
+            if (overlaps((uintptr_t)a.at, a.bytes, (uintptr_t)p->data, p->data_bytes)) {
+                return fail(BMQCRC_EINVAL, std::string(a.name) + " overlaps [data, data+data_bytes)");
+            }
+        }
+    }
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    const uint64_t n = p->n_records, cap = p->msg_cap;
+    const uint64_t slots = std::max<uint64_t>(cap, 1), recs = std::max<uint64_t>(n, 1);
+    if ((rc = w->runp_ctr.ensure(8 * kRecUnpCtrWords)) ||
+        (rc = w->runp_bsum.ensure(8ull * 2 * kPackBlocks)) || (rc = w->runp_off.ensure(8 * slots)) ||
+        (rc = w->runp_len.ensure(4 * slots)) || (rc = w->runp_exp.ensure(4 * slots)) ||
+        (p->out && (rc = w->runp_out.ensure(4 * slots))) || (rc = w->runp_pre.ensure(4 * recs)) ||
+        (rc = w->runp_roff.ensure(8 * recs)) || (rc = w->runp_rlen.ensure(4 * recs)) ||
+        (rc = w->runp_rflags.ensure(recs))) {
+        return rc;
+    }
+    HIP_TRY(hipMemsetAsync(w->runp_ctr.p, 0, 8 * kRecUnpCtrWords, c.s));
+    w->runp_records = n;
+    w->runp_any = true;
+    if (n) {
+        RecUnpackArgs a;
+        memset(&a, 0, sizeof(a));
+        a.journal = (const uint32_t*)p->journal;
+        a.n_records = n;
+        a.data = (const uint8_t*)p->data;
+        a.data_bytes = p->data_bytes;
+        a.data_file_pos = p->data_file_pos;
+        a.select = p->select;
+        a.msg_cap = cap;
+        a.record_index = p->record_index;
+        a.app_offsets = p->app_offsets;
+        a.lengths = p->lengths;
+        a.queue_keys = p->queue_keys;
+        a.guids = p->guids;
+        a.data_flags = p->data_flags;
+        a.ref_counts = p->ref_counts;
+        a.timestamps = p->timestamps;
+        a.expected = p->expected;
+        a.out = p->out;
+        a.ws_off = (unsigned long long*)w->runp_off.p;
+        a.ws_len = (uint32_t*)w->runp_len.p;
+        a.ws_exp = (uint32_t*)w->runp_exp.p;
+        a.ws_out = (const uint32_t*)w->runp_out.p;
+        a.pre = (uint32_t*)w->runp_pre.p;
+        a.rec_off = (unsigned long long*)w->runp_roff.p;
+        a.rec_len = (uint32_t*)w->runp_rlen.p;
+        a.rec_flags = (uint8_t*)w->runp_rflags.p;
+        a.bsum = (unsigned long long*)w->runp_bsum.p;
+        a.ctr = (unsigned long long*)w->runp_ctr.p;
+        layout_split(n, &a.per_block, &a.nblocks);
+        if (bmqcrc_launch_records_unpack_walk(&a, (void*)c.s)) {
+            return launch_failed("records-unpack walk");
+        }
+        // the fold over the workspace's descriptors, which the placing kernel
+        // filled for every slot: never over the caller's arrays
+        if (p->out && (rc = run_batch(c, BMQCRC_F_DEVICE_PTRS | BMQCRC_F_PLAN, 0, p->data,
+                                      p->data_bytes, (const uint64_t*)w->runp_off.p,
+                                      (const uint32_t*)w->runp_len.p, nullptr,
+                                      (uint32_t*)w->runp_out.p, cap))) {
+            return rc;
+        }
+        if (bmqcrc_launch_records_unpack_publish(&a, (void*)c.s)) {
+            return launch_failed("records-unpack publish");
+        }
+    }
+    if (o.flags & BMQCRC_F_ASYNC) {
+        return 0;
+    }
+    bmqcrc_records_unpack_result r;
+    if ((rc = records_unpack_result(c, &r))) {
+        return rc;
+    }
+    if (result) {
+        *result = r;
+    }
+    return r.refused_kind ? refused(kRecordsUnpackRefusals, r.refused_kind, r.refused_index) : 0;
+}
+
+int bmqcrc_last_records_unpack(int device, void* stream, bmqcrc_records_unpack_result* result)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    LockedCtx c;
+    int rc;
+    bmqcrc_records_unpack_result r;
+    if ((rc = lock_on(device, stream, true, &c)) || (rc = records_unpack_result(c, &r))) {
+        return rc;
+    }
+    if (result) {
+        *result = r;
+    }
+    return 0;
+}
+
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,
                        uint32_t* seg_bytes)
 {
@@ -2791,7 +3001,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 12u;
+    return (2u << 16) | 13u;
 }
 
 }  // extern "C"

@@ -317,7 +317,65 @@ struct UnpackArgs {
     unsigned long long* ctr;        // workspace, kUnpCtrWords, zeroed before the launch
 };
 
+// ---- bmqcrc_message_records_unpack (crc32c_records_unpack.hip, ABI 2.13) ---
+// The classify and place grid and block are kPackBlocks x kPackThreads over
+// contiguous record ranges (layout_split), the publish kernel's
+// kUnpackPublishBlocks x kUnpackPublishThreads.
+constexpr uint32_t kJournalRecordDwords = 15;  // a journal record: 60 bytes
+constexpr uint32_t kRecUnpMsgFlag = 0x80000000u;  // RecUnpackArgs::pre: the record takes a slot
+// RecUnpackArgs::ctr words
+constexpr int kRecUnpCtrRefusal = kLayoutCtrRefusal;
+constexpr int kRecUnpCtrMsgs = 1;      // selected MESSAGE records (k_recunp_place, refused or not)
+constexpr int kRecUnpCtrBad = 2;       // messages whose computed CRC differs from the stored one
+constexpr int kRecUnpCtrFirstBad = 3;  // ~(lowest such slot), 0: none
+constexpr int kRecUnpCtrSkipped = 4;   // unselected MESSAGE records (k_recunp_place)
+constexpr int kRecUnpCtrWords = 5;
+// BMQCRC_REC_UNPACK_* of bmqcrc_protocol.h, which the kernels do not include
+#define BMQCRC_RECUNP_KIND_RECORD_HEADER 1u
+#define BMQCRC_RECUNP_KIND_MESSAGE_RECORD 2u
+#define BMQCRC_RECUNP_KIND_DATA_OFFSET 3u
+#define BMQCRC_RECUNP_KIND_DATA_RECORD 4u
+#define BMQCRC_RECUNP_KIND_TOO_MANY_MESSAGES 5u
+
+struct RecUnpackArgs {
+    const uint32_t* journal;        // device, 4-byte aligned: n_records records of 15 dwords
+    uint64_t n_records;
+    const uint8_t* data;            // device, 8-byte aligned: the DATA-file window
+    uint64_t data_bytes;
+    uint64_t data_file_pos;         // byte of the DATA file that data[0] stands for
+    const uint8_t* select;          // device, n_records, or nullptr (every MESSAGE record)
+    uint64_t msg_cap;
+    uint32_t* record_index;         // the caller's arrays (device, msg_cap): written when nothing
+    uint64_t* app_offsets;          // was refused, and only by k_recunp_place (record_index,
+    uint32_t* lengths;              // queue_keys, guids, data_flags, ref_counts, timestamps) and
+    uint8_t* queue_keys;            // k_recunp_publish (the others); all but app_offsets and
+    uint8_t* guids;                 // lengths may be nullptr
+    uint8_t* data_flags;
+    uint32_t* ref_counts;
+    uint64_t* timestamps;
+    uint32_t* expected;
+    uint32_t* out;                  // nullptr: walk only, ws_out is then unused
+    unsigned long long* ws_off;     // workspace, msg_cap: what the fold reads, every slot filled
+    uint32_t* ws_len;               // workspace, msg_cap  by k_recunp_place (empty when unused)
+    uint32_t* ws_exp;               // workspace, msg_cap: the stored CRCs
+    const uint32_t* ws_out;         // workspace, msg_cap: the fold's CRCs
+    uint32_t* pre;                  // workspace, n_records: kRecUnpMsgFlag | block-local prefix
+    unsigned long long* rec_off;    // workspace, n_records: application data's offset in `data`,
+    uint32_t* rec_len;              // its length and the DataHeader's flags byte, of the records
+    uint8_t* rec_flags;             // that take a slot
+    unsigned long long* bsum;       // workspace, 2 * kPackBlocks: messages | skipped per block
+    unsigned long long* ctr;        // workspace, kRecUnpCtrWords, zeroed before the launch
+    uint64_t per_block;             // records per block (multiple of kPackThreads)
+    uint32_t nblocks;               // blocks (<= kPackBlocks)
+};
+
 }  // namespace bmqcrc
+
+// Launchers (crc32c_records_unpack.hip).  Asynchronous on `stream`: the walk
+// fills ws_off / ws_len for the fold (bmqcrc_launch_batch), the publish runs
+// after it.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_records_unpack_walk(const bmqcrc::RecUnpackArgs* a, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_records_unpack_publish(const bmqcrc::RecUnpackArgs* a, void* stream);
 
 // Launchers (crc32c_put_unpack.hip).  Asynchronous on `stream`: the walk fills
 // ws_off / ws_len for the fold (bmqcrc_launch_batch), the publish runs after it.

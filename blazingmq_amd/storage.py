@@ -34,6 +34,7 @@ On-disk layouts (mqbs_filestoreprotocol.h):
   bytes, each equal to the padding count (bmqp_protocolutil.cpp:44, dword
   padding); MessageOffsetDwords counts 8-byte units.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -617,3 +618,112 @@ def last_records_pack(device, stream=None):
     N.check(N.lib.bmqcrc_last_records_pack(
         device, stream.cuda_stream if stream is not None else None, ctypes.byref(res)))
     return res.as_dict()
+
+
+# ----------------------------------------------------------------------------
+# Device-side reader: the inverse of pack_records.
+# ----------------------------------------------------------------------------
+UnpackedRecords = collections.namedtuple(
+    "UnpackedRecords", "record_index app_offsets lengths queue_keys guids data_flags ref_counts "
+                       "timestamps expected crcs")
+
+
+def unpack_records(journal, data, *, data_file_pos, msg_cap=None, select=None, verify=True,
+                   stream=None, sync=True):
+    """Walk device-resident journal records and their DATA records on the GPU
+    (``bmqcrc_message_records_unpack``), the inverse of ``pack_records``: every
+    MESSAGE record and its DataHeader checked as ``FileStore::recoverMessages``
+    checks them, and what the packers take for every message, as device
+    tensors, with no payload byte and no descriptor crossing PCIe.
+
+    ``journal`` is a contiguous uint8 device tensor (4-byte aligned) of whole
+    60-byte records -- the record run, not the journal file with its headers;
+    ``journal_dst`` of ``pack_records`` is one.  ``data`` (uint8, 8-byte
+    aligned) stands for bytes ``[data_file_pos, data_file_pos + data.numel())``
+    of the DATA file; 0 means the whole file.  ``select`` (uint8, one byte per
+    record, or None) leaves the MESSAGE records whose byte is 0 out: they are
+    checked up to their data offset, take no slot, and their DATA record is
+    never read.  ``msg_cap`` is the capacity of the per-message arrays; None
+    is the record count.  With ``verify`` every message's application data is
+    CRC'd and compared with the stored CRC (ask ``last_records_unpack`` for
+    n_bad / first_bad); the CRC pass runs over all ``msg_cap`` slots, so a
+    tight ``msg_cap`` is cheaper.
+
+    Returns the named tuple ``(record_index, app_offsets, lengths, queue_keys,
+    guids, data_flags, ref_counts, timestamps, expected, crcs)``: int32 record
+    indices, int64 offsets in ``data`` of the application data, int32 lengths,
+    uint8 queue keys (5 per message), GUIDs (16) and DataHeader flags, int32
+    reference counts, int64 timestamps, the stored CRCs and the computed ones
+    (int32; ``crcs`` is None when ``verify=False``).  With ``sync=True`` the
+    tensors are sliced to the messages found, and a malformed record or more
+    than ``msg_cap`` messages raises ``BmqCrcError`` (BMQCRC_EINVAL) naming
+    kind and record: nothing is written then.  With ``sync=False`` the tensors
+    keep their full capacity and ``last_records_unpack`` reports the outcome.
+    Not meant to be captured into a graph."""
+    import torch
+    for name, t in (("journal", journal), ("data", data), ("select", select)):
+        if name == "select" and t is None:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise TypeError("%s must be a contiguous %s tensor" % (name, torch.uint8))
+    dev = journal.device
+    if not journal.is_cuda:
+        raise TypeError("unpack_records takes device tensors only (journal is on %s)" % dev)
+    for name, t in (("data", data), ("select", select)):
+        if t is not None and t.device != dev:
+            raise TypeError("%s must be on %s like journal" % (name, dev))
+    if journal.numel() % JOURNAL_RECORD_SIZE:
+        raise ValueError("journal must hold whole 60-byte records")
+    n_records = journal.numel() // JOURNAL_RECORD_SIZE
+    if select is not None and select.numel() != n_records:
+        raise ValueError("select needs one byte per record")
+    cap = n_records if msg_cap is None else int(msg_cap)
+    if cap < 0:
+        raise ValueError("msg_cap must not be negative")
+
+    def new(shape, dt):
+        return torch.empty(shape, dtype=dt, device=dev)
+    u = UnpackedRecords(new(cap, torch.int32), new(cap, torch.int64), new(cap, torch.int32),
+                        new((cap, 5), torch.uint8), new((cap, 16), torch.uint8),
+                        new(cap, torch.uint8), new(cap, torch.int32), new(cap, torch.int64),
+                        new(cap, torch.int32), new(cap, torch.int32) if verify else None)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    # (an empty tensor has no address: the call wants one for the required arrays)
+    spare = new(1, torch.int64)
+    p = N.RecordsUnpack()
+    p.struct_size = ctypes.sizeof(N.RecordsUnpack)
+    p.journal, p.journal_bytes = journal.data_ptr() or spare.data_ptr(), journal.numel()
+    p.n_records = n_records
+    p.data, p.data_bytes = data.data_ptr() or spare.data_ptr(), data.numel()
+    p.data_file_pos = int(data_file_pos)
+    p.select = select.data_ptr() if select is not None else None
+    p.msg_cap = cap
+    for name in u._fields[:9]:
+        setattr(p, name, getattr(u, name).data_ptr())
+    p.app_offsets = p.app_offsets or spare.data_ptr()
+    p.lengths = p.lengths or spare.data_ptr()
+    p.out = u.crcs.data_ptr() if verify else None
+    o = N.make_opts(device=dev.index if dev.index is not None else -1, stream=stream.cuda_stream,
+                    flags=N.BMQCRC_F_DEVICE_PTRS | (0 if sync else N.BMQCRC_F_ASYNC))
+    r = N.RecordsUnpackResult()
+    N.check(N.lib.bmqcrc_message_records_unpack(ctypes.byref(p), ctypes.byref(r), ctypes.byref(o)))
+    if not sync:
+        return u
+    n = int(r.n_msgs)
+    return UnpackedRecords(*[t[:n] if t is not None else None for t in u])
+
+
+def last_records_unpack(device, stream=None):
+    """The result of the previous ``unpack_records`` on (device, stream)
+    (bmqcrc_last_records_unpack), as a dict; waits for it.  ``n_records``,
+    ``n_msgs`` and ``n_skipped`` (the slots taken and the unselected MESSAGE
+    records; both 0 when refused), ``n_bad`` and ``first_bad`` (slots whose
+    computed CRC differs from the stored one, and the lowest; ``n_msgs`` when
+    none), ``refused_kind`` (0, ``BMQCRC_REC_UNPACK_OK``, or the kind) and
+    ``refused_index`` (a record index).  ``stream=None`` is the device's
+    default stream."""
+    r = N.RecordsUnpackResult()
+    N.check(N.lib.bmqcrc_last_records_unpack(
+        device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
+    return r.as_dict()

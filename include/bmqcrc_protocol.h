@@ -360,6 +360,134 @@ int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result
  * stream); waits for it.  `result` may be NULL. */
 int bmqcrc_last_put_unpack(int device, void* stream, bmqcrc_put_unpack_result* result);
 
+/* ABI 2.13.  The inverse of bmqcrc_message_records_pack: a run of journal
+ * records and a window of the DATA file in device memory are walked ON THE
+ * DEVICE, every MessageRecord and its DataHeader checked as
+ * FileStore::recoverMessages checks them (mqbs_filestore.cpp:2390-2575), and
+ * every message's descriptors come back as the arrays the packers take.  With
+ * `out` every stored CRC is checked against its application data in the same
+ * asynchronous call.  No payload byte and no descriptor crosses PCIe.
+ *
+ * Records.  Record r is bytes [60 r, 60 r + 60) of `journal`: the caller
+ *   passes the record run, not the journal file with its headers (the packer's
+ *   journal_dst is such a run; bmqcrc_journal_bounds bounds a file's).  `data`
+ *   stands for bytes [data_file_pos, data_file_pos + data_bytes) of the DATA
+ *   file; data_file_pos 0 means the whole file from its first byte.  The
+ *   packer's dst and data_file_pos go straight in.
+ * Messages are the MESSAGE records (type 1) with select[r] != 0 (select ==
+ *   NULL: all of them), numbered in ascending record order.  Message k yields
+ *   record_index[k]; app_offsets[k], the byte offset IN `data` of its
+ *   application data (usable as src_offsets with src = data in both packers);
+ *   lengths[k]; queue_keys[5 k ..] (record bytes @22); guids[16 k ..] (@36);
+ *   data_flags[k] (the DataHeader's flags byte); ref_counts[k] (20 bits: byte
+ *   @20 << 12, or'ed with the low 12 bits of the BE u16 @0); timestamps[k] (BE
+ *   u64 @12); expected[k] (the stored CRC @52, host order): the inputs of
+ *   bmqcrc_message_records_pack, so that unpack followed by pack with the same
+ *   file_key, lease_id, first_seq and data_file_pos reproduces both byte
+ *   streams.  DataHeader options are skipped, not interpreted: the
+ *   application data starts at o - data_file_pos + 4 headerWords + 4
+ *   optionsWords.
+ * Options.  Device pointers only: BMQCRC_F_DEVICE_PTRS is required,
+ *   BMQCRC_F_ASYNC allowed; any other flag, ndevices > 1, a wrong struct_size
+ *   or reserved, `journal`, `data`, app_offsets or lengths null, `journal` not
+ *   4-byte or `data` not 8-byte aligned, data_file_pos no multiple of 8,
+ *   n_records or msg_cap at or above 2^32, 60 n_records > journal_bytes, or
+ *   any given output array meeting [journal, journal + journal_bytes) or
+ *   [data, data + data_bytes) is BMQCRC_EINVAL, answered on the host before
+ *   the device lookup.  n_records == 0 writes nothing and reports zeros.
+ * All or nothing, decided on the device.  One violation anywhere refuses the
+ *   call, and a refused call writes nothing to any output array.  A record is
+ *   checked in the host walk's order (walk_recovery, bmqcrc_journal_scan) and
+ *   raises its first violation; across records the lowest kind wins and
+ *   within it the lowest record.  With o = 8 MessageOffsetDwords and end =
+ *   data_bytes, a selected MESSAGE record's DATA record is malformed when
+ *   o - data_file_pos + 8 > end; headerWords or messageWords is 0; 4
+ *   (headerWords + optionsWords) >= 4 messageWords; the record ends past end;
+ *   or its last byte, the padding count, is not in 1..8 or exceeds what the
+ *   header and the options leave.  Record types 2..15 are validated under
+ *   RECORD_HEADER and then skipped, as the host walk skips them.  A MESSAGE
+ *   record with select[r] == 0 is checked up to DATA_OFFSET, takes no slot and
+ *   is counted in n_skipped: no byte of its DATA record is read (where the
+ *   host walk says `continue` for deleted and purged messages).  A
+ *   synchronous call returns BMQCRC_EINVAL naming kind and record; after an
+ *   asynchronous call bmqcrc_last_records_unpack reports them.
+ * Not restated here, the caller's business: the primary sequence number
+ *   (lease id, sequence number) ordering checks, queue liveness
+ *   (BMQCRC_RECOVERY_INVALID_QUEUE_KEY), the selection itself (DELETION and
+ *   PURGE bookkeeping: `select` carries its outcome), and the journal bounds
+ *   (the caller passes a bounded run).
+ * CRC pass.  With out != NULL the application data of every message is CRC'd
+ *   (seed 0) by the batch kernels, planned, on the call's own stream; n_bad
+ *   and first_bad count the slots whose out[k] differs from expected[k].
+ *   Mismatches do not fail the call.  The call never synchronises under
+ *   BMQCRC_F_ASYNC and the device alone knows n_msgs, so the pass always runs
+ *   over msg_cap slots (the unused ones are empty messages): a tight msg_cap
+ *   is the caller's job.  The pass reads its descriptors from the call's own
+ *   workspace, never from the caller's arrays.
+ * After a successful call entries [n_msgs, msg_cap) of app_offsets, lengths,
+ *   expected and out are unspecified and the other arrays untouched there;
+ *   nothing at or beyond msg_cap is ever written.
+ * *result (may be NULL) is written by a synchronous call only.
+ * State.  As bmqcrc_put_event_unpack: takes the workspace mutex of (device,
+ *   stream); restores the caller's current device; allocates its own
+ *   workspace on first use and when msg_cap or n_records grows (20 bytes per
+ *   slot of msg_cap, 17 per record), which bmqcrc_reserve does not cover; is
+ *   not meant to be captured into a hipGraph; is deterministic.  With out !=
+ *   NULL it counts as a BMQCRC_F_DEVICE_PTRS | BMQCRC_F_PLAN batch of msg_cap
+ *   messages for bmqcrc_last_launch, bmqcrc_last_plan, bmqcrc_last_offsets and
+ *   the shape prediction; with out == NULL those stay untouched.  The records
+ *   of bmqcrc_last_copy, bmqcrc_last_put_pack, bmqcrc_last_records_pack and
+ *   bmqcrc_last_put_unpack are never touched. */
+#define BMQCRC_REC_UNPACK_OK 0
+#define BMQCRC_REC_UNPACK_RECORD_HEADER 1     /* any record: type 0, lease id 0, sequence number 0, or the
+                                                 magic @56 != 0x2A724563 */
+#define BMQCRC_REC_UNPACK_MESSAGE_RECORD 2    /* MESSAGE record with an all-zero GUID or queue key
+                                                 (recovery rc -16) */
+#define BMQCRC_REC_UNPACK_DATA_OFFSET 3       /* MESSAGE record: o is 0, below data_file_pos or above
+                                                 data_file_pos + data_bytes (rc -11) */
+#define BMQCRC_REC_UNPACK_DATA_RECORD 4       /* selected MESSAGE record with a malformed DATA record (rc -17) */
+#define BMQCRC_REC_UNPACK_TOO_MANY_MESSAGES 5 /* more selected MESSAGE records than msg_cap; index: the
+                                                 record that would take slot msg_cap */
+
+typedef struct bmqcrc_records_unpack {
+    uint32_t struct_size, reserved;       /* sizeof, 0 */
+    const void* journal;                  /* device, 4-byte aligned: 60-byte records back to back */
+    uint64_t journal_bytes;               /* at least 60 n_records */
+    uint64_t n_records;                   /* < 2^32 */
+    const void* data;                     /* device, 8-byte aligned: the DATA-file window */
+    uint64_t data_bytes;
+    uint64_t data_file_pos;               /* byte position in the DATA file that data[0] stands for:
+                                             a multiple of 8 */
+    const uint8_t* select;                /* device, n_records, may be NULL: 0 = leave this MESSAGE record out */
+    uint64_t msg_cap;                     /* capacity of the per-message arrays, < 2^32 */
+    uint32_t* record_index;               /* device, msg_cap, may be NULL: the journal record of each slot */
+    uint64_t* app_offsets;                /* device, msg_cap: byte offset in `data` of the application data */
+    uint32_t* lengths;                    /* device, msg_cap */
+    uint8_t* queue_keys;                  /* device, 5 msg_cap, may be NULL */
+    uint8_t* guids;                       /* device, 16 msg_cap, may be NULL */
+    uint8_t* data_flags;                  /* device, msg_cap, may be NULL: DataHeader flags */
+    uint32_t* ref_counts;                 /* device, msg_cap, may be NULL: 20 bits */
+    uint64_t* timestamps;                 /* device, msg_cap, may be NULL */
+    uint32_t* expected;                   /* device, msg_cap, may be NULL: the stored CRCs, host order */
+    uint32_t* out;                        /* device, msg_cap, may be NULL: the computed CRCs; NULL = walk only */
+} bmqcrc_records_unpack;
+
+/* All fields zero before the first call on (device, stream). */
+typedef struct bmqcrc_records_unpack_result {
+    uint64_t n_records;
+    uint64_t n_msgs, n_skipped;           /* slots taken; unselected MESSAGE records; both 0 when refused */
+    uint64_t n_bad, first_bad;            /* stored CRC != computed CRC; first_bad: a slot, n_msgs when none */
+    uint32_t refused_kind, reserved;
+    uint64_t refused_index;               /* a record index */
+} bmqcrc_records_unpack_result;
+
+int bmqcrc_message_records_unpack(const bmqcrc_records_unpack* p,
+                                  bmqcrc_records_unpack_result* result, const bmqcrc_opts* opts);
+
+/* ABI 2.13.  Result of the previous bmqcrc_message_records_unpack on (device,
+ * stream); waits for it.  `result` may be NULL. */
+int bmqcrc_last_records_unpack(int device, void* stream, bmqcrc_records_unpack_result* result);
+
 /* ---- partition recovery (mqbs_filestoreprotocol.h:306,426,483,703,953-1990) */
 
 /* mqbs::FileStore::recoverMessages result codes (mqbs_filestore.cpp:1073-1091)
