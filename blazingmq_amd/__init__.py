@@ -10,11 +10,12 @@ from .crc32c import (Blob, BmqCrcError, Crc32c, HostRegistration,  # noqa: F401
                      reserve)
 from .put_event import (last_put_pack, last_put_unpack, pack_events,  # noqa: F401
                         unpack_events)
-from .storage import (last_records_pack, last_records_unpack, pack_records,  # noqa: F401
-                      unpack_records)
+from .storage import (last_journal_select, last_records_pack,  # noqa: F401
+                      last_records_unpack, pack_records, select_records, unpack_records)
 
 __all__ = ["Blob", "BmqCrcError", "Crc32c", "HostRegistration", "calculate_batch_multi",
            "calculate_batch_ptr", "device_count", "fill_synthetic", "forget_shape", "plan_wait",
-           "kernel_timing", "last_copy", "last_launch", "last_offsets", "last_put_pack",
-           "last_put_unpack", "last_records_pack", "last_records_unpack", "pack_events",
-           "pack_records", "reserve", "unpack_events", "unpack_records"]
+           "kernel_timing", "last_copy", "last_journal_select", "last_launch", "last_offsets",
+           "last_put_pack", "last_put_unpack", "last_records_pack", "last_records_unpack",
+           "pack_events", "pack_records", "reserve", "select_records", "unpack_events",
+           "unpack_records"]

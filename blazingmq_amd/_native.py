@@ -244,6 +244,34 @@ if hasattr(lib, "bmqcrc_message_records_unpack"):  # ABI 2.13 (an older build lo
                                                   ctypes.POINTER(RecordsUnpackResult), _popts]
     lib.bmqcrc_last_records_unpack.restype = _int
     lib.bmqcrc_last_records_unpack.argtypes = [_int, _vp, ctypes.POINTER(RecordsUnpackResult)]
+BMQCRC_JSEL_OK = 0
+BMQCRC_JSEL_TOO_MANY_QUEUES = 1
+
+
+class JournalSelect(ctypes.Structure):
+    """bmqcrc_journal_select_args (include/bmqcrc_protocol.h, ABI 2.14)."""
+    _fields_ = [("struct_size", _u32), ("reserved", _u32), ("journal", _vp),
+                ("journal_bytes", _u64), ("n_records", _u64), ("data_file_bytes", _u64),
+                ("with_csl", ctypes.c_int32), ("reserved2", ctypes.c_int32), ("queue_keys", _vp),
+                ("n_queue_keys", _u64), ("queue_cap", _u64), ("select", _vp)]
+
+
+class JournalSelectResult(ctypes.Structure):
+    """bmqcrc_journal_select_result (include/bmqcrc_protocol.h, ABI 2.14)."""
+    _fields_ = [("n_records", _u64), ("first_record", _u64), ("n_selected", _u64),
+                ("n_deleted", _u64), ("n_purged", _u64), ("error_record", _u64),
+                ("recovery_rc", ctypes.c_int32), ("refused_kind", _u32)]
+
+    def as_dict(self):
+        return {f[0]: int(getattr(self, f[0])) for f in self._fields_}
+
+
+if hasattr(lib, "bmqcrc_journal_select"):  # ABI 2.14 (an older build loads for same-box A/B)
+    lib.bmqcrc_journal_select.restype = _int
+    lib.bmqcrc_journal_select.argtypes = [ctypes.POINTER(JournalSelect),
+                                          ctypes.POINTER(JournalSelectResult), _popts]
+    lib.bmqcrc_last_journal_select.restype = _int
+    lib.bmqcrc_last_journal_select.argtypes = [_int, _vp, ctypes.POINTER(JournalSelectResult)]
 lib.bmqcrc_journal_scan.restype = _i64
 lib.bmqcrc_journal_scan.argtypes = [_vp, _u64, _vp, _u64, _vp, _pint, _pu64, _vp, _vp, _vp, _vp,
                                     _u64]

@@ -175,6 +175,13 @@ struct Workspace {
         runp_bsum, runp_ctr;
     uint64_t runp_records = 0;
     bool runp_any = false;
+    // bmqcrc_journal_select: the part of its workspace every call zeroes (the
+    // counters, the queue-key and GUID tables, the claims) and the rest (the
+    // two record lists, the named DELETIONs, the states); the records of the
+    // last select enqueued (bmqcrc_last_journal_select)
+    DevBuf jsel_zero, jsel_rec;
+    uint64_t jsel_records = 0;
+    bool jsel_any = false;
     // Pinned staging ring for gathered host buffers (bmqcrc_crc32c_gather):
     // kGatherSlots chunks of kGatherChunk bytes, each reusable once the event
     // recorded after its H2D copy has completed.
@@ -2828,6 +2835,162 @@ int bmqcrc_last_records_unpack(int device, void* stream, bmqcrc_records_unpack_r
     return 0;
 }
 
+// Result of the journal select last enqueued on c's workspace, after
+// everything enqueued on its stream (w->mu held); zeros when there was none.
+static int journal_select_result(Ctx& c, bmqcrc_journal_select_result* r)
+{
+    memset(r, 0, sizeof(*r));
+    if (!c.w->jsel_any) {
+        return 0;
+    }
+    unsigned long long ctr[kJselCtrWords] = {0};
+    const uint64_t n = c.w->jsel_records;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(ctr, c.w->jsel_zero.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
+    }
+    HIP_TRY(hipStreamSynchronize(c.s));
+    r->n_records = n;
+    r->first_record = ctr[kJselCtrFirst];
+    r->n_selected = ctr[kJselCtrSelected];
+    r->n_deleted = ctr[kJselCtrDeleted];
+    r->n_purged = ctr[kJselCtrPurged];
+    r->error_record = n;
+    if (ctr[kJselCtrRefused]) {
+        r->refused_kind = BMQCRC_JSEL_TOO_MANY_QUEUES;
+        return 0;
+    }
+    const unsigned long long failure =
+        ctr[kJselCtrFail1] ? ctr[kJselCtrFail1] : ctr[kJselCtrFail2];
+    if (failure) {
+        r->recovery_rc = -(int32_t)(failure & 0xFFu);
+        r->error_record = (failure >> 8) - 1;
+    }
+    return 0;
+}
+
+static uint64_t pow2_at_least(uint64_t v)
+{
+    uint64_t p = 64;
+    while (p < v) {
+        p <<= 1;
+    }
+    return p;
+}
+
+int bmqcrc_journal_select(const bmqcrc_journal_select_args* p, bmqcrc_journal_select_result* result,
+                          const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    if (!p || p->struct_size != sizeof(bmqcrc_journal_select_args)) {
+        return fail(BMQCRC_EINVAL,
+                    "bmqcrc_journal_select_args.struct_size must be sizeof(bmqcrc_journal_select_args)");
+    }
+    if (p->reserved || p->reserved2) {
+        return fail(BMQCRC_EINVAL, "bmqcrc_journal_select_args.reserved and reserved2 must be 0");
+    }
+    bmqcrc_opts o;
+    int rc;
+    if ((rc = device_call_opts(opts, "bmqcrc_journal_select", &o))) {
+        return rc;
+    }
+    const struct {
+        bool bad;
+        const char* what;
+    } checks[] = {{!p->journal, "null pointer argument: journal"},
+                  {!p->select, "null pointer argument: select"},
+                  {p->n_queue_keys && !p->queue_keys, "null pointer argument: queue_keys"},
+                  {((uintptr_t)p->journal & 3u) != 0, "journal must be 4-byte aligned"},
+                  {p->n_records > 0xFFFFFFFFull, "n_records must be below 2^32"},
+                  {p->journal_bytes != kJournalRecordBytes * p->n_records,
+                   "journal_bytes must be 60 n_records"},
+                  {p->queue_cap == 0, "queue_cap must not be 0"}};
+    for (const auto& k : checks) {
+        if (k.bad) {
+            return fail(BMQCRC_EINVAL, std::string("bmqcrc_journal_select: ") + k.what);
+        }
+    }
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    const uint64_t n = p->n_records;
+    const uint64_t nkeys = p->with_csl ? p->n_queue_keys : 0;
+    w->jsel_records = n;
+    w->jsel_any = true;
+    if (n) {
+        // no more distinct keys than QueueOp records and queue_keys together
+        const uint64_t qslots = pow2_at_least(2 * std::min(p->queue_cap, n + nkeys));
+        const uint64_t gslots = pow2_at_least(2 * n);
+        const uint64_t zero_bytes = 8ull * kJselCtrWords + 24 * qslots + 4 * gslots + 4 * n;
+        if ((rc = w->jsel_zero.ensure(zero_bytes)) || (rc = w->jsel_rec.ensure(13 * n))) {
+            return rc;
+        }
+        HIP_TRY(hipMemsetAsync(w->jsel_zero.p, 0, zero_bytes, c.s));
+        JselArgs a;
+        memset(&a, 0, sizeof(a));
+        a.journal = (const uint32_t*)p->journal;
+        a.n_records = n;
+        a.data_file_bytes = p->data_file_bytes;
+        a.queue_keys = p->queue_keys;
+        a.n_queue_keys = nkeys;
+        a.queue_cap = p->queue_cap;
+        a.select = p->select;
+        a.with_csl = p->with_csl != 0;
+        a.ctr = (unsigned long long*)w->jsel_zero.p;
+        a.qkey = a.ctr + kJselCtrWords;
+        a.qdel = (uint32_t*)(a.qkey + qslots);
+        a.qtop = a.qdel + qslots;
+        a.qpurge = a.qtop + qslots;
+        a.qcsl = a.qpurge + qslots;
+        a.gslot = a.qcsl + qslots;
+        a.claim = a.gslot + gslots;
+        a.qlist = (uint32_t*)w->jsel_rec.p;
+        a.slist = a.qlist + n;
+        a.names = a.slist + n;
+        a.state = (uint8_t*)(a.names + n);
+        a.qslots = qslots;
+        a.gslots = gslots;
+        layout_split(n, &a.per_block, &a.nblocks);
+        if (bmqcrc_launch_journal_select(&a, (void*)c.s)) {
+            return launch_failed("journal-select");
+        }
+    }
+    if (o.flags & BMQCRC_F_ASYNC) {
+        return 0;
+    }
+    bmqcrc_journal_select_result r;
+    if ((rc = journal_select_result(c, &r))) {
+        return rc;
+    }
+    if (result) {
+        *result = r;
+    }
+    return r.refused_kind
+               ? fail(BMQCRC_EINVAL, "BMQCRC_JSEL_TOO_MANY_QUEUES: the journal's QueueOp records "
+                                     "and queue_keys hold more distinct queue keys than queue_cap: "
+                                     "nothing was selected")
+               : 0;
+}
+
+int bmqcrc_last_journal_select(int device, void* stream, bmqcrc_journal_select_result* result)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    LockedCtx c;
+    int rc;
+    bmqcrc_journal_select_result r;
+    if ((rc = lock_on(device, stream, true, &c)) || (rc = journal_select_result(c, &r))) {
+        return rc;
+    }
+    if (result) {
+        *result = r;
+    }
+    return 0;
+}
+
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,
                        uint32_t* seg_bytes)
 {
@@ -3001,7 +3164,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 13u;
+    return (2u << 16) | 14u;
 }
 
 }  // extern "C"

@@ -369,7 +369,65 @@ struct RecUnpackArgs {
     uint32_t nblocks;               // blocks (<= kPackBlocks)
 };
 
+// ---- bmqcrc_journal_select (crc32c_journal_select.hip, ABI 2.14) -----------
+// The per-record kernels' grid and block are kPackBlocks x kPackThreads over
+// contiguous record ranges (layout_split); k_jsel_queues is one block.  Every
+// "record + 1" word below is 0 for "none", so a maximum of them is the highest
+// record and a zeroed workspace is the empty state.
+// JselArgs::ctr words
+constexpr int kJselCtrStop = 0;       // stop + 1: the highest record that is not in the journal
+constexpr int kJselCtrFail1 = 1;      // (record + 1) << 8 | -rc of the first pass's failure
+constexpr int kJselCtrFail2 = 2;      // ... of the second pass's
+constexpr int kJselCtrQueueOps = 3;   // entries of qlist
+constexpr int kJselCtrSyncs = 4;      // entries of slist
+constexpr int kJselCtrKeys = 5;       // distinct queue keys published
+constexpr int kJselCtrRefused = 6;    // 1: more distinct queue keys than queue_cap
+constexpr int kJselCtrFirstSync = 7;  // the lowest JOURNAL_OP record of the walk, 0 when none
+constexpr int kJselCtrSelected = 8;   // the three counts over [first_record, n_records)
+constexpr int kJselCtrDeleted = 9;
+constexpr int kJselCtrPurged = 10;
+constexpr int kJselCtrFirst = 11;     // first_record
+constexpr int kJselCtrWords = 16;
+// JselArgs::state values: what a MESSAGE record of the walk came to
+constexpr uint8_t kJselNone = 0;      // not a MESSAGE record, not walked, or failed
+constexpr uint8_t kJselLive = 1;      // eligible, its queue is live: selected unless a DELETION claims it
+constexpr uint8_t kJselPurged = 2;    // below its queue's DELETION or PURGE
+constexpr uint8_t kJselDead = 3;      // eligible, its queue is not live: a failure unless claimed
+constexpr uint8_t kJselDeleted = 4;   // claimed by a DELETION of its GUID (k_jsel_resolve)
+
+struct JselArgs {
+    const uint32_t* journal;       // device, 4-byte aligned: n_records records of 15 dwords
+    uint64_t n_records;
+    uint64_t data_file_bytes;
+    const uint8_t* queue_keys;     // device, 5 n_queue_keys (with_csl only)
+    uint64_t n_queue_keys;
+    uint64_t queue_cap;
+    uint8_t* select;               // device, n_records, out
+    uint32_t with_csl;
+    // workspace, zeroed before the launch
+    unsigned long long* ctr;       // kJselCtrWords
+    unsigned long long* qkey;      // qslots: 1 << 63 | the 40-bit key, 0: empty
+    uint32_t* qdel;                // qslots: record + 1 of the key's highest queue DELETION
+    uint32_t* qtop;                // qslots: ... of its highest CREATION above that
+    uint32_t* qpurge;              // qslots: ... of its highest whole-queue PURGE above that, when live
+    uint32_t* qcsl;                // qslots: 1: the key is one of queue_keys
+    uint32_t* gslot;               // gslots: record + 1 of an eligible DELETION, hashed by its GUID
+    uint32_t* claim;               // n_records: at a DELETION, record + 1 of the highest MESSAGE naming it
+    // workspace, written before it is read
+    uint32_t* qlist;               // n_records: the QueueOp records, in no order
+    uint32_t* slist;               // n_records: the JOURNAL_OP records, in no order
+    uint32_t* names;               // n_records: at an eligible MESSAGE, record + 1 of the DELETION it names
+    uint8_t* state;                // n_records: kJsel*
+    uint64_t qslots;               // powers of two
+    uint64_t gslots;
+    uint64_t per_block;            // records per block (multiple of kPackThreads)
+    uint32_t nblocks;              // blocks (<= kPackBlocks)
+};
+
 }  // namespace bmqcrc
+
+// Launcher (crc32c_journal_select.hip): the six kernels, asynchronous on `stream`.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_journal_select(const bmqcrc::JselArgs* a, void* stream);
 
 // Launchers (crc32c_records_unpack.hip).  Asynchronous on `stream`: the walk
 // fills ws_off / ws_len for the fold (bmqcrc_launch_batch), the publish runs

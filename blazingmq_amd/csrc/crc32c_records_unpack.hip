@@ -13,10 +13,8 @@
 //
 //   1. k_recunp_classify: the grid is nblocks x kPackThreads and block b owns
 //      the contiguous records [b per_block, (b + 1) per_block), one record per
-//      thread and step.  A wave brings its 64 records into LDS with 15
-//      coalesced dword loads per lane and every lane reads its own record from
-//      there at a 15-dword stride (15 is odd: the lanes' dwords fall into
-//      different banks).  The record is checked in the host walk's order --
+//      thread and step, staged through LDS a wave's 64 records at a time
+//      (crc32c_journal_stage.h).  The record is checked in the host walk's order --
 //      RecordHeader, then for a MESSAGE record GUID and queue key, the data
 //      offset, and, when selected, the DATA record -- and the first violation
 //      raises the call's refusal word (crc32c_pack_layout.h).  It leaves
@@ -45,6 +43,7 @@
 #include <stdint.h>
 
 #include "bmqcrc_internal.h"
+#include "crc32c_journal_stage.h"
 #include "crc32c_pack_layout.h"
 
 namespace bmqcrc {
@@ -53,30 +52,7 @@ namespace {
 // byte-aligned dword: a GUID or queue-key array need not be 4-byte aligned
 typedef uint32_t u32u __attribute__((aligned(1)));
 
-constexpr uint32_t kWaves = kPackThreads / 64;
-constexpr uint32_t kWaveDwords = 64 * kJournalRecordDwords;  // a wave's 64 records: 3,840 bytes
-constexpr uint32_t kRecMessage = 1;                          // RecordType::e_MESSAGE
-constexpr uint32_t kMagicLE = 0x6345722Au;                   // bytes 2A 72 45 63 loaded as a dword
-
-// Records [r0, r0 + 64) below `hi` into the wave's kWaveDwords of LDS: lane l
-// loads dwords l, l + 64, ... of the wave's run, all in flight together.
-__device__ __forceinline__ void stage(const uint32_t* journal, uint64_t r0, uint64_t hi,
-                                      uint32_t* mine, uint32_t lane)
-{
-    const uint32_t cnt = r0 < hi ? (uint32_t)min(hi - r0, (uint64_t)64) : 0u;
-    const uint32_t ndw = cnt * kJournalRecordDwords;
-    const uint32_t* g = journal + kJournalRecordDwords * r0;
-    uint32_t v[kJournalRecordDwords];
-#pragma unroll
-    for (uint32_t j = 0; j < kJournalRecordDwords; ++j) {
-        const uint32_t i = 64u * j + lane;
-        v[j] = i < ndw ? g[i] : 0u;
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < kJournalRecordDwords; ++j) {
-        mine[64u * j + lane] = v[j];
-    }
-}
+constexpr uint32_t kRecMessage = 1;  // RecordType::e_MESSAGE
 
 // Step 1.
 __global__ __launch_bounds__(kPackThreads) void k_recunp_classify(RecUnpackArgs a)

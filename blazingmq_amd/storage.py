@@ -727,3 +727,93 @@ def last_records_unpack(device, stream=None):
     N.check(N.lib.bmqcrc_last_records_unpack(
         device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
     return r.as_dict()
+
+
+# ----------------------------------------------------------------------------
+# Device-side selection: which MESSAGE records recovery CRCs.
+# ----------------------------------------------------------------------------
+def select_records(journal, *, data_file_bytes, with_csl=False, queue_keys=(), queue_cap=1 << 16,
+                   stream=None, sync=True):
+    """The MESSAGE records ``FileStore::recoverMessages`` CRCs, decided on the
+    GPU from a device-resident run of journal records
+    (``bmqcrc_journal_select``): what ``scan_partition`` decides on the host,
+    as the ``select`` bytes ``unpack_records`` takes, so that ``unpack_events
+    -> pack_records -> select_records -> unpack_records(verify=True)`` recovers
+    a partition that lies in HBM with no per-record work on the host.
+
+    ``journal`` is a contiguous uint8 device tensor (4-byte aligned) of whole
+    60-byte records: the record run up to the journal's last valid record
+    (``journal_bounds`` gives it for a file), not the file with its headers.
+    ``data_file_bytes`` is the size of the DATA file; no DATA byte is read, so
+    a selected message with a malformed DATA record stays selected and
+    ``unpack_records`` refuses it (where the host walk says
+    RC_INVALID_DATA_RECORD).  With ``with_csl`` the live queues are
+    ``queue_keys``: a sequence of 5-byte keys, which is uploaded, or a uint8
+    device tensor of 5 bytes per key.  ``queue_cap`` bounds the distinct queue
+    keys (QueueOp records' and ``queue_keys``') the call holds.
+
+    Returns ``select``, a uint8 tensor on the journal's device with one byte
+    per record; with ``sync=True`` ``(select, result)``, ``result`` being the
+    dict of ``last_journal_select``.  A non-zero
+    ``recovery_rc`` is a result: the records above ``error_record`` are still
+    selected, as the reference had CRC'd them.  More distinct keys than
+    ``queue_cap`` raises ``BmqCrcError`` (BMQCRC_EINVAL) with ``sync=True``.
+    Not meant to be captured into a graph."""
+    import torch
+    if not (isinstance(journal, torch.Tensor) and journal.dtype == torch.uint8 and
+            journal.is_contiguous()):
+        raise TypeError("journal must be a contiguous %s tensor" % torch.uint8)
+    dev = journal.device
+    if not journal.is_cuda:
+        raise TypeError("select_records takes device tensors only (journal is on %s)" % dev)
+    if journal.numel() % JOURNAL_RECORD_SIZE:
+        raise ValueError("journal must hold whole 60-byte records")
+    if isinstance(queue_keys, torch.Tensor):
+        if not (queue_keys.dtype == torch.uint8 and queue_keys.is_contiguous() and
+                queue_keys.device == dev and queue_keys.numel() % 5 == 0):
+            raise TypeError("queue_keys must be a contiguous %s tensor of 5 bytes per key on %s"
+                            % (torch.uint8, dev))
+        keys = queue_keys
+    else:
+        raw = b"".join(bytes(k) for k in queue_keys)
+        if len(raw) != 5 * len(queue_keys):
+            raise ValueError("queue keys are 5 bytes each")
+        keys = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev) if raw else None
+    n_records = journal.numel() // JOURNAL_RECORD_SIZE
+    select = torch.empty(n_records, dtype=torch.uint8, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    # (an empty tensor has no address: the call wants one for the required arrays)
+    spare = torch.empty(8, dtype=torch.uint8, device=dev)
+    p = N.JournalSelect()
+    p.struct_size = ctypes.sizeof(N.JournalSelect)
+    p.journal, p.journal_bytes = journal.data_ptr() or spare.data_ptr(), journal.numel()
+    p.n_records, p.data_file_bytes = n_records, int(data_file_bytes)
+    p.with_csl = 1 if with_csl else 0
+    if keys is not None and keys.numel():
+        p.queue_keys, p.n_queue_keys = keys.data_ptr(), keys.numel() // 5
+    p.queue_cap = int(queue_cap)
+    p.select = select.data_ptr() or spare.data_ptr()
+    o = N.make_opts(device=dev.index if dev.index is not None else -1, stream=stream.cuda_stream,
+                    flags=N.BMQCRC_F_DEVICE_PTRS | (0 if sync else N.BMQCRC_F_ASYNC))
+    r = N.JournalSelectResult()
+    N.check(N.lib.bmqcrc_journal_select(ctypes.byref(p), ctypes.byref(r), ctypes.byref(o)))
+    return (select, r.as_dict()) if sync else select
+
+
+def last_journal_select(device, stream=None):
+    """The result of the previous ``select_records`` on (device, stream)
+    (bmqcrc_last_journal_select), as a dict; waits for it.  ``n_records``;
+    ``first_record`` (``select`` is meaningful from there on and 0 below: the
+    record above the walk's lower end or above the failing record;
+    ``n_records`` when nothing is selected); ``n_selected``, ``n_deleted`` and
+    ``n_purged`` (MESSAGE records of that run kept, skipped by a DELETION of
+    their GUID, skipped by their queue's PURGE or DELETION); ``recovery_rc``
+    (0 or a ``RC_*`` code) and ``error_record`` (the offending record's index,
+    ``n_records`` when none); ``refused_kind`` (0 or
+    ``BMQCRC_JSEL_TOO_MANY_QUEUES``).  ``stream=None`` is the device's default
+    stream."""
+    r = N.JournalSelectResult()
+    N.check(N.lib.bmqcrc_last_journal_select(
+        device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
+    return r.as_dict()

@@ -77,6 +77,27 @@ def partition(n, app_len, seed=11, lease_id=1, timestamp=0x6720EAB4,
     return journal, data, app_off, app_lens
 
 
+def append_deletions(journal, every=2):
+    """`journal` of ``partition`` with a DELETION record appended for every
+    `every`-th message (the first, the one after `every`, ...), in the
+    messages' order, continuing the sequence numbers: a queue in steady state,
+    where most of what was written has been consumed (DeletionRecord :1518)."""
+    start = S.PartitionWriter.JOURNAL_HEADER
+    recs = journal[start:].reshape(-1, S.JOURNAL_RECORD_SIZE)
+    msgs = recs[1::every]          # record 0 is the queue's CREATION
+    n = recs.shape[0]
+    seq = 1 + n + np.arange(msgs.shape[0], dtype=np.uint64)
+    d = np.zeros((msgs.shape[0], S.JOURNAL_RECORD_SIZE), np.uint8)
+    d[:, 0:2] = _be(S.REC_DELETION << 12, ">u2")
+    d[:, 2:4] = _be(seq >> 32, ">u2")
+    d[:, 4:8] = _be(seq & 0xFFFFFFFF, ">u4")
+    d[:, 8:20] = msgs[:, 8:20]     # lease id, timestamp
+    d[:, 23:28] = msgs[:, 22:27]   # queue key
+    d[:, 28:44] = msgs[:, 36:52]   # GUID
+    d[:, 56:60] = _be(S.RECORD_MAGIC, ">u4")
+    return np.concatenate([journal, d.reshape(-1)])
+
+
 def put_event(m, app_len, seed=12):
     """(event, app_offsets, app_lengths) for one PUT event of m messages whose
     application data are `app_len` random bytes, CRC fields pending (zero),

@@ -415,7 +415,8 @@ int bmqcrc_last_put_unpack(int device, void* stream, bmqcrc_put_unpack_result* r
  *   (lease id, sequence number) ordering checks, queue liveness
  *   (BMQCRC_RECOVERY_INVALID_QUEUE_KEY), the selection itself (DELETION and
  *   PURGE bookkeeping: `select` carries its outcome), and the journal bounds
- *   (the caller passes a bounded run).
+ *   (the caller passes a bounded run).  bmqcrc_journal_select (ABI 2.14,
+ *   below) makes the first three on the device and yields `select`.
  * CRC pass.  With out != NULL the application data of every message is CRC'd
  *   (seed 0) by the batch kernels, planned, on the call's own stream; n_bad
  *   and first_bad count the slots whose out[k] differs from expected[k].
@@ -556,6 +557,89 @@ int bmqcrc_recover_verify(const void* journal, uint64_t jlen, const void* data, 
                           const bmqcrc_recovery_cfg* cfg, int* recovery_rc,
                           uint64_t* error_record_off, uint64_t* n_msgs, uint64_t* n_bad,
                           uint64_t* bad_record_off, uint64_t bad_cap, const bmqcrc_opts* opts);
+
+/* ABI 2.14.  The selection of bmqcrc_journal_scan for a run of journal records
+ * that lies in HBM: which MESSAGE records FileStore::recoverMessages CRCs, as
+ * the `select` bytes bmqcrc_message_records_unpack takes, with the reference's
+ * result code and the offending record -- the two backward passes of
+ * walk_recovery restated as order-free reductions, so
+ * no record is walked on the host.  Device pointers only, one device:
+ * BMQCRC_F_DEVICE_PTRS is required and BMQCRC_F_ASYNC allowed; every other
+ * flag, unknown flag bits, ndevices > 1, a wrong struct_size, a non-zero
+ * reserved field, a null journal or select, a null queue_keys with
+ * n_queue_keys > 0, a misaligned journal, journal_bytes != 60 n_records,
+ * n_records >= 2^32 and queue_cap == 0 are BMQCRC_EINVAL before the device
+ * lookup.  n_records == 0 succeeds with an empty result.
+ * The run.  Record r is journal[60 r .. 60 r + 60); the host calls name a
+ *   record by its file offset, first record's offset + 60 r.  The caller bounds
+ *   the top: the last record is the journal's last valid record, as
+ *   bmqcrc_journal_bounds gives it for a file (bmqcrc_message_records_pack and
+ *   a replica know their count).  The walk covers the records above the
+ *   highest one with type 0, lease id 0, sequence number 0 or a wrong magic;
+ *   that record and those below it are not in the journal: select = 0 there
+ *   and no failure.
+ * What is decided.  The same recovery_rc, offending record and selected set as
+ *   bmqcrc_journal_scan, given the same with_csl / queue_keys, with ONE stated
+ *   exception: no DATA byte is read (data_file_bytes only bounds the two
+ *   DATA-offset checks: a MESSAGE record's 8 x MessageOffsetDwords being 0 or
+ *   above the file, and a sync point's data offset).  So
+ *   BMQCRC_RECOVERY_INVALID_DATA_RECORD (-17) is never raised here: a selected
+ *   message whose DATA record is malformed stays selected, and
+ *   bmqcrc_message_records_unpack then refuses it under
+ *   BMQCRC_REC_UNPACK_DATA_RECORD.  The INVALID_QUEUE_KEY check of a MESSAGE
+ *   record, which the reference makes after the DATA checks, is made as if
+ *   those had passed.
+ * Result.  A first-pass failure (QueueOp records) selects nothing:
+ *   first_record == n_records.  Otherwise, with E the highest failing record
+ *   of the second pass, select[r] = 0 for r <= max(E, the walk's lower end)
+ *   and first_record is the record above that; the three counts cover
+ *   [first_record, n_records) only.  A non-zero recovery_rc is a result, not
+ *   an error: the call returns BMQCRC_OK.  More distinct queue keys (QueueOp
+ *   records' and queue_keys') than queue_cap is the refusal
+ *   BMQCRC_JSEL_TOO_MANY_QUEUES: select is all zero, first_record ==
+ *   n_records, and a synchronous call returns BMQCRC_EINVAL naming queue_cap.
+ * *result (may be NULL) is written by a synchronous call only; after an
+ *   asynchronous one bmqcrc_last_journal_select waits and reports.
+ * State.  As bmqcrc_message_records_unpack: takes the workspace mutex of
+ *   (device, stream); restores the caller's current device; allocates its own
+ *   workspace on first use and when n_records or queue_cap grows (25 to 33
+ *   bytes per record and 48 to 96 per queue key it can hold), which
+ *   bmqcrc_reserve does not cover; is not meant to be captured into a hipGraph; is deterministic.  The
+ *   shape prediction and the records of every other bmqcrc_last_* call are
+ *   never touched. */
+#define BMQCRC_JSEL_OK 0
+#define BMQCRC_JSEL_TOO_MANY_QUEUES 1   /* more distinct queue keys than queue_cap */
+
+typedef struct bmqcrc_journal_select_args {
+    uint32_t struct_size, reserved;       /* sizeof, 0 */
+    const void* journal;                  /* device, 4-byte aligned: n_records 60-byte records, the record run */
+    uint64_t journal_bytes;               /* == 60 * n_records */
+    uint64_t n_records;                   /* < 2^32 */
+    uint64_t data_file_bytes;             /* size of the DATA file: the DATA-offset checks only; no DATA byte is read */
+    int32_t with_csl, reserved2;
+    const uint8_t* queue_keys;            /* device, 5 * n_queue_keys bytes; with_csl only, may be NULL when 0 keys */
+    uint64_t n_queue_keys;
+    uint64_t queue_cap;                   /* most distinct queue keys (QueueOp records' plus queue_keys') the call holds */
+    uint8_t* select;                      /* device, n_records, out */
+} bmqcrc_journal_select_args;
+
+/* All fields zero before the first call on (device, stream). */
+typedef struct bmqcrc_journal_select_result {
+    uint64_t n_records;
+    uint64_t first_record;                /* select[] is meaningful on [first_record, n_records), 0 below */
+    uint64_t n_selected, n_deleted, n_purged;  /* MESSAGE records of that run: kept; skipped by a DELETION
+                                                  GUID; skipped by a queue PURGE or queue DELETION */
+    uint64_t error_record;                /* record index; n_records when recovery_rc == 0 */
+    int32_t recovery_rc;                  /* 0 or BMQCRC_RECOVERY_* */
+    uint32_t refused_kind;                /* BMQCRC_JSEL_* */
+} bmqcrc_journal_select_result;
+
+int bmqcrc_journal_select(const bmqcrc_journal_select_args* p, bmqcrc_journal_select_result* result,
+                          const bmqcrc_opts* opts);
+
+/* ABI 2.14.  Result of the previous bmqcrc_journal_select on (device, stream);
+ * waits for it.  `result` may be NULL. */
+int bmqcrc_last_journal_select(int device, void* stream, bmqcrc_journal_select_result* result);
 
 /* ---- cluster state ledger (mqbc_clusterstateledgerprotocol.h:76,272) ------ */
 
