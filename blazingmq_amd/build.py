@@ -5,6 +5,8 @@
 * ``oracle/lib/liboracle_crc32c.so`` -- the CPU checker (test infrastructure).
 * ``tests/cpp/bin/bmqp_selftest`` -- the C++ drop-in (bmqp::Crc32c) test
   driver (test infrastructure), linked against libbmqcrc.so.
+* ``tests/cpp/bin/device_call_refusals`` -- the device calls' refusals in front
+  of the device lookup, from C++ (test infrastructure), linked likewise.
 
 hipcc cross-compiles gfx950 code objects without a GPU present.
 """
@@ -22,7 +24,7 @@ ARCH = "gfx950"
 
 PRODUCT_SOURCES = ["crc32c_kernels.hip", "crc32c_copy.hip", "crc32c_put_pack.hip", "crc32c_records_pack.hip", "crc32c_put_unpack.hip", "crc32c_records_unpack.hip", "crc32c_journal_select.hip", "bmqcrc_host.cpp", "crc32c_cpu.cpp", "bmqp_crc32c.cpp",
                    "bmqcrc_protocol.cpp"]
-PRODUCT_DEPS = ["bmqcrc_internal.h", "crc32c_pack_layout.h", "crc32c_journal_stage.h", "crc32c_consts.h", "crc32c_diag.h", "k_plan_map_body.inc"]
+PRODUCT_DEPS = ["bmqcrc_internal.h", "crc32c_pack_layout.h", "crc32c_unpack_slots.h", "crc32c_journal_stage.h", "crc32c_consts.h", "crc32c_diag.h", "k_plan_map_body.inc"]
 
 
 def _run(cmd):
@@ -73,21 +75,33 @@ def build_product(force=False, defines=(), target_name="libbmqcrc.so"):
     if target_name != "libbmqcrc.so":
         return target
     build_selftest(target, force)
+    build_refusals(target, force)
     build_scalar_ladder(target, force)
     return target
 
 
-def build_selftest(target, force=False):
-    """tests/cpp/bin/bmqp_selftest, the C++ drop-in's test driver, linked
-    against the product library `target`."""
-    selftest = os.path.join(ROOT, "tests", "cpp", "bin", "bmqp_selftest")
-    st_src = os.path.join(ROOT, "tests", "cpp", "bmqp_crc32c_selftest.cpp")
-    if os.path.exists(st_src) and (force or _stale(selftest, [st_src, target])):
-        os.makedirs(os.path.dirname(selftest), exist_ok=True)
-        _run(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), st_src,
-              "-o", selftest, "-L" + LIB, "-lbmqcrc", "-pthread",
+def _build_cpp_test(exe, src, target, force):
+    """tests/cpp/bin/<exe> from tests/cpp/<src>, linked against the product
+    library `target`."""
+    out = os.path.join(ROOT, "tests", "cpp", "bin", exe)
+    src = os.path.join(ROOT, "tests", "cpp", src)
+    if os.path.exists(src) and (force or _stale(out, [src, target])):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), src,
+              "-o", out, "-L" + LIB, "-lbmqcrc", "-pthread",
               "-Wl,-rpath,$ORIGIN/../../../blazingmq_amd/lib"])
-    return selftest
+    return out
+
+
+def build_selftest(target, force=False):
+    """tests/cpp/bin/bmqp_selftest, the C++ drop-in's test driver."""
+    return _build_cpp_test("bmqp_selftest", "bmqp_crc32c_selftest.cpp", target, force)
+
+
+def build_refusals(target, force=False):
+    """tests/cpp/bin/device_call_refusals: the device calls' refusals in front
+    of the device lookup, from C++."""
+    return _build_cpp_test("device_call_refusals", "device_call_refusals.cpp", target, force)
 
 
 def build_scalar_ladder(target, force=False):

@@ -123,6 +123,27 @@ struct PackScratch {
     }
 };
 
+// Scratch of one device unpacker (bmqcrc_put_event_unpack,
+// bmqcrc_message_records_unpack): per slot the descriptor its fold reads
+// (offset 8, length 4), the stored and the computed CRC (4 each); the
+// kSlotCtrWords counters; the events or records of the last unpack enqueued
+// (bmqcrc_last_*).
+struct UnpackScratch {
+    DevBuf off, len, exp, out, ctr;
+    uint64_t n = 0;
+    bool any = false;
+    int ensure(uint64_t msg_cap, bool need_out)
+    {
+        const uint64_t slots = std::max<uint64_t>(msg_cap, 1);
+        int rc;
+        if ((rc = ctr.ensure(8 * kSlotCtrWords)) || (rc = off.ensure(8 * slots)) ||
+            (rc = len.ensure(4 * slots)) || (rc = exp.ensure(4 * slots))) {
+            return rc;
+        }
+        return need_out ? out.ensure(4 * slots) : 0;
+    }
+};
+
 // Planner + staging scratch for one (device, stream).
 struct Workspace {
     std::mutex mu;
@@ -159,22 +180,14 @@ struct Workspace {
     // independently; the events of the last PUT pack
     PackScratch pack, rec;
     uint64_t pack_events = 0;
-    // bmqcrc_put_event_unpack: the descriptors its fold reads (offset 8,
-    // length 4), the header and the computed CRCs (4 each) per slot; the
-    // counts / their prefix and the refusal offset (8 each) per event; the
-    // counters; the events of the last unpack enqueued (bmqcrc_last_put_unpack)
-    DevBuf unp_off, unp_len, unp_exp, unp_out, unp_first, unp_bad, unp_ctr;
-    uint64_t unp_events = 0;
-    bool unp_any = false;
-    // bmqcrc_message_records_unpack: the same four per slot; per record the
-    // message flag with the block-local prefix (4), the application data's
-    // offset (8), length (4) and DataHeader flags (1); the block sums; the
-    // counters; the records of the last unpack enqueued
-    // (bmqcrc_last_records_unpack)
-    DevBuf runp_off, runp_len, runp_exp, runp_out, runp_pre, runp_roff, runp_rlen, runp_rflags,
-        runp_bsum, runp_ctr;
-    uint64_t runp_records = 0;
-    bool runp_any = false;
+    // bmqcrc_put_event_unpack and bmqcrc_message_records_unpack: a set each,
+    // like the packers'.  Beside it the PUT unpack keeps per event the counts /
+    // their prefix and the refusal offset (8 each); the records unpack per
+    // record the message flag with the block-local prefix (4), the application
+    // data's offset (8), length (4) and DataHeader flags (1), and the block sums
+    UnpackScratch unp, runp;
+    DevBuf unp_first, unp_bad;
+    DevBuf runp_pre, runp_roff, runp_rlen, runp_rflags, runp_bsum;
     // bmqcrc_journal_select: the part of its workspace every call zeroes (the
     // counters, the queue-key and GUID tables, the claims) and the rest (the
     // two record lists, the named DELETIONs, the states); the records of the
@@ -2004,6 +2017,105 @@ int pack_counters(Ctx& c, const PackScratch& s, int ctr_words, const char* call,
     return 0;
 }
 
+// The struct_size / reserved preamble of a call that takes its arguments in a
+// struct P, `name`d in the texts.  Answers before the options are read.
+template <class P>
+int check_struct(const P* p, const char* name, uint64_t reserved2 = 0,
+                 const char* reserved_text = ".reserved must be 0")
+{
+    if (!p || p->struct_size != sizeof(P)) {
+        return fail(BMQCRC_EINVAL,
+                    std::string(name) + ".struct_size must be sizeof(" + name + ")");
+    }
+    return p->reserved || reserved2 ? fail(BMQCRC_EINVAL, std::string(name) + reserved_text) : 0;
+}
+
+// The first of `outs` (null ones skipped) that shares a byte with one of `ins`.
+struct NamedRange {
+    const void* at;
+    uint64_t bytes;
+    const char* name;
+};
+
+int refuse_overlap(std::initializer_list<NamedRange> outs, std::initializer_list<NamedRange> ins)
+{
+    for (const NamedRange& a : outs) {
+        for (const NamedRange& b : ins) {
+            if (a.at && overlaps((uintptr_t)a.at, a.bytes, (uintptr_t)b.at, b.bytes)) {
+                return fail(BMQCRC_EINVAL, std::string(a.name) + " overlaps " + b.name);
+            }
+        }
+    }
+    return 0;
+}
+
+// The fold of an unpacker over its scratch's descriptors, which the placing
+// kernel filled for every slot: never over the caller's arrays.
+int fold_slots(Ctx& c, const UnpackScratch& s, const void* window, uint64_t window_bytes,
+               uint64_t cap)
+{
+    return run_batch(c, BMQCRC_F_DEVICE_PTRS | BMQCRC_F_PLAN, 0, window, window_bytes,
+                     (const uint64_t*)s.off.p, (const uint32_t*)s.len.p, nullptr,
+                     (uint32_t*)s.out.p, cap);
+}
+
+// Counters of the unpack last enqueued on `s`, after everything enqueued on
+// c's stream (w->mu held), into ctr[] and what both results (R) share: the
+// refusal (its index to *index), otherwise the messages, the mismatches and
+// the lowest of them.  All zeros when there was none.
+template <class R>
+int slot_counters(Ctx& c, const UnpackScratch& s, unsigned long long (&ctr)[kSlotCtrWords], R* r,
+                  uint64_t* index)
+{
+    memset(r, 0, sizeof(*r));
+    memset(ctr, 0, sizeof(ctr));
+    if (!s.any) {
+        return 0;
+    }
+    HIP_TRY(hipMemcpyAsync(ctr, s.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    if (ctr[kSlotCtrRefusal]) {
+        refusal_of(ctr[kSlotCtrRefusal], &r->refused_kind, index);
+        return 0;
+    }
+    r->n_msgs = ctr[kSlotCtrMsgs];
+    r->n_bad = ctr[kSlotCtrBad];
+    r->first_bad = r->n_bad ? ~ctr[kSlotCtrFirstBad] : r->n_msgs;
+    return 0;
+}
+
+// The end of a device call: unless asynchronous, the result `read` gives for
+// c's workspace, copied out when the caller wants it.  *r is zeros, no
+// refusal, after an asynchronous call.
+template <class R, class Read>
+int sync_result(Ctx& c, const bmqcrc_opts& o, Read read, R* result, R* r)
+{
+    memset(r, 0, sizeof(*r));
+    int rc = 0;
+    if (!(o.flags & BMQCRC_F_ASYNC) && !(rc = read(c, r)) && result) {
+        *result = *r;
+    }
+    return rc;
+}
+
+// The body of a bmqcrc_last_*: the result `read` gives for the stream's workspace.
+template <class R, class Read>
+int last_result(int device, void* stream, Read read, R* result)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    LockedCtx c;
+    int rc;
+    R r;
+    if ((rc = lock_on(device, stream, true, &c)) || (rc = read(c, &r))) {
+        return rc;
+    }
+    if (result) {
+        *result = r;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2135,15 +2247,10 @@ int bmqcrc_put_event_pack(const bmqcrc_put_pack* p, uint64_t* total_bytes, const
     t_err.clear();
     DeviceGuard keep_device;
     // every refusal below answers before the device lookup (no GPU needed)
-    if (!p || p->struct_size != sizeof(bmqcrc_put_pack)) {
-        return fail(BMQCRC_EINVAL, "bmqcrc_put_pack.struct_size must be sizeof(bmqcrc_put_pack)");
-    }
-    if (p->reserved) {
-        return fail(BMQCRC_EINVAL, "bmqcrc_put_pack.reserved must be 0");
-    }
     bmqcrc_opts o;
     int rc;
-    if ((rc = device_call_opts(opts, "bmqcrc_put_event_pack", &o))) {
+    if ((rc = check_struct(p, "bmqcrc_put_pack")) ||
+        (rc = device_call_opts(opts, "bmqcrc_put_event_pack", &o))) {
         return rc;
     }
     const uint64_t n = p->n;
@@ -2314,16 +2421,10 @@ int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_res
     t_err.clear();
     DeviceGuard keep_device;
     // every refusal below answers before the device lookup (no GPU needed)
-    if (!p || p->struct_size != sizeof(bmqcrc_records_pack)) {
-        return fail(BMQCRC_EINVAL,
-                    "bmqcrc_records_pack.struct_size must be sizeof(bmqcrc_records_pack)");
-    }
-    if (p->reserved) {
-        return fail(BMQCRC_EINVAL, "bmqcrc_records_pack.reserved must be 0");
-    }
     bmqcrc_opts o;
     int rc;
-    if ((rc = device_call_opts(opts, "bmqcrc_message_records_pack", &o))) {
+    if ((rc = check_struct(p, "bmqcrc_records_pack")) ||
+        (rc = device_call_opts(opts, "bmqcrc_message_records_pack", &o))) {
         return rc;
     }
     const uint64_t n = p->n;
@@ -2427,33 +2528,16 @@ int bmqcrc_message_records_pack(const bmqcrc_records_pack* p, bmqcrc_records_res
     }
     w->rec.n = n;
     w->rec.any = true;
-    if (o.flags & BMQCRC_F_ASYNC) {
-        return 0;
-    }
     bmqcrc_records_result r;
-    if ((rc = records_result(c, &r))) {
+    if ((rc = sync_result(c, o, records_result, result, &r))) {
         return rc;
-    }
-    if (result) {
-        *result = r;
     }
     return r.refused_kind ? refused(kRecordsRefusals, r.refused_kind, r.refused_index) : 0;
 }
 
 int bmqcrc_last_records_pack(int device, void* stream, bmqcrc_records_result* result)
 {
-    t_err.clear();
-    DeviceGuard keep_device;
-    LockedCtx c;
-    int rc;
-    bmqcrc_records_result r;
-    if ((rc = lock_on(device, stream, true, &c)) || (rc = records_result(c, &r))) {
-        return rc;
-    }
-    if (result) {
-        *result = r;
-    }
-    return 0;
+    return last_result(device, stream, records_result, result);
 }
 
 static_assert(BMQCRC_PUT_UNPACK_EVENT_OFFSETS == BMQCRC_UNPACK_KIND_EVENT_OFFSETS &&
@@ -2467,23 +2551,13 @@ static_assert(BMQCRC_PUT_UNPACK_EVENT_OFFSETS == BMQCRC_UNPACK_KIND_EVENT_OFFSET
 // enqueued on its stream (w->mu held); zeros when there was none.
 static int unpack_result(Ctx& c, bmqcrc_put_unpack_result* r)
 {
-    memset(r, 0, sizeof(*r));
-    if (!c.w->unp_any) {
-        return 0;
+    unsigned long long ctr[kSlotCtrWords];
+    const int rc = slot_counters(c, c.w->unp, ctr, r, &r->refused_event);
+    if (!rc) {
+        r->n_events = c.w->unp.n;
+        r->refused_offset = r->refused_kind ? ctr[kUnpCtrOffset] : 0;
     }
-    unsigned long long ctr[kUnpCtrWords];
-    HIP_TRY(hipMemcpyAsync(ctr, c.w->unp_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
-    HIP_TRY(hipStreamSynchronize(c.s));
-    r->n_events = c.w->unp_events;
-    if (ctr[kUnpCtrRefusal]) {
-        refusal_of(ctr[kUnpCtrRefusal], &r->refused_kind, &r->refused_event);
-        r->refused_offset = ctr[kUnpCtrOffset];
-        return 0;
-    }
-    r->n_msgs = ctr[kUnpCtrMsgs];
-    r->n_bad = ctr[kUnpCtrBad];
-    r->first_bad = r->n_bad ? ~ctr[kUnpCtrFirstBad] : r->n_msgs;
-    return 0;
+    return rc;
 }
 
 static const char* const kUnpackRefusals[6] = {
@@ -2502,16 +2576,10 @@ int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result
     t_err.clear();
     DeviceGuard keep_device;
     // every refusal below answers before the device lookup (no GPU needed)
-    if (!p || p->struct_size != sizeof(bmqcrc_put_unpack)) {
-        return fail(BMQCRC_EINVAL,
-                    "bmqcrc_put_unpack.struct_size must be sizeof(bmqcrc_put_unpack)");
-    }
-    if (p->reserved) {
-        return fail(BMQCRC_EINVAL, "bmqcrc_put_unpack.reserved must be 0");
-    }
     bmqcrc_opts o;
     int rc;
-    if ((rc = device_call_opts(opts, "bmqcrc_put_event_unpack", &o))) {
+    if ((rc = check_struct(p, "bmqcrc_put_unpack")) ||
+        (rc = device_call_opts(opts, "bmqcrc_put_event_unpack", &o))) {
         return rc;
     }
     if ((rc = refuse_null({{!p->events, "events"},
@@ -2528,43 +2596,32 @@ int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result
     if (p->n_events > 0xFFFFFFFFull || p->msg_cap > 0xFFFFFFFFull) {
         return fail(BMQCRC_EINVAL, "n_events and msg_cap must be below 2^32");
     }
-    {
-        const uint64_t cap = p->msg_cap;
-        const struct {
-            const void* at;
-            uint64_t bytes;
-            const char* name;
-        } outs[] = {{p->app_offsets, 8 * cap, "app_offsets"},
-                    {p->lengths, 4 * cap, "lengths"},
-                    {p->queue_ids, 4 * cap, "queue_ids"},
-                    {p->guids, 16 * cap, "guids"},
-                    {p->flags, cap, "flags"},
-                    {p->expected, 4 * cap, "expected"},
-                    {p->out, 4 * cap, "out"},
-                    {p->event_first, 8 * (p->n_events + 1), "event_first"}};
-        for (const auto& a : outs) {
-            if (a.at && overlaps((uintptr_t)a.at, a.bytes, (uintptr_t)p->events, p->events_bytes)) {
-                return fail(BMQCRC_EINVAL,
-                            std::string(a.name) + " overlaps [events, events+events_bytes)");
-            }
-        }
+    const uint64_t cap = p->msg_cap;
+    if ((rc = refuse_overlap({{p->app_offsets, 8 * cap, "app_offsets"},
+                              {p->lengths, 4 * cap, "lengths"},
+                              {p->queue_ids, 4 * cap, "queue_ids"},
+                              {p->guids, 16 * cap, "guids"},
+                              {p->flags, cap, "flags"},
+                              {p->expected, 4 * cap, "expected"},
+                              {p->out, 4 * cap, "out"},
+                              {p->event_first, 8 * (p->n_events + 1), "event_first"}},
+                             {{p->events, p->events_bytes, "[events, events+events_bytes)"}}))) {
+        return rc;
     }
     LockedCtx c;
     if ((rc = lock_on(o.device, o.stream, true, &c))) {
         return rc;
     }
     Workspace* w = c.w;
-    const uint64_t cap = p->msg_cap, slots = std::max<uint64_t>(cap, 1);
-    if ((rc = w->unp_ctr.ensure(8 * kUnpCtrWords)) || (rc = w->unp_off.ensure(8 * slots)) ||
-        (rc = w->unp_len.ensure(4 * slots)) || (rc = w->unp_exp.ensure(4 * slots)) ||
-        (p->out && (rc = w->unp_out.ensure(4 * slots))) ||
+    UnpackScratch& s = w->unp;
+    if ((rc = s.ensure(cap, p->out != nullptr)) ||
         (rc = w->unp_first.ensure(8 * (p->n_events + 1))) ||
         (rc = w->unp_bad.ensure(8 * std::max<uint64_t>(p->n_events, 1)))) {
         return rc;
     }
-    HIP_TRY(hipMemsetAsync(w->unp_ctr.p, 0, 8 * kUnpCtrWords, c.s));
-    w->unp_events = p->n_events;
-    w->unp_any = true;
+    HIP_TRY(hipMemsetAsync(s.ctr.p, 0, 8 * kSlotCtrWords, c.s));
+    s.n = p->n_events;
+    s.any = true;
     if (p->n_events) {
         UnpackArgs a;
         memset(&a, 0, sizeof(a));
@@ -2581,37 +2638,26 @@ int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result
         a.expected = p->expected;
         a.out = p->out;
         a.event_first = p->event_first;
-        a.ws_off = (unsigned long long*)w->unp_off.p;
-        a.ws_len = (uint32_t*)w->unp_len.p;
-        a.ws_exp = (uint32_t*)w->unp_exp.p;
-        a.ws_out = (const uint32_t*)w->unp_out.p;
+        a.ws_off = (unsigned long long*)s.off.p;
+        a.ws_len = (uint32_t*)s.len.p;
+        a.ws_exp = (uint32_t*)s.exp.p;
+        a.ws_out = (const uint32_t*)s.out.p;
         a.first = (unsigned long long*)w->unp_first.p;
         a.bad_off = (unsigned long long*)w->unp_bad.p;
-        a.ctr = (unsigned long long*)w->unp_ctr.p;
+        a.ctr = (unsigned long long*)s.ctr.p;
         if (bmqcrc_launch_unpack_walk(&a, (void*)c.s)) {
             return launch_failed("put-unpack walk");
         }
-        // the fold over the workspace's descriptors, which the placing kernel
-        // filled for every slot: never over the caller's arrays
-        if (p->out && (rc = run_batch(c, BMQCRC_F_DEVICE_PTRS | BMQCRC_F_PLAN, 0, p->events,
-                                      p->events_bytes, (const uint64_t*)w->unp_off.p,
-                                      (const uint32_t*)w->unp_len.p, nullptr,
-                                      (uint32_t*)w->unp_out.p, cap))) {
+        if (p->out && (rc = fold_slots(c, s, p->events, p->events_bytes, cap))) {
             return rc;
         }
         if (bmqcrc_launch_unpack_publish(&a, (void*)c.s)) {
             return launch_failed("put-unpack publish");
         }
     }
-    if (o.flags & BMQCRC_F_ASYNC) {
-        return 0;
-    }
     bmqcrc_put_unpack_result r;
-    if ((rc = unpack_result(c, &r))) {
+    if ((rc = sync_result(c, o, unpack_result, result, &r))) {
         return rc;
-    }
-    if (result) {
-        *result = r;
     }
     return r.refused_kind
                ? refused(kUnpackRefusals, r.refused_kind, r.refused_event, r.refused_offset)
@@ -2620,18 +2666,7 @@ int bmqcrc_put_event_unpack(const bmqcrc_put_unpack* p, bmqcrc_put_unpack_result
 
 int bmqcrc_last_put_unpack(int device, void* stream, bmqcrc_put_unpack_result* result)
 {
-    t_err.clear();
-    DeviceGuard keep_device;
-    LockedCtx c;
-    int rc;
-    bmqcrc_put_unpack_result r;
-    if ((rc = lock_on(device, stream, true, &c)) || (rc = unpack_result(c, &r))) {
-        return rc;
-    }
-    if (result) {
-        *result = r;
-    }
-    return 0;
+    return last_result(device, stream, unpack_result, result);
 }
 
 static_assert(BMQCRC_REC_UNPACK_RECORD_HEADER == BMQCRC_RECUNP_KIND_RECORD_HEADER &&
@@ -2646,23 +2681,13 @@ static_assert(kJournalRecordBytes == 4 * kJournalRecordDwords, "a journal record
 // everything enqueued on its stream (w->mu held); zeros when there was none.
 static int records_unpack_result(Ctx& c, bmqcrc_records_unpack_result* r)
 {
-    memset(r, 0, sizeof(*r));
-    if (!c.w->runp_any) {
-        return 0;
+    unsigned long long ctr[kSlotCtrWords];
+    const int rc = slot_counters(c, c.w->runp, ctr, r, &r->refused_index);
+    if (!rc) {
+        r->n_records = c.w->runp.n;
+        r->n_skipped = r->refused_kind ? 0 : ctr[kRecUnpCtrSkipped];
     }
-    unsigned long long ctr[kRecUnpCtrWords];
-    HIP_TRY(hipMemcpyAsync(ctr, c.w->runp_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
-    HIP_TRY(hipStreamSynchronize(c.s));
-    r->n_records = c.w->runp_records;
-    if (ctr[kRecUnpCtrRefusal]) {
-        refusal_of(ctr[kRecUnpCtrRefusal], &r->refused_kind, &r->refused_index);
-        return 0;
-    }
-    r->n_msgs = ctr[kRecUnpCtrMsgs];
-    r->n_skipped = ctr[kRecUnpCtrSkipped];
-    r->n_bad = ctr[kRecUnpCtrBad];
-    r->first_bad = r->n_bad ? ~ctr[kRecUnpCtrFirstBad] : r->n_msgs;
-    return 0;
+    return rc;
 }
 
 static const char* const kRecordsUnpackRefusals[6] = {
@@ -2680,16 +2705,10 @@ int bmqcrc_message_records_unpack(const bmqcrc_records_unpack* p,
     t_err.clear();
     DeviceGuard keep_device;
     // every refusal below answers before the device lookup (no GPU needed)
-    if (!p || p->struct_size != sizeof(bmqcrc_records_unpack)) {
-        return fail(BMQCRC_EINVAL,
-                    "bmqcrc_records_unpack.struct_size must be sizeof(bmqcrc_records_unpack)");
-    }
-    if (p->reserved) {
-        return fail(BMQCRC_EINVAL, "bmqcrc_records_unpack.reserved must be 0");
-    }
     bmqcrc_opts o;
     int rc;
-    if ((rc = device_call_opts(opts, "bmqcrc_message_records_unpack", &o))) {
+    if ((rc = check_struct(p, "bmqcrc_records_unpack")) ||
+        (rc = device_call_opts(opts, "bmqcrc_message_records_unpack", &o))) {
         return rc;
     }
     if ((rc = refuse_null({{!p->journal, "journal"},
@@ -2713,53 +2732,37 @@ int bmqcrc_message_records_unpack(const bmqcrc_records_unpack* p,
     if (kJournalRecordBytes * p->n_records > p->journal_bytes) {
         return fail(BMQCRC_EINVAL, "journal_bytes is below 60 n_records");
     }
-    {
-        const uint64_t cap = p->msg_cap;
-        const struct {
-            const void* at;
-            uint64_t bytes;
-            const char* name;
-        } outs[] = {{p->record_index, 4 * cap, "record_index"},
-                    {p->app_offsets, 8 * cap, "app_offsets"},
-                    {p->lengths, 4 * cap, "lengths"},
-                    {p->queue_keys, 5 * cap, "queue_keys"},
-                    {p->guids, 16 * cap, "guids"},
-                    {p->data_flags, cap, "data_flags"},
-                    {p->ref_counts, 4 * cap, "ref_counts"},
-                    {p->timestamps, 8 * cap, "timestamps"},
-                    {p->expected, 4 * cap, "expected"},
-                    {p->out, 4 * cap, "out"}};
-        for (const auto& a : outs) {
-            if (!a.at) {
-                continue;
-            }
-            if (overlaps((uintptr_t)a.at, a.bytes, (uintptr_t)p->journal, p->journal_bytes)) {
-                return fail(BMQCRC_EINVAL,
-                            std::string(a.name) + " overlaps [journal, journal+journal_bytes)");
-            }
-            if (overlaps((uintptr_t)a.at, a.bytes, (uintptr_t)p->data, p->data_bytes)) {
-                return fail(BMQCRC_EINVAL, std::string(a.name) + " overlaps [data, data+data_bytes)");
-            }
-        }
+    const uint64_t n = p->n_records, cap = p->msg_cap;
+    if ((rc = refuse_overlap({{p->record_index, 4 * cap, "record_index"},
+                              {p->app_offsets, 8 * cap, "app_offsets"},
+                              {p->lengths, 4 * cap, "lengths"},
+                              {p->queue_keys, 5 * cap, "queue_keys"},
+                              {p->guids, 16 * cap, "guids"},
+                              {p->data_flags, cap, "data_flags"},
+                              {p->ref_counts, 4 * cap, "ref_counts"},
+                              {p->timestamps, 8 * cap, "timestamps"},
+                              {p->expected, 4 * cap, "expected"},
+                              {p->out, 4 * cap, "out"}},
+                             {{p->journal, p->journal_bytes, "[journal, journal+journal_bytes)"},
+                              {p->data, p->data_bytes, "[data, data+data_bytes)"}}))) {
+        return rc;
     }
     LockedCtx c;
     if ((rc = lock_on(o.device, o.stream, true, &c))) {
         return rc;
     }
     Workspace* w = c.w;
-    const uint64_t n = p->n_records, cap = p->msg_cap;
-    const uint64_t slots = std::max<uint64_t>(cap, 1), recs = std::max<uint64_t>(n, 1);
-    if ((rc = w->runp_ctr.ensure(8 * kRecUnpCtrWords)) ||
-        (rc = w->runp_bsum.ensure(8ull * 2 * kPackBlocks)) || (rc = w->runp_off.ensure(8 * slots)) ||
-        (rc = w->runp_len.ensure(4 * slots)) || (rc = w->runp_exp.ensure(4 * slots)) ||
-        (p->out && (rc = w->runp_out.ensure(4 * slots))) || (rc = w->runp_pre.ensure(4 * recs)) ||
+    UnpackScratch& s = w->runp;
+    const uint64_t recs = std::max<uint64_t>(n, 1);
+    if ((rc = s.ensure(cap, p->out != nullptr)) ||
+        (rc = w->runp_bsum.ensure(8ull * 2 * kPackBlocks)) || (rc = w->runp_pre.ensure(4 * recs)) ||
         (rc = w->runp_roff.ensure(8 * recs)) || (rc = w->runp_rlen.ensure(4 * recs)) ||
         (rc = w->runp_rflags.ensure(recs))) {
         return rc;
     }
-    HIP_TRY(hipMemsetAsync(w->runp_ctr.p, 0, 8 * kRecUnpCtrWords, c.s));
-    w->runp_records = n;
-    w->runp_any = true;
+    HIP_TRY(hipMemsetAsync(s.ctr.p, 0, 8 * kSlotCtrWords, c.s));
+    s.n = n;
+    s.any = true;
     if (n) {
         RecUnpackArgs a;
         memset(&a, 0, sizeof(a));
@@ -2780,59 +2783,37 @@ int bmqcrc_message_records_unpack(const bmqcrc_records_unpack* p,
         a.timestamps = p->timestamps;
         a.expected = p->expected;
         a.out = p->out;
-        a.ws_off = (unsigned long long*)w->runp_off.p;
-        a.ws_len = (uint32_t*)w->runp_len.p;
-        a.ws_exp = (uint32_t*)w->runp_exp.p;
-        a.ws_out = (const uint32_t*)w->runp_out.p;
+        a.ws_off = (unsigned long long*)s.off.p;
+        a.ws_len = (uint32_t*)s.len.p;
+        a.ws_exp = (uint32_t*)s.exp.p;
+        a.ws_out = (const uint32_t*)s.out.p;
         a.pre = (uint32_t*)w->runp_pre.p;
         a.rec_off = (unsigned long long*)w->runp_roff.p;
         a.rec_len = (uint32_t*)w->runp_rlen.p;
         a.rec_flags = (uint8_t*)w->runp_rflags.p;
         a.bsum = (unsigned long long*)w->runp_bsum.p;
-        a.ctr = (unsigned long long*)w->runp_ctr.p;
+        a.ctr = (unsigned long long*)s.ctr.p;
         layout_split(n, &a.per_block, &a.nblocks);
         if (bmqcrc_launch_records_unpack_walk(&a, (void*)c.s)) {
             return launch_failed("records-unpack walk");
         }
-        // the fold over the workspace's descriptors, which the placing kernel
-        // filled for every slot: never over the caller's arrays
-        if (p->out && (rc = run_batch(c, BMQCRC_F_DEVICE_PTRS | BMQCRC_F_PLAN, 0, p->data,
-                                      p->data_bytes, (const uint64_t*)w->runp_off.p,
-                                      (const uint32_t*)w->runp_len.p, nullptr,
-                                      (uint32_t*)w->runp_out.p, cap))) {
+        if (p->out && (rc = fold_slots(c, s, p->data, p->data_bytes, cap))) {
             return rc;
         }
         if (bmqcrc_launch_records_unpack_publish(&a, (void*)c.s)) {
             return launch_failed("records-unpack publish");
         }
     }
-    if (o.flags & BMQCRC_F_ASYNC) {
-        return 0;
-    }
     bmqcrc_records_unpack_result r;
-    if ((rc = records_unpack_result(c, &r))) {
+    if ((rc = sync_result(c, o, records_unpack_result, result, &r))) {
         return rc;
-    }
-    if (result) {
-        *result = r;
     }
     return r.refused_kind ? refused(kRecordsUnpackRefusals, r.refused_kind, r.refused_index) : 0;
 }
 
 int bmqcrc_last_records_unpack(int device, void* stream, bmqcrc_records_unpack_result* result)
 {
-    t_err.clear();
-    DeviceGuard keep_device;
-    LockedCtx c;
-    int rc;
-    bmqcrc_records_unpack_result r;
-    if ((rc = lock_on(device, stream, true, &c)) || (rc = records_unpack_result(c, &r))) {
-        return rc;
-    }
-    if (result) {
-        *result = r;
-    }
-    return 0;
+    return last_result(device, stream, records_unpack_result, result);
 }
 
 // Result of the journal select last enqueued on c's workspace, after
@@ -2883,16 +2864,11 @@ int bmqcrc_journal_select(const bmqcrc_journal_select_args* p, bmqcrc_journal_se
     t_err.clear();
     DeviceGuard keep_device;
     // every refusal below answers before the device lookup (no GPU needed)
-    if (!p || p->struct_size != sizeof(bmqcrc_journal_select_args)) {
-        return fail(BMQCRC_EINVAL,
-                    "bmqcrc_journal_select_args.struct_size must be sizeof(bmqcrc_journal_select_args)");
-    }
-    if (p->reserved || p->reserved2) {
-        return fail(BMQCRC_EINVAL, "bmqcrc_journal_select_args.reserved and reserved2 must be 0");
-    }
     bmqcrc_opts o;
     int rc;
-    if ((rc = device_call_opts(opts, "bmqcrc_journal_select", &o))) {
+    if ((rc = check_struct(p, "bmqcrc_journal_select_args", p ? p->reserved2 : 0,
+                           ".reserved and reserved2 must be 0")) ||
+        (rc = device_call_opts(opts, "bmqcrc_journal_select", &o))) {
         return rc;
     }
     const struct {
@@ -2958,15 +2934,9 @@ int bmqcrc_journal_select(const bmqcrc_journal_select_args* p, bmqcrc_journal_se
             return launch_failed("journal-select");
         }
     }
-    if (o.flags & BMQCRC_F_ASYNC) {
-        return 0;
-    }
     bmqcrc_journal_select_result r;
-    if ((rc = journal_select_result(c, &r))) {
+    if ((rc = sync_result(c, o, journal_select_result, result, &r))) {
         return rc;
-    }
-    if (result) {
-        *result = r;
     }
     return r.refused_kind
                ? fail(BMQCRC_EINVAL, "BMQCRC_JSEL_TOO_MANY_QUEUES: the journal's QueueOp records "
@@ -2977,18 +2947,7 @@ int bmqcrc_journal_select(const bmqcrc_journal_select_args* p, bmqcrc_journal_se
 
 int bmqcrc_last_journal_select(int device, void* stream, bmqcrc_journal_select_result* result)
 {
-    t_err.clear();
-    DeviceGuard keep_device;
-    LockedCtx c;
-    int rc;
-    bmqcrc_journal_select_result r;
-    if ((rc = lock_on(device, stream, true, &c)) || (rc = journal_select_result(c, &r))) {
-        return rc;
-    }
-    if (result) {
-        *result = r;
-    }
-    return 0;
+    return last_result(device, stream, journal_select_result, result);
 }
 
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,

@@ -280,13 +280,19 @@ constexpr uint32_t kUnpackWindowBytes = 1024; // a chunk of a wave's window of i
 constexpr int kUnpackThreads = 1024;          // k_unpack_scan: one block
 constexpr int kUnpackPublishThreads = 256;    // k_unpack_publish: one message per thread and step
 constexpr uint32_t kUnpackPublishBlocks = 2048;
-// UnpackArgs::ctr words
-constexpr int kUnpCtrRefusal = kLayoutCtrRefusal;
-constexpr int kUnpCtrMsgs = 1;       // messages of all events (k_unpack_publish; 0 when refused)
-constexpr int kUnpCtrBad = 2;        // messages whose computed CRC differs from the header's
-constexpr int kUnpCtrFirstBad = 3;   // ~(lowest such message), 0: none
+// ctr[] words of both unpackers (crc32c_unpack_slots.h); the last is the unit's own
+constexpr int kSlotCtrRefusal = kLayoutCtrRefusal;
+constexpr int kSlotCtrMsgs = 1;      // messages found: PUT events' by k_unpack_publish (0 when
+                                     // refused), selected MESSAGE records by k_recunp_place
+                                     // (refused or not)
+constexpr int kSlotCtrBad = 2;       // slots whose computed CRC differs from the stored one
+constexpr int kSlotCtrFirstBad = 3;  // ~(lowest such slot), 0: none
 constexpr int kUnpCtrOffset = 4;     // the refused event's bad_off (k_unpack_publish)
-constexpr int kUnpCtrWords = 5;
+constexpr int kRecUnpCtrSkipped = 4; // unselected MESSAGE records (k_recunp_place)
+constexpr int kSlotCtrWords = 5;
+static_assert(kSlotCtrFirstBad < kUnpCtrOffset && kUnpCtrOffset < kSlotCtrWords &&
+                  kSlotCtrFirstBad < kRecUnpCtrSkipped && kRecUnpCtrSkipped < kSlotCtrWords,
+              "a unit's own word lies behind the shared ones, inside the array");
 // BMQCRC_PUT_UNPACK_* of bmqcrc_protocol.h, which the kernels do not include
 #define BMQCRC_UNPACK_KIND_EVENT_OFFSETS 1u
 #define BMQCRC_UNPACK_KIND_EVENT_HEADER 2u
@@ -314,7 +320,7 @@ struct UnpackArgs {
     const uint32_t* ws_out;         // workspace, msg_cap: the fold's CRCs
     unsigned long long* first;      // workspace, n_events + 1: counts, then their exclusive prefix
     unsigned long long* bad_off;    // workspace, n_events: the offset an event's refusal names
-    unsigned long long* ctr;        // workspace, kUnpCtrWords, zeroed before the launch
+    unsigned long long* ctr;        // workspace, kSlotCtrWords, zeroed before the launch
 };
 
 // ---- bmqcrc_message_records_unpack (crc32c_records_unpack.hip, ABI 2.13) ---
@@ -323,13 +329,6 @@ struct UnpackArgs {
 // kUnpackPublishBlocks x kUnpackPublishThreads.
 constexpr uint32_t kJournalRecordDwords = 15;  // a journal record: 60 bytes
 constexpr uint32_t kRecUnpMsgFlag = 0x80000000u;  // RecUnpackArgs::pre: the record takes a slot
-// RecUnpackArgs::ctr words
-constexpr int kRecUnpCtrRefusal = kLayoutCtrRefusal;
-constexpr int kRecUnpCtrMsgs = 1;      // selected MESSAGE records (k_recunp_place, refused or not)
-constexpr int kRecUnpCtrBad = 2;       // messages whose computed CRC differs from the stored one
-constexpr int kRecUnpCtrFirstBad = 3;  // ~(lowest such slot), 0: none
-constexpr int kRecUnpCtrSkipped = 4;   // unselected MESSAGE records (k_recunp_place)
-constexpr int kRecUnpCtrWords = 5;
 // BMQCRC_REC_UNPACK_* of bmqcrc_protocol.h, which the kernels do not include
 #define BMQCRC_RECUNP_KIND_RECORD_HEADER 1u
 #define BMQCRC_RECUNP_KIND_MESSAGE_RECORD 2u
@@ -364,7 +363,7 @@ struct RecUnpackArgs {
     uint32_t* rec_len;              // its length and the DataHeader's flags byte, of the records
     uint8_t* rec_flags;             // that take a slot
     unsigned long long* bsum;       // workspace, 2 * kPackBlocks: messages | skipped per block
-    unsigned long long* ctr;        // workspace, kRecUnpCtrWords, zeroed before the launch
+    unsigned long long* ctr;        // workspace, kSlotCtrWords, zeroed before the launch
     uint64_t per_block;             // records per block (multiple of kPackThreads)
     uint32_t nblocks;               // blocks (<= kPackBlocks)
 };

@@ -2,7 +2,8 @@
 // (crc32c_put_pack.hip, crc32c_records_pack.hip; DESIGN.md sections 12, 13).
 // Device only, in the anonymous namespace like the units' own code.  Templates
 // over the unit's args struct (PackArgs, RecArgs), of which they use src_bytes,
-// src_offsets, lengths, n, off, bsum, ctr, per_block and nblocks.
+// src_offsets, lengths, n, off, bsum, ctr, per_block and nblocks.  The
+// unpackers take refuse, wave_sum, block_prefix and tile_scan from here too.
 //
 // Pass 1 (layout_count): the grid is nblocks x kPackThreads and block b owns
 // the contiguous messages [b per_block, (b + 1) per_block).  With B[i] the
@@ -39,6 +40,37 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
     return v;  // lane 0
 }
 
+static_assert(kUnpackThreads == kPackThreads, "tile_scan: one tile is kPackThreads values");
+
+// One tile of a 64-bit scan over the block's kPackThreads threads: returns the
+// sum of the v of the threads before this one, *total = of all.  Called by the
+// whole block; wtot is __shared__, kPackThreads / 64 words.  The first barrier
+// follows the caller's loads of the tile, the second precedes its stores.
+__device__ __forceinline__ unsigned long long tile_scan(unsigned long long v,
+                                                        unsigned long long* wtot,
+                                                        unsigned long long* total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    unsigned long long incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long o = __shfl_up(incl, d);
+        incl += lane >= (uint32_t)d ? o : 0ull;
+    }
+    if (lane == 63) {
+        wtot[wv] = incl;
+    }
+    __syncthreads();
+    unsigned long long woff = 0, tot = 0;
+    for (uint32_t w = 0; w < kPackThreads / 64; ++w) {
+        woff += w < wv ? wtot[w] : 0ull;
+        tot += wtot[w];
+    }
+    __syncthreads();
+    *total = tot;
+    return woff + incl - v;
+}
+
 // Pass 1, called by the whole block.  size(i, src_offset, len) returns B[i]
 // and raises the unit's refusals of message i.
 template <class Args, class Size>
@@ -61,24 +93,10 @@ __device__ __forceinline__ void layout_count(const Args& a, Size size)
             // at most this many 16-byte pieces of destination, wherever it lies
             pieces += len ? (((uint64_t)len + 15u) >> 4) + 1u : 0u;
         }
-        unsigned long long incl = b;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long o = __shfl_up(incl, d);
-            incl += lane >= (uint32_t)d ? o : 0ull;
-        }
-        if (lane == 63) {
-            wtot[wv] = incl;
-        }
-        __syncthreads();
-        unsigned long long woff = 0, tot = 0;
-        for (uint32_t w = 0; w < kPackThreads / 64; ++w) {
-            woff += w < wv ? wtot[w] : 0ull;
-            tot += wtot[w];
-        }
-        __syncthreads();
+        unsigned long long tot;
+        const unsigned long long before = tile_scan(b, wtot, &tot);
         if (valid) {
-            a.off[i] = carry + woff + incl - b;
+            a.off[i] = carry + before;
         }
         carry += tot;
     }

@@ -12,14 +12,15 @@
 //      in the host walk's order, its messages counted into first[e]; the first
 //      violation of an event raises the call's refusal word
 //      (crc32c_pack_layout.h) and leaves its offset in bad_off[e].
-//   2. k_unpack_scan: first[] becomes the exclusive prefix of the counts, and
-//      the lowest event whose last message lies past msg_cap is refused.
+//   2. k_unpack_scan: first[] becomes the exclusive prefix of the counts
+//      (tile_scan of crc32c_pack_layout.h), and the lowest event whose last
+//      message lies past msg_cap is refused.
 //   3. k_unpack_walk<true>: the same walk again, now placing: after every 64
 //      messages the 64 lanes fetch their own message's queue id, GUID and CRC
 //      and store coalesced.  Offsets and lengths go to the WORKSPACE, which
 //      the fold reads; the slots no message took -- all of them when anything
-//      was refused -- become empty messages (offset 0, length 0), so the fold
-//      never reads a descriptor the walk did not validate.
+//      was refused -- become empty messages (empty_slots of
+//      crc32c_unpack_slots.h).
 //   (the fold: bmqcrc_launch_batch over the msg_cap slots, when out != NULL)
 //   4. k_unpack_publish: unless refused, the workspace's offsets, lengths,
 //      header CRCs and computed CRCs to the caller's arrays, the mismatches
@@ -39,6 +40,7 @@
 
 #include "bmqcrc_internal.h"
 #include "crc32c_pack_layout.h"
+#include "crc32c_unpack_slots.h"
 
 namespace bmqcrc {
 namespace {
@@ -282,20 +284,15 @@ template <bool kPlace>
 __global__ __launch_bounds__(kUnpackWalkThreads) void k_unpack_walk(UnpackArgs a)
 {
     __shared__ uint32_t win[2 * kWindowDwords];
-    const bool refused = kPlace && a.ctr[kUnpCtrRefusal] != 0;
+    const bool refused = kPlace && a.ctr[kSlotCtrRefusal] != 0;
     if (!refused) {
         for (uint64_t e = blockIdx.x; e < a.n_events; e += gridDim.x) {
             walk_event<kPlace>(a, e, win);
         }
     }
     if (kPlace) {
-        const uint64_t stride = (uint64_t)gridDim.x * kUnpackWalkThreads;
-        const uint64_t used = refused ? 0 : a.first[a.n_events];  // <= msg_cap: the scan
-        for (uint64_t i = used + (uint64_t)blockIdx.x * kUnpackWalkThreads + threadIdx.x;
-             i < a.msg_cap; i += stride) {
-            a.ws_off[i] = 0;
-            a.ws_len[i] = 0;
-        }
+        // (first[n_events] <= msg_cap: the scan)
+        empty_slots(a, refused ? 0 : a.first[a.n_events], kUnpackWalkThreads);
     }
 }
 
@@ -303,29 +300,14 @@ __global__ __launch_bounds__(kUnpackWalkThreads) void k_unpack_walk(UnpackArgs a
 __global__ __launch_bounds__(kUnpackThreads) void k_unpack_scan(UnpackArgs a)
 {
     __shared__ unsigned long long wtot[kUnpackThreads / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     unsigned long long carry = 0;
     for (uint64_t base = 0; base < a.n_events; base += kUnpackThreads) {
         const uint64_t e = base + tid;
         const unsigned long long c = e < a.n_events ? a.first[e] : 0ull;
-        unsigned long long incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long o = __shfl_up(incl, d);
-            incl += lane >= (uint32_t)d ? o : 0ull;
-        }
-        if (lane == 63) {
-            wtot[wv] = incl;
-        }
-        __syncthreads();
-        unsigned long long woff = 0, tot = 0;
-        for (uint32_t w = 0; w < kUnpackThreads / 64; ++w) {
-            woff += w < wv ? wtot[w] : 0ull;
-            tot += wtot[w];
-        }
-        __syncthreads();
+        unsigned long long tot;
+        const unsigned long long before = carry + tile_scan(c, wtot, &tot);
         if (e < a.n_events) {
-            const unsigned long long before = carry + woff + incl - c;
             a.first[e] = before;
             // the lowest event whose last message does not fit
             if (before <= a.msg_cap && before + c > a.msg_cap) {
@@ -343,7 +325,7 @@ __global__ __launch_bounds__(kUnpackThreads) void k_unpack_scan(UnpackArgs a)
 __global__ __launch_bounds__(kUnpackPublishThreads) void k_unpack_publish(UnpackArgs a)
 {
     const uint64_t t0 = (uint64_t)blockIdx.x * kUnpackPublishThreads + threadIdx.x;
-    const unsigned long long word = a.ctr[kUnpCtrRefusal];
+    const unsigned long long word = a.ctr[kSlotCtrRefusal];
     if (word != 0) {
         if (t0 == 0) {
             const unsigned long long key = ~word;
@@ -381,11 +363,11 @@ __global__ __launch_bounds__(kUnpackPublishThreads) void k_unpack_publish(Unpack
         }
     }
     if (t0 == 0) {
-        a.ctr[kUnpCtrMsgs] = n;
+        a.ctr[kSlotCtrMsgs] = n;
     }
     if (bad) {
-        atomicAdd(&a.ctr[kUnpCtrBad], bad);
-        atomicMax(&a.ctr[kUnpCtrFirstBad], lowest);
+        atomicAdd(&a.ctr[kSlotCtrBad], bad);
+        atomicMax(&a.ctr[kSlotCtrFirstBad], lowest);
     }
 }
 

@@ -27,8 +27,7 @@
 //      local prefix: offset, length and stored CRC to the WORKSPACE, which the
 //      fold reads, the other fields to the caller's arrays.  The slots no
 //      message took -- all of them when anything was refused -- become empty
-//      messages (offset 0, length 0), so the fold never reads a descriptor
-//      the walk did not validate.
+//      messages (empty_slots of crc32c_unpack_slots.h).
 //   (the fold: bmqcrc_launch_batch over the msg_cap slots, when out != NULL)
 //   3. k_recunp_publish: unless refused, the workspace's offsets, lengths,
 //      stored CRCs and computed CRCs to the caller's arrays, the mismatches
@@ -45,6 +44,7 @@
 #include "bmqcrc_internal.h"
 #include "crc32c_journal_stage.h"
 #include "crc32c_pack_layout.h"
+#include "crc32c_unpack_slots.h"
 
 namespace bmqcrc {
 namespace {
@@ -162,13 +162,13 @@ __global__ __launch_bounds__(kPackThreads) void k_recunp_place(RecUnpackArgs a)
     // Step 1's word.  A block that starts late may read TOO_MANY_MESSAGES
     // raised below by another block of this pass instead: then all > msg_cap
     // holds here as well, and `refused` is the same answer in every block.
-    const bool classified_clean = a.ctr[kRecUnpCtrRefusal] == 0;
+    const bool classified_clean = a.ctr[kSlotCtrRefusal] == 0;
     const unsigned long long skipped = block_prefix(a, bpre);
     const unsigned long long all = bpre[a.nblocks];
     const unsigned long long before = bpre[blockIdx.x], after = bpre[blockIdx.x + 1];
     const bool refused = !classified_clean || all > a.msg_cap;
     if (blockIdx.x == 0 && tid == 0) {
-        a.ctr[kRecUnpCtrMsgs] = all;
+        a.ctr[kSlotCtrMsgs] = all;
         a.ctr[kRecUnpCtrSkipped] = skipped;
     }
     if (before <= a.msg_cap && a.msg_cap < after) {
@@ -224,24 +224,19 @@ __global__ __launch_bounds__(kPackThreads) void k_recunp_place(RecUnpackArgs a)
             __syncthreads();  // this step's LDS reads before the next stage
         }
     }
-    const uint64_t stride = (uint64_t)gridDim.x * kPackThreads;
-    const uint64_t used = refused ? 0 : all;
-    for (uint64_t i = used + (uint64_t)blockIdx.x * kPackThreads + tid; i < a.msg_cap;
-         i += stride) {
-        a.ws_off[i] = 0;
-        a.ws_len[i] = 0;
-    }
+    empty_slots(a, refused ? 0 : all, kPackThreads);
 }
 
-// Step 3, after the fold.
+// Step 3, after the fold.  The loop is k_unpack_publish's: as one function
+// behind the early return it cost this kernel two SGPRs (profiles/r14/unpack_slots).
 __global__ __launch_bounds__(kUnpackPublishThreads) void k_recunp_publish(RecUnpackArgs a)
 {
-    if (a.ctr[kRecUnpCtrRefusal] != 0) {
+    if (a.ctr[kSlotCtrRefusal] != 0) {
         return;
     }
     const uint64_t t0 = (uint64_t)blockIdx.x * kUnpackPublishThreads + threadIdx.x;
     const uint64_t stride = (uint64_t)gridDim.x * kUnpackPublishThreads;
-    const uint64_t n = a.ctr[kRecUnpCtrMsgs];  // <= msg_cap: k_recunp_place
+    const uint64_t n = a.ctr[kSlotCtrMsgs];  // <= msg_cap: k_recunp_place
     unsigned long long bad = 0, lowest = 0;
     for (uint64_t i = t0; i < n; i += stride) {
         const uint32_t exp = a.ws_exp[i];
@@ -260,8 +255,8 @@ __global__ __launch_bounds__(kUnpackPublishThreads) void k_recunp_publish(RecUnp
         }
     }
     if (bad) {
-        atomicAdd(&a.ctr[kRecUnpCtrBad], bad);
-        atomicMax(&a.ctr[kRecUnpCtrFirstBad], lowest);
+        atomicAdd(&a.ctr[kSlotCtrBad], bad);
+        atomicMax(&a.ctr[kSlotCtrFirstBad], lowest);
     }
 }
 

@@ -135,6 +135,16 @@ def test_cpp_spellings_fall_back_without_gpu():
     assert "PASS" in r.stdout
 
 
+def test_cpp_device_call_refusals():
+    """tests/cpp/device_call_refusals.cpp: the struct-taking device calls'
+    preamble and overlap refusals, their texts and order, through the C
+    headers.  Built here when missing, like the self-test."""
+    from blazingmq_amd import build
+    exe = build.build_refusals(os.path.join(build.LIB, "libbmqcrc.so"))
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "PASS" in r.stdout, r.stdout + r.stderr
+
+
 @pytest.mark.skipif(device_count() > 0, reason="GPU present: batch path is exercised by -m gpu")
 def test_batch_refuses_without_gpu():
     # the batch path never falls back to the CPU

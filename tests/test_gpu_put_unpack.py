@@ -234,6 +234,40 @@ def test_more_events_than_the_walk_grid(cuda):
     assert m["n"] == 5000 and np.array_equal(host["out"][:5000], m["crcs"])
 
 
+def test_more_messages_than_one_step_of_the_publish_grid(cuda):
+    # above 2,048 x 256 messages a publish thread copies a second slot, and with
+    # msg_cap 300,000 above the count a placing thread empties a second one: one
+    # event of 2,049 short messages 257 times over, the model tiled with it
+    rng = np.random.default_rng(34)
+    k, reps = 2049, 257
+    assert k * reps > 2048 * 256
+    ev = M.build_event(rng, rng.integers(0, 24, size=k))
+    small = M.model(ev)
+    n = k * reps
+    model = dict(refused=None, n=n)
+    for name in ("lengths", "queue_ids", "guids", "flags", "expected", "crcs"):
+        model[name] = np.concatenate([small[name]] * reps)
+    model["app_offsets"] = np.tile(small["app_offsets"], reps) + \
+        np.repeat(np.arange(reps, dtype=np.int64) * ev.size, k)
+    model["event_first"] = np.arange(reps + 1, dtype=np.int64) * k
+    buf, offs = np.tile(ev, reps), np.arange(reps + 1, dtype=np.int64) * ev.size
+    _, exact = _ok(cuda, buf, offs, cap=n, model=model)
+    assert np.array_equal(exact["out"][:n], model["crcs"])
+    # more than one step of the placing grid of empty slots behind the messages
+    _, wide = _ok(cuda, buf, offs, cap=n + 300000, model=model)
+    for name, a in exact.items():
+        used = a.size - GUARD * PER.get(name, 1)
+        assert np.array_equal(wide[name][:used], a[:used]), name
+    # one wrong header CRC in the second step
+    victim = 2048 * 256 + 1000
+    bad = buf.copy()
+    bad[(victim // k) * ev.size + M.walk(ev)[0][victim % k] + 28] ^= 0x01
+    wrong = dict(model, expected=model["expected"].copy())
+    wrong["expected"][victim] ^= 0x01000000
+    _, host = _ok(cuda, bad, offs, cap=n, model=wrong, n_bad=1, first_bad=victim)
+    assert np.array_equal(host["out"][:n], model["crcs"])
+
+
 def test_one_event_without_offsets_and_optional_arrays_left_out(cuda):
     rng = np.random.default_rng(25)
     ev = M.build_event(rng, rng.integers(0, 200, size=150))

@@ -251,6 +251,37 @@ def test_more_records_than_one_step_of_the_layout_grid(cuda):
     _ok(cuda, np.tile(run[:M.REC * k], reps), d, model=model, cap=n)
 
 
+def test_more_messages_than_one_step_of_the_publish_grid(cuda):
+    # above 2,048 x 256 messages a publish thread copies a second slot, and with
+    # msg_cap 300,000 above the count a placing thread empties a second one: a
+    # message-only run of 2,049 records 257 times over, all over one DATA window
+    rng = np.random.default_rng(48)
+    k, reps = 2049, 257
+    assert k * reps > 2048 * 256
+    j, d = M.build_partition(rng, rng.integers(0, 24, size=k), others=0.0)
+    run = j[M.JH + M.REC:]
+    small = M.model(run, d)
+    assert small["n"] == small["n_records"] == k
+    n = k * reps
+    model = dict(refused=None, n_records=n, n=n, n_skipped=0)
+    for name in M.FIELDS + ("crcs",):
+        model[name] = np.concatenate([small[name]] * reps)
+    model["record_index"] = np.arange(n, dtype=np.uint32)
+    tiled = np.tile(run, reps)
+    _, exact = _ok(cuda, tiled, d, model=model, cap=n)
+    # more than one step of the placing grid of empty slots behind the messages
+    _, wide = _ok(cuda, tiled, d, model=model, cap=n + 300000)
+    for name, a in exact.items():
+        assert np.array_equal(wide[name][:n * PER[name]], a[:n * PER[name]]), name
+    # one wrong stored CRC in the second step
+    victim = 2048 * 256 + 1000
+    tiled[M.REC * victim + 55] ^= 0x01
+    wrong = dict(model, expected=model["expected"].copy())
+    wrong["expected"][victim] ^= 1
+    _, host = _ok(cuda, tiled, d, model=wrong, cap=n, n_bad=1, first_bad=victim)
+    assert np.array_equal(host["out"][:n], model["crcs"])
+
+
 def test_no_message_record_and_msg_cap_0(cuda):
     w = S.PartitionWriter(lease_id=2)
     w.queue_op(S.OP_CREATION, S.DEFAULT_QUEUE_KEY)
