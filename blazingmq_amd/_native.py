@@ -272,6 +272,45 @@ if hasattr(lib, "bmqcrc_journal_select"):  # ABI 2.14 (an older build loads for 
                                           ctypes.POINTER(JournalSelectResult), _popts]
     lib.bmqcrc_last_journal_select.restype = _int
     lib.bmqcrc_last_journal_select.argtypes = [_int, _vp, ctypes.POINTER(JournalSelectResult)]
+BMQCRC_STORAGE_APPLY_OK = 0
+BMQCRC_STORAGE_APPLY_EVENT_OFFSETS = 1
+BMQCRC_STORAGE_APPLY_EVENT_HEADER = 2
+BMQCRC_STORAGE_APPLY_STORAGE_HEADER = 3
+BMQCRC_STORAGE_APPLY_DATA_RECORD = 4
+BMQCRC_STORAGE_APPLY_TOO_MANY_MESSAGES = 5
+BMQCRC_STORAGE_APPLY_OUT_OF_SYNC = 6
+BMQCRC_STORAGE_APPLY_DST_TOO_SMALL = 7
+BMQCRC_STORAGE_APPLY_TOO_MANY_PIECES = 8
+
+
+class StorageApply(ctypes.Structure):
+    """bmqcrc_storage_apply (include/bmqcrc_protocol.h, ABI 2.15)."""
+    _fields_ = [("struct_size", _u32), ("reserved", _u32), ("events", _vp), ("events_bytes", _u64),
+                ("event_offsets", _vp), ("n_events", _u64), ("msg_cap", _u64),
+                ("partition_id", _u32), ("lease_id", _u32), ("seq", _u64), ("journal_pos", _u64),
+                ("data_file_pos", _u64), ("journal_dst", _vp), ("journal_dst_bytes", _u64),
+                ("data_dst", _vp), ("data_dst_bytes", _u64), ("types", _vp), ("flags", _vp),
+                ("payload_offsets", _vp), ("payload_lengths", _vp), ("record_offsets", _vp),
+                ("lengths", _vp), ("expected", _vp), ("out", _vp), ("event_first", _vp)]
+
+
+class StorageApplyResult(ctypes.Structure):
+    """bmqcrc_storage_apply_result (include/bmqcrc_protocol.h, ABI 2.15)."""
+    _fields_ = [("n_events", _u64), ("n_msgs", _u64), ("n_data", _u64), ("journal_bytes", _u64),
+                ("data_bytes", _u64), ("head_seq", _u64), ("head_lease_id", _u32),
+                ("refused_kind", _u32), ("n_bad", _u64), ("first_bad", _u64),
+                ("refused_event", _u64), ("refused_index", _u64), ("refused_offset", _u64)]
+
+    def as_dict(self):
+        return {f[0]: int(getattr(self, f[0])) for f in self._fields_}
+
+
+if hasattr(lib, "bmqcrc_storage_event_apply"):  # ABI 2.15 (an older build loads for same-box A/B)
+    lib.bmqcrc_storage_event_apply.restype = _int
+    lib.bmqcrc_storage_event_apply.argtypes = [ctypes.POINTER(StorageApply),
+                                               ctypes.POINTER(StorageApplyResult), _popts]
+    lib.bmqcrc_last_storage_apply.restype = _int
+    lib.bmqcrc_last_storage_apply.argtypes = [_int, _vp, ctypes.POINTER(StorageApplyResult)]
 lib.bmqcrc_journal_scan.restype = _i64
 lib.bmqcrc_journal_scan.argtypes = [_vp, _u64, _vp, _u64, _vp, _pint, _pu64, _vp, _vp, _vp, _vp,
                                     _u64]

@@ -132,11 +132,11 @@ struct UnpackScratch {
     DevBuf off, len, exp, out, ctr;
     uint64_t n = 0;
     bool any = false;
-    int ensure(uint64_t msg_cap, bool need_out)
+    int ensure(uint64_t msg_cap, bool need_out, int ctr_words = kSlotCtrWords)
     {
         const uint64_t slots = std::max<uint64_t>(msg_cap, 1);
         int rc;
-        if ((rc = ctr.ensure(8 * kSlotCtrWords)) || (rc = off.ensure(8 * slots)) ||
+        if ((rc = ctr.ensure(8 * ctr_words)) || (rc = off.ensure(8 * slots)) ||
             (rc = len.ensure(4 * slots)) || (rc = exp.ensure(4 * slots))) {
             return rc;
         }
@@ -188,6 +188,17 @@ struct Workspace {
     UnpackScratch unp, runp;
     DevBuf unp_first, unp_bad;
     DevBuf runp_pre, runp_roff, runp_rlen, runp_rflags, runp_bsum;
+    // bmqcrc_storage_event_apply: a set of its own again, its counters followed
+    // by its copy pass's.  Beside it per event what the PUT unpack keeps, per
+    // slot the destination offset and the journal record's offset (8 each),
+    // the DATA record's size, its header + options size, the bytes after the
+    // journal record and type | flags (4 each), the layout's block sums and
+    // the copy pass's scratch; the write head the last apply was given
+    UnpackScratch sap;
+    DevBuf sap_first, sap_bad, sap_dst, sap_jrn, sap_rec, sap_hdr, sap_pay, sap_meta, sap_bsum;
+    DevBuf sap_copy_first, sap_copy_bsum;
+    uint32_t sap_lease = 0;
+    uint64_t sap_seq = 0;
     // bmqcrc_journal_select: the part of its workspace every call zeroes (the
     // counters, the queue-key and GUID tables, the claims) and the rest (the
     // two record lists, the named DELETIONs, the states); the records of the
@@ -1913,12 +1924,15 @@ void refusal_of(unsigned long long ctr, uint32_t* kind, uint64_t* index)
 }
 
 // The refusal `kind` of a device call in words: what[kind] is its text,
-// with %llu for the index and, where the text has a second, for the offset.
-int refused(const char* const (&what)[6], uint32_t kind, uint64_t index, uint64_t offset = 0)
+// with %llu for the index and, where the text has a second, for the offset,
+// and where it has a third, for the message.
+template <size_t K>
+int refused(const char* const (&what)[K], uint32_t kind, uint64_t index, uint64_t offset = 0,
+            uint64_t message = 0)
 {
     char buf[256];
-    snprintf(buf, sizeof(buf), what[kind <= 5 ? kind : 0], (unsigned long long)index,
-             (unsigned long long)offset);
+    snprintf(buf, sizeof(buf), what[kind < K ? kind : 0], (unsigned long long)index,
+             (unsigned long long)offset, (unsigned long long)message);
     return fail(BMQCRC_EINVAL, std::string(buf) + ": nothing was written");
 }
 
@@ -2063,8 +2077,8 @@ int fold_slots(Ctx& c, const UnpackScratch& s, const void* window, uint64_t wind
 // c's stream (w->mu held), into ctr[] and what both results (R) share: the
 // refusal (its index to *index), otherwise the messages, the mismatches and
 // the lowest of them.  All zeros when there was none.
-template <class R>
-int slot_counters(Ctx& c, const UnpackScratch& s, unsigned long long (&ctr)[kSlotCtrWords], R* r,
+template <class R, size_t W>
+int slot_counters(Ctx& c, const UnpackScratch& s, unsigned long long (&ctr)[W], R* r,
                   uint64_t* index)
 {
     memset(r, 0, sizeof(*r));
@@ -2950,6 +2964,227 @@ int bmqcrc_last_journal_select(int device, void* stream, bmqcrc_journal_select_r
     return last_result(device, stream, journal_select_result, result);
 }
 
+static_assert(BMQCRC_STORAGE_APPLY_EVENT_OFFSETS == BMQCRC_SAP_KIND_EVENT_OFFSETS &&
+                  BMQCRC_STORAGE_APPLY_EVENT_HEADER == BMQCRC_SAP_KIND_EVENT_HEADER &&
+                  BMQCRC_STORAGE_APPLY_STORAGE_HEADER == BMQCRC_SAP_KIND_STORAGE_HEADER &&
+                  BMQCRC_STORAGE_APPLY_DATA_RECORD == BMQCRC_SAP_KIND_DATA_RECORD &&
+                  BMQCRC_STORAGE_APPLY_TOO_MANY_MESSAGES == BMQCRC_SAP_KIND_TOO_MANY_MESSAGES &&
+                  BMQCRC_STORAGE_APPLY_OUT_OF_SYNC == BMQCRC_SAP_KIND_OUT_OF_SYNC &&
+                  BMQCRC_STORAGE_APPLY_DST_TOO_SMALL == BMQCRC_SAP_KIND_DST_TOO_SMALL &&
+                  BMQCRC_STORAGE_APPLY_TOO_MANY_PIECES == BMQCRC_SAP_KIND_TOO_MANY_PIECES,
+              "the kernels' refusal kinds are the public ones");
+
+// Result of the storage apply last enqueued on c's workspace, after
+// everything enqueued on its stream (w->mu held); zeros when there was none.
+static int storage_apply_result(Ctx& c, bmqcrc_storage_apply_result* r)
+{
+    unsigned long long ctr[kSapCtrWords + kCopyCtrWords];
+    const int rc = slot_counters(c, c.w->sap, ctr, r, &r->refused_event);
+    if (rc || !c.w->sap.any) {
+        return rc;
+    }
+    r->n_events = c.w->sap.n;
+    if (r->refused_kind) {
+        r->refused_event = ctr[kSapCtrEvent];
+        r->refused_index = ctr[kSapCtrIndex];
+        r->refused_offset = ctr[kSapCtrOffset];
+        return 0;
+    }
+    // the layout placed every message inside data_dst: the copy pass has nothing to refuse
+    const unsigned long long* cc = ctr + kSapCtrWords;
+    if (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow]) {
+        return fail(BMQCRC_EIO, "bmqcrc_storage_event_apply: the copy pass refused a message "
+                                "the layout had placed (internal error)");
+    }
+    r->n_data = ctr[kSapCtrData];
+    r->journal_bytes = kJournalRecordBytes * r->n_msgs;
+    r->data_bytes = ctr[kSapCtrTotal];
+    r->head_lease_id = r->n_msgs ? (uint32_t)ctr[kSapCtrHeadLease] : c.w->sap_lease;
+    r->head_seq = r->n_msgs ? ctr[kSapCtrHeadSeq] : c.w->sap_seq;
+    return 0;
+}
+
+static const char* const kStorageApplyRefusals[9] = {
+    "", "BMQCRC_STORAGE_APPLY_EVENT_OFFSETS: event_offsets[%llu] is above its successor, no "
+        "multiple of 4, or the event ends past events_bytes (offset %llu, message %llu)",
+    "BMQCRC_STORAGE_APPLY_EVENT_HEADER: event %llu has a malformed EventHeader (offset %llu, "
+    "message %llu)",
+    "BMQCRC_STORAGE_APPLY_STORAGE_HEADER: event %llu has a truncated or inconsistent "
+    "StorageHeader, or one of another partition (offset %llu, message %llu)",
+    "BMQCRC_STORAGE_APPLY_DATA_RECORD: event %llu has a DATA message with a malformed DATA "
+    "record (offset %llu, message %llu)",
+    "BMQCRC_STORAGE_APPLY_TOO_MANY_MESSAGES: the messages of event %llu do not fit msg_cap "
+    "(offset %llu, message %llu)",
+    "BMQCRC_STORAGE_APPLY_OUT_OF_SYNC: event %llu has a message that does not continue the "
+    "journal, the DATA file or the sequence numbers (offset %llu, message %llu)",
+    "BMQCRC_STORAGE_APPLY_DST_TOO_SMALL: event %llu has the first message that ends past "
+    "journal_dst_bytes or data_dst_bytes (offset %llu, message %llu)",
+    "BMQCRC_STORAGE_APPLY_TOO_MANY_PIECES: more than 2^32-1 16-byte pieces of application data "
+    "in one call (event %llu, offset %llu, message %llu)"};
+
+int bmqcrc_storage_event_apply(const bmqcrc_storage_apply* p, bmqcrc_storage_apply_result* result,
+                               const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    bmqcrc_opts o;
+    int rc;
+    if ((rc = check_struct(p, "bmqcrc_storage_apply")) ||
+        (rc = device_call_opts(opts, "bmqcrc_storage_event_apply", &o))) {
+        return rc;
+    }
+    if ((rc = refuse_null({{!p->events, "events"},
+                           {!p->journal_dst, "journal_dst"},
+                           {!p->data_dst, "data_dst"}}))) {
+        return rc;
+    }
+    if ((uintptr_t)p->events & 3u) {
+        return fail(BMQCRC_EINVAL, "events must be 4-byte aligned");
+    }
+    if ((uintptr_t)p->journal_dst & 3u) {
+        return fail(BMQCRC_EINVAL, "journal_dst must be 4-byte aligned");
+    }
+    if ((uintptr_t)p->data_dst & 7u) {
+        return fail(BMQCRC_EINVAL, "data_dst must be 8-byte aligned");
+    }
+    if (!p->event_offsets && p->n_events != 1) {
+        return fail(BMQCRC_EINVAL, "event_offsets == NULL means one event: n_events must be 1");
+    }
+    if (p->n_events > 0xFFFFFFFFull || p->msg_cap > 0xFFFFFFFFull) {
+        return fail(BMQCRC_EINVAL, "n_events and msg_cap must be below 2^32");
+    }
+    if (p->journal_pos == 0 || (p->journal_pos & 3u)) {
+        return fail(BMQCRC_EINVAL, "journal_pos must be a multiple of 4 and not 0 (a journal "
+                                   "begins with its file headers)");
+    }
+    if (p->data_file_pos == 0 || (p->data_file_pos & 7u)) {
+        return fail(BMQCRC_EINVAL, "data_file_pos must be a multiple of 8 and not 0 (recovery "
+                                   "treats a MessageOffsetDwords of 0 as invalid)");
+    }
+    if (p->partition_id > 0xFFFFu) {
+        return fail(BMQCRC_EINVAL, "partition_id must be at most 65535");
+    }
+    if (p->lease_id == 0 && p->seq != 0) {
+        return fail(BMQCRC_EINVAL, "lease_id == 0 means no write head is known: seq must be 0");
+    }
+    const uint64_t cap = p->msg_cap;
+    const NamedRange events = {p->events, p->events_bytes, "[events, events+events_bytes)"};
+    const NamedRange journal = {p->journal_dst, p->journal_dst_bytes,
+                                "[journal_dst, journal_dst+journal_dst_bytes)"};
+    const NamedRange data = {p->data_dst, p->data_dst_bytes, "[data_dst, data_dst+data_dst_bytes)"};
+    if ((rc = refuse_overlap({journal, data}, {events})) ||
+        (rc = refuse_overlap({data}, {journal})) ||
+        (rc = refuse_overlap({{p->types, cap, "types"},
+                              {p->flags, cap, "flags"},
+                              {p->payload_offsets, 8 * cap, "payload_offsets"},
+                              {p->payload_lengths, 4 * cap, "payload_lengths"},
+                              {p->record_offsets, 8 * (cap + 1), "record_offsets"},
+                              {p->lengths, 4 * cap, "lengths"},
+                              {p->expected, 4 * cap, "expected"},
+                              {p->out, 4 * cap, "out"},
+                              {p->event_first, 8 * (p->n_events + 1), "event_first"}},
+                             {events, journal, data}))) {
+        return rc;
+    }
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    UnpackScratch& s = w->sap;
+    const uint64_t slots = std::max<uint64_t>(cap, 1);
+    if ((rc = s.ensure(cap, true, kSapCtrWords + kCopyCtrWords)) ||
+        (rc = w->sap_first.ensure(8 * (p->n_events + 1))) ||
+        (rc = w->sap_bad.ensure(8 * std::max<uint64_t>(p->n_events, 1))) ||
+        (rc = w->sap_bsum.ensure(8ull * 2 * kPackBlocks)) || (rc = w->sap_dst.ensure(8 * slots)) ||
+        (rc = w->sap_jrn.ensure(8 * slots)) || (rc = w->sap_rec.ensure(4 * slots)) ||
+        (rc = w->sap_hdr.ensure(4 * slots)) || (rc = w->sap_pay.ensure(4 * slots)) ||
+        (rc = w->sap_meta.ensure(4 * slots))) {
+        return rc;
+    }
+    HIP_TRY(hipMemsetAsync(s.ctr.p, 0, 8 * (kSapCtrWords + kCopyCtrWords), c.s));
+    s.n = p->n_events;
+    s.any = true;
+    w->sap_lease = p->lease_id;
+    w->sap_seq = p->seq;
+    if (p->n_events) {
+        SapArgs a;
+        memset(&a, 0, sizeof(a));
+        a.events = (const uint8_t*)p->events;
+        a.events_bytes = p->events_bytes;
+        a.event_offsets = p->event_offsets;
+        a.n_events = p->n_events;
+        a.msg_cap = cap;
+        a.journal_pos = p->journal_pos;
+        a.data_file_pos = p->data_file_pos;
+        a.seq = p->seq;
+        a.lease_id = p->lease_id;
+        a.partition_id = p->partition_id;
+        a.journal_dst = (uint8_t*)p->journal_dst;
+        a.journal_dst_bytes = p->journal_dst_bytes;
+        a.data_dst = (uint8_t*)p->data_dst;
+        a.data_dst_bytes = p->data_dst_bytes;
+        a.types = p->types;
+        a.flags = p->flags;
+        a.payload_offsets = p->payload_offsets;
+        a.payload_lengths = p->payload_lengths;
+        a.record_offsets = p->record_offsets;
+        a.lengths = p->lengths;
+        a.expected = p->expected;
+        a.out = p->out;
+        a.event_first = p->event_first;
+        a.ws_off = (unsigned long long*)s.off.p;
+        a.ws_len = (uint32_t*)s.len.p;
+        a.off = (unsigned long long*)w->sap_dst.p;
+        a.ws_exp = (uint32_t*)s.exp.p;
+        a.ws_out = (const uint32_t*)s.out.p;
+        a.ws_jrn = (unsigned long long*)w->sap_jrn.p;
+        a.ws_rec = (uint32_t*)w->sap_rec.p;
+        a.ws_hdr = (uint32_t*)w->sap_hdr.p;
+        a.ws_pay = (uint32_t*)w->sap_pay.p;
+        a.ws_meta = (uint32_t*)w->sap_meta.p;
+        a.first = (unsigned long long*)w->sap_first.p;
+        a.bad_off = (unsigned long long*)w->sap_bad.p;
+        a.bsum = (unsigned long long*)w->sap_bsum.p;
+        a.ctr = (unsigned long long*)s.ctr.p;
+        layout_split(slots, &a.per_block, &a.nblocks);
+        if (bmqcrc_launch_storage_apply_layout(&a, (void*)c.s)) {
+            return launch_failed("storage-apply layout");
+        }
+        // the slots as the copy's messages: the descriptors are the workspace's, never the caller's
+        CopyArgs ca;
+        memset(&ca, 0, sizeof(ca));
+        ca.src = a.events;
+        ca.src_bytes = a.events_bytes;
+        ca.src_offsets = (const uint64_t*)a.ws_off;
+        ca.lengths = a.ws_len;
+        ca.dst = a.data_dst;
+        ca.dst_bytes = a.data_dst_bytes;
+        ca.dst_offsets = (const uint64_t*)a.off;
+        ca.out = (uint32_t*)s.out.p;
+        ca.n = cap;
+        if ((rc = enqueue_copy(c, ca, w->sap_copy_first, w->sap_copy_bsum, a.ctr + kSapCtrWords))) {
+            return rc;
+        }
+        if (bmqcrc_launch_storage_apply_frame(&a, (void*)c.s)) {
+            return launch_failed("storage-apply frame");
+        }
+    }
+    bmqcrc_storage_apply_result r;
+    if ((rc = sync_result(c, o, storage_apply_result, result, &r))) {
+        return rc;
+    }
+    return r.refused_kind ? refused(kStorageApplyRefusals, r.refused_kind, r.refused_event,
+                                    r.refused_offset, r.refused_index)
+                          : 0;
+}
+
+int bmqcrc_last_storage_apply(int device, void* stream, bmqcrc_storage_apply_result* result)
+{
+    return last_result(device, stream, storage_apply_result, result);
+}
+
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,
                        uint32_t* seg_bytes)
 {
@@ -3123,7 +3358,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 14u;
+    return (2u << 16) | 15u;
 }
 
 }  // extern "C"

@@ -423,7 +423,79 @@ struct JselArgs {
     uint32_t nblocks;              // blocks (<= kPackBlocks)
 };
 
+// ---- bmqcrc_storage_event_apply (crc32c_storage_apply.hip, ABI 2.15) -------
+// The walks' grid and block are the PUT unpack's (kUnpackWalkBlocks x
+// kUnpackWalkThreads, one wave per event), the per-slot layout kernels'
+// kPackBlocks x kPackThreads over contiguous slot ranges (layout_split), the
+// frame kernel's kPackFrameBlocks x kPackFrameThreads.  SapArgs::ctr words: the
+// first four are the unpackers' (kSlotCtr*), behind them the call's own
+constexpr int kSapCtrOffset = 4;     // the refusal's byte in `events` (k_sap_frame)
+constexpr int kSapCtrEvent = 5;      // the refused event
+constexpr int kSapCtrIndex = 6;      // the refused message
+constexpr int kSapCtrData = 7;       // DATA messages
+constexpr int kSapCtrTotal = 8;      // bytes of all DATA records (k_sap_check)
+constexpr int kSapCtrHeadLease = 9;  // the last message's lease id and sequence number
+constexpr int kSapCtrHeadSeq = 10;
+constexpr int kSapCtrWords = 12;
+// BMQCRC_STORAGE_APPLY_* of bmqcrc_protocol.h, which the kernels do not include
+#define BMQCRC_SAP_KIND_EVENT_OFFSETS 1u
+#define BMQCRC_SAP_KIND_EVENT_HEADER 2u
+#define BMQCRC_SAP_KIND_STORAGE_HEADER 3u
+#define BMQCRC_SAP_KIND_DATA_RECORD 4u
+#define BMQCRC_SAP_KIND_TOO_MANY_MESSAGES 5u
+#define BMQCRC_SAP_KIND_OUT_OF_SYNC 6u
+#define BMQCRC_SAP_KIND_DST_TOO_SMALL 7u
+#define BMQCRC_SAP_KIND_TOO_MANY_PIECES 8u
+constexpr uint32_t kSapTypeData = 1;  // StorageMessageType::e_DATA
+
+struct SapArgs {
+    const uint8_t* events;          // device, 4-byte aligned
+    uint64_t events_bytes;
+    const uint64_t* event_offsets;  // device, n_events + 1, or nullptr (one event, the buffer)
+    uint64_t n_events;
+    uint64_t msg_cap;
+    uint64_t journal_pos;           // the replica's state: byte of the journal file that
+    uint64_t data_file_pos;         // journal_dst[0] stands for, of the DATA file that data_dst[0]
+    uint64_t seq;                   // does, and the write head (lease_id 0: none known)
+    uint32_t lease_id;
+    uint32_t partition_id;
+    uint8_t* journal_dst;           // device, 4-byte aligned
+    uint64_t journal_dst_bytes;
+    uint8_t* data_dst;              // device, 8-byte aligned
+    uint64_t data_dst_bytes;
+    uint8_t* types;                 // the caller's arrays (device, msg_cap; record_offsets
+    uint8_t* flags;                 // msg_cap + 1, event_first n_events + 1), each may be
+    uint64_t* payload_offsets;      // nullptr: written by k_sap_frame, when nothing was
+    uint32_t* payload_lengths;      // refused
+    uint64_t* record_offsets;
+    uint32_t* lengths;
+    uint32_t* expected;
+    uint32_t* out;
+    uint64_t* event_first;
+    unsigned long long* ws_off;     // workspace, msg_cap: what the copy reads -- the application
+    uint32_t* ws_len;               // data's offset in `events` and length (0 when not DATA) --
+    unsigned long long* off;        // and where it goes in data_dst; every slot filled
+    uint32_t* ws_exp;               // workspace, msg_cap: the MessageRecords' stored CRCs
+    const uint32_t* ws_out;         // workspace, msg_cap: the copy's CRCs
+    unsigned long long* ws_jrn;     // workspace, msg_cap: the journal record's offset in `events`,
+    uint32_t* ws_rec;               // the DATA record's bytes R, its header + options bytes, the
+    uint32_t* ws_hdr;               // bytes after the journal record, and type | flags << 8 |
+    uint32_t* ws_pay;               // StorageHeader bytes << 16
+    uint32_t* ws_meta;
+    unsigned long long* first;      // workspace, n_events + 1: counts, then their exclusive prefix
+    unsigned long long* bad_off;    // workspace, n_events: the offset an event's refusal names
+    unsigned long long* bsum;       // workspace, 2 * kPackBlocks: record bytes | pieces per block
+    unsigned long long* ctr;        // workspace, kSapCtrWords, zeroed before the launch
+    uint64_t per_block;             // slots per layout block (multiple of kPackThreads)
+    uint32_t nblocks;               // layout blocks (<= kPackBlocks)
+};
+
 }  // namespace bmqcrc
+
+// Launchers (crc32c_storage_apply.hip).  Asynchronous on `stream`: the layout
+// before bmqcrc_launch_copy (it writes the copy's descriptors), the frame after.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_storage_apply_layout(const bmqcrc::SapArgs* a, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_storage_apply_frame(const bmqcrc::SapArgs* a, void* stream);
 
 // Launcher (crc32c_journal_select.hip): the six kernels, asynchronous on `stream`.
 extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_journal_select(const bmqcrc::JselArgs* a, void* stream);

@@ -98,6 +98,66 @@ def append_deletions(journal, every=2):
     return np.concatenate([journal, d.reshape(-1)])
 
 
+def storage_events(journal_run, data, data_file_pos, journal_pos, partition_id, per_event):
+    """(events, event_offsets) replicating a partition: one storage message per
+    60-byte record of `journal_run` (the record run, not the journal file with
+    its headers), `per_event` messages to an event -- the bytes a primary's
+    ``storage_event.StorageEventBuilder`` emits for them with a flush after
+    every `per_event` messages (checked in ``tests/test_storage_apply_model.py``),
+    built with numpy.  `journal_run` begins at byte `journal_pos` of the journal
+    file; `data` is the DATA file from byte `data_file_pos` on (0: the whole
+    file), from which a MESSAGE record's DATA record is taken.  What
+    ``partition`` / ``append_deletions`` made, or any other journal: QLIST
+    messages, which carry a QLIST record, are not made."""
+    from . import storage_event as E
+    kinds = np.zeros(16, np.uint8)
+    kinds[[S.REC_MESSAGE, S.REC_CONFIRM, S.REC_DELETION, S.REC_QUEUE_OP, S.REC_JOURNAL_OP]] = [
+        E.MSG_DATA, E.MSG_CONFIRM, E.MSG_DELETION, E.MSG_QUEUE_OP, E.MSG_JOURNAL_OP]
+    recs = np.asarray(journal_run, np.uint8).reshape(-1, S.JOURNAL_RECORD_SIZE)
+    data = np.asarray(data, np.uint8)
+    n = recs.shape[0]
+    kind = kinds[recs[:, 0] >> 4]
+    if n and kind.min() == 0:
+        raise ValueError("a record of no known type")
+    is_data = kind == E.MSG_DATA
+    at = recs[:, 32:36].copy().view(">u4")[:, 0].astype(np.int64) * S.DWORD - data_file_pos
+    at[~is_data] = 0
+    size = np.zeros(n, np.int64)
+    head = data[at[is_data][:, None] + np.arange(4)].astype(np.int64)
+    size[is_data] = (((head[:, 0] & 0x1F) << 24) | (head[:, 1] << 16) | (head[:, 2] << 8) |
+                     head[:, 3]) * S.WORD
+    msg = E.STORAGE_HEADER_SIZE + S.JOURNAL_RECORD_SIZE + size
+    n_events = max(-(-n // per_event), 1)
+    event = np.arange(n) // per_event
+    before = np.concatenate([[0], np.cumsum(msg)])
+    pos = before[:-1] + E.EVENT_HEADER_SIZE * (event + 1)
+    offsets = np.concatenate([before[np.arange(n_events) * per_event] +
+                              E.EVENT_HEADER_SIZE * np.arange(n_events),
+                              [before[-1] + E.EVENT_HEADER_SIZE * n_events]])
+    if n_events and np.diff(offsets).max() > E.MAX_EVENT_SIZE_SOFT:
+        raise ValueError("EVENT_TOO_BIG: fewer messages per event")
+    events = np.zeros(int(offsets[-1]), np.uint8)
+    eh = np.zeros((n_events, E.EVENT_HEADER_SIZE), np.uint8)
+    eh[:, 0:4] = _be(np.diff(offsets), ">u4")
+    eh[:, 4] = (E.PROTOCOL_VERSION << 6) | E.EVENT_TYPE_STORAGE
+    eh[:, 5] = E.EVENT_HEADER_SIZE // E.WORD
+    events[offsets[:-1, None] + np.arange(E.EVENT_HEADER_SIZE)] = eh
+    sh = np.zeros((n, E.STORAGE_HEADER_SIZE), np.uint8)
+    sh[:, 0:4] = _be(msg // E.WORD, ">u4")
+    sh[:, 4] = (E.STORAGE_PROTOCOL_VERSION << 4) | (E.STORAGE_HEADER_SIZE // E.WORD)
+    sh[:, 5] = kind
+    sh[:, 6:8] = _be(partition_id, ">u2")
+    sh[:, 8:12] = _be((journal_pos + S.JOURNAL_RECORD_SIZE * np.arange(n)) // S.WORD, ">u4")
+    events[pos[:, None] + np.arange(E.STORAGE_HEADER_SIZE)] = sh
+    events[pos[:, None] + E.STORAGE_HEADER_SIZE + np.arange(S.JOURNAL_RECORD_SIZE)] = recs
+    # the DATA records: byte k of all of them is byte within[k] of record owner[k]
+    total = int(size.sum())
+    within = np.arange(total) - np.repeat(np.cumsum(size) - size, size)
+    events[np.repeat(pos + E.STORAGE_HEADER_SIZE + S.JOURNAL_RECORD_SIZE, size) + within] = \
+        data[np.repeat(at, size) + within]
+    return events, offsets.astype(np.uint64)
+
+
 def put_event(m, app_len, seed=12):
     """(event, app_offsets, app_lengths) for one PUT event of m messages whose
     application data are `app_len` random bytes, CRC fields pending (zero),

@@ -641,6 +641,173 @@ int bmqcrc_journal_select(const bmqcrc_journal_select_args* p, bmqcrc_journal_se
  * waits for it.  `result` may be NULL. */
 int bmqcrc_last_journal_select(int device, void* stream, bmqcrc_journal_select_result* result);
 
+/* ABI 2.15.  The replica's side of replication: STORAGE events in device
+ * memory are applied ON THE DEVICE to a run of the journal file and a window of
+ * the DATA file, also in device memory -- FileStore::processStorageEvent with
+ * FileStoreUtil::writeMessageRecordImpl for a batch of events in one
+ * asynchronous call, and with what the reference leaves to recovery: the
+ * application data of every DATA message is moved by the fused copy of
+ * bmqcrc_crc32c_copy, whose CRC32-C is compared with the one the producer
+ * stored.  No payload byte and no descriptor crosses PCIe.
+ *
+ * Events.  Event e is bytes [event_offsets[e], event_offsets[e + 1]) of
+ *   `events`; event_offsets == NULL means one event, the whole buffer.  An
+ *   event is an EventHeader of type STORAGE (8) or PARTITION_SYNC (10) and
+ *   storage messages back to back: a StorageHeader of headerWords * 4 >= 12
+ *   bytes, a 60-byte journal record and, for the types DATA (1) and QLIST (2),
+ *   a payload: messageWords counts all three.  A DATA message's payload is its
+ *   whole DATA record: DataHeader, options, application data, 1..8 padding
+ *   bytes.  An event of 8 bytes with no message is legal.
+ * Messages are numbered event by event in walk order, i = 0 .. n_msgs - 1;
+ *   event_first (may be NULL) receives the exclusive prefix of the per-event
+ *   counts, n_msgs last.
+ * The replica's state.  partition_id; journal_pos and data_file_pos, the byte
+ *   positions in the journal and the DATA file that journal_dst[0] and
+ *   data_dst[0] stand for; (lease_id, seq), the write head: the primary
+ *   sequence number of the last record applied, lease_id 0 when none is known
+ *   yet (seq must be 0 then).
+ * What is written, byte for byte what the reference's replica appends to its
+ *   two files: journal_dst + 60 i receives message i's journal record,
+ *   whatever its type.  With R[i] = 4 x DataHeader.messageWords for a DATA
+ *   message, 0 for any other, and Q the 64-bit exclusive prefix of R, a DATA
+ *   message's record goes to data_dst + Q[i]: DataHeader, option words and
+ *   padding bytes copied as they are, the application data moved by the fused
+ *   copy.  A QLIST message's payload is written nowhere (the QLIST file stays
+ *   on the host): payload_offsets / payload_lengths report it.
+ * Per-message outputs, each of msg_cap entries and each may be NULL:
+ *   types[i] (StorageMessageType), flags[i] (the StorageHeader's 5 flag bits,
+ *   bit 0 RECEIPT_REQUESTED), payload_offsets[i] / payload_lengths[i] (what
+ *   follows the journal record: byte offset in `events`, bytes),
+ *   record_offsets[i] = Q[i] with Q[n_msgs] behind the last (msg_cap + 1
+ *   entries), lengths[i] (application data bytes), expected[i] (the
+ *   MessageRecord's CRC at byte 52, host order), out[i] (the computed CRC);
+ *   the last three are 0 for a message that is not DATA.
+ * Verify on write.  n_bad counts the DATA messages whose computed CRC differs
+ *   from the stored one, first_bad is the lowest (n_msgs when none).
+ *   Mismatches do not fail the call and the bytes are applied all the same:
+ *   whether to withhold the receipt is the caller's decision.
+ * Options.  Device pointers only: BMQCRC_F_DEVICE_PTRS is required,
+ *   BMQCRC_F_ASYNC allowed; any other flag, ndevices > 1, a wrong struct_size
+ *   or reserved; `events`, journal_dst or data_dst null; `events` or
+ *   journal_dst not 4-byte aligned, data_dst not 8-byte aligned;
+ *   event_offsets == NULL with n_events != 1; n_events or msg_cap at or above
+ *   2^32; journal_pos 0 or no multiple of 4; data_file_pos 0 or no multiple of
+ *   8; partition_id above 65535; lease_id == 0 with seq != 0; any destination
+ *   or output array meeting [events, events + events_bytes) or a destination
+ *   is BMQCRC_EINVAL, answered on the host before the device lookup.
+ *   n_events == 0 writes nothing and reports zeros with the write head
+ *   unchanged.
+ * All or nothing, decided on the device.  One violation anywhere refuses the
+ *   call, and a refused call writes nothing to journal_dst, data_dst or any
+ *   output array.  Across events the lowest kind wins and within it the lowest
+ *   event (kinds 1..5) or message (kinds 6..8); within an event the violation
+ *   reported is the first in walk order.  The walk never loads a byte it has
+ *   not first shown to lie inside its event.  refused_event, refused_index and
+ *   refused_offset name the event, the message and a byte of `events`:
+ *   EVENT_OFFSETS    event_offsets[e] (the offset), the event's first message;
+ *   EVENT_HEADER     the event's offset plus 0 (shorter than 8, or the length
+ *                    field), 4 (the type) or 5 (headerWords); its first message;
+ *   STORAGE_HEADER   the StorageHeader's offset and its message;
+ *   DATA_RECORD      the DataHeader's offset and its message;
+ *   TOO_MANY_MESSAGES the event's start and first message;
+ *   OUT_OF_SYNC, DST_TOO_SMALL  the message, its event, its StorageHeader's
+ *                    offset; TOO_MANY_PIECES names message 0.
+ *   A message's number counts, in every event before it, the messages in front
+ *   of that event's first violation (all of them in a well-formed event).
+ *   OUT_OF_SYNC and the kinds behind it are evaluated only when the walk
+ *   (kinds 1..5) refused nothing.  The reference answers an event that is out
+ *   of sync by ignoring it or by aborting the broker; here it is a refusal.  A
+ *   synchronous call returns BMQCRC_EINVAL naming kind, event, message and
+ *   offset; after an asynchronous call bmqcrc_last_storage_apply reports them.
+ * Stricter than the reference.  DATA_RECORD applies the conditions of
+ *   BMQCRC_REC_UNPACK_DATA_RECORD, with "the record ends past end" read as
+ *   "past the message"; the reference only asks that the record fit the blob.
+ *   Nothing StorageEventBuilder emits is refused.  Bytes of a DATA message
+ *   beyond 60 + R are ignored.
+ * The copy runs over all msg_cap slots (the unused ones are empty messages):
+ *   a tight msg_cap is the caller's job.  After a successful call entries
+ *   [n_msgs, msg_cap) of the output arrays are untouched, and nothing at or
+ *   beyond msg_cap (msg_cap + 1 for record_offsets) is ever written.
+ * *result (may be NULL) is written by a synchronous call only.
+ * State.  As bmqcrc_message_records_unpack: takes the workspace mutex of
+ *   (device, stream); restores the caller's current device; allocates its own
+ *   workspace on first use and when msg_cap or n_events grows (56 bytes per
+ *   slot of msg_cap, 16 per event), which bmqcrc_reserve does not cover; is
+ *   not meant to be captured into a hipGraph; is deterministic.  The copy's
+ *   counters live in the call's own scratch: the shape prediction and the
+ *   records of every other bmqcrc_last_* call are never touched. */
+#define BMQCRC_STORAGE_APPLY_OK 0
+#define BMQCRC_STORAGE_APPLY_EVENT_OFFSETS 1     /* event_offsets[e] > event_offsets[e+1], event_offsets[e+1] >
+                                                    events_bytes, or event_offsets[e] not a multiple of 4 */
+#define BMQCRC_STORAGE_APPLY_EVENT_HEADER 2      /* shorter than 8; length field != event size; type neither
+                                                    STORAGE nor PARTITION_SYNC; headerWords * 4 outside [8, size] */
+#define BMQCRC_STORAGE_APPLY_STORAGE_HEADER 3    /* fewer than 12 bytes left; headerWords * 4 < 12; messageWords * 4
+                                                    below the header or past the event; type outside 1..6; fewer
+                                                    than 60 payload bytes; partitionId != partition_id; a DATA
+                                                    message whose journal record is not a MESSAGE record */
+#define BMQCRC_STORAGE_APPLY_DATA_RECORD 4       /* fewer than 8 bytes behind the journal record; DataHeader
+                                                    headerWords or messageWords 0; header + options >= the record;
+                                                    the record ends past the message; last byte not in 1..8 or
+                                                    larger than what header and options leave */
+#define BMQCRC_STORAGE_APPLY_TOO_MANY_MESSAGES 5 /* more than msg_cap messages; index: the lowest event whose
+                                                    last message does not fit */
+#define BMQCRC_STORAGE_APPLY_OUT_OF_SYNC 6       /* 4 x journalOffsetWords != journal_pos + 60 i; a lease id below
+                                                    the predecessor's; the predecessor's lease id with another
+                                                    sequence number than its + 1 (message 0's predecessor is the
+                                                    write head; a higher lease id comes with any sequence
+                                                    number); DATA: 8 x MessageOffsetDwords != data_file_pos + Q[i] */
+#define BMQCRC_STORAGE_APPLY_DST_TOO_SMALL 7     /* 60 n_msgs > journal_dst_bytes or Q[n_msgs] > data_dst_bytes;
+                                                    index: the lowest message ending past its destination, the
+                                                    journal's before the DATA window's */
+#define BMQCRC_STORAGE_APPLY_TOO_MANY_PIECES 8   /* beyond the copy kernel's 2^32-1 16-byte pieces per call */
+
+typedef struct bmqcrc_storage_apply {
+    uint32_t struct_size, reserved;       /* sizeof, 0 */
+    const void* events;                   /* device, 4-byte aligned */
+    uint64_t events_bytes;
+    const uint64_t* event_offsets;        /* device, n_events + 1: event e is [event_offsets[e], event_offsets[e+1]);
+                                             NULL = one event, the whole buffer (n_events must be 1) */
+    uint64_t n_events;
+    uint64_t msg_cap;                     /* capacity of the per-message arrays, < 2^32 */
+    uint32_t partition_id;                /* <= 65535 */
+    uint32_t lease_id;                    /* the write head; 0: none known yet */
+    uint64_t seq;
+    uint64_t journal_pos;                 /* byte of the journal file that journal_dst[0] stands for: multiple of 4, > 0 */
+    uint64_t data_file_pos;               /* byte of the DATA file that data_dst[0] stands for: multiple of 8, > 0 */
+    void* journal_dst;                    /* device, 4-byte aligned */
+    uint64_t journal_dst_bytes;
+    void* data_dst;                       /* device, 8-byte aligned */
+    uint64_t data_dst_bytes;
+    uint8_t* types;                       /* device, msg_cap, may be NULL: StorageMessageType */
+    uint8_t* flags;                       /* device, msg_cap, may be NULL: StorageHeader flags (5 bits) */
+    uint64_t* payload_offsets;            /* device, msg_cap, may be NULL: byte offset in `events` behind the journal record */
+    uint32_t* payload_lengths;            /* device, msg_cap, may be NULL */
+    uint64_t* record_offsets;             /* device, msg_cap + 1, may be NULL: Q, the total behind the last */
+    uint32_t* lengths;                    /* device, msg_cap, may be NULL: application data bytes */
+    uint32_t* expected;                   /* device, msg_cap, may be NULL: the stored CRCs, host order */
+    uint32_t* out;                        /* device, msg_cap, may be NULL: the computed CRCs */
+    uint64_t* event_first;                /* device, n_events + 1, may be NULL: first message of each event, n last */
+} bmqcrc_storage_apply;
+
+/* All fields zero before the first call on (device, stream); after a refused
+ * call only n_events and the refused_* fields are set. */
+typedef struct bmqcrc_storage_apply_result {
+    uint64_t n_events, n_msgs, n_data;    /* n_data: DATA messages */
+    uint64_t journal_bytes, data_bytes;   /* 60 n_msgs, Q[n_msgs] */
+    uint64_t head_seq;                    /* the last message's sequence number and lease id: the new write head */
+    uint32_t head_lease_id;               /* (the one given when there was no message) */
+    uint32_t refused_kind;
+    uint64_t n_bad, first_bad;            /* stored CRC != computed CRC; first_bad = n_msgs when none */
+    uint64_t refused_event, refused_index, refused_offset;
+} bmqcrc_storage_apply_result;
+
+int bmqcrc_storage_event_apply(const bmqcrc_storage_apply* p, bmqcrc_storage_apply_result* result,
+                               const bmqcrc_opts* opts);
+
+/* ABI 2.15.  Result of the previous bmqcrc_storage_event_apply on (device,
+ * stream); waits for it.  `result` may be NULL. */
+int bmqcrc_last_storage_apply(int device, void* stream, bmqcrc_storage_apply_result* result);
+
 /* ---- cluster state ledger (mqbc_clusterstateledgerprotocol.h:76,272) ------ */
 
 /* mqbc::ClusterStateLedgerUtilRc values (mqbc_clusterstateledgerutil.h:65-124)
