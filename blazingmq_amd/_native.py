@@ -311,6 +311,45 @@ if hasattr(lib, "bmqcrc_storage_event_apply"):  # ABI 2.15 (an older build loads
                                                ctypes.POINTER(StorageApplyResult), _popts]
     lib.bmqcrc_last_storage_apply.restype = _int
     lib.bmqcrc_last_storage_apply.argtypes = [_int, _vp, ctypes.POINTER(StorageApplyResult)]
+BMQCRC_STORAGE_PACK_OK = 0
+BMQCRC_STORAGE_PACK_RECORD_HEADER = 1
+BMQCRC_STORAGE_PACK_DATA_OFFSET = 2
+BMQCRC_STORAGE_PACK_DATA_RECORD = 3
+BMQCRC_STORAGE_PACK_EVENT_FIRST = 4
+BMQCRC_STORAGE_PACK_PAYLOAD_TOO_BIG = 5
+BMQCRC_STORAGE_PACK_EVENT_TOO_BIG = 6
+BMQCRC_STORAGE_PACK_DST_TOO_SMALL = 7
+BMQCRC_STORAGE_PACK_TOO_MANY_PIECES = 8
+
+
+class StoragePack(ctypes.Structure):
+    """bmqcrc_storage_pack (include/bmqcrc_protocol.h, ABI 2.16)."""
+    _fields_ = [("struct_size", _u32), ("reserved", _u32), ("journal", _vp),
+                ("journal_bytes", _u64), ("n_records", _u64), ("journal_pos", _u64),
+                ("data", _vp), ("data_bytes", _u64), ("data_file_pos", _u64),
+                ("partition_id", _u32), ("event_type", _u32),
+                ("storage_protocol_version", _u32), ("reserved2", _u32), ("flags", _vp),
+                ("event_first", _vp), ("n_events", _u64), ("max_event_bytes", _u64),
+                ("max_payload_bytes", _u64), ("dst", _vp), ("dst_bytes", _u64),
+                ("event_offsets", _vp), ("types", _vp), ("out", _vp)]
+
+
+class StoragePackResult(ctypes.Structure):
+    """bmqcrc_storage_pack_result (include/bmqcrc_protocol.h, ABI 2.16)."""
+    _fields_ = [("n_events", _u64), ("n_msgs", _u64), ("n_data", _u64), ("total_bytes", _u64),
+                ("n_bad", _u64), ("first_bad", _u64), ("refused_kind", _u32), ("reserved", _u32),
+                ("refused_index", _u64)]
+
+    def as_dict(self):
+        return {f[0]: int(getattr(self, f[0])) for f in self._fields_ if f[0] != "reserved"}
+
+
+if hasattr(lib, "bmqcrc_storage_event_pack"):  # ABI 2.16 (an older build loads for same-box A/B)
+    lib.bmqcrc_storage_event_pack.restype = _int
+    lib.bmqcrc_storage_event_pack.argtypes = [ctypes.POINTER(StoragePack),
+                                              ctypes.POINTER(StoragePackResult), _popts]
+    lib.bmqcrc_last_storage_pack.restype = _int
+    lib.bmqcrc_last_storage_pack.argtypes = [_int, _vp, ctypes.POINTER(StoragePackResult)]
 lib.bmqcrc_journal_scan.restype = _i64
 lib.bmqcrc_journal_scan.argtypes = [_vp, _u64, _vp, _u64, _vp, _pint, _pu64, _vp, _vp, _vp, _vp,
                                     _u64]

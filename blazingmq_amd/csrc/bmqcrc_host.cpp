@@ -199,6 +199,15 @@ struct Workspace {
     DevBuf sap_copy_first, sap_copy_bsum;
     uint32_t sap_lease = 0;
     uint64_t sap_seq = 0;
+    // bmqcrc_storage_event_pack: a set of its own again, its counters followed
+    // by its copy pass's: per record the descriptor its copy reads (8 + 4), the
+    // stored and the computed CRC (4 each), the destination offset (8), the
+    // DATA record's size and its header + options size (4 each), the message
+    // type (1) and the copy pass's piece prefix (4); the layout's block sums
+    // and the copy pass's; the events of the last pack enqueued
+    UnpackScratch spk;
+    DevBuf spk_dst, spk_rec, spk_hdr, spk_type, spk_bsum, spk_copy_first, spk_copy_bsum;
+    uint64_t spk_events = 0;
     // bmqcrc_journal_select: the part of its workspace every call zeroes (the
     // counters, the queue-key and GUID tables, the claims) and the rest (the
     // two record lists, the named DELETIONs, the states); the records of the
@@ -3185,6 +3194,207 @@ int bmqcrc_last_storage_apply(int device, void* stream, bmqcrc_storage_apply_res
     return last_result(device, stream, storage_apply_result, result);
 }
 
+static_assert(BMQCRC_STORAGE_PACK_RECORD_HEADER == BMQCRC_SPK_KIND_RECORD_HEADER &&
+                  BMQCRC_STORAGE_PACK_DATA_OFFSET == BMQCRC_SPK_KIND_DATA_OFFSET &&
+                  BMQCRC_STORAGE_PACK_DATA_RECORD == BMQCRC_SPK_KIND_DATA_RECORD &&
+                  BMQCRC_STORAGE_PACK_EVENT_FIRST == BMQCRC_SPK_KIND_EVENT_FIRST &&
+                  BMQCRC_STORAGE_PACK_PAYLOAD_TOO_BIG == BMQCRC_SPK_KIND_PAYLOAD_TOO_BIG &&
+                  BMQCRC_STORAGE_PACK_EVENT_TOO_BIG == BMQCRC_SPK_KIND_EVENT_TOO_BIG &&
+                  BMQCRC_STORAGE_PACK_DST_TOO_SMALL == BMQCRC_SPK_KIND_DST_TOO_SMALL &&
+                  BMQCRC_STORAGE_PACK_TOO_MANY_PIECES == BMQCRC_SPK_KIND_TOO_MANY_PIECES,
+              "the kernels' refusal kinds are the public ones");
+
+constexpr uint64_t kStorageMaxEventSoft = 512ull << 20;    // EventHeader::k_MAX_SIZE_SOFT
+constexpr uint64_t kStorageMaxEventBytes = (1ull << 31) - 1;  // 31 bits of Length
+constexpr uint64_t kStorageMaxPayloadSoft = 65ull << 20;   // StorageHeader::k_MAX_PAYLOAD_SIZE_SOFT
+constexpr uint64_t kStorageMaxPayloadBytes = 4 * ((1ull << 27) - 1) - 12;  // 27 bits of MessageWords
+constexpr uint64_t kJournalMaxBytes = 4 * 0xFFFFFFFFull;   // where JournalOffsetWords stops
+
+// Result of the storage pack last enqueued on c's workspace, after everything
+// enqueued on its stream (w->mu held); zeros when there was none.
+static int storage_pack_result(Ctx& c, bmqcrc_storage_pack_result* r)
+{
+    unsigned long long ctr[kSpkCtrWords + kCopyCtrWords];
+    const int rc = slot_counters(c, c.w->spk, ctr, r, &r->refused_index);
+    if (rc || !c.w->spk.any) {
+        return rc;
+    }
+    r->n_events = c.w->spk_events;
+    if (r->refused_kind) {
+        return 0;
+    }
+    // the layout placed every message inside dst: the copy pass has nothing to refuse
+    const unsigned long long* cc = ctr + kSpkCtrWords;
+    if (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow]) {
+        return fail(BMQCRC_EIO, "bmqcrc_storage_event_pack: the copy pass refused a message "
+                                "the layout had placed (internal error)");
+    }
+    r->n_data = ctr[kSpkCtrData];
+    r->total_bytes = ctr[kSpkCtrTotal];
+    return 0;
+}
+
+static const char* const kStoragePackRefusals[9] = {
+    "", "BMQCRC_STORAGE_PACK_RECORD_HEADER: record %llu has type 0 or above 5, lease id 0, "
+        "sequence number 0, a wrong magic or a QueueOpType outside 1..4",
+    "BMQCRC_STORAGE_PACK_DATA_OFFSET: MESSAGE record %llu points at offset 0 or outside "
+    "[data_file_pos, data_file_pos+data_bytes]",
+    "BMQCRC_STORAGE_PACK_DATA_RECORD: MESSAGE record %llu points at a malformed DATA record",
+    "BMQCRC_STORAGE_PACK_EVENT_FIRST: event_first[%llu] breaks 0 = first < ... < last = n_records",
+    "BMQCRC_STORAGE_PACK_PAYLOAD_TOO_BIG: the journal and DATA record of record %llu are longer "
+    "than max_payload_bytes",
+    "BMQCRC_STORAGE_PACK_EVENT_TOO_BIG: event %llu is longer than max_event_bytes",
+    "BMQCRC_STORAGE_PACK_DST_TOO_SMALL: event %llu ends past dst_bytes",
+    "BMQCRC_STORAGE_PACK_TOO_MANY_PIECES: more than 2^32-1 16-byte pieces of application data "
+    "in one call (index %llu)"};
+
+int bmqcrc_storage_event_pack(const bmqcrc_storage_pack* p, bmqcrc_storage_pack_result* result,
+                              const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    bmqcrc_opts o;
+    int rc;
+    if ((rc = check_struct(p, "bmqcrc_storage_pack", p ? p->reserved2 : 0,
+                           ".reserved and reserved2 must be 0")) ||
+        (rc = device_call_opts(opts, "bmqcrc_storage_event_pack", &o))) {
+        return rc;
+    }
+    if ((rc = refuse_null({{!p->journal, "journal"}, {!p->data, "data"}, {!p->dst, "dst"}}))) {
+        return rc;
+    }
+    const uint64_t n = p->n_records;
+    const struct {
+        bool bad;
+        const char* what;
+    } checks[] = {
+        {((uintptr_t)p->journal & 3u) != 0, "journal must be 4-byte aligned"},
+        {((uintptr_t)p->data & 7u) != 0, "data must be 8-byte aligned"},
+        {((uintptr_t)p->dst & 3u) != 0, "dst must be 4-byte aligned"},
+        {n > 0xFFFFFFFFull || p->journal_bytes != kJournalRecordBytes * n,
+         "journal_bytes must be 60 n_records"},
+        {!p->event_first && p->n_events != 1,
+         "event_first == NULL means one event: n_events must be 1"},
+        {n && (p->n_events < 1 || p->n_events > n),
+         "n_events must lie in [1, n_records]: no event is empty"},
+        {p->journal_pos == 0 || (p->journal_pos & 3u),
+         "journal_pos must be a multiple of 4 and not 0 (a journal begins with its file headers)"},
+        {p->journal_pos > kJournalMaxBytes ||
+             kJournalRecordBytes * n > kJournalMaxBytes - p->journal_pos,
+         "journal_pos + 60 n_records above 4 (2^32-1): JournalOffsetWords would overflow"},
+        {(p->data_file_pos & 7u) != 0, "data_file_pos must be a multiple of 8"},
+        {p->partition_id > 0xFFFFu, "partition_id must be at most 65535"},
+        {p->event_type != 0 && p->event_type != 8 && p->event_type != 10,
+         "event_type must be 8 (STORAGE), 10 (PARTITION_SYNC) or 0 (STORAGE)"},
+        {p->storage_protocol_version > 3, "storage_protocol_version must be at most 3"},
+        {p->max_event_bytes > kStorageMaxEventBytes,
+         "max_event_bytes above 2^31-1: the EventHeader's length would overflow"},
+        {p->max_payload_bytes > kStorageMaxPayloadBytes,
+         "max_payload_bytes above 4 (2^27-1) - 12: MessageWords would overflow"}};
+    for (const auto& k : checks) {
+        if (k.bad) {
+            return fail(BMQCRC_EINVAL, k.what);
+        }
+    }
+    const uint64_t entries = 8 * (p->n_events + 1);
+    const NamedRange journal = {p->journal, p->journal_bytes, "[journal, journal+journal_bytes)"};
+    const NamedRange data = {p->data, p->data_bytes, "[data, data+data_bytes)"};
+    const NamedRange flags = {p->flags, p->flags ? n : 0, "flags"};
+    const NamedRange first = {p->event_first, p->event_first ? entries : 0, "event_first"};
+    const NamedRange dst = {p->dst, p->dst_bytes, "[dst, dst+dst_bytes)"};
+    const NamedRange offsets = {p->event_offsets, entries, "event_offsets"};
+    const NamedRange types = {p->types, n, "types"};
+    const NamedRange out = {p->out, 4 * n, "out"};
+    if ((rc = refuse_overlap({dst, offsets, types, out}, {journal, data, flags, first})) ||
+        (rc = refuse_overlap({offsets, types, out}, {dst})) ||
+        (rc = refuse_overlap({types, out}, {offsets})) || (rc = refuse_overlap({out}, {types}))) {
+        return rc;
+    }
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    UnpackScratch& s = w->spk;
+    const uint64_t recs = std::max<uint64_t>(n, 1);
+    if ((rc = s.ensure(n, true, kSpkCtrWords + kCopyCtrWords)) ||
+        (rc = w->spk_bsum.ensure(8ull * 2 * kPackBlocks)) || (rc = w->spk_dst.ensure(8 * recs)) ||
+        (rc = w->spk_rec.ensure(4 * recs)) || (rc = w->spk_hdr.ensure(4 * recs)) ||
+        (rc = w->spk_type.ensure(recs))) {
+        return rc;
+    }
+    HIP_TRY(hipMemsetAsync(s.ctr.p, 0, 8 * (kSpkCtrWords + kCopyCtrWords), c.s));
+    s.n = n;
+    s.any = true;
+    w->spk_events = n ? p->n_events : 0;
+    if (n) {
+        SpkArgs a;
+        memset(&a, 0, sizeof(a));
+        a.journal = (const uint32_t*)p->journal;
+        a.n = n;
+        a.journal_pos = p->journal_pos;
+        a.data = (const uint8_t*)p->data;
+        a.data_bytes = p->data_bytes;
+        a.data_file_pos = p->data_file_pos;
+        a.flags = p->flags;
+        a.event_first = p->event_first;
+        a.n_events = p->n_events;
+        a.max_event_bytes = p->max_event_bytes ? p->max_event_bytes : kStorageMaxEventSoft;
+        a.max_payload_bytes = p->max_payload_bytes ? p->max_payload_bytes : kStorageMaxPayloadSoft;
+        a.partition_id = p->partition_id;
+        a.event_type = p->event_type ? p->event_type : 8u;
+        a.spv = p->storage_protocol_version;
+        a.dst = (uint8_t*)p->dst;
+        a.dst_bytes = p->dst_bytes;
+        a.event_offsets = p->event_offsets;
+        a.types = p->types;
+        a.out = p->out;
+        a.ws_off = (unsigned long long*)s.off.p;
+        a.ws_len = (uint32_t*)s.len.p;
+        a.off = (unsigned long long*)w->spk_dst.p;
+        a.ws_exp = (uint32_t*)s.exp.p;
+        a.ws_out = (const uint32_t*)s.out.p;
+        a.ws_rec = (uint32_t*)w->spk_rec.p;
+        a.ws_hdr = (uint32_t*)w->spk_hdr.p;
+        a.ws_type = (uint8_t*)w->spk_type.p;
+        a.bsum = (unsigned long long*)w->spk_bsum.p;
+        a.ctr = (unsigned long long*)s.ctr.p;
+        layout_split(n, &a.per_block, &a.nblocks);
+        if (bmqcrc_launch_storage_pack_layout(&a, (void*)c.s)) {
+            return launch_failed("storage-pack layout");
+        }
+        // the records as the copy's messages: the descriptors are the workspace's
+        CopyArgs ca;
+        memset(&ca, 0, sizeof(ca));
+        ca.src = a.data;
+        ca.src_bytes = a.data_bytes;
+        ca.src_offsets = (const uint64_t*)a.ws_off;
+        ca.lengths = a.ws_len;
+        ca.dst = a.dst;
+        ca.dst_bytes = a.dst_bytes;
+        ca.dst_offsets = (const uint64_t*)a.off;
+        ca.out = (uint32_t*)s.out.p;
+        ca.n = n;
+        if ((rc = enqueue_copy(c, ca, w->spk_copy_first, w->spk_copy_bsum, a.ctr + kSpkCtrWords))) {
+            return rc;
+        }
+        if (bmqcrc_launch_storage_pack_frame(&a, (void*)c.s)) {
+            return launch_failed("storage-pack frame");
+        }
+    }
+    bmqcrc_storage_pack_result r;
+    if ((rc = sync_result(c, o, storage_pack_result, result, &r))) {
+        return rc;
+    }
+    return r.refused_kind ? refused(kStoragePackRefusals, r.refused_kind, r.refused_index) : 0;
+}
+
+int bmqcrc_last_storage_pack(int device, void* stream, bmqcrc_storage_pack_result* result)
+{
+    return last_result(device, stream, storage_pack_result, result);
+}
+
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,
                        uint32_t* seg_bytes)
 {
@@ -3358,7 +3568,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 15u;
+    return (2u << 16) | 16u;
 }
 
 }  // extern "C"

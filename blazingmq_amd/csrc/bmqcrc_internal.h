@@ -490,7 +490,65 @@ struct SapArgs {
     uint32_t nblocks;               // layout blocks (<= kPackBlocks)
 };
 
+// ---- bmqcrc_storage_event_pack (crc32c_storage_pack.hip, ABI 2.16) ---------
+// The classify, count and seal grid and block are kPackBlocks x kPackThreads
+// over contiguous record ranges (layout_split), the check kernel's one event
+// per thread, the frame kernel's kPackFrameBlocks x kPackFrameThreads.
+// SpkArgs::ctr words: the first four are the unpackers' (kSlotCtr*: the
+// refusal, the records, the mismatches and the lowest), behind them the call's
+constexpr int kSpkCtrTotal = 4;      // bytes of all events (k_spk_check)
+constexpr int kSpkCtrData = 5;       // DATA messages (k_spk_frame)
+constexpr int kSpkCtrWords = 6;
+// BMQCRC_STORAGE_PACK_* of bmqcrc_protocol.h, which the kernels do not include
+#define BMQCRC_SPK_KIND_RECORD_HEADER 1u
+#define BMQCRC_SPK_KIND_DATA_OFFSET 2u
+#define BMQCRC_SPK_KIND_DATA_RECORD 3u
+#define BMQCRC_SPK_KIND_EVENT_FIRST 4u
+#define BMQCRC_SPK_KIND_PAYLOAD_TOO_BIG 5u
+#define BMQCRC_SPK_KIND_EVENT_TOO_BIG 6u
+#define BMQCRC_SPK_KIND_DST_TOO_SMALL 7u
+#define BMQCRC_SPK_KIND_TOO_MANY_PIECES 8u
+
+struct SpkArgs {
+    const uint32_t* journal;        // device, 4-byte aligned: n records of 15 dwords
+    uint64_t n;                     // records = storage messages
+    uint64_t journal_pos;           // byte of the journal file that record 0 stands for
+    const uint8_t* data;            // device, 8-byte aligned: the DATA-file window
+    uint64_t data_bytes;
+    uint64_t data_file_pos;         // byte of the DATA file that data[0] stands for
+    const uint8_t* flags;           // device, n, or nullptr (all zero)
+    const uint64_t* event_first;    // device, n_events + 1, or nullptr (one event)
+    uint64_t n_events;
+    uint64_t max_event_bytes;
+    uint64_t max_payload_bytes;
+    uint32_t partition_id;
+    uint32_t event_type;            // 8 or 10
+    uint32_t spv;                   // StorageProtocolVersion, 2 bits
+    uint8_t* dst;                   // device, 4-byte aligned
+    uint64_t dst_bytes;
+    uint64_t* event_offsets;        // the caller's arrays (device; n_events + 1, n, n), each may
+    uint8_t* types;                 // be nullptr: written by k_spk_frame, when nothing was
+    uint32_t* out;                  // refused
+    unsigned long long* ws_off;     // workspace, n: what the copy reads -- the application data's
+    uint32_t* ws_len;               // offset in `data` and length (0 when not a MESSAGE record) --
+    unsigned long long* off;        // and where it goes in dst (before: the prefix of B)
+    uint32_t* ws_exp;               // workspace, n: the MessageRecords' stored CRCs
+    const uint32_t* ws_out;         // workspace, n: the copy's CRCs
+    uint32_t* ws_rec;               // workspace, n: the DATA record's bytes R, its header + options
+    uint32_t* ws_hdr;               // bytes, and the StorageMessageType (0: the record was
+    uint8_t* ws_type;               // refused)
+    unsigned long long* bsum;       // workspace, 2 * kPackBlocks: framed bytes | pieces per block
+    unsigned long long* ctr;        // workspace, kSpkCtrWords, zeroed before the launch
+    uint64_t per_block;             // records per layout block (multiple of kPackThreads)
+    uint32_t nblocks;               // layout blocks (<= kPackBlocks)
+};
+
 }  // namespace bmqcrc
+
+// Launchers (crc32c_storage_pack.hip).  Asynchronous on `stream`: the layout
+// before bmqcrc_launch_copy (it writes the copy's descriptors), the frame after.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_storage_pack_layout(const bmqcrc::SpkArgs* a, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_storage_pack_frame(const bmqcrc::SpkArgs* a, void* stream);
 
 // Launchers (crc32c_storage_apply.hip).  Asynchronous on `stream`: the layout
 // before bmqcrc_launch_copy (it writes the copy's descriptors), the frame after.

@@ -23,7 +23,9 @@ bmqp_protocol.h):
 (mqbs_filestore.cpp:6339) with ``FileStoreUtil::writeMessageRecordImpl``
 (mqbs_filestoreutil.cpp:1408): ``bmqcrc_storage_event_apply``, which also
 checks the CRC the producer stored at the cost of the copy the replica has to
-make anyway.
+make anyway.  ``pack_storage_events`` is the primary's side,
+``FileStore::replicateRecord`` (mqbs_filestore.cpp:5763) with the builder above:
+``bmqcrc_storage_event_pack``, which checks the same CRC on the way out.
 """
 import collections
 import ctypes
@@ -281,6 +283,129 @@ def apply_events(events, event_offsets=None, *, partition_id, journal_pos, data_
     return Applied(journal_dst[:int(r.journal_bytes)], data_dst[:int(r.data_bytes)],
                    *[t[:n] for t in u[2:6]], u.record_offsets[:n + 1],
                    *[t[:n] for t in u[7:10]], u.event_first, r.as_dict())
+
+
+Packed = collections.namedtuple("Packed", "events event_offsets types crcs result")
+
+PACK_REFUSALS = ("OK", "RECORD_HEADER", "DATA_OFFSET", "DATA_RECORD", "EVENT_FIRST",
+                 "PAYLOAD_TOO_BIG", "EVENT_TOO_BIG", "DST_TOO_SMALL", "TOO_MANY_PIECES")
+
+
+def pack_storage_events(journal_run, data, *, journal_pos, data_file_pos, partition_id,
+                        event_first=None, flags=None, event_type=EVENT_TYPE_STORAGE,
+                        storage_protocol_version=STORAGE_PROTOCOL_VERSION,
+                        max_event_bytes=None, max_payload_bytes=None, dst=None, stream=None,
+                        sync=True):
+    """Pack device-resident journal records and the DATA records they name
+    into STORAGE events on the GPU (``bmqcrc_storage_event_pack``): the
+    device-side form of ``FileStore::replicateRecord`` with
+    ``StorageEventBuilder.pack_message``, byte for byte what the builder emits
+    -- and the application data's CRC32-C compared with the one the
+    MessageRecord stores, at the cost of the copy the primary has to make
+    anyway ("verify on send").
+
+    ``journal_run`` is a contiguous uint8 device tensor of 60-byte records (the
+    record run, not the journal file with its headers; 4-byte aligned) whose
+    record 0 stands for byte ``journal_pos`` of the journal file; ``data`` a
+    uint8 window of the DATA file (8-byte aligned) whose byte 0 stands for byte
+    ``data_file_pos`` of that file.  A MESSAGE record becomes a DATA message
+    with its whole DATA record as payload, CONFIRM, DELETION and JOURNAL_OP
+    records messages of their own type, a QUEUE_OP record a QUEUE_OP message
+    (PURGE, DELETION) or a QLIST message carrying the journal record only
+    (CREATION, ADDITION).  ``event_first`` (int64, one entry more than there
+    are events, 0 first and the record count last) cuts the events; None is one
+    event.  ``flags`` (uint8 per record, low 5 bits) are the StorageHeader
+    flags; None is 0.  ``max_event_bytes`` / ``max_payload_bytes`` None are the
+    reference's soft limits.  ``dst=None`` allocates the bound
+    ``8 n_events + 72 n + data.numel()``, which is enough when no two MESSAGE
+    records share a DATA record; otherwise the call refuses with
+    DST_TOO_SMALL and the caller passes a larger ``dst``.  With ``sync=True``
+    the events are sliced to ``total_bytes``.  ``sync=False`` requires ``dst``.
+
+    Returns the named tuple ``(events, event_offsets, types, crcs, result)``:
+    the event bytes, int64 offsets of the events with the total last, uint8
+    message types, int32 computed CRCs (0 for a record that is not a MESSAGE
+    record) and the dict of ``last_storage_pack`` (None with ``sync=False``).
+    CRC mismatches do not fail the call: ``result["n_bad"]`` /
+    ``["first_bad"]`` report them and the bytes go out as they are.  All or
+    nothing: a malformed record, a DATA record outside the window, a bad
+    ``event_first``, a payload or event above its cap or a destination too
+    small (``PACK_REFUSALS``) writes nothing and, with ``sync=True``, raises
+    ``BmqCrcError`` (BMQCRC_EINVAL) naming kind and index; with ``sync=False``
+    ask ``last_storage_pack``.  Not meant to be captured into a graph."""
+    import torch
+    for name, t, dt in (("journal_run", journal_run, torch.uint8), ("data", data, torch.uint8),
+                        ("event_first", event_first, torch.int64), ("flags", flags, torch.uint8),
+                        ("dst", dst, torch.uint8)):
+        if name not in ("journal_run", "data") and t is None:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous()):
+            raise TypeError("%s must be a contiguous %s tensor" % (name, dt))
+    dev = journal_run.device
+    if not journal_run.is_cuda:
+        raise TypeError("pack_storage_events takes device tensors only (journal_run is on %s)"
+                        % dev)
+    for name, t in (("data", data), ("event_first", event_first), ("flags", flags), ("dst", dst)):
+        if t is not None and t.device != dev:
+            raise TypeError("%s must be on %s like journal_run" % (name, dev))
+    if journal_run.numel() % JOURNAL_RECORD_SIZE:
+        raise ValueError("journal_run must hold whole 60-byte records")
+    n = journal_run.numel() // JOURNAL_RECORD_SIZE
+    if event_first is not None and event_first.numel() < 1:
+        raise ValueError("event_first needs one entry more than there are events")
+    if flags is not None and flags.numel() != n:
+        raise ValueError("flags needs one entry per record")
+    if not sync and dst is None:
+        raise ValueError("dst is required when sync=False")
+    n_events = event_first.numel() - 1 if event_first is not None else 1
+
+    def new(shape, dt):
+        return torch.empty(shape, dtype=dt, device=dev)
+    spare = new(8, torch.uint8)  # (an empty tensor has no address: the call wants one)
+    if dst is None:
+        dst = new(EVENT_HEADER_SIZE * n_events +
+                  (STORAGE_HEADER_SIZE + JOURNAL_RECORD_SIZE) * n + data.numel(), torch.uint8)
+    u = Packed(dst, new(n_events + 1, torch.int64), new(n, torch.uint8), new(n, torch.int32), None)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    p = N.StoragePack()
+    p.struct_size = ctypes.sizeof(N.StoragePack)
+    p.journal = journal_run.data_ptr() or spare.data_ptr()
+    p.journal_bytes, p.n_records, p.journal_pos = journal_run.numel(), n, int(journal_pos)
+    p.data, p.data_bytes = data.data_ptr() or spare.data_ptr(), data.numel()
+    p.data_file_pos, p.partition_id = int(data_file_pos), int(partition_id)
+    p.event_type, p.storage_protocol_version = int(event_type), int(storage_protocol_version)
+    p.flags = flags.data_ptr() or None if flags is not None else None
+    p.event_first = event_first.data_ptr() if event_first is not None else None
+    p.n_events = n_events
+    p.max_event_bytes = int(max_event_bytes or 0)
+    p.max_payload_bytes = int(max_payload_bytes or 0)
+    p.dst, p.dst_bytes = dst.data_ptr() or spare.data_ptr(), dst.numel()
+    p.event_offsets = u.event_offsets.data_ptr()
+    p.types, p.out = u.types.data_ptr() or None, u.crcs.data_ptr() or None
+    o = N.make_opts(device=dev.index if dev.index is not None else -1, stream=stream.cuda_stream,
+                    flags=N.BMQCRC_F_DEVICE_PTRS | (0 if sync else N.BMQCRC_F_ASYNC))
+    r = N.StoragePackResult()
+    N.check(N.lib.bmqcrc_storage_event_pack(ctypes.byref(p), ctypes.byref(r), ctypes.byref(o)))
+    if not sync:
+        return u
+    return Packed(dst[:int(r.total_bytes)], u.event_offsets, u.types, u.crcs, r.as_dict())
+
+
+def last_storage_pack(device, stream=None):
+    """The result of the previous ``pack_storage_events`` on (device, stream)
+    (bmqcrc_last_storage_pack), as a dict; waits for it.  ``n_events``,
+    ``n_msgs`` (the records), ``n_data`` (DATA messages), ``total_bytes`` (of
+    all events), ``n_bad`` and ``first_bad`` (MESSAGE records whose computed
+    CRC differs from the stored one, and the lowest; ``n_msgs`` when none),
+    ``refused_kind`` (0, ``BMQCRC_STORAGE_PACK_OK``, or the kind, see
+    ``PACK_REFUSALS``: then all of the above but ``n_events`` are 0) and
+    ``refused_index`` (a record, an ``event_first`` entry or an event, by
+    kind).  ``stream=None`` is the device's default stream."""
+    r = N.StoragePackResult()
+    N.check(N.lib.bmqcrc_last_storage_pack(
+        device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
+    return r.as_dict()
 
 
 def last_storage_apply(device, stream=None):

@@ -808,6 +808,168 @@ int bmqcrc_storage_event_apply(const bmqcrc_storage_apply* p, bmqcrc_storage_app
  * stream); waits for it.  `result` may be NULL. */
 int bmqcrc_last_storage_apply(int device, void* stream, bmqcrc_storage_apply_result* result);
 
+/* ABI 2.16.  The primary's side of replication: journal records and the DATA
+ * records they name, both in device memory, are packed ON THE DEVICE into the
+ * STORAGE events the replicas receive -- FileStore::replicateRecord with
+ * bmqp::StorageEventBuilder::packMessage for a batch of records in one
+ * asynchronous call, byte for byte what the builder emits.  The application
+ * data of every DATA message is moved by the fused copy of bmqcrc_crc32c_copy,
+ * whose CRC32-C is compared with the one the MessageRecord stores ("verify on
+ * send"), at the cost of the copy the primary has to make anyway.  No payload
+ * byte and no descriptor crosses PCIe.
+ *
+ * Records.  Record i is journal[60 i .. 60 i + 60), i = 0 .. n_records - 1: the
+ *   record run, not the journal file with its headers.  journal_pos is the byte
+ *   of the journal file that record 0 stands for.  `data` is a window of the
+ *   DATA file and data_file_pos the byte of that file that data[0] stands for,
+ *   as in bmqcrc_message_records_unpack: a MESSAGE record's DATA record begins
+ *   at byte o = 8 x MessageOffsetDwords (the BE u32 at byte 32) of the file,
+ *   byte o - data_file_pos of the window.
+ * One storage message per record, in record order.  Its StorageMessageType
+ *   comes from the RecordType (the high 4 bits of byte 0):
+ *     MESSAGE (1)     DATA (1), with its whole DATA record as payload:
+ *                     DataHeader, option words, application data, 1..8 padding
+ *                     bytes, R = 4 x DataHeader.messageWords bytes in all;
+ *     CONFIRM (2)     CONFIRM (3);    DELETION (3)  DELETION (4);
+ *     JOURNAL_OP (5)  JOURNAL_OP (5);
+ *     QUEUE_OP (4)    by its QueueOpType, the BE u32 at byte 32: PURGE (1) or
+ *                     DELETION (3) give QUEUE_OP (6); CREATION (2) or ADDITION
+ *                     (4) give QLIST (2) CARRYING THE JOURNAL RECORD ONLY, which
+ *                     is what FileStore::writeQueueCreationRecord hands
+ *                     replicateRecord when the cluster is not QLIST aware.
+ *   Not built: the QLIST file and a QLIST message's payload (the QLIST record)
+ *   stay on the host, as in bmqcrc_storage_event_apply.  R = 0 for every record
+ *   that is not a MESSAGE record.
+ * Events.  Event e holds records [event_first[e], event_first[e + 1]);
+ *   event_first has n_events + 1 entries, 0 first and n_records last, strictly
+ *   increasing (no event is empty).  event_first == NULL means one event
+ *   (n_events must be 1).  The caller cuts the events, as in
+ *   bmqcrc_put_event_pack: a greedy fill to a size cap is a serial decision the
+ *   broker makes by its own flush policy.
+ * Layout.  With B[i] = 12 + 60 + R[i], P the 64-bit exclusive prefix of B and
+ *   e(i) the event of message i: event e lies at dst + 8 e + P[event_first[e]],
+ *   message i's StorageHeader at dst + 8 (e(i) + 1) + P[i], its journal record
+ *   12 bytes behind that and its DATA record 72 bytes behind it.
+ *   EventHeader (8 bytes): BE u32 length of the event (fragment bit 0); a byte
+ *   (1 << 6) | event_type; a byte 2 (headerWords); two bytes 0.  event_type is
+ *   STORAGE (8) or PARTITION_SYNC (10), 0 means STORAGE; PARTITION_SYNC is the
+ *   same bytes under another type.
+ *   StorageHeader (12 bytes): BE u32 (flags[i] & 31) << 27 | (18 + R[i] / 4); a
+ *   byte (storage_protocol_version << 4) | 3; a byte StorageMessageType; BE u16
+ *   partition_id; BE u32 JournalOffsetWords = (journal_pos + 60 i) / 4.
+ *   flags == NULL means 0 for every record.  The reference sets bit 0
+ *   (RECEIPT_REQUESTED) on DATA messages that want a receipt and 0 elsewhere;
+ *   here the caller decides, for any type.
+ *   The journal record and the DATA record's DataHeader, option words and
+ *   padding bytes are copied as they are; the application data, which lies
+ *   between header plus options and the padding, is moved by the fused copy.
+ * Outputs, each may be NULL: event_offsets (n_events + 1 entries: the byte of
+ *   dst where each event starts, the total behind the last), types[i] (the
+ *   StorageMessageType chosen), out[i] (the computed CRC32-C of the application
+ *   data, 0 for a record that is not a MESSAGE record).
+ * Verify on send.  expected[i] is the MessageRecord's CRC, the BE u32 at byte 52.
+ *   n_bad counts the MESSAGE records whose computed CRC differs, first_bad is the
+ *   lowest (n_records when none).  A mismatch does not fail the call and the
+ *   bytes go out as they are: whether to replicate them is the caller's decision.
+ * All or nothing, decided on the device.  One violation anywhere refuses the
+ *   call, and a refused call writes nothing to dst or to any output array.  The
+ *   lowest kind wins and within it the lowest index (BMQCRC_STORAGE_PACK_* below;
+ *   the index is a record, an event_first entry or an event, by kind).  The
+ *   DATA-window checks are made in this order and no DATA byte is loaded before
+ *   its range is shown to lie in the window.  EVENT_TOO_BIG, DST_TOO_SMALL and
+ *   TOO_MANY_PIECES are evaluated only when no lower kind was raised.
+ *   NOT checked: GUIDs, queue keys, the order of sequence numbers, queue
+ *   liveness.  The primary wrote these records itself, and bmqcrc_journal_select
+ *   holds those checks.  A synchronous call returns BMQCRC_EINVAL naming kind and
+ *   index; after an asynchronous call bmqcrc_last_storage_pack reports them.
+ * Caps.  max_event_bytes 0 means EventHeader::k_MAX_SIZE_SOFT (512 MiB), at most
+ *   2^31 - 1; max_payload_bytes 0 means StorageHeader::k_MAX_PAYLOAD_SIZE_SOFT
+ *   (65 MiB), at most 4 (2^27 - 1) - 12 so that MessageWords cannot overflow.
+ * Options.  Device pointers only: BMQCRC_F_DEVICE_PTRS is required,
+ *   BMQCRC_F_ASYNC allowed; any other flag, ndevices > 1, a wrong struct_size or
+ *   a non-zero reserved field; journal, data or dst null; journal or dst not
+ *   4-byte aligned, data not 8-byte aligned; journal_bytes != 60 n_records;
+ *   event_first == NULL with n_events != 1; n_events outside [1, n_records] when
+ *   n_records > 0; journal_pos 0 or no multiple of 4, or journal_pos + 60
+ *   n_records above 4 (2^32 - 1); data_file_pos no multiple of 8; partition_id
+ *   above 65535; event_type other than 0, 8 or 10; storage_protocol_version
+ *   above 3; a cap above its limit; dst or an output array meeting an input
+ *   (journal, data, flags, event_first), dst or another output array is
+ *   BMQCRC_EINVAL, answered on the host before the device lookup.
+ *   n_records == 0 launches nothing, writes nothing and reports zeros.
+ * The copy runs over the n_records records (those that are not MESSAGE records
+ *   are empty messages).  Nothing at or beyond dst_bytes, n_events + 1 entries
+ *   of event_offsets or n_records entries of types and out is ever written.
+ * *result (may be NULL) is written by a synchronous call only.
+ * State.  As bmqcrc_storage_event_apply: takes the workspace mutex of (device,
+ *   stream); restores the caller's current device; allocates its own workspace
+ *   on first use and when n_records grows (41 bytes per record, none per event),
+ *   which bmqcrc_reserve does not cover; is not meant to be captured into a
+ *   hipGraph; is deterministic.  The copy's counters live in the call's own
+ *   scratch: the shape prediction and the records of every other bmqcrc_last_*
+ *   call are never touched. */
+#define BMQCRC_STORAGE_PACK_OK 0
+#define BMQCRC_STORAGE_PACK_RECORD_HEADER 1    /* BMQCRC_REC_UNPACK_RECORD_HEADER's conditions (type 0, lease id 0,
+                                                  sequence number 0, a wrong magic); a type above 5; a QUEUE_OP
+                                                  record whose QueueOpType is outside 1..4.  Index: the record */
+#define BMQCRC_STORAGE_PACK_DATA_OFFSET 2      /* a MESSAGE record with o == 0, o < data_file_pos or
+                                                  o - data_file_pos > data_bytes.  Index: the record */
+#define BMQCRC_STORAGE_PACK_DATA_RECORD 3      /* a MESSAGE record with fewer than 8 bytes of window at its
+                                                  offset; DataHeader headerWords or messageWords 0; header +
+                                                  options >= the record; the record ends past the window; last
+                                                  byte not in 1..8 or larger than what header and options leave.
+                                                  Index: the record */
+#define BMQCRC_STORAGE_PACK_EVENT_FIRST 4      /* event_first[0] != 0, event_first[e] >= event_first[e + 1] or
+                                                  event_first[n_events] != n_records.  Index: the entry */
+#define BMQCRC_STORAGE_PACK_PAYLOAD_TOO_BIG 5  /* 60 + R[i] > max_payload_bytes.  Index: the record */
+#define BMQCRC_STORAGE_PACK_EVENT_TOO_BIG 6    /* an event longer than max_event_bytes.  Index: the event */
+#define BMQCRC_STORAGE_PACK_DST_TOO_SMALL 7    /* index: the lowest event ending past dst_bytes */
+#define BMQCRC_STORAGE_PACK_TOO_MANY_PIECES 8  /* beyond the copy kernel's 2^32-1 16-byte pieces per call: the sum
+                                                  over the MESSAGE records with application data of
+                                                  ((length + 15) >> 4) + 1.  Index 0 */
+
+typedef struct bmqcrc_storage_pack {
+    uint32_t struct_size, reserved;       /* sizeof, 0 */
+    const void* journal;                  /* device, 4-byte aligned: n_records 60-byte records, the record run */
+    uint64_t journal_bytes;               /* == 60 * n_records */
+    uint64_t n_records;
+    uint64_t journal_pos;                 /* byte of the journal file that record 0 stands for: multiple of 4, > 0 */
+    const void* data;                     /* device, 8-byte aligned: the DATA-file window */
+    uint64_t data_bytes;
+    uint64_t data_file_pos;               /* byte of the DATA file that data[0] stands for: multiple of 8 */
+    uint32_t partition_id;                /* <= 65535 */
+    uint32_t event_type;                  /* 8 STORAGE, 10 PARTITION_SYNC, 0 = STORAGE */
+    uint32_t storage_protocol_version;    /* <= 3 */
+    uint32_t reserved2;                   /* 0 */
+    const uint8_t* flags;                 /* device, n_records, may be NULL (all 0): StorageHeader flags, low 5 bits */
+    const uint64_t* event_first;          /* device, n_events + 1; NULL = one event (n_events must be 1) */
+    uint64_t n_events;
+    uint64_t max_event_bytes;             /* 0 = 512 MiB; <= 2^31 - 1 */
+    uint64_t max_payload_bytes;           /* 0 = 65 MiB; <= 4 (2^27 - 1) - 12 */
+    void* dst;                            /* device, 4-byte aligned */
+    uint64_t dst_bytes;
+    uint64_t* event_offsets;              /* device, n_events + 1, may be NULL: the total behind the last */
+    uint8_t* types;                       /* device, n_records, may be NULL: StorageMessageType */
+    uint32_t* out;                        /* device, n_records, may be NULL: the computed CRCs */
+} bmqcrc_storage_pack;
+
+/* All fields zero before the first call on (device, stream); after a refused
+ * call only n_events and the refused_* fields are set. */
+typedef struct bmqcrc_storage_pack_result {
+    uint64_t n_events, n_msgs, n_data;    /* n_msgs = n_records; n_data: DATA messages */
+    uint64_t total_bytes;                 /* bytes of all events */
+    uint64_t n_bad, first_bad;            /* stored CRC != computed CRC; first_bad = n_msgs when none */
+    uint32_t refused_kind, reserved;
+    uint64_t refused_index;               /* a record, an event_first entry or an event, by kind */
+} bmqcrc_storage_pack_result;
+
+int bmqcrc_storage_event_pack(const bmqcrc_storage_pack* p, bmqcrc_storage_pack_result* result,
+                              const bmqcrc_opts* opts);
+
+/* ABI 2.16.  Result of the previous bmqcrc_storage_event_pack on (device,
+ * stream); waits for it.  `result` may be NULL. */
+int bmqcrc_last_storage_pack(int device, void* stream, bmqcrc_storage_pack_result* result);
+
 /* ---- cluster state ledger (mqbc_clusterstateledgerprotocol.h:76,272) ------ */
 
 /* mqbc::ClusterStateLedgerUtilRc values (mqbc_clusterstateledgerutil.h:65-124)
