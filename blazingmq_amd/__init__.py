@@ -10,13 +10,16 @@ from .crc32c import (Blob, BmqCrcError, Crc32c, HostRegistration,  # noqa: F401
                      reserve)
 from .put_event import (last_put_pack, last_put_unpack, pack_events,  # noqa: F401
                         unpack_events)
+from .push_event import (PushEventBuilder, PushMessageIterator, last_push_pack,  # noqa: F401
+                         pack_push_events)
 from .storage import (last_journal_select, last_records_pack,  # noqa: F401
                       last_records_unpack, pack_records, select_records, unpack_records)
 from .storage_event import (StorageEventBuilder, StorageMessageIterator,  # noqa: F401
                             apply_events, last_storage_apply, last_storage_pack,
                             pack_storage_events)
 
-__all__ = ["Blob", "BmqCrcError", "Crc32c", "HostRegistration", "StorageEventBuilder",
+__all__ = ["Blob", "BmqCrcError", "Crc32c", "HostRegistration", "PushEventBuilder",
+           "PushMessageIterator", "last_push_pack", "pack_push_events", "StorageEventBuilder",
            "StorageMessageIterator", "apply_events", "last_storage_apply", "calculate_batch_multi",
            "calculate_batch_ptr", "device_count", "fill_synthetic", "forget_shape", "plan_wait",
            "kernel_timing", "last_copy", "last_journal_select", "last_launch", "last_offsets",

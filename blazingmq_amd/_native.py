@@ -350,6 +350,50 @@ if hasattr(lib, "bmqcrc_storage_event_pack"):  # ABI 2.16 (an older build loads 
                                               ctypes.POINTER(StoragePackResult), _popts]
     lib.bmqcrc_last_storage_pack.restype = _int
     lib.bmqcrc_last_storage_pack.argtypes = [_int, _vp, ctypes.POINTER(StoragePackResult)]
+BMQCRC_PUSH_PACK_OK = 0
+BMQCRC_PUSH_PACK_RECORD_INDEX = 1
+BMQCRC_PUSH_PACK_RECORD = 2
+BMQCRC_PUSH_PACK_DATA_OFFSET = 3
+BMQCRC_PUSH_PACK_DATA_RECORD = 4
+BMQCRC_PUSH_PACK_FLAGS = 5
+BMQCRC_PUSH_PACK_EVENT_FIRST = 6
+BMQCRC_PUSH_PACK_PAYLOAD_TOO_BIG = 7
+BMQCRC_PUSH_PACK_EVENT_TOO_BIG = 8
+BMQCRC_PUSH_PACK_DST_TOO_SMALL = 9
+BMQCRC_PUSH_PACK_TOO_MANY_PIECES = 10
+BMQCRC_PUSH_OPTION_NONE = 0
+BMQCRC_PUSH_OPTION_PACKED_RDA = 1
+BMQCRC_PUSH_OPTION_SUB_QUEUE_ID = 2
+BMQCRC_PUSH_OPTION_SUB_QUEUE_INFO = 3
+
+
+class PushPack(ctypes.Structure):
+    """bmqcrc_push_pack (include/bmqcrc_protocol.h, ABI 2.17)."""
+    _fields_ = [("struct_size", _u32), ("reserved", _u32), ("journal", _vp),
+                ("journal_bytes", _u64), ("n_records", _u64), ("data", _vp), ("data_bytes", _u64),
+                ("data_file_pos", _u64), ("records", _vp), ("n", _u64), ("queue_ids", _vp),
+                ("flags", _vp), ("option_mode", _u32), ("reserved2", _u32), ("rda", _vp),
+                ("sub_ids", _vp), ("event_first", _vp), ("n_events", _u64),
+                ("max_event_bytes", _u64), ("max_payload_bytes", _u64), ("dst", _vp),
+                ("dst_bytes", _u64), ("event_offsets", _vp), ("out", _vp), ("lengths", _vp)]
+
+
+class PushPackResult(ctypes.Structure):
+    """bmqcrc_push_pack_result (include/bmqcrc_protocol.h, ABI 2.17)."""
+    _fields_ = [("n_events", _u64), ("n_msgs", _u64), ("total_bytes", _u64), ("n_bad", _u64),
+                ("first_bad", _u64), ("refused_kind", _u32), ("reserved", _u32),
+                ("refused_index", _u64)]
+
+    def as_dict(self):
+        return {f[0]: int(getattr(self, f[0])) for f in self._fields_ if f[0] != "reserved"}
+
+
+if hasattr(lib, "bmqcrc_push_event_pack"):  # ABI 2.17 (an older build loads for same-box A/B)
+    lib.bmqcrc_push_event_pack.restype = _int
+    lib.bmqcrc_push_event_pack.argtypes = [ctypes.POINTER(PushPack),
+                                           ctypes.POINTER(PushPackResult), _popts]
+    lib.bmqcrc_last_push_pack.restype = _int
+    lib.bmqcrc_last_push_pack.argtypes = [_int, _vp, ctypes.POINTER(PushPackResult)]
 lib.bmqcrc_journal_scan.restype = _i64
 lib.bmqcrc_journal_scan.argtypes = [_vp, _u64, _vp, _u64, _vp, _pint, _pu64, _vp, _vp, _vp, _vp,
                                     _u64]

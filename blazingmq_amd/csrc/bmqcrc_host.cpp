@@ -208,6 +208,15 @@ struct Workspace {
     UnpackScratch spk;
     DevBuf spk_dst, spk_rec, spk_hdr, spk_type, spk_bsum, spk_copy_first, spk_copy_bsum;
     uint64_t spk_events = 0;
+    // bmqcrc_push_event_pack: a set of its own again, its counters followed by
+    // its copy pass's: per message the descriptor its copy reads (8 + 4), the
+    // stored and the computed CRC (4 each), the destination offset (8), CAT,
+    // SchemaId and the properties flag (4) and the copy pass's piece prefix
+    // (4); the layout's block sums and the copy pass's; the events of the last
+    // pack enqueued
+    UnpackScratch ppk;
+    DevBuf ppk_dst, ppk_meta, ppk_bsum, ppk_copy_first, ppk_copy_bsum;
+    uint64_t ppk_events = 0;
     // bmqcrc_journal_select: the part of its workspace every call zeroes (the
     // counters, the queue-key and GUID tables, the claims) and the rest (the
     // two record lists, the named DELETIONs, the states); the records of the
@@ -3395,6 +3404,223 @@ int bmqcrc_last_storage_pack(int device, void* stream, bmqcrc_storage_pack_resul
     return last_result(device, stream, storage_pack_result, result);
 }
 
+static_assert(BMQCRC_PUSH_PACK_RECORD_INDEX == BMQCRC_PPK_KIND_RECORD_INDEX &&
+                  BMQCRC_PUSH_PACK_RECORD == BMQCRC_PPK_KIND_RECORD &&
+                  BMQCRC_PUSH_PACK_DATA_OFFSET == BMQCRC_PPK_KIND_DATA_OFFSET &&
+                  BMQCRC_PUSH_PACK_DATA_RECORD == BMQCRC_PPK_KIND_DATA_RECORD &&
+                  BMQCRC_PUSH_PACK_FLAGS == BMQCRC_PPK_KIND_FLAGS &&
+                  BMQCRC_PUSH_PACK_EVENT_FIRST == BMQCRC_PPK_KIND_EVENT_FIRST &&
+                  BMQCRC_PUSH_PACK_PAYLOAD_TOO_BIG == BMQCRC_PPK_KIND_PAYLOAD_TOO_BIG &&
+                  BMQCRC_PUSH_PACK_EVENT_TOO_BIG == BMQCRC_PPK_KIND_EVENT_TOO_BIG &&
+                  BMQCRC_PUSH_PACK_DST_TOO_SMALL == BMQCRC_PPK_KIND_DST_TOO_SMALL &&
+                  BMQCRC_PUSH_PACK_TOO_MANY_PIECES == BMQCRC_PPK_KIND_TOO_MANY_PIECES,
+              "the kernels' refusal kinds are the public ones");
+
+constexpr uint64_t kPushMaxPayloadSoft = 64ull << 20;  // PushHeader::k_MAX_PAYLOAD_SIZE_SOFT
+// 28 bits of MessageWords: the PushHeader, the longest option and the padding beside it
+constexpr uint64_t kPushMaxPayloadBytes = 4 * ((1ull << 28) - 1) - kPushHeaderBytes - 12 - 4;
+
+// Result of the push pack last enqueued on c's workspace, after everything
+// enqueued on its stream (w->mu held); zeros when there was none.
+static int push_pack_result(Ctx& c, bmqcrc_push_pack_result* r)
+{
+    unsigned long long ctr[kPpkCtrWords + kCopyCtrWords];
+    const int rc = slot_counters(c, c.w->ppk, ctr, r, &r->refused_index);
+    if (rc || !c.w->ppk.any) {
+        return rc;
+    }
+    r->n_events = c.w->ppk_events;
+    if (r->refused_kind) {
+        return 0;
+    }
+    // the layout placed every message inside dst: the copy pass has nothing to refuse
+    const unsigned long long* cc = ctr + kPpkCtrWords;
+    if (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow]) {
+        return fail(BMQCRC_EIO, "bmqcrc_push_event_pack: the copy pass refused a message "
+                                "the layout had placed (internal error)");
+    }
+    r->total_bytes = ctr[kPpkCtrTotal];
+    return 0;
+}
+
+static const char* const kPushPackRefusals[11] = {
+    "", "BMQCRC_PUSH_PACK_RECORD_INDEX: records[%llu] is not below n_records",
+    "BMQCRC_PUSH_PACK_RECORD: the record of message %llu is not a MESSAGE record or has type 0, "
+    "lease id 0, sequence number 0 or a wrong magic",
+    "BMQCRC_PUSH_PACK_DATA_OFFSET: the record of message %llu points at offset 0 or outside "
+    "[data_file_pos, data_file_pos+data_bytes]",
+    "BMQCRC_PUSH_PACK_DATA_RECORD: the record of message %llu points at a malformed DATA record",
+    "BMQCRC_PUSH_PACK_FLAGS: flags[%llu] has a bit other than e_OUT_OF_ORDER (4)",
+    "BMQCRC_PUSH_PACK_EVENT_FIRST: event_first[%llu] breaks 0 = first < ... < last = n",
+    "BMQCRC_PUSH_PACK_PAYLOAD_TOO_BIG: the application data of message %llu is longer than "
+    "max_payload_bytes",
+    "BMQCRC_PUSH_PACK_EVENT_TOO_BIG: event %llu is longer than max_event_bytes",
+    "BMQCRC_PUSH_PACK_DST_TOO_SMALL: event %llu ends past dst_bytes",
+    "BMQCRC_PUSH_PACK_TOO_MANY_PIECES: more than 2^32-1 16-byte pieces of application data "
+    "in one call (index %llu)"};
+
+int bmqcrc_push_event_pack(const bmqcrc_push_pack* p, bmqcrc_push_pack_result* result,
+                           const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    bmqcrc_opts o;
+    int rc;
+    if ((rc = check_struct(p, "bmqcrc_push_pack", p ? p->reserved2 : 0,
+                           ".reserved and reserved2 must be 0")) ||
+        (rc = device_call_opts(opts, "bmqcrc_push_event_pack", &o))) {
+        return rc;
+    }
+    if ((rc = refuse_null({{!p->journal, "journal"}, {!p->data, "data"},
+                           {!p->queue_ids, "queue_ids"}}))) {
+        return rc;
+    }
+    const uint64_t n = p->n, nrec = p->n_records;
+    const uint32_t mode = p->option_mode;
+    const bool wants_rda = mode == BMQCRC_PUSH_OPTION_PACKED_RDA ||
+                           mode == BMQCRC_PUSH_OPTION_SUB_QUEUE_INFO;
+    const bool wants_sub = mode == BMQCRC_PUSH_OPTION_SUB_QUEUE_ID ||
+                           mode == BMQCRC_PUSH_OPTION_SUB_QUEUE_INFO;
+    const struct {
+        bool bad;
+        const char* what;
+    } checks[] = {
+        {!p->dst && p->dst_bytes != 0, "dst == NULL is the size-only call: dst_bytes must be 0"},
+        {((uintptr_t)p->journal & 3u) != 0, "journal must be 4-byte aligned"},
+        {((uintptr_t)p->data & 7u) != 0, "data must be 8-byte aligned"},
+        {((uintptr_t)p->dst & 3u) != 0, "dst must be 4-byte aligned"},
+        {nrec > 0xFFFFFFFFull || p->journal_bytes != kJournalRecordBytes * nrec,
+         "journal_bytes must be 60 n_records"},
+        {n > 0xFFFFFFFFull, "n must be below 2^32"},
+        {!p->records && n != nrec, "records == NULL means message m is record m: n must be n_records"},
+        {!p->event_first && p->n_events != 1,
+         "event_first == NULL means one event: n_events must be 1"},
+        {n && (p->n_events < 1 || p->n_events > n),
+         "n_events must lie in [1, n]: no event is empty"},
+        {(p->data_file_pos & 7u) != 0, "data_file_pos must be a multiple of 8"},
+        {mode > BMQCRC_PUSH_OPTION_SUB_QUEUE_INFO, "option_mode must be at most 3"},
+        {wants_rda != (p->rda != nullptr),
+         "rda is required in option modes 1 and 3 and must be NULL in modes 0 and 2"},
+        {wants_sub != (p->sub_ids != nullptr),
+         "sub_ids is required in option modes 2 and 3 and must be NULL in modes 0 and 1"},
+        {p->max_event_bytes > kStorageMaxEventBytes,
+         "max_event_bytes above 2^31-1: the EventHeader's length would overflow"},
+        {p->max_payload_bytes > kPushMaxPayloadBytes,
+         "max_payload_bytes above 4 (2^28-1) - 48: MessageWords would overflow"}};
+    for (const auto& k : checks) {
+        if (k.bad) {
+            return fail(BMQCRC_EINVAL, k.what);
+        }
+    }
+    const uint64_t entries = 8 * (p->n_events + 1);
+    const NamedRange journal = {p->journal, p->journal_bytes, "[journal, journal+journal_bytes)"};
+    const NamedRange data = {p->data, p->data_bytes, "[data, data+data_bytes)"};
+    const NamedRange records = {p->records, p->records ? 4 * n : 0, "records"};
+    const NamedRange queue_ids = {p->queue_ids, 4 * n, "queue_ids"};
+    const NamedRange flags = {p->flags, p->flags ? n : 0, "flags"};
+    const NamedRange rda = {p->rda, p->rda ? n : 0, "rda"};
+    const NamedRange sub_ids = {p->sub_ids, p->sub_ids ? 4 * n : 0, "sub_ids"};
+    const NamedRange first = {p->event_first, p->event_first ? entries : 0, "event_first"};
+    const NamedRange dst = {p->dst, p->dst_bytes, "[dst, dst+dst_bytes)"};
+    const NamedRange offsets = {p->event_offsets, entries, "event_offsets"};
+    const NamedRange out = {p->out, 4 * n, "out"};
+    const NamedRange lengths = {p->lengths, 4 * n, "lengths"};
+    if ((rc = refuse_overlap({dst, offsets, out, lengths},
+                             {journal, data, records, queue_ids, flags, rda, sub_ids, first})) ||
+        (rc = refuse_overlap({offsets, out, lengths}, {dst})) ||
+        (rc = refuse_overlap({out, lengths}, {offsets})) ||
+        (rc = refuse_overlap({lengths}, {out}))) {
+        return rc;
+    }
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    UnpackScratch& s = w->ppk;
+    const uint64_t msgs = std::max<uint64_t>(n, 1);
+    const bool size_only = !p->dst;
+    if ((rc = s.ensure(n, !size_only, kPpkCtrWords + kCopyCtrWords)) ||
+        (rc = w->ppk_bsum.ensure(8ull * 2 * kPackBlocks)) || (rc = w->ppk_dst.ensure(8 * msgs)) ||
+        (rc = w->ppk_meta.ensure(4 * msgs))) {
+        return rc;
+    }
+    HIP_TRY(hipMemsetAsync(s.ctr.p, 0, 8 * (kPpkCtrWords + kCopyCtrWords), c.s));
+    s.n = n;
+    s.any = true;
+    w->ppk_events = n ? p->n_events : 0;
+    if (n) {
+        PpkArgs a;
+        memset(&a, 0, sizeof(a));
+        a.journal = (const uint32_t*)p->journal;
+        a.n_records = nrec;
+        a.data = (const uint8_t*)p->data;
+        a.data_bytes = p->data_bytes;
+        a.data_file_pos = p->data_file_pos;
+        a.records = p->records;
+        a.queue_ids = p->queue_ids;
+        a.flags = p->flags;
+        a.rda = p->rda;
+        a.sub_ids = p->sub_ids;
+        a.option_mode = mode;
+        a.opt_bytes = 4 * mode;  // 0, 4, 8, 12
+        a.event_first = p->event_first;
+        a.n = n;
+        a.n_events = p->n_events;
+        a.max_event_bytes = p->max_event_bytes ? p->max_event_bytes : kStorageMaxEventSoft;
+        a.max_payload_bytes = p->max_payload_bytes ? p->max_payload_bytes : kPushMaxPayloadSoft;
+        a.dst = (uint8_t*)p->dst;
+        a.dst_bytes = p->dst_bytes;
+        a.event_offsets = p->event_offsets;
+        a.out = p->out;
+        a.lengths = p->lengths;
+        a.ws_off = (unsigned long long*)s.off.p;
+        a.ws_len = (uint32_t*)s.len.p;
+        a.off = (unsigned long long*)w->ppk_dst.p;
+        a.ws_exp = (uint32_t*)s.exp.p;
+        a.ws_out = (const uint32_t*)s.out.p;
+        a.ws_meta = (uint32_t*)w->ppk_meta.p;
+        a.bsum = (unsigned long long*)w->ppk_bsum.p;
+        a.ctr = (unsigned long long*)s.ctr.p;
+        layout_split(n, &a.per_block, &a.nblocks);
+        if (bmqcrc_launch_push_pack_layout(&a, (void*)c.s)) {
+            return launch_failed("push-pack layout");
+        }
+        if (!size_only) {
+            // the messages as the copy's: the descriptors are the workspace's
+            CopyArgs ca;
+            memset(&ca, 0, sizeof(ca));
+            ca.src = a.data;
+            ca.src_bytes = a.data_bytes;
+            ca.src_offsets = (const uint64_t*)a.ws_off;
+            ca.lengths = a.ws_len;
+            ca.dst = a.dst;
+            ca.dst_bytes = a.dst_bytes;
+            ca.dst_offsets = (const uint64_t*)a.off;
+            ca.out = (uint32_t*)s.out.p;
+            ca.n = n;
+            if ((rc = enqueue_copy(c, ca, w->ppk_copy_first, w->ppk_copy_bsum,
+                                   a.ctr + kPpkCtrWords))) {
+                return rc;
+            }
+            if (bmqcrc_launch_push_pack_frame(&a, (void*)c.s)) {
+                return launch_failed("push-pack frame");
+            }
+        }
+    }
+    bmqcrc_push_pack_result r;
+    if ((rc = sync_result(c, o, push_pack_result, result, &r))) {
+        return rc;
+    }
+    return r.refused_kind ? refused(kPushPackRefusals, r.refused_kind, r.refused_index) : 0;
+}
+
+int bmqcrc_last_push_pack(int device, void* stream, bmqcrc_push_pack_result* result)
+{
+    return last_result(device, stream, push_pack_result, result);
+}
+
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,
                        uint32_t* seg_bytes)
 {
@@ -3568,7 +3794,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 16u;
+    return (2u << 16) | 17u;
 }
 
 }  // extern "C"

@@ -543,7 +543,72 @@ struct SpkArgs {
     uint32_t nblocks;               // layout blocks (<= kPackBlocks)
 };
 
+// ---- bmqcrc_push_event_pack (crc32c_push_pack.hip, ABI 2.17) ---------------
+// The classify, count and seal grid and block are kPackBlocks x kPackThreads
+// over contiguous MESSAGE ranges (layout_split over n, not n_records: a message
+// names its record), the check kernel's one event per thread, the frame
+// kernel's kPackFrameBlocks x kPackFrameThreads.  PpkArgs::ctr words: the first
+// four are the unpackers' (kSlotCtr*), behind them the call's
+constexpr int kPpkCtrTotal = 4;      // bytes of all events (k_ppk_check)
+constexpr int kPpkCtrWords = 6;      // (one spare: the copy's counters start 16-byte aligned)
+constexpr uint32_t kPushHeaderBytes = 32;
+// PpkArgs::ws_meta: SchemaId as its two bytes lie in memory | CAT << 16 |
+// (DataHeader.flags & 1) << 19
+constexpr uint32_t kPpkMetaCatShift = 16, kPpkMetaPropsBit = 1u << 19;
+// BMQCRC_PUSH_PACK_* of bmqcrc_protocol.h, which the kernels do not include
+#define BMQCRC_PPK_KIND_RECORD_INDEX 1u
+#define BMQCRC_PPK_KIND_RECORD 2u
+#define BMQCRC_PPK_KIND_DATA_OFFSET 3u
+#define BMQCRC_PPK_KIND_DATA_RECORD 4u
+#define BMQCRC_PPK_KIND_FLAGS 5u
+#define BMQCRC_PPK_KIND_EVENT_FIRST 6u
+#define BMQCRC_PPK_KIND_PAYLOAD_TOO_BIG 7u
+#define BMQCRC_PPK_KIND_EVENT_TOO_BIG 8u
+#define BMQCRC_PPK_KIND_DST_TOO_SMALL 9u
+#define BMQCRC_PPK_KIND_TOO_MANY_PIECES 10u
+
+struct PpkArgs {
+    const uint32_t* journal;        // device, 4-byte aligned: n_records records of 15 dwords
+    uint64_t n_records;
+    const uint8_t* data;            // device, 8-byte aligned: the DATA-file window
+    uint64_t data_bytes;
+    uint64_t data_file_pos;         // byte of the DATA file that data[0] stands for
+    const uint32_t* records;        // device, n, or nullptr (message m is record m)
+    const int32_t* queue_ids;       // device, n
+    const uint8_t* flags;           // device, n, or nullptr (all zero)
+    const uint8_t* rda;             // device, n (option modes 1 and 3)
+    const uint32_t* sub_ids;        // device, n (option modes 2 and 3)
+    uint32_t option_mode;           // 0..3
+    uint32_t opt_bytes;             // O: 0, 4, 8 or 12
+    const uint64_t* event_first;    // device, n_events + 1, or nullptr (one event)
+    uint64_t n;                     // messages
+    uint64_t n_events;
+    uint64_t max_event_bytes;
+    uint64_t max_payload_bytes;
+    uint8_t* dst;                   // device, 4-byte aligned; nullptr: size only
+    uint64_t dst_bytes;
+    uint64_t* event_offsets;        // the caller's arrays (device; n_events + 1, n, n), each may
+    uint32_t* out;                  // be nullptr: written by k_ppk_frame (size only: event_offsets
+    uint32_t* lengths;              // by k_ppk_seal), when nothing was refused
+    unsigned long long* ws_off;     // workspace, n: what the copy reads -- the application data's
+    uint32_t* ws_len;               // offset in `data` and length (0 when refused) --
+    unsigned long long* off;        // and where it goes in dst (before: the prefix of B)
+    uint32_t* ws_exp;               // workspace, n: the MessageRecords' stored CRCs
+    const uint32_t* ws_out;         // workspace, n: the copy's CRCs
+    uint32_t* ws_meta;              // workspace, n: kPpkMeta*
+    unsigned long long* bsum;       // workspace, 2 * kPackBlocks: framed bytes | pieces per block
+    unsigned long long* ctr;        // workspace, kPpkCtrWords, zeroed before the launch
+    uint64_t per_block;             // messages per layout block (multiple of kPackThreads)
+    uint32_t nblocks;               // layout blocks (<= kPackBlocks)
+};
+
 }  // namespace bmqcrc
+
+// Launchers (crc32c_push_pack.hip).  Asynchronous on `stream`: the layout
+// before bmqcrc_launch_copy (it writes the copy's descriptors), the frame after;
+// a size-only call (dst nullptr) launches the layout alone.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_push_pack_layout(const bmqcrc::PpkArgs* a, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_push_pack_frame(const bmqcrc::PpkArgs* a, void* stream);
 
 // Launchers (crc32c_storage_pack.hip).  Asynchronous on `stream`: the layout
 // before bmqcrc_launch_copy (it writes the copy's descriptors), the frame after.

@@ -970,6 +970,179 @@ int bmqcrc_storage_event_pack(const bmqcrc_storage_pack* p, bmqcrc_storage_pack_
  * stream); waits for it.  `result` may be NULL. */
 int bmqcrc_last_storage_pack(int device, void* stream, bmqcrc_storage_pack_result* result);
 
+/* ABI 2.17.  Delivery to consumers: stored messages, journal and DATA records
+ * both in device memory, are packed ON THE DEVICE into the PUSH events the
+ * consumers receive -- mqba::ClientSession's delivery loop with
+ * bmqp::PushEventBuilder::packMessage for a batch of messages in one
+ * asynchronous call, byte for byte what the builder emits.  The application
+ * data of every message is moved by the fused copy of bmqcrc_crc32c_copy, whose
+ * CRC32-C is compared with the one the MessageRecord stores ("verify on
+ * delivery", a check the reference never makes), at the cost of the copy the
+ * broker has to make anyway.  No payload byte and no descriptor crosses PCIe.
+ *
+ * Records.  Record i is journal[60 i .. 60 i + 60), i = 0 .. n_records - 1, and
+ *   `data` a window of the DATA file whose byte 0 stands for byte data_file_pos
+ *   of that file, as in bmqcrc_storage_event_pack (alignment included).
+ * Messages.  Message m, m = 0 .. n - 1, is journal record records[m], which must
+ *   be a MESSAGE record.  The entries may come in any order and may repeat: a
+ *   fan-out to several consumer handles is the same record under several queue
+ *   ids.  records == NULL means message m is record m; n must then equal
+ *   n_records (and every record be a MESSAGE record).  queue_ids[m] is the id
+ *   the consumer opened the queue under.  flags[m] may carry
+ *   PushHeaderFlags::e_OUT_OF_ORDER (4) and nothing else; flags == NULL means 0.
+ *   e_MESSAGE_PROPERTIES (2) is taken from the DATA record; e_IMPLICIT_PAYLOAD
+ *   is not supported.
+ * Options.  One form per call (option_mode), so the option size O is uniform:
+ *     0                 O = 0   none;
+ *     1 PACKED_RDA      O = 4   one packed SUB_QUEUE_INFOS OptionHeader, BE u32
+ *                               (3 << 26) | (1 << 25) | rda[m]: the default
+ *                               sub-queue with its redelivery counter, what a
+ *                               downstream broker gets in non-fan-out mode;
+ *     2 SUB_QUEUE_ID    O = 8   SUB_QUEUE_IDS_OLD with one id, BE u32
+ *                               (1 << 26) | 2, then BE u32 sub_ids[m]: what a
+ *                               first-hop SDK client gets;
+ *     3 SUB_QUEUE_INFO  O = 12  unpacked SUB_QUEUE_INFOS with one item, BE u32
+ *                               (3 << 26) | (2 << 21) | 3, then BE u32
+ *                               sub_ids[m], the byte rda[m], three bytes 0.
+ *   These are the forms of PushEventBuilder::addSubQueueInfosOption for one
+ *   sub-queue.  rda (u8 per message) is required in modes 1 and 3, sub_ids (u32
+ *   per message) in modes 2 and 3; an array the mode does not use must be NULL.
+ * Events.  Event e holds messages [event_first[e], event_first[e + 1]), as in
+ *   bmqcrc_storage_event_pack: n_events + 1 entries, 0 first and n last,
+ *   strictly increasing; NULL means one event (n_events must be 1).  The caller
+ *   cuts the events.
+ * Layout.  With L[m] the application data's length, pad(L) = 4 - L % 4 (1..4
+ *   bytes, each equal to the count; L = 0 gives four bytes of 4), B[m] = 32 + O +
+ *   L[m] + pad(L[m]), P the 64-bit exclusive prefix of B and e(m) the event of
+ *   message m: event e lies at dst + 8 e + P[event_first[e]], message m's
+ *   PushHeader at dst + 8 (e(m) + 1) + P[m], its option 32 bytes behind that and
+ *   its application data 32 + O bytes behind it.
+ *   EventHeader (8 bytes): BE u32 length of the event (fragment bit 0); a byte
+ *   (1 << 6) | 4 (PUSH); a byte 2 (headerWords); two bytes 0.
+ *   PushHeader (32 bytes): BE u32 F << 28 | (8 + O / 4 + (L + pad) / 4); BE u32
+ *   (O / 4) << 8 | CAT << 5 | 8; BE i32 queue_ids[m]; the 16 GUID bytes of the
+ *   MessageRecord (bytes 36..51); two SchemaId bytes; two bytes 0.  CAT is the
+ *   low 3 bits of MessageRecord byte 21; F is (flags[m] & 4) |
+ *   (DataHeader.flags & 1 ? 2 : 0); SchemaId is DataHeader bytes 8..9 when its
+ *   headerWords >= 3, else 0: MessagePropertiesInfo(dataHeader).applyTo(
+ *   pushHeader) and the attributes FileStore::get returns.
+ *   The application data is the DATA record minus DataHeader, option words and
+ *   padding, moved as stored: compressed bytes stay compressed and the CRC is
+ *   over them, as the PUT header's was.  A DATA record's own option words are
+ *   skipped, not forwarded.
+ * Outputs, each may be NULL: event_offsets (n_events + 1 entries: the byte of
+ *   dst where each event starts, the total behind the last), out[m] (the
+ *   computed CRC32-C of the application data), lengths[m] (L[m]).
+ * Verify on delivery.  The stored CRC is the MessageRecord's BE u32 at byte 52.
+ *   n_bad counts the messages whose computed CRC differs, first_bad is the
+ *   lowest (n when none).  A mismatch does not fail the call and the bytes go
+ *   out as they are: whether to deliver them is the caller's decision.
+ * Size only.  dst == NULL with dst_bytes == 0 runs the layout and every check
+ *   except DST_TOO_SMALL, writes event_offsets and the result (total_bytes) and
+ *   nothing else (n_bad is 0, first_bad n), and launches neither the copy nor
+ *   the frame.  With repeats allowed the size of `data` gives no bound on dst:
+ *   this is how a caller sizes it exactly.
+ * All or nothing, decided on the device.  One violation anywhere refuses the
+ *   call, and a refused call writes nothing to dst or to any output array.  The
+ *   lowest kind wins and within it the lowest index (BMQCRC_PUSH_PACK_* below;
+ *   the index is a message, an event_first entry or an event, by kind).  No
+ *   journal byte outside the run is loaded and no DATA byte before its range is
+ *   shown to lie in the window.  EVENT_TOO_BIG, DST_TOO_SMALL and
+ *   TOO_MANY_PIECES are evaluated only when no lower kind was raised.  A
+ *   synchronous call returns BMQCRC_EINVAL naming kind and index; after an
+ *   asynchronous call bmqcrc_last_push_pack reports them.
+ * Caps.  max_event_bytes 0 means EventHeader::k_MAX_SIZE_SOFT (512 MiB), at most
+ *   2^31 - 1; max_payload_bytes 0 means PushHeader::k_MAX_PAYLOAD_SIZE_SOFT
+ *   (64 MiB), at most 4 (2^28 - 1) - 32 - 12 - 4 so that MessageWords (28 bits)
+ *   cannot overflow.
+ * Options of the call.  Device pointers only: BMQCRC_F_DEVICE_PTRS is required,
+ *   BMQCRC_F_ASYNC allowed; any other flag, ndevices > 1, a wrong struct_size or
+ *   a non-zero reserved field; journal, data or queue_ids null; dst null with
+ *   dst_bytes != 0; journal or dst not 4-byte aligned, data not 8-byte aligned;
+ *   journal_bytes != 60 n_records; n >= 2^32; records == NULL with n !=
+ *   n_records; event_first == NULL with n_events != 1; n_events outside [1, n]
+ *   when n > 0; data_file_pos no multiple of 8; option_mode above 3; an rda or
+ *   sub_ids pointer that does not fit the mode; a cap above its limit; dst or an
+ *   output array meeting an input (journal, data, records, queue_ids, flags,
+ *   rda, sub_ids, event_first), dst or another output array is BMQCRC_EINVAL,
+ *   answered on the host before the device lookup.
+ *   n == 0 launches nothing, writes nothing and reports zeros.
+ * The copy runs over the n messages.  Nothing at or beyond dst_bytes, n_events +
+ *   1 entries of event_offsets or n entries of out and lengths is ever written.
+ * *result (may be NULL) is written by a synchronous call only.
+ * State.  As bmqcrc_storage_event_pack: takes the workspace mutex of (device,
+ *   stream); restores the caller's current device; allocates its own workspace
+ *   on first use and when n grows (36 bytes per message, none per event), which
+ *   bmqcrc_reserve does not cover; is not meant to be captured into a hipGraph;
+ *   is deterministic.  The copy's counters live in the call's own scratch: the
+ *   shape prediction and the records of every other bmqcrc_last_* call are never
+ *   touched. */
+#define BMQCRC_PUSH_PACK_OK 0
+#define BMQCRC_PUSH_PACK_RECORD_INDEX 1     /* records[m] >= n_records.  Index: the message */
+#define BMQCRC_PUSH_PACK_RECORD 2           /* BMQCRC_REC_UNPACK_RECORD_HEADER's conditions (type 0, lease id 0,
+                                               sequence number 0, a wrong magic), or the record's type is not
+                                               MESSAGE.  Index: the message */
+#define BMQCRC_PUSH_PACK_DATA_OFFSET 3      /* BMQCRC_STORAGE_PACK_DATA_OFFSET's conditions.  Index: the message */
+#define BMQCRC_PUSH_PACK_DATA_RECORD 4      /* BMQCRC_STORAGE_PACK_DATA_RECORD's conditions.  Index: the message */
+#define BMQCRC_PUSH_PACK_FLAGS 5            /* flags[m] has a bit other than 4.  Index: the message */
+#define BMQCRC_PUSH_PACK_EVENT_FIRST 6      /* event_first[0] != 0, event_first[e] >= event_first[e + 1] or
+                                               event_first[n_events] != n.  Index: the entry */
+#define BMQCRC_PUSH_PACK_PAYLOAD_TOO_BIG 7  /* L[m] > max_payload_bytes.  Index: the message */
+#define BMQCRC_PUSH_PACK_EVENT_TOO_BIG 8    /* an event longer than max_event_bytes.  Index: the event */
+#define BMQCRC_PUSH_PACK_DST_TOO_SMALL 9    /* index: the lowest event ending past dst_bytes */
+#define BMQCRC_PUSH_PACK_TOO_MANY_PIECES 10 /* beyond the copy kernel's 2^32-1 16-byte pieces per call: the sum
+                                               over the messages with application data of
+                                               ((length + 15) >> 4) + 1.  Index 0 */
+
+#define BMQCRC_PUSH_OPTION_NONE 0
+#define BMQCRC_PUSH_OPTION_PACKED_RDA 1
+#define BMQCRC_PUSH_OPTION_SUB_QUEUE_ID 2
+#define BMQCRC_PUSH_OPTION_SUB_QUEUE_INFO 3
+
+typedef struct bmqcrc_push_pack {
+    uint32_t struct_size, reserved;       /* sizeof, 0 */
+    const void* journal;                  /* device, 4-byte aligned: n_records 60-byte records, the record run */
+    uint64_t journal_bytes;               /* == 60 * n_records */
+    uint64_t n_records;
+    const void* data;                     /* device, 8-byte aligned: the DATA-file window */
+    uint64_t data_bytes;
+    uint64_t data_file_pos;               /* byte of the DATA file that data[0] stands for: multiple of 8 */
+    const uint32_t* records;              /* device, n; NULL = message m is record m (n must be n_records) */
+    uint64_t n;                           /* messages, < 2^32 */
+    const int32_t* queue_ids;             /* device, n */
+    const uint8_t* flags;                 /* device, n, may be NULL (all 0): only e_OUT_OF_ORDER (4) */
+    uint32_t option_mode;                 /* BMQCRC_PUSH_OPTION_* */
+    uint32_t reserved2;                   /* 0 */
+    const uint8_t* rda;                   /* device, n: modes 1 and 3, NULL otherwise */
+    const uint32_t* sub_ids;              /* device, n: modes 2 and 3, NULL otherwise */
+    const uint64_t* event_first;          /* device, n_events + 1; NULL = one event (n_events must be 1) */
+    uint64_t n_events;
+    uint64_t max_event_bytes;             /* 0 = 512 MiB; <= 2^31 - 1 */
+    uint64_t max_payload_bytes;           /* 0 = 64 MiB; <= 4 (2^28 - 1) - 48 */
+    void* dst;                            /* device, 4-byte aligned; NULL with dst_bytes 0: size only */
+    uint64_t dst_bytes;
+    uint64_t* event_offsets;              /* device, n_events + 1, may be NULL: the total behind the last */
+    uint32_t* out;                        /* device, n, may be NULL: the computed CRCs */
+    uint32_t* lengths;                    /* device, n, may be NULL: the application data's lengths */
+} bmqcrc_push_pack;
+
+/* All fields zero before the first call on (device, stream); after a refused
+ * call only n_events and the refused_* fields are set. */
+typedef struct bmqcrc_push_pack_result {
+    uint64_t n_events, n_msgs;            /* n_msgs = n */
+    uint64_t total_bytes;                 /* bytes of all events */
+    uint64_t n_bad, first_bad;            /* stored CRC != computed CRC; first_bad = n_msgs when none */
+    uint32_t refused_kind, reserved;
+    uint64_t refused_index;               /* a message, an event_first entry or an event, by kind */
+} bmqcrc_push_pack_result;
+
+int bmqcrc_push_event_pack(const bmqcrc_push_pack* p, bmqcrc_push_pack_result* result,
+                           const bmqcrc_opts* opts);
+
+/* ABI 2.17.  Result of the previous bmqcrc_push_event_pack on (device, stream);
+ * waits for it.  `result` may be NULL. */
+int bmqcrc_last_push_pack(int device, void* stream, bmqcrc_push_pack_result* result);
+
 /* ---- cluster state ledger (mqbc_clusterstateledgerprotocol.h:76,272) ------ */
 
 /* mqbc::ClusterStateLedgerUtilRc values (mqbc_clusterstateledgerutil.h:65-124)
