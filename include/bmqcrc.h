@@ -146,8 +146,19 @@ uint32_t bmqcrc_combine(uint32_t crcA, uint32_t crcB, uint64_t lenB);
  * for i < n (with BMQCRC_F_OFFSETS32, `offsets` is n uint32_t, see the flag).  Messages may sit anywhere in [arena, arena + arena_bytes) at any
  * byte alignment and may overlap.  With BMQCRC_F_DEVICE_PTRS all five arrays
  * are device memory of opts->device (inputs "device resident"); otherwise they
- * are host memory and the library stages them through HBM.  Returns 0,
- * BMQCRC_EINVAL, BMQCRC_ENODEV, BMQCRC_ENOMEM or BMQCRC_EIO. */
+ * are host memory and the library stages them through HBM.
+ *
+ * Alignment.  `arena` may start at any byte address: a sub-buffer of a pool is
+ * as good as the start of an allocation, and results and launch plans do not
+ * depend on it.  `offsets`, `lengths`, `seeds` and `out` (and `expected` of
+ * bmqcrc_crc32c_verify) need the natural alignment of their elements and no
+ * more: 8 bytes for 64-bit offsets, 4 bytes for 32-bit offsets, lengths, seeds,
+ * out and expected.  The kernels read and write them four elements at a time,
+ * with accesses that assume only that; each array may sit at its own
+ * alignment.  bad_idx of bmqcrc_crc32c_verify is host memory, 8-byte aligned.
+ * (tests/test_gpu_base_alignment.py holds every path to this.)
+ *
+ * Returns 0, BMQCRC_EINVAL, BMQCRC_ENODEV, BMQCRC_ENOMEM or BMQCRC_EIO. */
 int bmqcrc_crc32c_batch(const void* arena, uint64_t arena_bytes, const uint64_t* offsets,
                         const uint32_t* lengths, const uint32_t* seeds, uint32_t* out,
                         uint64_t n, const bmqcrc_opts* opts);
@@ -202,6 +213,11 @@ int bmqcrc_crc32c_gather(const void* const* bufs, const uint32_t* buf_lengths, u
  *   ndevices > 1 or a missing BMQCRC_F_DEVICE_PTRS is BMQCRC_EINVAL with a
  *   message naming it, answered before the device lookup.  seg_bytes, max_len
  *   and min_len are ignored.  Host-resident callers keep bmqcrc_crc32c_gather.
+ * Alignment.  `src` and `dst` may start at any byte address, like the
+ *   messages inside them: the 16-byte pieces a message is cut into are those
+ *   of its destination ADDRESS, dst + dst_offsets[i].  src_offsets and
+ *   dst_offsets need 8-byte alignment, lengths, seeds and out 4-byte
+ *   alignment (their elements' own), and no more.
  * Byte-exact destination.  Bytes of dst outside the n destination ranges are
  *   never written and never read; two destination ranges may touch at any
  *   byte position.  A message of length 0 writes nothing and out[i] is its

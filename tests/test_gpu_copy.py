@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import device_views as V
 import oracle
 from blazingmq_amd import BmqCrcError, Crc32c, _native as N, last_copy, last_launch
 
@@ -34,16 +35,35 @@ def _image(src, soff, lens, doff, size, skip=()):
     return img
 
 
-def _check(cuda, src, soff, lens, doff, dst_size, seeds=None, **kw):
+def _check(cuda, src, soff, lens, doff, dst_size, seeds=None, phases=None, **kw):
     """One copy_batch into a fresh 0xA5 destination: out against the oracle,
-    the whole destination against the image.  Returns (out, dst tensor)."""
+    the whole destination against the image.  Returns (out, dst tensor).
+    `phases` = (src, dst) base-pointer phases: both buffers are then views
+    inside longer allocations (tests/device_views.py) whose margins are checked
+    too; None is the start of a fresh allocation each."""
     import torch
     lens = np.asarray(lens, np.uint32)
-    d_src = torch.from_numpy(src).to(cuda)
-    d_dst = torch.full((dst_size,), FILL, dtype=torch.uint8, device=cuda)
-    d_sd = _i32(seeds).to(cuda) if seeds is not None else None
-    out = Crc32c.copy_batch(d_src, _i64(soff).to(cuda), _i32(lens).to(cuda), d_dst,
-                            _i64(doff).to(cuda), d_sd, **kw)
+    if phases is None:
+        d_src = torch.from_numpy(src).to(cuda)
+        d_dst = torch.full((dst_size,), FILL, dtype=torch.uint8, device=cuda)
+    else:
+        d_src = V.place(src, phases[0], cuda)
+        d_dst = V.place(np.full(dst_size, FILL, np.uint8), phases[1], cuda)
+        assert (V.phase_of(d_src), V.phase_of(d_dst)) == tuple(phases)
+    if phases is None:
+        d_sd = _i32(seeds).to(cuda) if seeds is not None else None
+        out = Crc32c.copy_batch(d_src, _i64(soff).to(cuda), _i32(lens).to(cuda), d_dst,
+                                _i64(doff).to(cuda), d_sd, **kw)
+    else:
+        # the descriptor and output arrays at their elements' alignment, no more
+        arrays = [V.place(np.asarray(soff, np.int64), 8, cuda), V.place(lens, 12, cuda),
+                  V.place(np.asarray(doff, np.int64), 72, cuda),
+                  V.filled(lens.size, np.uint32, 0x5A5A5A5A, 20, cuda)]
+        d_sd = V.place(np.asarray(seeds, np.uint32), 4, cuda) if seeds is not None else None
+        assert [V.phase_of(a) for a in arrays] == [8, 12, 72, 20]
+        out = Crc32c.copy_batch(d_src, arrays[0], arrays[1], d_dst, arrays[2], d_sd,
+                                out=arrays[3], **kw)
+        V.check_margins(*arrays)
     torch.cuda.synchronize(cuda)
     got = out.cpu().numpy().view(np.uint32)
     exp = oracle.batch(src, soff, lens, seeds, nthreads=8)
@@ -54,6 +74,8 @@ def _check(cuda, src, soff, lens, doff, dst_size, seeds=None, **kw):
     diff = np.nonzero(host != img)[0]
     assert diff.size == 0, (diff.size, [int(i) for i in diff[:8]])
     assert torch.equal(d_src.cpu(), torch.from_numpy(src))  # the source is only read
+    if phases is not None:
+        V.check_margins(d_src, d_dst)
     return got, d_dst
 
 
@@ -74,7 +96,7 @@ def _seeds(rng, n):
     return rng.integers(0, 2**32, size=n, dtype=np.uint64).astype(np.uint32)
 
 
-def test_every_length_at_every_misalignment(cuda):
+def _every_length_at_every_misalignment():
     rng = np.random.default_rng(1)
     lens = rng.permutation(2201)
     smis = np.arange(lens.size) % 16
@@ -82,10 +104,14 @@ def test_every_length_at_every_misalignment(cuda):
     assert set(smis) == set(dmis) == set(range(16))
     soff, doff, ssize, dsize = _layout(rng, lens, smis, dmis)
     src = rng.integers(0, 256, size=ssize, dtype=np.uint8)
-    _check(cuda, src, soff, lens, doff, dsize, _seeds(rng, lens.size))
+    return src, soff, lens, doff, dsize, _seeds(rng, lens.size)
 
 
-def test_all_misalignment_pairs(cuda):
+def test_every_length_at_every_misalignment(cuda):
+    _check(cuda, *_every_length_at_every_misalignment())
+
+
+def _all_misalignment_pairs():
     # every (source, destination) misalignment pair at lengths around one and
     # two pieces and around a row
     rng = np.random.default_rng(2)
@@ -97,20 +123,28 @@ def test_all_misalignment_pairs(cuda):
             dmis.append(k // 16)
     soff, doff, ssize, dsize = _layout(rng, lens, smis, dmis)
     src = rng.integers(0, 256, size=ssize, dtype=np.uint8)
-    _check(cuda, src, soff, lens, doff, dsize, _seeds(rng, len(lens)))
+    return src, soff, lens, doff, dsize, _seeds(rng, len(lens))
 
 
-def test_lengths_around_the_chunk(cuda):
+def test_all_misalignment_pairs(cuda):
+    _check(cuda, *_all_misalignment_pairs())
+
+
+def _lengths_around_the_chunk():
     rng = np.random.default_rng(3)
     lens = [C - 1, C, C + 1, 2 * C + 17] * 3
     smis = [0] * 4 + [5] * 4 + [11] * 4
     dmis = [0] * 4 + [0] * 4 + [3] * 4
     soff, doff, ssize, dsize = _layout(rng, lens, smis, dmis)
     src = rng.integers(0, 256, size=ssize, dtype=np.uint8)
-    _check(cuda, src, soff, lens, doff, dsize, _seeds(rng, len(lens)))
+    return src, soff, lens, doff, dsize, _seeds(rng, len(lens))
 
 
-def test_packed_layout_shares_pieces_between_waves(cuda):
+def test_lengths_around_the_chunk(cuda):
+    _check(cuda, *_lengths_around_the_chunk())
+
+
+def _packed_layout():
     # destination ranges end to end with no gap: neighbours share 16-byte
     # pieces, which a read-modify-write of a shared piece would corrupt
     rng = np.random.default_rng(4)
@@ -119,7 +153,11 @@ def test_packed_layout_shares_pieces_between_waves(cuda):
     doff = 7 + np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
     src = rng.integers(0, 256, size=1 << 20, dtype=np.uint8)
     soff = (rng.random(n) * (src.size - lens)).astype(np.int64)
-    _check(cuda, src, soff, lens, doff, int(doff[-1] + lens[-1]) + 9, _seeds(rng, n))
+    return src, soff, lens, doff, int(doff[-1] + lens[-1]) + 9, _seeds(rng, n)
+
+
+def test_packed_layout_shares_pieces_between_waves(cuda):
+    _check(cuda, *_packed_layout())
 
 
 def test_long_message_alone_and_among_short_ones(cuda):

@@ -22,6 +22,7 @@ import push_pack_cases as C
 import push_pack_model as M
 import put_pack_model as P
 import put_unpack_model as PU
+import device_views as V
 
 pytestmark = pytest.mark.gpu
 
@@ -52,10 +53,14 @@ def _t(cuda, a, dtype):
     return torch.from_numpy(a).to(cuda)
 
 
-def _dev(cuda, buf):
-    """`buf` on the device as a view of a longer allocation."""
+def _dev(cuda, buf, place=None, name=None):
+    """`buf` on the device as a view of a longer allocation: one that starts
+    with it, or with `place` (a device_views.Placer) one that holds it at the
+    phase the placer has for `name`."""
     import torch
     buf = np.array(buf, dtype=np.uint8)  # (a copy: shared inputs are read-only)
+    if place is not None:
+        return place.put(name, buf)
     back = torch.full((buf.size + SLACK,), 0xEE, dtype=torch.uint8, device=cuda)
     back[:buf.size] = torch.from_numpy(buf).to(cuda)
     return back[:buf.size]
@@ -71,33 +76,49 @@ def _kw(n, **changes):
     return kw
 
 
-def _raw(cuda, run, data, kw, sync=True, stream=None, skip=()):
+def _raw(cuda, run, data, kw, sync=True, stream=None, skip=(), phases=None):
     """One bmqcrc_push_event_pack over device tensors into a sentinel-filled
     destination and arrays; dst_bytes None is the size-only call.  Returns (rc,
     error text, result of the call or of bmqcrc_last_push_pack, everything
-    written on the host with its guards)."""
+    written on the host with its guards).  `phases` maps every pointer of the
+    call (journal, data, records, queue_ids, flags, rda, sub_ids, event_first,
+    dst, event_offsets, out, lengths) to the phase of its base; the sentinel
+    margins around each are checked after the call.  None: every buffer starts
+    its allocation."""
     import torch
+    place = V.Placer(cuda, phases) if phases is not None else None
     stream = stream or torch.cuda.current_stream(cuda)
     n = len(kw["queue_ids"])
     first = kw["event_first"]
     n_events = 1 if first is None else len(first) - 1
     count = {"event_offsets": n_events + 1, "out": n, "lengths": n}
     with torch.cuda.stream(stream):
-        d_run, d_data = _dev(cuda, run), _dev(cuda, data)
+        d_run, d_data = _dev(cuda, run, place, "journal"), _dev(cuda, data, place, "data")
         spare = torch.zeros(8, dtype=torch.uint8, device=cuda)
         ins = {}
         for name, dt in (("records", np.uint32), ("queue_ids", np.int32), ("flags", np.uint8),
                          ("rda", np.uint8), ("sub_ids", np.uint32)):
-            if kw[name] is not None:
+            if kw[name] is not None and place is not None:
+                ins[name] = place.put(name, np.asarray(kw[name]).astype(dt))
+            elif kw[name] is not None:
                 ins[name] = _t(cuda, np.asarray(kw[name]).astype(dt), dt)
-        d_first = _t(cuda, np.asarray(first, np.uint64).view(np.int64), np.int64) \
-            if first is not None else None
+        if first is None:
+            d_first = None
+        elif place is not None:
+            d_first = place.put("event_first", np.asarray(first, np.uint64))
+        else:
+            d_first = _t(cuda, np.asarray(first, np.uint64).view(np.int64), np.int64)
         arr = {}
-        if kw["dst_bytes"] is not None:
+        if kw["dst_bytes"] is not None and place is not None:
+            arr["dst"] = place.fill("dst", kw["dst_bytes"] + SLACK, np.uint8, SENTINEL)
+        elif kw["dst_bytes"] is not None:
             arr["dst"] = torch.full((kw["dst_bytes"] + SLACK,), SENTINEL, dtype=torch.uint8,
                                     device=cuda)
         for name, dt in NP.items():
             if name in skip:
+                continue
+            if place is not None:
+                arr[name] = place.fill(name, count[name] + GUARD, dt, CANARY[name])
                 continue
             fill = np.array([CANARY[name]], np.uint64).astype(dt)
             arr[name] = torch.from_numpy(np.repeat(fill, count[name] + GUARD).view(
@@ -126,6 +147,8 @@ def _raw(cuda, run, data, kw, sync=True, stream=None, skip=()):
         err = N.lib.bmqcrc_last_error()
         res = r.as_dict() if sync else last_push_pack(cuda.index, stream)
         host = {name: t.cpu().numpy() for name, t in arr.items()}
+        if place is not None:
+            place.check()
     for name, dt in NP.items():
         if name in host:
             host[name] = host[name].view(dt)
@@ -137,17 +160,19 @@ def _untouched(name, a):
     return bool((a == want).all())
 
 
-def _check(cuda, run, data, kw, sync=True, stream=None, skip=(), model=None):
+def _check(cuda, run, data, kw, sync=True, stream=None, skip=(), model=None, phases=None):
     """The call against the model: a refusal identical and nothing written, or
     every destination byte, array entry and result field.  `dst_bytes` "exact"
-    is the exact size, None the size-only call.  Returns (model, host)."""
+    is the exact size, None the size-only call.  `phases`: as in _raw.  Returns
+    (model, host)."""
     kw = dict(kw)
     if kw["dst_bytes"] == "exact":
         kw["dst_bytes"] = 1 << 40
         m = M.pack(run, data, crc32c=CRC, **kw) if model is None else model
         kw["dst_bytes"] = m.result["total_bytes"] if isinstance(m, M.Packed) else 4096
     m = model if model is not None else M.pack(run, data, crc32c=CRC, **kw)
-    rc, err, res, host = _raw(cuda, run, data, kw, sync=sync, stream=stream, skip=skip)
+    rc, err, res, host = _raw(cuda, run, data, kw, sync=sync, stream=stream, skip=skip,
+                              phases=phases)
     n = len(kw["queue_ids"])
     n_events = (1 if kw["event_first"] is None else len(kw["event_first"]) - 1) if n else 0
     if isinstance(m, M.Refusal):

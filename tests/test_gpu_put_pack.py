@@ -9,6 +9,7 @@ import pytest
 
 from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, last_copy, last_launch,
                            last_put_pack, pack_events)
+import device_views as V
 from put_pack_model import host_crcs, layout, model_bytes, oracle_events, random_meta
 
 pytestmark = pytest.mark.gpu
@@ -19,26 +20,63 @@ FILL64 = 0x5A5A5A5A5A5A5A5A
 CAP = 66 << 20
 
 
-def _t(cuda, a, dtype):
+def _t(cuda, a, dtype, place=None, name=None):
+    """`a` on the device at the start of an allocation, or with `place` (a
+    device_views.Placer) inside one, at the phase the placer has for `name`."""
     import torch
     a = np.ascontiguousarray(a, dtype=dtype)
+    if place is not None:
+        return place.put(name, a)
     if dtype == np.uint32:
         a = a.view(np.int32)
     return torch.from_numpy(a).to(cuda)
 
 
-def _inputs(cuda, src, soff, lens, qids, guids, flags, ef):
-    return dict(src=_t(cuda, src, np.uint8), src_offsets=_t(cuda, soff, np.int64),
-                lengths=_t(cuda, lens, np.uint32), queue_ids=_t(cuda, qids, np.int32),
-                guids=_t(cuda, guids, np.uint8),
-                flags=_t(cuda, flags, np.uint8) if flags is not None else None,
-                event_first=_t(cuda, ef, np.int64) if ef is not None else None)
+def _inputs(cuda, src, soff, lens, qids, guids, flags, ef, place=None):
+    t = lambda name, a, dtype: _t(cuda, a, dtype, place, name)
+    return dict(src=t("src", src, np.uint8), src_offsets=t("src_offsets", soff, np.int64),
+                lengths=t("lengths", lens, np.uint32), queue_ids=t("queue_ids", qids, np.int32),
+                guids=t("guids", guids, np.uint8),
+                flags=t("flags", flags, np.uint8) if flags is not None else None,
+                event_first=t("event_first", ef, np.int64) if ef is not None else None)
 
 
-def _check(cuda, src, soff, lens, qids, guids, flags=None, ef=None, slack=64, **kw):
-    """One pack into a canary destination against the oracle.  Returns the
-    packed bytes (host)."""
+def _check_placed(cuda, place, src, soff, lens, qids, guids, flags, ef, slack, max_event_bytes=0):
+    """_check's call and checks through the raw call, every buffer placed."""
+    exp = np.concatenate(oracle_events(src, soff, lens, qids, guids, flags, ef))
+    total, n, n_events = exp.size, len(lens), 1 if ef is None else len(ef) - 1
+    d = _inputs(cuda, src, soff, lens, qids, guids, flags, ef, place)
+    dst = place.fill("dst", total + slack, np.uint8, FILL)
+    out = place.fill("out", n, np.uint32, FILL32)
+    evoff = place.fill("event_offsets", n_events + 1, np.uint64, FILL64)
+    rc, err, got_total = _raw(cuda, d, n, n_events, dst, total + slack, out, evoff,
+                              max_event_bytes=max_event_bytes)
+    assert rc == 0 and got_total == total, (rc, err, got_total)
     import torch
+    assert last_put_pack(cuda.index, torch.cuda.current_stream(cuda)) == (
+        n, n_events, total, N.BMQCRC_PUT_PACK_OK, 0)
+    host = dst.cpu().numpy()
+    diff = np.nonzero(host[:total] != exp)[0]
+    assert diff.size == 0, (diff.size, [int(i) for i in diff[:8]])
+    assert np.all(host[total:] == FILL)
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), host_crcs(src, soff, lens))
+    assert np.array_equal(evoff.cpu().numpy(), layout(lens, ef)[1])
+    assert np.array_equal(d["src"].cpu().numpy(), src)  # the source is only read
+    place.check()
+    return host[:total]
+
+
+def _check(cuda, src, soff, lens, qids, guids, flags=None, ef=None, slack=64, phases=None, **kw):
+    """One pack into a canary destination against the oracle.  Returns the
+    packed bytes (host).  `phases` maps every pointer of the call (src,
+    src_offsets, lengths, queue_ids, guids, flags, event_first, dst,
+    event_offsets, out) to the phase of its base: the call then goes through
+    the raw entry point and the sentinel margins around every buffer are
+    checked; None: the wrapper, every buffer at the start of an allocation."""
+    import torch
+    if phases is not None:
+        return _check_placed(cuda, V.Placer(cuda, phases), src, soff, lens, qids, guids, flags, ef,
+                             slack, **kw)
     # (n = 0 writes nothing, not even an empty event)
     exp = np.concatenate(oracle_events(src, soff, lens, qids, guids, flags, ef)) if len(lens) \
         else np.zeros(0, np.uint8)
@@ -85,19 +123,26 @@ def _raw(cuda, d, n, n_events, dst, dst_bytes, out, evoff, flags=N.BMQCRC_F_DEVI
 
 
 def _refused(cuda, kind, index, src, soff, lens, qids, guids, flags=None, ef=None,
-             dst_bytes=None, **kw):
+             dst_bytes=None, phases=None, **kw):
     """The call is refused with (kind, index), synchronously and asynchronously,
-    and the whole dst, out and event_offsets keep their canaries."""
+    and the whole dst, out and event_offsets keep their canaries.  `phases`:
+    as in _check."""
     import torch
     n, n_events = len(lens), 1 if ef is None else len(ef) - 1
-    d = _inputs(cuda, src, soff, lens, qids, guids, flags, ef)
+    place = V.Placer(cuda, phases) if phases is not None else None
+    d = _inputs(cuda, src, soff, lens, qids, guids, flags, ef, place)
     size = int(layout(lens, None)[1][-1]) + 8 * n_events + 64
     stream = torch.cuda.current_stream(cuda)
     name = {1: b"SRC_RANGE", 2: b"EVENT_FIRST", 3: b"EVENT_TOO_BIG", 4: b"DST_TOO_SMALL"}[kind]
     for flags_ in (N.BMQCRC_F_DEVICE_PTRS, N.BMQCRC_F_DEVICE_PTRS | N.BMQCRC_F_ASYNC):
-        dst = torch.full((size,), FILL, dtype=torch.uint8, device=cuda)
-        out = torch.full((n,), FILL32, dtype=torch.int32, device=cuda)
-        evoff = torch.full((n_events + 1,), FILL64, dtype=torch.int64, device=cuda)
+        if place is not None:
+            dst = place.fill("dst", size, np.uint8, FILL)
+            out = place.fill("out", n, np.uint32, FILL32)
+            evoff = place.fill("event_offsets", n_events + 1, np.uint64, FILL64)
+        else:
+            dst = torch.full((size,), FILL, dtype=torch.uint8, device=cuda)
+            out = torch.full((n,), FILL32, dtype=torch.int32, device=cuda)
+            evoff = torch.full((n_events + 1,), FILL64, dtype=torch.int64, device=cuda)
         rc, err, total = _raw(cuda, d, n, n_events, dst, size if dst_bytes is None else dst_bytes,
                               out, evoff, flags_, **kw)
         if flags_ & N.BMQCRC_F_ASYNC:
@@ -108,6 +153,8 @@ def _refused(cuda, kind, index, src, soff, lens, qids, guids, flags=None, ef=Non
         assert last_put_pack(cuda.index, stream) == (n, n_events, 0, kind, index)
         assert bool((dst == FILL).all()) and bool((out == FILL32).all())
         assert bool((evoff == FILL64).all())
+        if place is not None:
+            place.check()
 
 
 def _short(rng, n, lo=1, hi=41, src_size=1 << 16):

@@ -13,6 +13,7 @@ from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, last_copy, last_la
                            last_put_pack, last_put_unpack, last_records_pack, pack_events,
                            pack_records, unpack_events)
 from blazingmq_amd import storage as S
+import device_views as V
 import put_pack_model as P
 import put_unpack_model as M
 from records_pack_model import REC, wrap_partition
@@ -45,18 +46,25 @@ def _t(cuda, a, dtype):
     return torch.from_numpy(a).to(cuda)
 
 
-def _device_events(cuda, buf):
-    """`buf` on the device as a view of a longer allocation."""
+def _device_events(cuda, buf, place=None):
+    """`buf` on the device as a view of a longer allocation: one that starts
+    with it, or with `place` (a device_views.Placer) one that holds it, and
+    the SLACK bytes behind it, at the placer's phase for `events`."""
     import torch
+    if place is not None:
+        whole = np.concatenate([np.asarray(buf, np.uint8), np.full(SLACK, 0xEE, np.uint8)])
+        return place.put("events", whole)[:buf.size]
     back = torch.full((buf.size + SLACK,), 0xEE, dtype=torch.uint8, device=cuda)
     back[:buf.size] = torch.from_numpy(np.ascontiguousarray(buf)).to(cuda)
     return back[:buf.size]
 
 
-def _raw(cuda, events, offs, cap, verify=True, sync=True, stream=None, skip=()):
+def _raw(cuda, events, offs, cap, verify=True, sync=True, stream=None, skip=(), place=None):
     """One bmqcrc_put_event_unpack into canary-filled arrays.  Returns (rc,
     error text, result of the call or of bmqcrc_last_put_unpack, the arrays
-    on the host with their guards)."""
+    on the host with their guards).  With `place` (a device_views.Placer that
+    placed `events`) every array lies at the placer's phase for its name, and
+    the sentinel margins around all of them are checked after the call."""
     import torch
     stream = stream or torch.cuda.current_stream(cuda)
     n_events = 1 if offs is None else len(offs) - 1
@@ -64,12 +72,21 @@ def _raw(cuda, events, offs, cap, verify=True, sync=True, stream=None, skip=()):
           "guids": torch.uint8, "flags": torch.uint8, "expected": torch.int32,
           "out": torch.int32, "event_first": torch.int64}
     with torch.cuda.stream(stream):
-        d_offs = _t(cuda, offs, np.int64) if offs is not None else None
+        if offs is None:
+            d_offs = None
+        elif place is not None:
+            d_offs = place.put("event_offsets", np.ascontiguousarray(offs, dtype=np.int64))
+        else:
+            d_offs = _t(cuda, offs, np.int64)
         arr = {}
         for name, t in dt.items():
             if name in skip or (name == "out" and not verify):
                 continue
             size = n_events + 1 + GUARD if name == "event_first" else (cap + GUARD) * PER[name]
+            if place is not None:
+                arr[name] = place.fill(name, size, {torch.int64: np.uint64, torch.int32: np.uint32,
+                                                    torch.uint8: np.uint8}[t], CANARY[name])
+                continue
             fill = CANARY[name] - (1 << 64 if t == torch.int64 and CANARY[name] >> 63 else 0)
             arr[name] = torch.full((size,), fill, dtype=t, device=cuda)
         p = N.PutUnpack()
@@ -94,6 +111,8 @@ def _raw(cuda, events, offs, cap, verify=True, sync=True, stream=None, skip=()):
             a = t.cpu().numpy()
             host[name] = a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.itemsize]) \
                 if name != "queue_ids" else a
+        if place is not None:
+            place.check()
     return rc, err, res, host
 
 
@@ -109,15 +128,19 @@ def _guards_intact(host, cap, n_events):
 
 
 def _ok(cuda, buf, offs, cap=None, verify=True, sync=True, stream=None, model=None, n_bad=0,
-        first_bad=None, skip=()):
-    """A call that must succeed, against the model.  Returns (model, arrays)."""
+        first_bad=None, skip=(), phases=None):
+    """A call that must succeed, against the model.  `phases` maps every
+    pointer of the call (events, event_offsets and the arrays by name) to the
+    phase of its base; None: every buffer starts its allocation.  Returns
+    (model, arrays)."""
+    place = V.Placer(cuda, phases) if phases is not None else None
     m = model or M.model(buf, offs)
     assert m["refused"] is None
     n = m["n"]
     cap = n + 5 if cap is None else cap
     n_events = 1 if offs is None else len(offs) - 1
-    rc, err, res, host = _raw(cuda, _device_events(cuda, buf), offs, cap, verify, sync, stream,
-                              skip)
+    rc, err, res, host = _raw(cuda, _device_events(cuda, buf, place), offs, cap, verify, sync,
+                              stream, skip, place)
     assert rc == 0, (rc, err)
     assert res == dict(n_events=n_events, n_msgs=n, n_bad=n_bad,
                        first_bad=n if first_bad is None else first_bad, refused_kind=0,
@@ -135,14 +158,16 @@ def _ok(cuda, buf, offs, cap=None, verify=True, sync=True, stream=None, model=No
     return m, host
 
 
-def _refused(cuda, buf, offs, cap, want=None, verify=True):
+def _refused(cuda, buf, offs, cap, want=None, verify=True, phases=None):
     """A call that must be refused, synchronously and asynchronously: the
-    model's (kind, event, offset), and not one element written."""
+    model's (kind, event, offset), and not one element written.  `phases`: as
+    in _ok."""
     kind, event, offset = want or M.model(buf, offs, cap)["refused"]
-    events = _device_events(cuda, buf)
+    place = V.Placer(cuda, phases) if phases is not None else None
+    events = _device_events(cuda, buf, place)
     n_events = 1 if offs is None else len(offs) - 1
     for sync in (True, False):
-        rc, err, res, host = _raw(cuda, events, offs, cap, verify, sync)
+        rc, err, res, host = _raw(cuda, events, offs, cap, verify, sync, place=place)
         if sync:
             assert rc == N.BMQCRC_EINVAL and KIND_NAME[kind] in err and \
                 b"nothing was written" in err, (rc, err)

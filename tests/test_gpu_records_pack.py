@@ -11,6 +11,7 @@ import pytest
 from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, last_copy, last_launch,
                            last_put_pack, last_records_pack, pack_events, pack_records)
 from blazingmq_amd import storage as S
+import device_views as V
 import put_pack_model as P
 from records_pack_model import (DH, REC, golden_case, host_crcs, layout, model_bytes,
                                 random_meta, wrap_partition)
@@ -36,20 +37,25 @@ def _side_stream(cuda):
     return torch.cuda.Stream(cuda, priority=-1)
 
 
-def _t(cuda, a, dtype):
+def _t(cuda, a, dtype, place=None, name=None):
+    """`a` on the device at the start of an allocation, or with `place` (a
+    device_views.Placer) inside one, at the phase the placer has for `name`."""
     import torch
     a = np.ascontiguousarray(a, dtype=dtype)
+    if place is not None:
+        return place.put(name, a)
     if dtype == np.uint32:
         a = a.view(np.int32)
     return torch.from_numpy(a).to(cuda)
 
 
-def _inputs(cuda, src, soff, lens, qkeys, guids, kw):
-    d = dict(src=_t(cuda, src, np.uint8), src_offsets=_t(cuda, soff, np.int64),
-             lengths=_t(cuda, lens, np.uint32), queue_keys=_t(cuda, qkeys, np.uint8),
-             guids=_t(cuda, guids, np.uint8))
+def _inputs(cuda, src, soff, lens, qkeys, guids, kw, place=None):
+    t = lambda name, a, dtype: _t(cuda, a, dtype, place, name)
+    d = dict(src=t("src", src, np.uint8), src_offsets=t("src_offsets", soff, np.int64),
+             lengths=t("lengths", lens, np.uint32), queue_keys=t("queue_keys", qkeys, np.uint8),
+             guids=t("guids", guids, np.uint8))
     for name, dt in OPTIONAL.items():
-        d[name] = _t(cuda, kw[name], dt) if kw.get(name) is not None else None
+        d[name] = t(name, kw[name], dt) if kw.get(name) is not None else None
     return d
 
 
@@ -64,23 +70,41 @@ def _result(n, total, n_bad=0, first_bad=None, kind=0, index=0):
 
 
 def _check(cuda, src, soff, lens, qkeys, guids, kw=KW, slack=64, sync=True, stream=None,
-           n_bad=0, first_bad=None):
+           n_bad=0, first_bad=None, phases=None):
     """One pack into canary destinations against the model.  Returns the
-    packed (DATA, journal) bytes (host)."""
+    packed (DATA, journal) bytes (host).  `phases` maps every pointer of the
+    call (src, src_offsets, lengths, queue_keys, guids, the optional arrays,
+    dst, journal_dst, record_offsets, out) to the phase of its base: the call
+    then goes through the raw entry point (synchronous, on the current stream)
+    and the sentinel margins around every buffer are checked; None: the
+    wrapper, every buffer at the start of an allocation."""
     import torch
+    place = V.Placer(cuda, phases) if phases is not None else None
     n = len(lens)
     crcs = host_crcs(src, soff, lens)
     stored = crcs if kw.get("expected") is None else np.asarray(kw["expected"], np.uint32)
     model_kw = {k: v for k, v in kw.items() if k != "expected"}
     exp_d, exp_j = model_bytes(src, soff, lens, qkeys, guids, stored, **model_kw)
     total = exp_d.size
-    d = _inputs(cuda, src, soff, lens, qkeys, guids, kw)
-    dst = torch.full((total + slack,), FILL, dtype=torch.uint8, device=cuda)
-    jour = torch.full((REC * n + slack,), FILL, dtype=torch.uint8, device=cuda)
-    out = torch.full((n,), FILL32, dtype=torch.int32, device=cuda)
-    rdst, rjour, roff, rout, res = pack_records(dst=dst, journal_dst=jour, out=out, sync=sync,
-                                                stream=stream, **d, **_scalars(kw))
-    assert rdst is dst and rjour is jour and rout is out
+    d = _inputs(cuda, src, soff, lens, qkeys, guids, kw, place)
+    if place is not None:
+        assert sync and stream is None
+        dst = place.fill("dst", total + slack, np.uint8, FILL)
+        jour = place.fill("journal_dst", REC * n + slack, np.uint8, FILL)
+        out = place.fill("out", n, np.uint32, FILL32)
+        roff = place.fill("record_offsets", n + 1, np.uint64, FILL64)
+        rc, err, r = _raw(cuda, d, dict(dict(timestamp=0), **kw), n, dst, total + slack, jour, roff, out,
+                          N.BMQCRC_F_DEVICE_PTRS)
+        assert rc == 0, err
+        res = r.as_dict()
+        place.check()
+    else:
+        dst = torch.full((total + slack,), FILL, dtype=torch.uint8, device=cuda)
+        jour = torch.full((REC * n + slack,), FILL, dtype=torch.uint8, device=cuda)
+        out = torch.full((n,), FILL32, dtype=torch.int32, device=cuda)
+        rdst, rjour, roff, rout, res = pack_records(dst=dst, journal_dst=jour, out=out, sync=sync,
+                                                    stream=stream, **d, **_scalars(kw))
+        assert rdst is dst and rjour is jour and rout is out
     s = stream if stream is not None else torch.cuda.current_stream(cuda)
     want = _result(n, total, n_bad, first_bad)
     assert res == (want if sync else None)
@@ -121,20 +145,28 @@ def _raw(cuda, d, kw, n, dst, dst_bytes, jour, roff, out, flags, src_bytes=None)
 
 
 def _refused(cuda, kind, index, src, soff, lens, qkeys, guids, kw=KW, dst_bytes=None,
-             src_bytes=None, size=None):
+             src_bytes=None, size=None, phases=None):
     """The call is refused with (kind, index), synchronously and asynchronously,
-    and dst, journal_dst, out and record_offsets keep their canaries whole."""
+    and dst, journal_dst, out and record_offsets keep their canaries whole.
+    `phases`: as in _check."""
     import torch
     n = len(lens)
-    d = _inputs(cuda, src, soff, lens, qkeys, guids, kw)
+    place = V.Placer(cuda, phases) if phases is not None else None
+    d = _inputs(cuda, src, soff, lens, qkeys, guids, kw, place)
     if size is None:
         size = int(layout(lens)[1][-1]) + 64
     stream = torch.cuda.current_stream(cuda)
     for flags in (N.BMQCRC_F_DEVICE_PTRS, N.BMQCRC_F_DEVICE_PTRS | N.BMQCRC_F_ASYNC):
-        dst = torch.full((size,), FILL, dtype=torch.uint8, device=cuda)
-        jour = torch.full((REC * n + 64,), FILL, dtype=torch.uint8, device=cuda)
-        out = torch.full((n,), FILL32, dtype=torch.int32, device=cuda)
-        roff = torch.full((n + 1,), FILL64, dtype=torch.int64, device=cuda)
+        if place is not None:
+            dst = place.fill("dst", size, np.uint8, FILL)
+            jour = place.fill("journal_dst", REC * n + 64, np.uint8, FILL)
+            out = place.fill("out", n, np.uint32, FILL32)
+            roff = place.fill("record_offsets", n + 1, np.uint64, FILL64)
+        else:
+            dst = torch.full((size,), FILL, dtype=torch.uint8, device=cuda)
+            jour = torch.full((REC * n + 64,), FILL, dtype=torch.uint8, device=cuda)
+            out = torch.full((n,), FILL32, dtype=torch.int32, device=cuda)
+            roff = torch.full((n + 1,), FILL64, dtype=torch.int64, device=cuda)
         rc, err, res = _raw(cuda, d, kw, n, dst, size if dst_bytes is None else dst_bytes, jour,
                             roff, out, flags, src_bytes)
         want = _result(n, 0, kind=kind, index=index)
@@ -147,6 +179,8 @@ def _refused(cuda, kind, index, src, soff, lens, qkeys, guids, kw=KW, dst_bytes=
         assert last_records_pack(cuda.index, stream) == want
         assert bool((dst == FILL).all()) and bool((jour == FILL).all())
         assert bool((out == FILL32).all()) and bool((roff == FILL64).all())
+        if place is not None:
+            place.check()
 
 
 def _short(rng, n, lo=1, hi=41, src_size=1 << 16):

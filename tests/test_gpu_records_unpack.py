@@ -15,6 +15,7 @@ from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, last_copy, last_la
                            last_records_unpack, pack_events, pack_records, unpack_events,
                            unpack_records)
 from blazingmq_amd import storage as S
+import device_views as V
 import put_pack_model as P
 import put_unpack_model as PU
 import records_unpack_model as M
@@ -50,19 +51,27 @@ def _t(cuda, a, dtype):
     return torch.from_numpy(a).to(cuda)
 
 
-def _dev(cuda, buf):
-    """`buf` on the device as a view of a longer allocation."""
+def _dev(cuda, buf, place=None, name=None):
+    """`buf` on the device as a view of a longer allocation: one that starts
+    with it, or with `place` (a device_views.Placer) one that holds it at the
+    phase the placer has for `name`."""
     import torch
     buf = np.array(buf, dtype=np.uint8)  # (a copy: shared inputs are read-only)
+    if place is not None:
+        return place.put(name, buf)
     back = torch.full((buf.size + SLACK,), 0xEE, dtype=torch.uint8, device=cuda)
     back[:buf.size] = torch.from_numpy(buf).to(cuda)
     return back[:buf.size]
 
 
-def _raw(cuda, run, data, pos, cap, select=None, verify=True, sync=True, stream=None, skip=()):
+def _raw(cuda, run, data, pos, cap, select=None, verify=True, sync=True, stream=None, skip=(),
+         place=None):
     """One bmqcrc_message_records_unpack over device tensors into canary-filled
     arrays.  Returns (rc, error text, result of the call or of
-    bmqcrc_last_records_unpack, the arrays on the host with their guards)."""
+    bmqcrc_last_records_unpack, the arrays on the host with their guards).
+    With `place` (a device_views.Placer that placed `run` and `data`) `select`
+    and every array lie at the placer's phase for their names, and the sentinel
+    margins around all of them are checked after the call."""
     import torch
     stream = stream or torch.cuda.current_stream(cuda)
     dt = {"record_index": torch.int32, "app_offsets": torch.int64, "lengths": torch.int32,
@@ -70,10 +79,20 @@ def _raw(cuda, run, data, pos, cap, select=None, verify=True, sync=True, stream=
           "ref_counts": torch.int32, "timestamps": torch.int64, "expected": torch.int32,
           "out": torch.int32}
     with torch.cuda.stream(stream):
-        d_sel = _t(cuda, select, np.uint8) if select is not None else None
+        if select is None:
+            d_sel = None
+        elif place is not None:
+            d_sel = place.put("select", np.ascontiguousarray(select, dtype=np.uint8))
+        else:
+            d_sel = _t(cuda, select, np.uint8)
         arr = {}
         for name, t in dt.items():
             if name in skip or (name == "out" and not verify):
+                continue
+            if place is not None:
+                arr[name] = place.fill(name, (cap + GUARD) * PER[name],
+                                       {torch.int64: np.uint64, torch.int32: np.uint32,
+                                        torch.uint8: np.uint8}[t], CANARY[name])
                 continue
             fill = CANARY[name] - (1 << 64 if t == torch.int64 and CANARY[name] >> 63 else 0)
             arr[name] = torch.full(((cap + GUARD) * PER[name],), fill, dtype=t, device=cuda)
@@ -101,6 +120,8 @@ def _raw(cuda, run, data, pos, cap, select=None, verify=True, sync=True, stream=
         for name, t in arr.items():
             a = t.cpu().numpy()
             host[name] = a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.itemsize])
+        if place is not None:
+            place.check()
     return rc, err, res, host
 
 
@@ -115,15 +136,19 @@ def _guards_intact(host, cap):
 
 
 def _ok(cuda, run, data, pos=0, select=None, cap=None, verify=True, sync=True, stream=None,
-        model=None, n_bad=0, first_bad=None, skip=()):
-    """A call over host bytes that must succeed, against the model.  Returns
-    (model, arrays)."""
+        model=None, n_bad=0, first_bad=None, skip=(), phases=None):
+    """A call over host bytes that must succeed, against the model.  `phases`
+    maps every pointer of the call (journal, data, select and the arrays by
+    name) to the phase of its base; None: every buffer starts its allocation.
+    Returns (model, arrays)."""
+    place = V.Placer(cuda, phases) if phases is not None else None
     m = model or M.model(run, data, pos, select)
     assert m["refused"] is None
     n = m["n"]
     cap = n + 5 if cap is None else cap
-    rc, err, res, host = _raw(cuda, _dev(cuda, run), _dev(cuda, data), pos, cap, select, verify,
-                              sync, stream, skip)
+    rc, err, res, host = _raw(cuda, _dev(cuda, run, place, "journal"),
+                              _dev(cuda, data, place, "data"), pos, cap, select, verify, sync,
+                              stream, skip, place)
     assert rc == 0, (rc, err)
     assert res == dict(n_records=m["n_records"], n_msgs=n, n_skipped=m["n_skipped"], n_bad=n_bad,
                        first_bad=n if first_bad is None else first_bad, refused_kind=0,
@@ -142,14 +167,17 @@ def _ok(cuda, run, data, pos=0, select=None, cap=None, verify=True, sync=True, s
     return m, host
 
 
-def _refused(cuda, run, data, pos=0, cap=None, select=None, want=None, verify=True):
+def _refused(cuda, run, data, pos=0, cap=None, select=None, want=None, verify=True,
+             phases=None):
     """A call that must be refused, synchronously and asynchronously: the
-    model's (kind, record), and not one element written."""
+    model's (kind, record), and not one element written.  `phases`: as in _ok."""
+    place = V.Placer(cuda, phases) if phases is not None else None
     kind, index = want or M.model(run, data, pos, select, cap, crcs=False)["refused"]
     cap = run.size // M.REC if cap is None else cap
-    d_run, d_data = _dev(cuda, run), _dev(cuda, data)
+    d_run, d_data = _dev(cuda, run, place, "journal"), _dev(cuda, data, place, "data")
     for sync in (True, False):
-        rc, err, res, host = _raw(cuda, d_run, d_data, pos, cap, select, verify, sync)
+        rc, err, res, host = _raw(cuda, d_run, d_data, pos, cap, select, verify, sync,
+                                  place=place)
         if sync:
             assert rc == N.BMQCRC_EINVAL and KIND_NAME[kind] in err and \
                 b"nothing was written" in err, (rc, err)

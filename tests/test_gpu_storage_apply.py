@@ -20,6 +20,7 @@ from blazingmq_amd import storage_event as E
 from blazingmq_amd import synth
 import put_pack_model as P
 import put_unpack_model as PU
+import device_views as V
 import storage_apply_cases as C
 import storage_apply_model as M
 from records_pack_model import random_meta
@@ -59,10 +60,14 @@ def _t(cuda, a, dtype):
     return torch.from_numpy(a).to(cuda)
 
 
-def _dev(cuda, buf):
-    """`buf` on the device as a view of a longer allocation."""
+def _dev(cuda, buf, place=None, name=None):
+    """`buf` on the device as a view of a longer allocation: one that starts
+    with it, or with `place` (a device_views.Placer) one that holds it at the
+    phase the placer has for `name`."""
     import torch
     buf = np.array(buf, dtype=np.uint8)  # (a copy: shared inputs are read-only)
+    if place is not None:
+        return place.put(name, buf)
     back = torch.full((buf.size + SLACK,), 0xEE, dtype=torch.uint8, device=cuda)
     back[:buf.size] = torch.from_numpy(buf).to(cuda)
     return back[:buf.size]
@@ -72,24 +77,41 @@ def _count(name, cap, n_events):
     return cap + 1 if name == "record_offsets" else n_events + 1 if name == "event_first" else cap
 
 
-def _raw(cuda, events, offsets, kw, sync=True, stream=None, skip=()):
+def _raw(cuda, events, offsets, kw, sync=True, stream=None, skip=(), phases=None):
     """One bmqcrc_storage_event_apply over device tensors into sentinel-filled
     destinations and arrays.  Returns (rc, error text, result of the call or of
-    bmqcrc_last_storage_apply, everything written on the host with its guards)."""
+    bmqcrc_last_storage_apply, everything written on the host with its guards).
+    `phases` maps every pointer of the call (events, event_offsets, journal,
+    data and the output arrays by name) to the phase of its base; the sentinel
+    margins around each are checked after the call.  None: every buffer starts
+    its allocation."""
     import torch
+    place = V.Placer(cuda, phases) if phases is not None else None
     stream = stream or torch.cuda.current_stream(cuda)
     cap = kw["msg_cap"]
     n_events = 1 if offsets is None else len(offsets) - 1
     with torch.cuda.stream(stream):
-        d_ev = _dev(cuda, events)
-        d_offs = _t(cuda, np.asarray(offsets, np.uint64).view(np.int64), np.int64) \
-            if offsets is not None else None
-        arr = {"journal": torch.full((kw["journal_dst_bytes"] + SLACK,), SENTINEL,
-                                     dtype=torch.uint8, device=cuda),
-               "data": torch.full((kw["data_dst_bytes"] + SLACK,), SENTINEL, dtype=torch.uint8,
-                                  device=cuda)}
+        d_ev = _dev(cuda, events, place, "events")
+        if offsets is None:
+            d_offs = None
+        elif place is not None:
+            d_offs = place.put("event_offsets", np.asarray(offsets, np.uint64))
+        else:
+            d_offs = _t(cuda, np.asarray(offsets, np.uint64).view(np.int64), np.int64)
+        if place is not None:
+            arr = {"journal": place.fill("journal", kw["journal_dst_bytes"] + SLACK, np.uint8,
+                                         SENTINEL),
+                   "data": place.fill("data", kw["data_dst_bytes"] + SLACK, np.uint8, SENTINEL)}
+        else:
+            arr = {"journal": torch.full((kw["journal_dst_bytes"] + SLACK,), SENTINEL,
+                                         dtype=torch.uint8, device=cuda),
+                   "data": torch.full((kw["data_dst_bytes"] + SLACK,), SENTINEL,
+                                      dtype=torch.uint8, device=cuda)}
         for name, dt in NP.items():
             if name in skip:
+                continue
+            if place is not None:
+                arr[name] = place.fill(name, _count(name, cap, n_events) + GUARD, dt, CANARY[name])
                 continue
             fill = np.array([CANARY[name]], np.uint64).astype(dt)
             arr[name] = torch.from_numpy(np.repeat(fill, _count(name, cap, n_events) + GUARD).view(
@@ -114,6 +136,8 @@ def _raw(cuda, events, offsets, kw, sync=True, stream=None, skip=()):
         err = N.lib.bmqcrc_last_error()
         res = r.as_dict() if sync else last_storage_apply(cuda.index, stream)
         host = {name: t.cpu().numpy() for name, t in arr.items()}
+        if place is not None:
+            place.check()
     for name, dt in NP.items():
         if name in host:
             host[name] = host[name].view(dt)
@@ -126,12 +150,14 @@ def _untouched(name, a):
     return bool((a == want).all())
 
 
-def _check(cuda, events, offsets, kw, sync=True, stream=None, skip=(), model=None):
+def _check(cuda, events, offsets, kw, sync=True, stream=None, skip=(), model=None, phases=None):
     """The call against the model: a refusal identical and nothing written, or
-    every destination byte, array entry and result field.  Returns (model, host)."""
+    every destination byte, array entry and result field.  `phases`: as in
+    _raw.  Returns (model, host)."""
     kw = dict(dict(lease_id=0, seq=0), **kw)
     m = model if model is not None else M.apply(events, offsets, crc32c=CRC, **kw)
-    rc, err, res, host = _raw(cuda, events, offsets, kw, sync=sync, stream=stream, skip=skip)
+    rc, err, res, host = _raw(cuda, events, offsets, kw, sync=sync, stream=stream, skip=skip,
+                              phases=phases)
     n_events = 1 if offsets is None else len(offsets) - 1
     if isinstance(m, M.Refusal):
         if sync:

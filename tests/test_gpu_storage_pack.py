@@ -18,6 +18,7 @@ from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, apply_events, last
 from blazingmq_amd import storage as S
 from blazingmq_amd import storage_event as E
 from blazingmq_amd import synth
+import device_views as V
 import put_pack_model as P
 import put_unpack_model as PU
 import storage_pack_cases as C
@@ -53,10 +54,14 @@ def _t(cuda, a, dtype):
     return torch.from_numpy(a).to(cuda)
 
 
-def _dev(cuda, buf):
-    """`buf` on the device as a view of a longer allocation."""
+def _dev(cuda, buf, place=None, name=None):
+    """`buf` on the device as a view of a longer allocation: one that starts
+    with it, or with `place` (a device_views.Placer) one that holds it at the
+    phase the placer has for `name`."""
     import torch
     buf = np.array(buf, dtype=np.uint8)  # (a copy: shared inputs are read-only)
+    if place is not None:
+        return place.put(name, buf)
     back = torch.full((buf.size + SLACK,), 0xEE, dtype=torch.uint8, device=cuda)
     back[:buf.size] = torch.from_numpy(buf).to(cuda)
     return back[:buf.size]
@@ -72,25 +77,40 @@ def _kw(run, d, **changes):
     return kw
 
 
-def _raw(cuda, run, data, kw, sync=True, stream=None, skip=()):
+def _raw(cuda, run, data, kw, sync=True, stream=None, skip=(), phases=None):
     """One bmqcrc_storage_event_pack over device tensors into a sentinel-filled
     destination and arrays.  Returns (rc, error text, result of the call or of
-    bmqcrc_last_storage_pack, everything written on the host with its guards)."""
+    bmqcrc_last_storage_pack, everything written on the host with its guards).
+    `phases` maps every pointer of the call (journal, data, flags, event_first,
+    dst, event_offsets, types, out) to the phase of its base; the sentinel
+    margins around each are checked after the call.  None: every buffer starts
+    its allocation."""
     import torch
+    place = V.Placer(cuda, phases) if phases is not None else None
     stream = stream or torch.cuda.current_stream(cuda)
     n = len(run) // 60
     first = kw["event_first"]
     n_events = 1 if first is None else len(first) - 1
     count = {"event_offsets": n_events + 1, "types": n, "out": n}
     with torch.cuda.stream(stream):
-        d_run, d_data = _dev(cuda, run), _dev(cuda, data)
-        d_first = _t(cuda, np.asarray(first, np.uint64).view(np.int64), np.int64) \
-            if first is not None else None
-        d_flags = _dev(cuda, kw["flags"]) if kw["flags"] is not None else None
-        arr = {"dst": torch.full((kw["dst_bytes"] + SLACK,), SENTINEL, dtype=torch.uint8,
-                                 device=cuda)}
+        d_run, d_data = _dev(cuda, run, place, "journal"), _dev(cuda, data, place, "data")
+        d_flags = _dev(cuda, kw["flags"], place, "flags") if kw["flags"] is not None else None
+        if first is None:
+            d_first = None
+        elif place is not None:
+            d_first = place.put("event_first", np.asarray(first, np.uint64))
+        else:
+            d_first = _t(cuda, np.asarray(first, np.uint64).view(np.int64), np.int64)
+        if place is not None:
+            arr = {"dst": place.fill("dst", kw["dst_bytes"] + SLACK, np.uint8, SENTINEL)}
+        else:
+            arr = {"dst": torch.full((kw["dst_bytes"] + SLACK,), SENTINEL, dtype=torch.uint8,
+                                     device=cuda)}
         for name, dt in NP.items():
             if name in skip:
+                continue
+            if place is not None:
+                arr[name] = place.fill(name, count[name] + GUARD, dt, CANARY[name])
                 continue
             fill = np.array([CANARY[name]], np.uint64).astype(dt)
             arr[name] = torch.from_numpy(np.repeat(fill, count[name] + GUARD).view(
@@ -118,6 +138,8 @@ def _raw(cuda, run, data, kw, sync=True, stream=None, skip=()):
         err = N.lib.bmqcrc_last_error()
         res = r.as_dict() if sync else last_storage_pack(cuda.index, stream)
         host = {name: t.cpu().numpy() for name, t in arr.items()}
+        if place is not None:
+            place.check()
     for name, dt in NP.items():
         if name in host:
             host[name] = host[name].view(dt)
@@ -129,17 +151,18 @@ def _untouched(name, a):
     return bool((a == want).all())
 
 
-def _check(cuda, run, data, kw, sync=True, stream=None, skip=(), model=None):
+def _check(cuda, run, data, kw, sync=True, stream=None, skip=(), model=None, phases=None):
     """The call against the model: a refusal identical and nothing written, or
     every destination byte, array entry and result field.  `dst_bytes` None is
-    the exact size.  Returns (model, host)."""
+    the exact size.  `phases`: as in _raw.  Returns (model, host)."""
     kw = dict(kw)
     if kw["dst_bytes"] is None:
         kw["dst_bytes"] = 1 << 40
         m = M.pack(run, data, crc32c=CRC, **kw) if model is None else model
         kw["dst_bytes"] = m.result["total_bytes"] if isinstance(m, M.Packed) else 4096
     m = model if model is not None else M.pack(run, data, crc32c=CRC, **kw)
-    rc, err, res, host = _raw(cuda, run, data, kw, sync=sync, stream=stream, skip=skip)
+    rc, err, res, host = _raw(cuda, run, data, kw, sync=sync, stream=stream, skip=skip,
+                              phases=phases)
     n = len(run) // 60
     n_events = (1 if kw["event_first"] is None else len(kw["event_first"]) - 1) if n else 0
     if isinstance(m, M.Refusal):
