@@ -13,7 +13,8 @@ from .put_event import (last_put_pack, last_put_unpack, pack_events,  # noqa: F4
 from .push_event import (PushEventBuilder, PushMessageIterator, last_push_pack,  # noqa: F401
                          pack_push_events)
 from .storage import (last_journal_select, last_records_pack,  # noqa: F401
-                      last_records_unpack, pack_records, select_records, unpack_records)
+                      last_records_unpack, last_rollover, pack_records, rollover_records,
+                      select_records, unpack_records)
 from .storage_event import (StorageEventBuilder, StorageMessageIterator,  # noqa: F401
                             apply_events, last_storage_apply, last_storage_pack,
                             pack_storage_events)
@@ -24,5 +25,5 @@ __all__ = ["Blob", "BmqCrcError", "Crc32c", "HostRegistration", "PushEventBuilde
            "calculate_batch_ptr", "device_count", "fill_synthetic", "forget_shape", "plan_wait",
            "kernel_timing", "last_copy", "last_journal_select", "last_launch", "last_offsets",
            "last_put_pack", "last_put_unpack", "last_records_pack", "last_records_unpack",
-           "last_storage_pack", "pack_events", "pack_records", "pack_storage_events", "reserve", "select_records", "unpack_events",
-           "unpack_records"]
+           "last_rollover", "last_storage_pack", "pack_events", "pack_records", "pack_storage_events",
+           "reserve", "rollover_records", "select_records", "unpack_events", "unpack_records"]

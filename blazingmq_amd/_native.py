@@ -394,6 +394,48 @@ if hasattr(lib, "bmqcrc_push_event_pack"):  # ABI 2.17 (an older build loads for
                                            ctypes.POINTER(PushPackResult), _popts]
     lib.bmqcrc_last_push_pack.restype = _int
     lib.bmqcrc_last_push_pack.argtypes = [_int, _vp, ctypes.POINTER(PushPackResult)]
+BMQCRC_ROLLOVER_OK = 0
+BMQCRC_ROLLOVER_RECORD_HEADER = 1
+BMQCRC_ROLLOVER_KEEP_JOURNAL_OP = 2
+BMQCRC_ROLLOVER_SYNC_POINT = 3
+BMQCRC_ROLLOVER_DATA_OFFSET = 4
+BMQCRC_ROLLOVER_DATA_RECORD = 5
+BMQCRC_ROLLOVER_DST_TOO_SMALL = 6
+BMQCRC_ROLLOVER_DATA_FILE_FULL = 7
+BMQCRC_ROLLOVER_TOO_MANY_PIECES = 8
+BMQCRC_ROLLOVER_CONFIRMS_AS_KEPT = 0
+BMQCRC_ROLLOVER_CONFIRMS_FOLLOW_MESSAGES = 1
+BMQCRC_ROLLOVER_NO_SYNC_POINT = 0xFFFFFFFFFFFFFFFF
+
+
+class Rollover(ctypes.Structure):
+    """bmqcrc_rollover (include/bmqcrc_protocol.h, ABI 2.18)."""
+    _fields_ = [("struct_size", _u32), ("reserved", _u32), ("journal", _vp),
+                ("journal_bytes", _u64), ("n_records", _u64), ("data", _vp), ("data_bytes", _u64),
+                ("data_file_pos", _u64), ("keep", _vp), ("confirm_mode", _u32),
+                ("reserved2", _u32), ("sync_point", _u64), ("timestamp", _u64),
+                ("new_data_file_pos", _u64), ("dst", _vp), ("dst_bytes", _u64),
+                ("journal_dst", _vp), ("journal_dst_bytes", _u64), ("new_index", _vp),
+                ("out", _vp)]
+
+
+class RolloverResult(ctypes.Structure):
+    """bmqcrc_rollover_result (include/bmqcrc_protocol.h, ABI 2.18)."""
+    _fields_ = [("n_records", _u64), ("n_kept", _u64), ("n_messages", _u64),
+                ("journal_bytes", _u64), ("data_bytes", _u64), ("n_bad", _u64),
+                ("first_bad", _u64), ("refused_kind", _u32), ("reserved", _u32),
+                ("refused_index", _u64)]
+
+    def as_dict(self):
+        return {f[0]: int(getattr(self, f[0])) for f in self._fields_ if f[0] != "reserved"}
+
+
+if hasattr(lib, "bmqcrc_partition_rollover"):  # ABI 2.18 (an older build loads for same-box A/B)
+    lib.bmqcrc_partition_rollover.restype = _int
+    lib.bmqcrc_partition_rollover.argtypes = [ctypes.POINTER(Rollover),
+                                              ctypes.POINTER(RolloverResult), _popts]
+    lib.bmqcrc_last_rollover.restype = _int
+    lib.bmqcrc_last_rollover.argtypes = [_int, _vp, ctypes.POINTER(RolloverResult)]
 lib.bmqcrc_journal_scan.restype = _i64
 lib.bmqcrc_journal_scan.argtypes = [_vp, _u64, _vp, _u64, _vp, _pint, _pu64, _vp, _vp, _vp, _vp,
                                     _u64]

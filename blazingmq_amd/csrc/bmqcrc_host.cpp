@@ -217,6 +217,18 @@ struct Workspace {
     UnpackScratch ppk;
     DevBuf ppk_dst, ppk_meta, ppk_bsum, ppk_copy_first, ppk_copy_bsum;
     uint64_t ppk_events = 0;
+    // bmqcrc_partition_rollover: a set of its own again, its counters followed
+    // by its copy pass's: per record the descriptor its copy reads (8 + 4), the
+    // stored and the computed CRC (4 each), the destination offset (8), the
+    // DATA record's size and its header + options size (4 each), the kind (1),
+    // the index in the new run (8) and the copy pass's piece prefix (4); in
+    // FOLLOW mode the hash of the kept MESSAGE records (8 to 16, a power of
+    // two); the layout's block sums and the copy pass's; whether the last
+    // rollover enqueued restates a sync point
+    UnpackScratch rov;
+    DevBuf rov_dst, rov_rec, rov_hdr, rov_kind, rov_joff, rov_gslot, rov_bsum, rov_copy_first,
+        rov_copy_bsum;
+    bool rov_sync = false;
     // bmqcrc_journal_select: the part of its workspace every call zeroes (the
     // counters, the queue-key and GUID tables, the claims) and the rest (the
     // two record lists, the named DELETIONs, the states); the records of the
@@ -3621,6 +3633,218 @@ int bmqcrc_last_push_pack(int device, void* stream, bmqcrc_push_pack_result* res
     return last_result(device, stream, push_pack_result, result);
 }
 
+static_assert(BMQCRC_ROLLOVER_RECORD_HEADER == BMQCRC_ROV_KIND_RECORD_HEADER &&
+                  BMQCRC_ROLLOVER_KEEP_JOURNAL_OP == BMQCRC_ROV_KIND_KEEP_JOURNAL_OP &&
+                  BMQCRC_ROLLOVER_SYNC_POINT == BMQCRC_ROV_KIND_SYNC_POINT &&
+                  BMQCRC_ROLLOVER_DATA_OFFSET == BMQCRC_ROV_KIND_DATA_OFFSET &&
+                  BMQCRC_ROLLOVER_DATA_RECORD == BMQCRC_ROV_KIND_DATA_RECORD &&
+                  BMQCRC_ROLLOVER_DST_TOO_SMALL == BMQCRC_ROV_KIND_DST_TOO_SMALL &&
+                  BMQCRC_ROLLOVER_DATA_FILE_FULL == BMQCRC_ROV_KIND_DATA_FILE_FULL &&
+                  BMQCRC_ROLLOVER_TOO_MANY_PIECES == BMQCRC_ROV_KIND_TOO_MANY_PIECES &&
+                  BMQCRC_ROLLOVER_NO_SYNC_POINT == kRovNoSyncPoint,
+              "the kernels' refusal kinds are the public ones");
+
+// Result of the rollover last enqueued on c's workspace, after everything
+// enqueued on its stream (w->mu held); zeros when there was none.
+static int rollover_result(Ctx& c, bmqcrc_rollover_result* r)
+{
+    const UnpackScratch& s = c.w->rov;
+    unsigned long long ctr[kRovCtrWords + kCopyCtrWords];
+    memset(r, 0, sizeof(*r));
+    if (!s.any) {
+        return 0;
+    }
+    HIP_TRY(hipMemcpyAsync(ctr, s.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    r->n_records = s.n;
+    if (ctr[kSlotCtrRefusal]) {
+        refusal_of(ctr[kSlotCtrRefusal], &r->refused_kind, &r->refused_index);
+        return 0;
+    }
+    // the layout placed every DATA record inside dst: the copy pass has nothing to refuse
+    const unsigned long long* cc = ctr + kRovCtrWords;
+    if (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow]) {
+        return fail(BMQCRC_EIO, "bmqcrc_partition_rollover: the copy pass refused a message "
+                                "the layout had placed (internal error)");
+    }
+    r->n_kept = ctr[kRovCtrKept];
+    r->n_messages = ctr[kSlotCtrMsgs];
+    r->journal_bytes = kJournalRecordBytes * (r->n_kept + (c.w->rov_sync ? 1 : 0));
+    r->data_bytes = ctr[kRovCtrData];
+    r->n_bad = ctr[kSlotCtrBad];
+    r->first_bad = r->n_bad ? ~ctr[kSlotCtrFirstBad] : r->n_records;
+    return 0;
+}
+
+static const char* const kRolloverRefusals[9] = {
+    "", "BMQCRC_ROLLOVER_RECORD_HEADER: record %llu has type 0 or above 5, lease id 0, "
+        "sequence number 0, a wrong magic or a QueueOpType outside 1..4",
+    "BMQCRC_ROLLOVER_KEEP_JOURNAL_OP: keep[%llu] is set on a JOURNAL_OP record, which is never "
+    "rolled",
+    "BMQCRC_ROLLOVER_SYNC_POINT: record %llu (sync_point) is not a JOURNAL_OP SYNCPOINT record",
+    "BMQCRC_ROLLOVER_DATA_OFFSET: kept MESSAGE record %llu points at offset 0 or outside "
+    "[data_file_pos, data_file_pos+data_bytes]",
+    "BMQCRC_ROLLOVER_DATA_RECORD: kept MESSAGE record %llu points at a malformed DATA record",
+    "BMQCRC_ROLLOVER_DST_TOO_SMALL: the DATA record of record %llu ends past dst_bytes or its "
+    "journal record past journal_dst_bytes (n_records: the sync point)",
+    "BMQCRC_ROLLOVER_DATA_FILE_FULL: the DATA record of record %llu ends past 8*(2^32-1) bytes "
+    "of the new DATA file, where MessageOffsetDwords stops (n_records: new_data_file_pos itself)",
+    "BMQCRC_ROLLOVER_TOO_MANY_PIECES: more than 2^32-1 16-byte pieces of application data "
+    "in one call (index %llu)"};
+
+int bmqcrc_partition_rollover(const bmqcrc_rollover* p, bmqcrc_rollover_result* result,
+                              const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    bmqcrc_opts o;
+    int rc;
+    if ((rc = check_struct(p, "bmqcrc_rollover", p ? p->reserved2 : 0,
+                           ".reserved and reserved2 must be 0")) ||
+        (rc = device_call_opts(opts, "bmqcrc_partition_rollover", &o))) {
+        return rc;
+    }
+    if ((rc = refuse_null({{!p->journal, "journal"},
+                           {!p->data, "data"},
+                           {!p->dst, "dst"},
+                           {!p->journal_dst, "journal_dst"}}))) {
+        return rc;
+    }
+    const uint64_t n = p->n_records;
+    const bool with_sync = p->sync_point != BMQCRC_ROLLOVER_NO_SYNC_POINT;
+    const struct {
+        bool bad;
+        const char* what;
+    } checks[] = {
+        {((uintptr_t)p->journal & 3u) != 0, "journal must be 4-byte aligned"},
+        {((uintptr_t)p->data & 7u) != 0, "data must be 8-byte aligned"},
+        {((uintptr_t)p->dst & 7u) != 0, "dst must be 8-byte aligned"},
+        {((uintptr_t)p->journal_dst & 3u) != 0, "journal_dst must be 4-byte aligned"},
+        {((uintptr_t)p->new_index & 3u) != 0, "new_index must be 4-byte aligned"},
+        {((uintptr_t)p->out & 3u) != 0, "out must be 4-byte aligned"},
+        {n > 0xFFFFFFFFull, "n_records must be below 2^32"},
+        {p->journal_bytes != kJournalRecordBytes * n, "journal_bytes must be 60 n_records"},
+        {(p->data_file_pos & 7u) != 0, "data_file_pos must be a multiple of 8"},
+        {p->new_data_file_pos == 0 || (p->new_data_file_pos & 7u) != 0,
+         "new_data_file_pos must be a multiple of 8 and not 0 (a DATA file begins with its file "
+         "headers)"},
+        {p->confirm_mode > BMQCRC_ROLLOVER_CONFIRMS_FOLLOW_MESSAGES,
+         "confirm_mode must be at most 1"},
+        {with_sync && p->sync_point >= n,
+         "sync_point must be a record of the run or BMQCRC_ROLLOVER_NO_SYNC_POINT"}};
+    for (const auto& k : checks) {
+        if (k.bad) {
+            return fail(BMQCRC_EINVAL, k.what);
+        }
+    }
+    const NamedRange journal = {p->journal, p->journal_bytes, "[journal, journal+journal_bytes)"};
+    const NamedRange data = {p->data, p->data_bytes, "[data, data+data_bytes)"};
+    const NamedRange keep = {p->keep, p->keep ? n : 0, "keep"};
+    const NamedRange dst = {p->dst, p->dst_bytes, "[dst, dst+dst_bytes)"};
+    const NamedRange jdst = {p->journal_dst, p->journal_dst_bytes,
+                             "[journal_dst, journal_dst+journal_dst_bytes)"};
+    const NamedRange index = {p->new_index, 4 * n, "new_index"};
+    const NamedRange out = {p->out, 4 * n, "out"};
+    if ((rc = refuse_overlap({dst, jdst, index, out}, {journal, data, keep})) ||
+        (rc = refuse_overlap({jdst, index, out}, {dst})) ||
+        (rc = refuse_overlap({index, out}, {jdst})) || (rc = refuse_overlap({out}, {index}))) {
+        return rc;
+    }
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    UnpackScratch& s = w->rov;
+    const uint64_t recs = std::max<uint64_t>(n, 1);
+    const bool follow = p->confirm_mode == BMQCRC_ROLLOVER_CONFIRMS_FOLLOW_MESSAGES;
+    // the hash: a power of two, at least twice the records, so that a walk ends
+    uint64_t gslots = 64;
+    while (gslots < 2 * recs) {
+        gslots <<= 1;
+    }
+    if ((rc = s.ensure(n, true, kRovCtrWords + kCopyCtrWords)) ||
+        (rc = w->rov_bsum.ensure(8ull * 4 * kPackBlocks)) || (rc = w->rov_dst.ensure(8 * recs)) ||
+        (rc = w->rov_rec.ensure(4 * recs)) || (rc = w->rov_hdr.ensure(4 * recs)) ||
+        (rc = w->rov_kind.ensure(recs)) || (rc = w->rov_joff.ensure(8 * recs)) ||
+        (follow && n && (rc = w->rov_gslot.ensure(4 * gslots)))) {
+        return rc;
+    }
+    HIP_TRY(hipMemsetAsync(s.ctr.p, 0, 8 * (kRovCtrWords + kCopyCtrWords), c.s));
+    s.n = n;
+    s.any = true;
+    w->rov_sync = with_sync;
+    if (n) {
+        if (follow) {
+            HIP_TRY(hipMemsetAsync(w->rov_gslot.p, 0, 4 * gslots, c.s));
+        }
+        RovArgs a;
+        memset(&a, 0, sizeof(a));
+        a.journal = (const uint32_t*)p->journal;
+        a.n = n;
+        a.data = (const uint8_t*)p->data;
+        a.data_bytes = p->data_bytes;
+        a.data_file_pos = p->data_file_pos;
+        a.keep = p->keep;
+        a.follow = follow ? 1u : 0u;
+        a.sync_point = p->sync_point;
+        a.timestamp = p->timestamp;
+        a.new_data_file_pos = p->new_data_file_pos;
+        a.dst = (uint8_t*)p->dst;
+        a.dst_bytes = p->dst_bytes;
+        a.journal_dst = (uint32_t*)p->journal_dst;
+        a.journal_dst_bytes = p->journal_dst_bytes;
+        a.new_index = p->new_index;
+        a.out = p->out;
+        a.ws_off = (unsigned long long*)s.off.p;
+        a.ws_len = (uint32_t*)s.len.p;
+        a.off = (unsigned long long*)w->rov_dst.p;
+        a.ws_exp = (uint32_t*)s.exp.p;
+        a.ws_out = (const uint32_t*)s.out.p;
+        a.ws_rec = (uint32_t*)w->rov_rec.p;
+        a.ws_hdr = (uint32_t*)w->rov_hdr.p;
+        a.kind = (uint8_t*)w->rov_kind.p;
+        a.joff = (unsigned long long*)w->rov_joff.p;
+        a.gslot = follow ? (uint32_t*)w->rov_gslot.p : nullptr;
+        a.gslots = gslots;
+        a.bsum = (unsigned long long*)w->rov_bsum.p;
+        a.ctr = (unsigned long long*)s.ctr.p;
+        layout_split(n, &a.per_block, &a.nblocks);
+        if (bmqcrc_launch_rollover_layout(&a, (void*)c.s)) {
+            return launch_failed("rollover layout");
+        }
+        // the records as the copy's messages: the descriptors are the workspace's
+        CopyArgs ca;
+        memset(&ca, 0, sizeof(ca));
+        ca.src = a.data;
+        ca.src_bytes = a.data_bytes;
+        ca.src_offsets = (const uint64_t*)a.ws_off;
+        ca.lengths = a.ws_len;
+        ca.dst = a.dst;
+        ca.dst_bytes = a.dst_bytes;
+        ca.dst_offsets = (const uint64_t*)a.off;
+        ca.out = (uint32_t*)s.out.p;
+        ca.n = n;
+        if ((rc = enqueue_copy(c, ca, w->rov_copy_first, w->rov_copy_bsum, a.ctr + kRovCtrWords))) {
+            return rc;
+        }
+        if (bmqcrc_launch_rollover_frame(&a, (void*)c.s)) {
+            return launch_failed("rollover frame");
+        }
+    }
+    bmqcrc_rollover_result r;
+    if ((rc = sync_result(c, o, rollover_result, result, &r))) {
+        return rc;
+    }
+    return r.refused_kind ? refused(kRolloverRefusals, r.refused_kind, r.refused_index) : 0;
+}
+
+int bmqcrc_last_rollover(int device, void* stream, bmqcrc_rollover_result* result)
+{
+    return last_result(device, stream, rollover_result, result);
+}
+
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,
                        uint32_t* seg_bytes)
 {
@@ -3794,7 +4018,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 17u;
+    return (2u << 16) | 18u;
 }
 
 }  // extern "C"

@@ -602,7 +602,73 @@ struct PpkArgs {
     uint32_t nblocks;               // layout blocks (<= kPackBlocks)
 };
 
+// ---- bmqcrc_partition_rollover (crc32c_rollover.hip, ABI 2.18) -------------
+// The classify, count, check and seal grid and block are kPackBlocks x
+// kPackThreads over contiguous record ranges (layout_split), the frame kernel's
+// kPackFrameBlocks x kPackFrameThreads.  RovArgs::ctr words: the first four are
+// the unpackers' (kSlotCtr*: the refusal, the kept MESSAGE records, the
+// mismatches and the lowest), behind them the call's
+constexpr int kRovCtrData = 4;       // bytes of all DATA records rolled (k_rov_check)
+constexpr int kRovCtrKept = 5;       // records kept, the sync point not counted (k_rov_check)
+constexpr int kRovCtrWords = 6;
+constexpr uint64_t kRovNoSyncPoint = ~0ull;  // BMQCRC_ROLLOVER_NO_SYNC_POINT
+// RovArgs::kind: what becomes of a record
+constexpr uint8_t kRovDrop = 0;      // not kept
+constexpr uint8_t kRovPlain = 1;     // kept, copied as it is
+constexpr uint8_t kRovMessage = 2;   // kept MESSAGE record: its DATA record goes with it
+constexpr uint8_t kRovQueueUri = 3;  // kept QUEUE_OP CREATION / ADDITION: the QLIST offset is zeroed
+constexpr uint8_t kRovConfirm = 4;   // CONFIRM record k_rov_count decides by the join (FOLLOW mode)
+// BMQCRC_ROLLOVER_* of bmqcrc_protocol.h, which the kernels do not include
+#define BMQCRC_ROV_KIND_RECORD_HEADER 1u
+#define BMQCRC_ROV_KIND_KEEP_JOURNAL_OP 2u
+#define BMQCRC_ROV_KIND_SYNC_POINT 3u
+#define BMQCRC_ROV_KIND_DATA_OFFSET 4u
+#define BMQCRC_ROV_KIND_DATA_RECORD 5u
+#define BMQCRC_ROV_KIND_DST_TOO_SMALL 6u
+#define BMQCRC_ROV_KIND_DATA_FILE_FULL 7u
+#define BMQCRC_ROV_KIND_TOO_MANY_PIECES 8u
+
+struct RovArgs {
+    const uint32_t* journal;        // device, 4-byte aligned: n records of 15 dwords
+    uint64_t n;                     // records
+    const uint8_t* data;            // device, 8-byte aligned: the DATA-file window
+    uint64_t data_bytes;
+    uint64_t data_file_pos;         // byte of the DATA file that data[0] stands for
+    const uint8_t* keep;            // device, n, or nullptr (every record that may be kept)
+    uint32_t follow;                // 1: BMQCRC_ROLLOVER_CONFIRMS_FOLLOW_MESSAGES
+    uint64_t sync_point;            // the record restated behind the kept ones, or kRovNoSyncPoint
+    uint64_t timestamp;
+    uint64_t new_data_file_pos;     // byte of the new DATA file that dst[0] stands for
+    uint8_t* dst;                   // device, 8-byte aligned
+    uint64_t dst_bytes;
+    uint32_t* journal_dst;          // device, 4-byte aligned
+    uint64_t journal_dst_bytes;
+    uint32_t* new_index;            // the caller's arrays (device, n), each may be nullptr:
+    uint32_t* out;                  // written by k_rov_frame, when nothing was refused
+    unsigned long long* ws_off;     // workspace, n: what the copy reads -- the application data's
+    uint32_t* ws_len;               // offset in `data` and length (0 when not a kept MESSAGE
+    unsigned long long* off;        // record) -- and where it goes in dst (before: the prefix of R)
+    uint32_t* ws_exp;               // workspace, n: the MessageRecords' stored CRCs
+    const uint32_t* ws_out;         // workspace, n: the copy's CRCs
+    uint32_t* ws_rec;               // workspace, n: the DATA record's bytes R and its header +
+    uint32_t* ws_hdr;               // options bytes
+    uint8_t* kind;                  // workspace, n: kRov*
+    unsigned long long* joff;       // workspace, n: the prefix of "kept", then the record's index
+                                    // in the new run (~0: not kept)
+    uint32_t* gslot;                // workspace, gslots, zeroed (FOLLOW mode): record + 1 of a kept
+    uint64_t gslots;                // MESSAGE record, hashed by GUID and queue key; a power of two
+    unsigned long long* bsum;       // workspace, 4 * kPackBlocks: R bytes | pieces | kept | (unused)
+    unsigned long long* ctr;        // workspace, kRovCtrWords, zeroed before the launch
+    uint64_t per_block;             // records per layout block (multiple of kPackThreads)
+    uint32_t nblocks;               // layout blocks (<= kPackBlocks)
+};
+
 }  // namespace bmqcrc
+
+// Launchers (crc32c_rollover.hip).  Asynchronous on `stream`: the layout
+// before bmqcrc_launch_copy (it writes the copy's descriptors), the frame after.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_rollover_layout(const bmqcrc::RovArgs* a, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_rollover_frame(const bmqcrc::RovArgs* a, void* stream);
 
 // Launchers (crc32c_push_pack.hip).  Asynchronous on `stream`: the layout
 // before bmqcrc_launch_copy (it writes the copy's descriptors), the frame after;

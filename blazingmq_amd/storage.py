@@ -817,3 +817,123 @@ def last_journal_select(device, stream=None):
     N.check(N.lib.bmqcrc_last_journal_select(
         device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
     return r.as_dict()
+
+
+# ----------------------------------------------------------------------------
+# Device-side compaction: the outstanding records into a new run and window.
+# ----------------------------------------------------------------------------
+CONFIRMS_AS_KEPT = N.BMQCRC_ROLLOVER_CONFIRMS_AS_KEPT
+CONFIRMS_FOLLOW_MESSAGES = N.BMQCRC_ROLLOVER_CONFIRMS_FOLLOW_MESSAGES
+
+RolledRecords = collections.namedtuple("RolledRecords", "dst journal_dst new_index crcs result")
+
+
+def rollover_records(journal, data, *, data_file_pos, new_data_file_pos, keep=None,
+                     confirm_mode=CONFIRMS_AS_KEPT, sync_point=None, timestamp=0, dst=None,
+                     journal_dst=None, stream=None, sync=True):
+    """Roll the outstanding records of a device-resident partition over into a
+    new journal run and a new DATA window on the GPU
+    (``bmqcrc_partition_rollover``): the loop of ``FileStore::rolloverImpl``
+    over ``writeRolledOverRecord`` and the sync point behind it, with every
+    kept message's stored CRC checked against the bytes carried over.
+
+    ``journal`` (uint8, 4-byte aligned, whole 60-byte records) and ``data``
+    (uint8, 8-byte aligned, standing for bytes ``[data_file_pos, data_file_pos
+    + data.numel())`` of the DATA file) are what ``unpack_records`` takes.
+    ``keep`` (uint8, one byte per record, or None for every record that may be
+    kept) says which records are rolled; for MESSAGE records it is the
+    ``select`` of ``select_records``.  A JOURNAL_OP record is never rolled and
+    a non-zero ``keep`` on one refuses the call.  With ``confirm_mode =
+    CONFIRMS_FOLLOW_MESSAGES`` a CONFIRM record is kept exactly when a kept
+    MESSAGE record of the run has its GUID and queue key, whatever ``keep``
+    says.  ``sync_point`` (a record index, or None) names the run's SYNCPOINT
+    record restated behind the kept records with ``timestamp`` and the new DATA
+    file's end.  ``new_data_file_pos`` is the byte of the new DATA file that
+    ``dst[0]`` stands for (a non-zero multiple of 8: the new file's headers).
+
+    ``dst=None`` allocates ``data.numel()`` bytes and ``journal_dst=None`` 60
+    bytes per record and sync point: both bounds hold unless two kept MESSAGE
+    records share a DATA record.
+
+    Returns the named tuple ``(dst, journal_dst, new_index, crcs, result)``:
+    ``new_index`` (int32, the record's position in the new run, -1 when not
+    kept), ``crcs`` (int32, the computed CRC of a kept MESSAGE record's
+    application data, 0 elsewhere) and ``result`` the dict of
+    ``last_rollover`` (None with ``sync=False``); with ``sync=True`` ``dst``
+    and ``journal_dst`` are sliced to the bytes written.  All or nothing: a
+    malformed record, a destination too small or a DATA file position past
+    what MessageOffsetDwords addresses writes nothing and, with ``sync=True``,
+    raises ``BmqCrcError`` (BMQCRC_EINVAL) naming kind and record.  A CRC
+    mismatch does not fail the call: ``result["n_bad"]`` counts them.  Not
+    meant to be captured into a graph."""
+    import torch
+    for name, t in (("journal", journal), ("data", data), ("keep", keep), ("dst", dst),
+                    ("journal_dst", journal_dst)):
+        if t is None and name not in ("journal", "data"):
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise TypeError("%s must be a contiguous %s tensor" % (name, torch.uint8))
+    dev = journal.device
+    if not journal.is_cuda:
+        raise TypeError("rollover_records takes device tensors only (journal is on %s)" % dev)
+    for name, t in (("data", data), ("keep", keep), ("dst", dst), ("journal_dst", journal_dst)):
+        if t is not None and t.device != dev:
+            raise TypeError("%s must be on %s like journal" % (name, dev))
+    if journal.numel() % JOURNAL_RECORD_SIZE:
+        raise ValueError("journal must hold whole 60-byte records")
+    n_records = journal.numel() // JOURNAL_RECORD_SIZE
+    if keep is not None and keep.numel() != n_records:
+        raise ValueError("keep needs one byte per record")
+    if dst is None:
+        dst = torch.empty(data.numel(), dtype=torch.uint8, device=dev)
+    if journal_dst is None:
+        journal_dst = torch.empty(JOURNAL_RECORD_SIZE * (n_records + (sync_point is not None)),
+                                  dtype=torch.uint8, device=dev)
+    new_index = torch.empty(n_records, dtype=torch.int32, device=dev)
+    crcs = torch.empty(n_records, dtype=torch.int32, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    # (an empty tensor has no address: the call wants one for the required arrays)
+    spare = torch.empty(8, dtype=torch.uint8, device=dev)
+    p = N.Rollover()
+    p.struct_size = ctypes.sizeof(N.Rollover)
+    p.journal, p.journal_bytes = journal.data_ptr() or spare.data_ptr(), journal.numel()
+    p.n_records = n_records
+    p.data, p.data_bytes = data.data_ptr() or spare.data_ptr(), data.numel()
+    p.data_file_pos = int(data_file_pos)
+    p.keep = keep.data_ptr() if keep is not None and n_records else None
+    p.confirm_mode = int(confirm_mode)
+    p.sync_point = N.BMQCRC_ROLLOVER_NO_SYNC_POINT if sync_point is None else int(sync_point)
+    p.timestamp = int(timestamp)
+    p.new_data_file_pos = int(new_data_file_pos)
+    p.dst, p.dst_bytes = dst.data_ptr() or spare.data_ptr(), dst.numel()
+    p.journal_dst = journal_dst.data_ptr() or spare.data_ptr()
+    p.journal_dst_bytes = journal_dst.numel()
+    p.new_index = new_index.data_ptr() if n_records else None
+    p.out = crcs.data_ptr() if n_records else None
+    o = N.make_opts(device=dev.index if dev.index is not None else -1, stream=stream.cuda_stream,
+                    flags=N.BMQCRC_F_DEVICE_PTRS | (0 if sync else N.BMQCRC_F_ASYNC))
+    r = N.RolloverResult()
+    N.check(N.lib.bmqcrc_partition_rollover(ctypes.byref(p), ctypes.byref(r), ctypes.byref(o)))
+    if not sync:
+        return RolledRecords(dst, journal_dst, new_index, crcs, None)
+    return RolledRecords(dst[:int(r.data_bytes)], journal_dst[:int(r.journal_bytes)], new_index,
+                         crcs, r.as_dict())
+
+
+def last_rollover(device, stream=None):
+    """The result of the previous ``rollover_records`` on (device, stream)
+    (bmqcrc_last_rollover), as a dict; waits for it.  ``n_records``;
+    ``n_kept`` (records rolled, the sync point not counted) and ``n_messages``
+    (the MESSAGE records among them); ``journal_bytes`` (the sync point
+    included) and ``data_bytes`` written; ``n_bad`` and ``first_bad`` (kept
+    MESSAGE records whose computed CRC differs from the stored one, and the
+    lowest; ``n_records`` when none); ``refused_kind`` (0,
+    ``BMQCRC_ROLLOVER_OK``, or the kind) and ``refused_index`` (a record, or
+    ``n_records`` for the sync point).  After a refused call only
+    ``n_records`` and the two ``refused_*`` are set.  ``stream=None`` is the
+    device's default stream."""
+    r = N.RolloverResult()
+    N.check(N.lib.bmqcrc_last_rollover(
+        device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
+    return r.as_dict()

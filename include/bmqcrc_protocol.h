@@ -1143,6 +1143,168 @@ int bmqcrc_push_event_pack(const bmqcrc_push_pack* p, bmqcrc_push_pack_result* r
  * waits for it.  `result` may be NULL. */
 int bmqcrc_last_push_pack(int device, void* stream, bmqcrc_push_pack_result* result);
 
+/* ABI 2.18.  Compaction: the outstanding records of a device-resident
+ * partition, journal run and DATA window both in device memory, are rolled over
+ * ON THE DEVICE into a new journal run and a new DATA window -- the loop of
+ * FileStore::rolloverImpl over FileStore::writeRolledOverRecord and the sync
+ * point it writes behind it, in one asynchronous call, byte for byte what the
+ * reference's loop writes when its d_records holds exactly the kept records in
+ * run order, in a cluster that is not QLIST aware.  The application data of
+ * every kept message is moved by the fused copy of bmqcrc_crc32c_copy, whose
+ * CRC32-C is compared with the one the MessageRecord stores ("verify on
+ * rollover", a check the reference never makes: a byte that rots in the old
+ * DATA file is carried into the new one), at the cost of the copy the rollover
+ * has to make anyway.  No payload byte and no descriptor crosses PCIe.
+ *
+ * Records.  Record i is journal[60 i .. 60 i + 60), i = 0 .. n_records - 1, and
+ *   `data` a window of the DATA file whose byte 0 stands for byte data_file_pos
+ *   of that file, as in bmqcrc_storage_event_pack (alignment included).
+ * Which records are kept.  keep[i] != 0 keeps record i; keep == NULL keeps
+ *   every record that may be kept.  For MESSAGE records keep is exactly the
+ *   select array of bmqcrc_journal_select.  A JOURNAL_OP record is never rolled:
+ *   keep[i] != 0 on one refuses the call (keep == NULL: it is not kept).  What
+ *   is outstanding is the caller's decision, with one exception:
+ *   confirm_mode BMQCRC_ROLLOVER_CONFIRMS_AS_KEPT (0): keep decides CONFIRM
+ *     records like the others;
+ *   confirm_mode BMQCRC_ROLLOVER_CONFIRMS_FOLLOW_MESSAGES (1): a CONFIRM record
+ *     is kept if and only if some kept MESSAGE record of the run has the same
+ *     GUID (bytes 36..51 of the MESSAGE record, 32..47 of the CONFIRM record)
+ *     and the same queue key (bytes 22..26 of both), wherever in the run it
+ *     lies; keep[] is ignored for CONFIRM records.  The live broker's rule
+ *     (FileBackedStorage keeps a message's CONFIRM handles with its MESSAGE
+ *     handle and removes them together): with it bmqcrc_journal_select ->
+ *     bmqcrc_partition_rollover needs no per-record work on the host for the
+ *     two record types that exist per message.  QUEUE_OP and DELETION records
+ *     stay with the caller.
+ * What is written.  With R[i] = 4 DataHeader.messageWords of a kept MESSAGE
+ *   record (0 for every other record), Q the 64-bit exclusive prefix of R and J
+ *   the exclusive prefix of "kept": record i goes to journal_dst + 60 J[i].
+ *   A kept MESSAGE record's whole DATA record (DataHeader, option words,
+ *   application data, padding) is copied to dst + Q[i] -- the DataHeader, option
+ *   words and padding bytes as they are, the application data by the fused copy
+ *   -- and its journal record with the BE u32 at byte 32 (MessageOffsetDwords)
+ *   set to (new_data_file_pos + Q[i]) / 8.  Two kept MESSAGE records that name
+ *   one DATA record each get a copy of their own.  A kept QUEUE_OP CREATION (2)
+ *   or ADDITION (4) record is copied with the BE u32 at byte 36
+ *   (queueUriRecordOffsetWords) set to 0; PURGE / DELETION QUEUE_OP records,
+ *   CONFIRM and DELETION records are copied as they are.
+ * Sync point.  With sync_point != BMQCRC_ROLLOVER_NO_SYNC_POINT one more record
+ *   follows the last kept one, built from record s = sync_point, which must be
+ *   a JOURNAL_OP record of JournalOpType SYNCPOINT: BE u16 0x5000; bytes 2..11
+ *   of s (sequence number, lease id); BE u64 timestamp at 12; bytes 20..22 zero;
+ *   byte 23 = 1 (REGULAR); BE u32 2 (SYNCPOINT) at 24; bytes 28..43 of s
+ *   (sequence number, primary node id, primary lease id); BE u32
+ *   (new_data_file_pos + Q[n_records]) / 8 at 44; bytes 48..55 zero; the magic
+ *   0x2A724563 at 56.  Setting JournalFileHeader.
+ *   firstSyncPointAfterRolloverOffsetWords stays with the caller, who owns the
+ *   file headers.  Every other sync point is dropped, as the reference drops it.
+ * Not built: the QLIST file; the file headers of the new files.
+ * Outputs, each may be NULL: new_index[i] (J[i], 0xFFFFFFFF for a record not
+ *   kept), out[i] (the computed CRC32-C of a kept MESSAGE record's application
+ *   data, 0 elsewhere).
+ * Verify on rollover.  The stored CRC is the MessageRecord's BE u32 at byte 52.
+ *   n_bad counts the kept MESSAGE records whose computed CRC differs, first_bad
+ *   is the lowest (n_records when none).  A mismatch does not fail the call and
+ *   the bytes are rolled as they are: what to do about it is the caller's
+ *   decision.
+ * All or nothing, decided on the device.  One violation anywhere refuses the
+ *   call, and a refused call writes nothing to dst, journal_dst or any output
+ *   array.  The lowest kind wins and within it the lowest index
+ *   (BMQCRC_ROLLOVER_* below).  No DATA byte of a record that is not kept is
+ *   ever loaded, and no DATA byte before its range is shown to lie in the
+ *   window.  DST_TOO_SMALL, DATA_FILE_FULL and TOO_MANY_PIECES are evaluated
+ *   only when no lower kind was raised.  NOT checked: GUIDs, queue keys, the
+ *   order of sequence numbers, queue liveness: bmqcrc_journal_select holds
+ *   those checks.  A synchronous call returns BMQCRC_EINVAL naming kind and
+ *   index; after an asynchronous call bmqcrc_last_rollover reports them.
+ * Options.  Device pointers only: BMQCRC_F_DEVICE_PTRS is required,
+ *   BMQCRC_F_ASYNC allowed; any other flag, ndevices > 1, a wrong struct_size or
+ *   a non-zero reserved field; journal, data, dst or journal_dst null; journal,
+ *   journal_dst, new_index or out not 4-byte aligned, data or dst not 8-byte
+ *   aligned; journal_bytes != 60 n_records; n_records >= 2^32; data_file_pos no
+ *   multiple of 8; new_data_file_pos 0 or no multiple of 8; confirm_mode above
+ *   1; sync_point neither below n_records nor BMQCRC_ROLLOVER_NO_SYNC_POINT;
+ *   dst, journal_dst or an output array meeting an input (journal, data, keep)
+ *   or one another is BMQCRC_EINVAL, answered on the host before the device
+ *   lookup.  n_records == 0 (which admits no sync point) launches nothing,
+ *   writes nothing and reports zeros.
+ * The copy runs over the n_records records (those that are not kept MESSAGE
+ *   records are empty messages).  Nothing at or beyond dst_bytes,
+ *   journal_dst_bytes or n_records entries of new_index and out is ever written.
+ * *result (may be NULL) is written by a synchronous call only.
+ * State.  As bmqcrc_storage_event_pack: takes the workspace mutex of (device,
+ *   stream); restores the caller's current device; allocates its own workspace
+ *   on first use and when n_records grows (49 bytes per record, and in
+ *   FOLLOW mode 8 to 16 more for the hash), which bmqcrc_reserve does not
+ *   cover; is not meant to be captured into a hipGraph; is deterministic.  The
+ *   copy's counters live in the call's own scratch: the shape prediction and
+ *   the records of every other bmqcrc_last_* call are never touched. */
+#define BMQCRC_ROLLOVER_OK 0
+#define BMQCRC_ROLLOVER_RECORD_HEADER 1    /* BMQCRC_REC_UNPACK_RECORD_HEADER's conditions (type 0, lease id 0,
+                                              sequence number 0, a wrong magic); a type above 5; a QUEUE_OP
+                                              record whose QueueOpType is outside 1..4 -- on every record
+                                              of the run, kept or not.  Index: the record */
+#define BMQCRC_ROLLOVER_KEEP_JOURNAL_OP 2  /* keep[i] != 0 on a JOURNAL_OP record.  Index: the record */
+#define BMQCRC_ROLLOVER_SYNC_POINT 3       /* record sync_point is not a JOURNAL_OP record of JournalOpType
+                                              SYNCPOINT.  Index: sync_point */
+#define BMQCRC_ROLLOVER_DATA_OFFSET 4      /* BMQCRC_STORAGE_PACK_DATA_OFFSET's conditions, on kept MESSAGE
+                                              records only.  Index: the record */
+#define BMQCRC_ROLLOVER_DATA_RECORD 5      /* BMQCRC_STORAGE_PACK_DATA_RECORD's conditions, on kept MESSAGE
+                                              records only.  Index: the record */
+#define BMQCRC_ROLLOVER_DST_TOO_SMALL 6    /* index: the lowest kept record whose DATA record ends past
+                                              dst_bytes or whose journal record ends past
+                                              journal_dst_bytes; n_records: the sync point does */
+#define BMQCRC_ROLLOVER_DATA_FILE_FULL 7   /* index: the lowest kept MESSAGE record whose DATA record ends
+                                              past byte 8 (2^32 - 1) of the new DATA file; n_records:
+                                              new_data_file_pos itself lies past it */
+#define BMQCRC_ROLLOVER_TOO_MANY_PIECES 8  /* beyond the copy kernel's 2^32-1 16-byte pieces per call: the sum
+                                              over the kept MESSAGE records with application data of
+                                              ((length + 15) >> 4) + 1.  Index 0 */
+
+#define BMQCRC_ROLLOVER_CONFIRMS_AS_KEPT 0
+#define BMQCRC_ROLLOVER_CONFIRMS_FOLLOW_MESSAGES 1
+#define BMQCRC_ROLLOVER_NO_SYNC_POINT 0xFFFFFFFFFFFFFFFFull
+
+typedef struct bmqcrc_rollover {
+    uint32_t struct_size, reserved;       /* sizeof, 0 */
+    const void* journal;                  /* device, 4-byte aligned: n_records 60-byte records, the record run */
+    uint64_t journal_bytes;               /* == 60 * n_records */
+    uint64_t n_records;                   /* < 2^32 */
+    const void* data;                     /* device, 8-byte aligned: the DATA-file window */
+    uint64_t data_bytes;
+    uint64_t data_file_pos;               /* byte of the DATA file that data[0] stands for: multiple of 8 */
+    const uint8_t* keep;                  /* device, n_records, may be NULL (every record that may be kept) */
+    uint32_t confirm_mode;                /* BMQCRC_ROLLOVER_CONFIRMS_* */
+    uint32_t reserved2;                   /* 0 */
+    uint64_t sync_point;                  /* the record restated behind the kept ones, or ..._NO_SYNC_POINT */
+    uint64_t timestamp;                   /* the restated sync point's */
+    uint64_t new_data_file_pos;           /* byte of the NEW DATA file that dst[0] stands for: multiple of 8, > 0 */
+    void* dst;                            /* device, 8-byte aligned: the DATA records back to back */
+    uint64_t dst_bytes;
+    void* journal_dst;                    /* device, 4-byte aligned: the 60-byte records back to back */
+    uint64_t journal_dst_bytes;
+    uint32_t* new_index;                  /* device, n_records, may be NULL: position in the new run */
+    uint32_t* out;                        /* device, n_records, may be NULL: the computed CRCs */
+} bmqcrc_rollover;
+
+/* All fields zero before the first call on (device, stream); after a refused
+ * call only n_records and the refused_* fields are set. */
+typedef struct bmqcrc_rollover_result {
+    uint64_t n_records, n_kept, n_messages; /* n_kept: records rolled, the sync point not counted;
+                                               n_messages: MESSAGE records among them */
+    uint64_t journal_bytes, data_bytes;   /* bytes written to journal_dst (the sync point included) and dst */
+    uint64_t n_bad, first_bad;            /* stored CRC != computed CRC; first_bad = n_records when none */
+    uint32_t refused_kind, reserved;
+    uint64_t refused_index;               /* a record, or n_records, by kind */
+} bmqcrc_rollover_result;
+
+int bmqcrc_partition_rollover(const bmqcrc_rollover* p, bmqcrc_rollover_result* result,
+                              const bmqcrc_opts* opts);
+
+/* ABI 2.18.  Result of the previous bmqcrc_partition_rollover on (device,
+ * stream); waits for it.  `result` may be NULL. */
+int bmqcrc_last_rollover(int device, void* stream, bmqcrc_rollover_result* result);
+
 /* ---- cluster state ledger (mqbc_clusterstateledgerprotocol.h:76,272) ------ */
 
 /* mqbc::ClusterStateLedgerUtilRc values (mqbc_clusterstateledgerutil.h:65-124)
