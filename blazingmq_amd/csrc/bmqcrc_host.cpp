@@ -144,6 +144,35 @@ struct UnpackScratch {
     }
 };
 
+struct Ctx;
+
+// Scratch of one device call that copies the slots it found to where its
+// layout placed them (bmqcrc_storage_event_apply, bmqcrc_storage_event_pack,
+// bmqcrc_push_event_pack, bmqcrc_partition_rollover): an UnpackScratch whose
+// counters are followed by the copy pass's (kCopyCtrWords); per slot the
+// destination offset (8); the layout's block sums, `prefixes` pairs of
+// kPackBlocks; the copy pass's piece prefix (4 a slot) and block sums.
+struct SlotCopyScratch : UnpackScratch {
+    DevBuf dst, bsum, copy_first, copy_bsum;
+    // (copy_first and copy_bsum are sized by enqueue_copy)
+    int ensure(uint64_t cap, bool need_out, int ctr_words, uint32_t prefixes = 1)
+    {
+        int rc;
+        if ((rc = UnpackScratch::ensure(cap, need_out, ctr_words + kCopyCtrWords)) ||
+            (rc = bsum.ensure(8ull * 2 * prefixes * kPackBlocks))) {
+            return rc;
+        }
+        return dst.ensure(8 * std::max<uint64_t>(cap, 1));
+    }
+    // A call begins: its counters and the copy pass's zeroed on c's stream, and
+    // n_units what bmqcrc_last_* reports the call was given.
+    int begin(Ctx& c, int ctr_words, uint64_t n_units);
+    // The slots as the copy's n_slots messages, from [src, +src_bytes) to
+    // [to, +to_bytes): the descriptors are the workspace's, never the caller's.
+    int enqueue_slot_copy(Ctx& c, const void* src, uint64_t src_bytes, void* to, uint64_t to_bytes,
+                          uint64_t n_slots, int ctr_words);
+};
+
 // Planner + staging scratch for one (device, stream).
 struct Workspace {
     std::mutex mu;
@@ -188,46 +217,35 @@ struct Workspace {
     UnpackScratch unp, runp;
     DevBuf unp_first, unp_bad;
     DevBuf runp_pre, runp_roff, runp_rlen, runp_rflags, runp_bsum;
-    // bmqcrc_storage_event_apply: a set of its own again, its counters followed
-    // by its copy pass's.  Beside it per event what the PUT unpack keeps, per
-    // slot the destination offset and the journal record's offset (8 each),
-    // the DATA record's size, its header + options size, the bytes after the
-    // journal record and type | flags (4 each), the layout's block sums and
-    // the copy pass's scratch; the write head the last apply was given
-    UnpackScratch sap;
-    DevBuf sap_first, sap_bad, sap_dst, sap_jrn, sap_rec, sap_hdr, sap_pay, sap_meta, sap_bsum;
-    DevBuf sap_copy_first, sap_copy_bsum;
+    // bmqcrc_storage_event_apply, bmqcrc_storage_event_pack,
+    // bmqcrc_push_event_pack and bmqcrc_partition_rollover: a set each again,
+    // because their bmqcrc_last_* report independently.  Beside it:
+    // the apply keeps per event what the PUT unpack keeps, per slot the journal
+    // record's offset (8), the DATA record's size, its header + options size,
+    // the bytes after the journal record and type | flags (4 each), and the
+    // write head the last apply was given
+    SlotCopyScratch sap;
+    DevBuf sap_first, sap_bad, sap_jrn, sap_rec, sap_hdr, sap_pay, sap_meta;
     uint32_t sap_lease = 0;
     uint64_t sap_seq = 0;
-    // bmqcrc_storage_event_pack: a set of its own again, its counters followed
-    // by its copy pass's: per record the descriptor its copy reads (8 + 4), the
-    // stored and the computed CRC (4 each), the destination offset (8), the
-    // DATA record's size and its header + options size (4 each), the message
-    // type (1) and the copy pass's piece prefix (4); the layout's block sums
-    // and the copy pass's; the events of the last pack enqueued
-    UnpackScratch spk;
-    DevBuf spk_dst, spk_rec, spk_hdr, spk_type, spk_bsum, spk_copy_first, spk_copy_bsum;
+    // the storage pack per record the DATA record's size and its header +
+    // options size (4 each) and the message type (1), and the events of the
+    // last pack enqueued
+    SlotCopyScratch spk;
+    DevBuf spk_rec, spk_hdr, spk_type;
     uint64_t spk_events = 0;
-    // bmqcrc_push_event_pack: a set of its own again, its counters followed by
-    // its copy pass's: per message the descriptor its copy reads (8 + 4), the
-    // stored and the computed CRC (4 each), the destination offset (8), CAT,
-    // SchemaId and the properties flag (4) and the copy pass's piece prefix
-    // (4); the layout's block sums and the copy pass's; the events of the last
-    // pack enqueued
-    UnpackScratch ppk;
-    DevBuf ppk_dst, ppk_meta, ppk_bsum, ppk_copy_first, ppk_copy_bsum;
+    // the push pack per message CAT, SchemaId and the properties flag (4), and
+    // the events of the last pack enqueued
+    SlotCopyScratch ppk;
+    DevBuf ppk_meta;
     uint64_t ppk_events = 0;
-    // bmqcrc_partition_rollover: a set of its own again, its counters followed
-    // by its copy pass's: per record the descriptor its copy reads (8 + 4), the
-    // stored and the computed CRC (4 each), the destination offset (8), the
-    // DATA record's size and its header + options size (4 each), the kind (1),
-    // the index in the new run (8) and the copy pass's piece prefix (4); in
-    // FOLLOW mode the hash of the kept MESSAGE records (8 to 16, a power of
-    // two); the layout's block sums and the copy pass's; whether the last
-    // rollover enqueued restates a sync point
-    UnpackScratch rov;
-    DevBuf rov_dst, rov_rec, rov_hdr, rov_kind, rov_joff, rov_gslot, rov_bsum, rov_copy_first,
-        rov_copy_bsum;
+    // the rollover per record the DATA record's size and its header + options
+    // size (4 each), the kind (1) and the index in the new run (8); in FOLLOW
+    // mode the hash of the kept MESSAGE records (8 to 16 a record, a power of
+    // two); two pairs of block sums; whether the last rollover enqueued
+    // restates a sync point
+    SlotCopyScratch rov;
+    DevBuf rov_rec, rov_hdr, rov_kind, rov_joff, rov_gslot;
     bool rov_sync = false;
     // bmqcrc_journal_select: the part of its workspace every call zeroes (the
     // counters, the queue-key and GUID tables, the claims) and the rest (the
@@ -2042,6 +2060,43 @@ int enqueue_payload(Ctx& c, PackScratch& s, int ctr_words, const void* src, cons
     return enqueue_copy(c, ca, s.first, s.copy_bsum, a.ctr + ctr_words);
 }
 
+// The copy pass behind a layout that refused nothing, from its counters `cc`:
+// the layout placed every message inside the destination, so the copy pass has
+// nothing to refuse.
+int copy_pass_clean(const unsigned long long* cc, const char* call)
+{
+    if (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow]) {
+        return fail(BMQCRC_EIO, std::string(call) + ": the copy pass refused a message the "
+                                                    "layout had placed (internal error)");
+    }
+    return 0;
+}
+
+int SlotCopyScratch::begin(Ctx& c, int ctr_words, uint64_t n_units)
+{
+    HIP_TRY(hipMemsetAsync(ctr.p, 0, 8 * (ctr_words + kCopyCtrWords), c.s));
+    n = n_units;
+    any = true;
+    return 0;
+}
+
+int SlotCopyScratch::enqueue_slot_copy(Ctx& c, const void* src, uint64_t src_bytes, void* to,
+                                       uint64_t to_bytes, uint64_t n_slots, int ctr_words)
+{
+    CopyArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.src = (const uint8_t*)src;
+    ca.src_bytes = src_bytes;
+    ca.src_offsets = (const uint64_t*)off.p;
+    ca.lengths = (const uint32_t*)len.p;
+    ca.dst = (uint8_t*)to;
+    ca.dst_bytes = to_bytes;
+    ca.dst_offsets = (const uint64_t*)dst.p;
+    ca.out = (uint32_t*)out.p;
+    ca.n = n_slots;
+    return enqueue_copy(c, ca, copy_first, copy_bsum, (unsigned long long*)ctr.p + ctr_words);
+}
+
 // Counters of the pack last enqueued on `s`, after everything enqueued on c's
 // stream (w->mu held): ctr[] receives the layout's ctr_words and the copy
 // pass's kCopyCtrWords, kind and index the refusal (kind 0: nothing refused).
@@ -2052,13 +2107,7 @@ int pack_counters(Ctx& c, const PackScratch& s, int ctr_words, const char* call,
                            c.s));
     HIP_TRY(hipStreamSynchronize(c.s));
     refusal_of(ctr[kLayoutCtrRefusal], kind, index);
-    // the layout placed every message inside dst: the copy pass has nothing to refuse
-    const unsigned long long* cc = ctr + ctr_words;
-    if (!*kind && (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow])) {
-        return fail(BMQCRC_EIO, std::string(call) + ": the copy pass refused a message the "
-                                                    "layout had placed (internal error)");
-    }
-    return 0;
+    return *kind ? 0 : copy_pass_clean(ctr + ctr_words, call);
 }
 
 // The struct_size / reserved preamble of a call that takes its arguments in a
@@ -2140,6 +2189,17 @@ int sync_result(Ctx& c, const bmqcrc_opts& o, Read read, R* result, R* r)
         *result = *r;
     }
     return rc;
+}
+
+// ... and, for a result that names its refusal by kind and index alone, the
+// refusal's text and code.
+template <class R, class Read, size_t K>
+int sync_result_or_refusal(Ctx& c, const bmqcrc_opts& o, Read read, R* result,
+                           const char* const (&what)[K])
+{
+    R r;
+    const int rc = sync_result(c, o, read, result, &r);
+    return rc ? rc : r.refused_kind ? refused(what, r.refused_kind, r.refused_index) : 0;
 }
 
 // The body of a bmqcrc_last_*: the result `read` gives for the stream's workspace.
@@ -3020,11 +3080,8 @@ static int storage_apply_result(Ctx& c, bmqcrc_storage_apply_result* r)
         r->refused_offset = ctr[kSapCtrOffset];
         return 0;
     }
-    // the layout placed every message inside data_dst: the copy pass has nothing to refuse
-    const unsigned long long* cc = ctr + kSapCtrWords;
-    if (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow]) {
-        return fail(BMQCRC_EIO, "bmqcrc_storage_event_apply: the copy pass refused a message "
-                                "the layout had placed (internal error)");
+    if (int bad = copy_pass_clean(ctr + kSapCtrWords, "bmqcrc_storage_event_apply")) {
+        return bad;
     }
     r->n_data = ctr[kSapCtrData];
     r->journal_bytes = kJournalRecordBytes * r->n_msgs;
@@ -3069,34 +3126,29 @@ int bmqcrc_storage_event_apply(const bmqcrc_storage_apply* p, bmqcrc_storage_app
                            {!p->data_dst, "data_dst"}}))) {
         return rc;
     }
-    if ((uintptr_t)p->events & 3u) {
-        return fail(BMQCRC_EINVAL, "events must be 4-byte aligned");
-    }
-    if ((uintptr_t)p->journal_dst & 3u) {
-        return fail(BMQCRC_EINVAL, "journal_dst must be 4-byte aligned");
-    }
-    if ((uintptr_t)p->data_dst & 7u) {
-        return fail(BMQCRC_EINVAL, "data_dst must be 8-byte aligned");
-    }
-    if (!p->event_offsets && p->n_events != 1) {
-        return fail(BMQCRC_EINVAL, "event_offsets == NULL means one event: n_events must be 1");
-    }
-    if (p->n_events > 0xFFFFFFFFull || p->msg_cap > 0xFFFFFFFFull) {
-        return fail(BMQCRC_EINVAL, "n_events and msg_cap must be below 2^32");
-    }
-    if (p->journal_pos == 0 || (p->journal_pos & 3u)) {
-        return fail(BMQCRC_EINVAL, "journal_pos must be a multiple of 4 and not 0 (a journal "
-                                   "begins with its file headers)");
-    }
-    if (p->data_file_pos == 0 || (p->data_file_pos & 7u)) {
-        return fail(BMQCRC_EINVAL, "data_file_pos must be a multiple of 8 and not 0 (recovery "
-                                   "treats a MessageOffsetDwords of 0 as invalid)");
-    }
-    if (p->partition_id > 0xFFFFu) {
-        return fail(BMQCRC_EINVAL, "partition_id must be at most 65535");
-    }
-    if (p->lease_id == 0 && p->seq != 0) {
-        return fail(BMQCRC_EINVAL, "lease_id == 0 means no write head is known: seq must be 0");
+    const struct {
+        bool bad;
+        const char* what;
+    } checks[] = {
+        {((uintptr_t)p->events & 3u) != 0, "events must be 4-byte aligned"},
+        {((uintptr_t)p->journal_dst & 3u) != 0, "journal_dst must be 4-byte aligned"},
+        {((uintptr_t)p->data_dst & 7u) != 0, "data_dst must be 8-byte aligned"},
+        {!p->event_offsets && p->n_events != 1,
+         "event_offsets == NULL means one event: n_events must be 1"},
+        {p->n_events > 0xFFFFFFFFull || p->msg_cap > 0xFFFFFFFFull,
+         "n_events and msg_cap must be below 2^32"},
+        {p->journal_pos == 0 || (p->journal_pos & 3u),
+         "journal_pos must be a multiple of 4 and not 0 (a journal begins with its file headers)"},
+        {p->data_file_pos == 0 || (p->data_file_pos & 7u),
+         "data_file_pos must be a multiple of 8 and not 0 (recovery treats a MessageOffsetDwords "
+         "of 0 as invalid)"},
+        {p->partition_id > 0xFFFFu, "partition_id must be at most 65535"},
+        {p->lease_id == 0 && p->seq != 0,
+         "lease_id == 0 means no write head is known: seq must be 0"}};
+    for (const auto& k : checks) {
+        if (k.bad) {
+            return fail(BMQCRC_EINVAL, k.what);
+        }
     }
     const uint64_t cap = p->msg_cap;
     const NamedRange events = {p->events, p->events_bytes, "[events, events+events_bytes)"};
@@ -3122,20 +3174,16 @@ int bmqcrc_storage_event_apply(const bmqcrc_storage_apply* p, bmqcrc_storage_app
         return rc;
     }
     Workspace* w = c.w;
-    UnpackScratch& s = w->sap;
+    SlotCopyScratch& s = w->sap;
     const uint64_t slots = std::max<uint64_t>(cap, 1);
-    if ((rc = s.ensure(cap, true, kSapCtrWords + kCopyCtrWords)) ||
+    if ((rc = s.ensure(cap, true, kSapCtrWords)) ||
         (rc = w->sap_first.ensure(8 * (p->n_events + 1))) ||
         (rc = w->sap_bad.ensure(8 * std::max<uint64_t>(p->n_events, 1))) ||
-        (rc = w->sap_bsum.ensure(8ull * 2 * kPackBlocks)) || (rc = w->sap_dst.ensure(8 * slots)) ||
         (rc = w->sap_jrn.ensure(8 * slots)) || (rc = w->sap_rec.ensure(4 * slots)) ||
         (rc = w->sap_hdr.ensure(4 * slots)) || (rc = w->sap_pay.ensure(4 * slots)) ||
-        (rc = w->sap_meta.ensure(4 * slots))) {
+        (rc = w->sap_meta.ensure(4 * slots)) || (rc = s.begin(c, kSapCtrWords, p->n_events))) {
         return rc;
     }
-    HIP_TRY(hipMemsetAsync(s.ctr.p, 0, 8 * (kSapCtrWords + kCopyCtrWords), c.s));
-    s.n = p->n_events;
-    s.any = true;
     w->sap_lease = p->lease_id;
     w->sap_seq = p->seq;
     if (p->n_events) {
@@ -3166,7 +3214,7 @@ int bmqcrc_storage_event_apply(const bmqcrc_storage_apply* p, bmqcrc_storage_app
         a.event_first = p->event_first;
         a.ws_off = (unsigned long long*)s.off.p;
         a.ws_len = (uint32_t*)s.len.p;
-        a.off = (unsigned long long*)w->sap_dst.p;
+        a.off = (unsigned long long*)s.dst.p;
         a.ws_exp = (uint32_t*)s.exp.p;
         a.ws_out = (const uint32_t*)s.out.p;
         a.ws_jrn = (unsigned long long*)w->sap_jrn.p;
@@ -3176,25 +3224,14 @@ int bmqcrc_storage_event_apply(const bmqcrc_storage_apply* p, bmqcrc_storage_app
         a.ws_meta = (uint32_t*)w->sap_meta.p;
         a.first = (unsigned long long*)w->sap_first.p;
         a.bad_off = (unsigned long long*)w->sap_bad.p;
-        a.bsum = (unsigned long long*)w->sap_bsum.p;
+        a.bsum = (unsigned long long*)s.bsum.p;
         a.ctr = (unsigned long long*)s.ctr.p;
         layout_split(slots, &a.per_block, &a.nblocks);
         if (bmqcrc_launch_storage_apply_layout(&a, (void*)c.s)) {
             return launch_failed("storage-apply layout");
         }
-        // the slots as the copy's messages: the descriptors are the workspace's, never the caller's
-        CopyArgs ca;
-        memset(&ca, 0, sizeof(ca));
-        ca.src = a.events;
-        ca.src_bytes = a.events_bytes;
-        ca.src_offsets = (const uint64_t*)a.ws_off;
-        ca.lengths = a.ws_len;
-        ca.dst = a.data_dst;
-        ca.dst_bytes = a.data_dst_bytes;
-        ca.dst_offsets = (const uint64_t*)a.off;
-        ca.out = (uint32_t*)s.out.p;
-        ca.n = cap;
-        if ((rc = enqueue_copy(c, ca, w->sap_copy_first, w->sap_copy_bsum, a.ctr + kSapCtrWords))) {
+        if ((rc = s.enqueue_slot_copy(c, a.events, a.events_bytes, a.data_dst, a.data_dst_bytes, cap,
+                                      kSapCtrWords))) {
             return rc;
         }
         if (bmqcrc_launch_storage_apply_frame(&a, (void*)c.s)) {
@@ -3244,11 +3281,8 @@ static int storage_pack_result(Ctx& c, bmqcrc_storage_pack_result* r)
     if (r->refused_kind) {
         return 0;
     }
-    // the layout placed every message inside dst: the copy pass has nothing to refuse
-    const unsigned long long* cc = ctr + kSpkCtrWords;
-    if (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow]) {
-        return fail(BMQCRC_EIO, "bmqcrc_storage_event_pack: the copy pass refused a message "
-                                "the layout had placed (internal error)");
+    if (int bad = copy_pass_clean(ctr + kSpkCtrWords, "bmqcrc_storage_event_pack")) {
+        return bad;
     }
     r->n_data = ctr[kSpkCtrData];
     r->total_bytes = ctr[kSpkCtrTotal];
@@ -3337,17 +3371,13 @@ int bmqcrc_storage_event_pack(const bmqcrc_storage_pack* p, bmqcrc_storage_pack_
         return rc;
     }
     Workspace* w = c.w;
-    UnpackScratch& s = w->spk;
+    SlotCopyScratch& s = w->spk;
     const uint64_t recs = std::max<uint64_t>(n, 1);
-    if ((rc = s.ensure(n, true, kSpkCtrWords + kCopyCtrWords)) ||
-        (rc = w->spk_bsum.ensure(8ull * 2 * kPackBlocks)) || (rc = w->spk_dst.ensure(8 * recs)) ||
-        (rc = w->spk_rec.ensure(4 * recs)) || (rc = w->spk_hdr.ensure(4 * recs)) ||
-        (rc = w->spk_type.ensure(recs))) {
+    if ((rc = s.ensure(n, true, kSpkCtrWords)) || (rc = w->spk_rec.ensure(4 * recs)) ||
+        (rc = w->spk_hdr.ensure(4 * recs)) || (rc = w->spk_type.ensure(recs)) ||
+        (rc = s.begin(c, kSpkCtrWords, n))) {
         return rc;
     }
-    HIP_TRY(hipMemsetAsync(s.ctr.p, 0, 8 * (kSpkCtrWords + kCopyCtrWords), c.s));
-    s.n = n;
-    s.any = true;
     w->spk_events = n ? p->n_events : 0;
     if (n) {
         SpkArgs a;
@@ -3373,42 +3403,27 @@ int bmqcrc_storage_event_pack(const bmqcrc_storage_pack* p, bmqcrc_storage_pack_
         a.out = p->out;
         a.ws_off = (unsigned long long*)s.off.p;
         a.ws_len = (uint32_t*)s.len.p;
-        a.off = (unsigned long long*)w->spk_dst.p;
+        a.off = (unsigned long long*)s.dst.p;
         a.ws_exp = (uint32_t*)s.exp.p;
         a.ws_out = (const uint32_t*)s.out.p;
         a.ws_rec = (uint32_t*)w->spk_rec.p;
         a.ws_hdr = (uint32_t*)w->spk_hdr.p;
         a.ws_type = (uint8_t*)w->spk_type.p;
-        a.bsum = (unsigned long long*)w->spk_bsum.p;
+        a.bsum = (unsigned long long*)s.bsum.p;
         a.ctr = (unsigned long long*)s.ctr.p;
         layout_split(n, &a.per_block, &a.nblocks);
         if (bmqcrc_launch_storage_pack_layout(&a, (void*)c.s)) {
             return launch_failed("storage-pack layout");
         }
-        // the records as the copy's messages: the descriptors are the workspace's
-        CopyArgs ca;
-        memset(&ca, 0, sizeof(ca));
-        ca.src = a.data;
-        ca.src_bytes = a.data_bytes;
-        ca.src_offsets = (const uint64_t*)a.ws_off;
-        ca.lengths = a.ws_len;
-        ca.dst = a.dst;
-        ca.dst_bytes = a.dst_bytes;
-        ca.dst_offsets = (const uint64_t*)a.off;
-        ca.out = (uint32_t*)s.out.p;
-        ca.n = n;
-        if ((rc = enqueue_copy(c, ca, w->spk_copy_first, w->spk_copy_bsum, a.ctr + kSpkCtrWords))) {
+        if ((rc = s.enqueue_slot_copy(c, a.data, a.data_bytes, a.dst, a.dst_bytes, n,
+                                      kSpkCtrWords))) {
             return rc;
         }
         if (bmqcrc_launch_storage_pack_frame(&a, (void*)c.s)) {
             return launch_failed("storage-pack frame");
         }
     }
-    bmqcrc_storage_pack_result r;
-    if ((rc = sync_result(c, o, storage_pack_result, result, &r))) {
-        return rc;
-    }
-    return r.refused_kind ? refused(kStoragePackRefusals, r.refused_kind, r.refused_index) : 0;
+    return sync_result_or_refusal(c, o, storage_pack_result, result, kStoragePackRefusals);
 }
 
 int bmqcrc_last_storage_pack(int device, void* stream, bmqcrc_storage_pack_result* result)
@@ -3445,11 +3460,8 @@ static int push_pack_result(Ctx& c, bmqcrc_push_pack_result* r)
     if (r->refused_kind) {
         return 0;
     }
-    // the layout placed every message inside dst: the copy pass has nothing to refuse
-    const unsigned long long* cc = ctr + kPpkCtrWords;
-    if (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow]) {
-        return fail(BMQCRC_EIO, "bmqcrc_push_event_pack: the copy pass refused a message "
-                                "the layout had placed (internal error)");
+    if (int bad = copy_pass_clean(ctr + kPpkCtrWords, "bmqcrc_push_event_pack")) {
+        return bad;
     }
     r->total_bytes = ctr[kPpkCtrTotal];
     return 0;
@@ -3550,17 +3562,13 @@ int bmqcrc_push_event_pack(const bmqcrc_push_pack* p, bmqcrc_push_pack_result* r
         return rc;
     }
     Workspace* w = c.w;
-    UnpackScratch& s = w->ppk;
-    const uint64_t msgs = std::max<uint64_t>(n, 1);
+    SlotCopyScratch& s = w->ppk;
     const bool size_only = !p->dst;
-    if ((rc = s.ensure(n, !size_only, kPpkCtrWords + kCopyCtrWords)) ||
-        (rc = w->ppk_bsum.ensure(8ull * 2 * kPackBlocks)) || (rc = w->ppk_dst.ensure(8 * msgs)) ||
-        (rc = w->ppk_meta.ensure(4 * msgs))) {
+    if ((rc = s.ensure(n, !size_only, kPpkCtrWords)) ||
+        (rc = w->ppk_meta.ensure(4 * std::max<uint64_t>(n, 1))) ||
+        (rc = s.begin(c, kPpkCtrWords, n))) {
         return rc;
     }
-    HIP_TRY(hipMemsetAsync(s.ctr.p, 0, 8 * (kPpkCtrWords + kCopyCtrWords), c.s));
-    s.n = n;
-    s.any = true;
     w->ppk_events = n ? p->n_events : 0;
     if (n) {
         PpkArgs a;
@@ -3589,31 +3597,19 @@ int bmqcrc_push_event_pack(const bmqcrc_push_pack* p, bmqcrc_push_pack_result* r
         a.lengths = p->lengths;
         a.ws_off = (unsigned long long*)s.off.p;
         a.ws_len = (uint32_t*)s.len.p;
-        a.off = (unsigned long long*)w->ppk_dst.p;
+        a.off = (unsigned long long*)s.dst.p;
         a.ws_exp = (uint32_t*)s.exp.p;
         a.ws_out = (const uint32_t*)s.out.p;
         a.ws_meta = (uint32_t*)w->ppk_meta.p;
-        a.bsum = (unsigned long long*)w->ppk_bsum.p;
+        a.bsum = (unsigned long long*)s.bsum.p;
         a.ctr = (unsigned long long*)s.ctr.p;
         layout_split(n, &a.per_block, &a.nblocks);
         if (bmqcrc_launch_push_pack_layout(&a, (void*)c.s)) {
             return launch_failed("push-pack layout");
         }
         if (!size_only) {
-            // the messages as the copy's: the descriptors are the workspace's
-            CopyArgs ca;
-            memset(&ca, 0, sizeof(ca));
-            ca.src = a.data;
-            ca.src_bytes = a.data_bytes;
-            ca.src_offsets = (const uint64_t*)a.ws_off;
-            ca.lengths = a.ws_len;
-            ca.dst = a.dst;
-            ca.dst_bytes = a.dst_bytes;
-            ca.dst_offsets = (const uint64_t*)a.off;
-            ca.out = (uint32_t*)s.out.p;
-            ca.n = n;
-            if ((rc = enqueue_copy(c, ca, w->ppk_copy_first, w->ppk_copy_bsum,
-                                   a.ctr + kPpkCtrWords))) {
+            if ((rc = s.enqueue_slot_copy(c, a.data, a.data_bytes, a.dst, a.dst_bytes, n,
+                                          kPpkCtrWords))) {
                 return rc;
             }
             if (bmqcrc_launch_push_pack_frame(&a, (void*)c.s)) {
@@ -3621,11 +3617,7 @@ int bmqcrc_push_event_pack(const bmqcrc_push_pack* p, bmqcrc_push_pack_result* r
             }
         }
     }
-    bmqcrc_push_pack_result r;
-    if ((rc = sync_result(c, o, push_pack_result, result, &r))) {
-        return rc;
-    }
-    return r.refused_kind ? refused(kPushPackRefusals, r.refused_kind, r.refused_index) : 0;
+    return sync_result_or_refusal(c, o, push_pack_result, result, kPushPackRefusals);
 }
 
 int bmqcrc_last_push_pack(int device, void* stream, bmqcrc_push_pack_result* result)
@@ -3648,7 +3640,7 @@ static_assert(BMQCRC_ROLLOVER_RECORD_HEADER == BMQCRC_ROV_KIND_RECORD_HEADER &&
 // enqueued on its stream (w->mu held); zeros when there was none.
 static int rollover_result(Ctx& c, bmqcrc_rollover_result* r)
 {
-    const UnpackScratch& s = c.w->rov;
+    const SlotCopyScratch& s = c.w->rov;
     unsigned long long ctr[kRovCtrWords + kCopyCtrWords];
     memset(r, 0, sizeof(*r));
     if (!s.any) {
@@ -3661,11 +3653,8 @@ static int rollover_result(Ctx& c, bmqcrc_rollover_result* r)
         refusal_of(ctr[kSlotCtrRefusal], &r->refused_kind, &r->refused_index);
         return 0;
     }
-    // the layout placed every DATA record inside dst: the copy pass has nothing to refuse
-    const unsigned long long* cc = ctr + kRovCtrWords;
-    if (cc[kCopyCtrRefused] || cc[kCopyCtrOverflow]) {
-        return fail(BMQCRC_EIO, "bmqcrc_partition_rollover: the copy pass refused a message "
-                                "the layout had placed (internal error)");
+    if (int bad = copy_pass_clean(ctr + kRovCtrWords, "bmqcrc_partition_rollover")) {
+        return bad;
     }
     r->n_kept = ctr[kRovCtrKept];
     r->n_messages = ctr[kSlotCtrMsgs];
@@ -3756,7 +3745,7 @@ int bmqcrc_partition_rollover(const bmqcrc_rollover* p, bmqcrc_rollover_result* 
         return rc;
     }
     Workspace* w = c.w;
-    UnpackScratch& s = w->rov;
+    SlotCopyScratch& s = w->rov;
     const uint64_t recs = std::max<uint64_t>(n, 1);
     const bool follow = p->confirm_mode == BMQCRC_ROLLOVER_CONFIRMS_FOLLOW_MESSAGES;
     // the hash: a power of two, at least twice the records, so that a walk ends
@@ -3764,16 +3753,13 @@ int bmqcrc_partition_rollover(const bmqcrc_rollover* p, bmqcrc_rollover_result* 
     while (gslots < 2 * recs) {
         gslots <<= 1;
     }
-    if ((rc = s.ensure(n, true, kRovCtrWords + kCopyCtrWords)) ||
-        (rc = w->rov_bsum.ensure(8ull * 4 * kPackBlocks)) || (rc = w->rov_dst.ensure(8 * recs)) ||
-        (rc = w->rov_rec.ensure(4 * recs)) || (rc = w->rov_hdr.ensure(4 * recs)) ||
-        (rc = w->rov_kind.ensure(recs)) || (rc = w->rov_joff.ensure(8 * recs)) ||
-        (follow && n && (rc = w->rov_gslot.ensure(4 * gslots)))) {
+    if ((rc = s.ensure(n, true, kRovCtrWords, 2)) || (rc = w->rov_rec.ensure(4 * recs)) ||
+        (rc = w->rov_hdr.ensure(4 * recs)) || (rc = w->rov_kind.ensure(recs)) ||
+        (rc = w->rov_joff.ensure(8 * recs)) ||
+        (follow && n && (rc = w->rov_gslot.ensure(4 * gslots))) ||
+        (rc = s.begin(c, kRovCtrWords, n))) {
         return rc;
     }
-    HIP_TRY(hipMemsetAsync(s.ctr.p, 0, 8 * (kRovCtrWords + kCopyCtrWords), c.s));
-    s.n = n;
-    s.any = true;
     w->rov_sync = with_sync;
     if (n) {
         if (follow) {
@@ -3799,7 +3785,7 @@ int bmqcrc_partition_rollover(const bmqcrc_rollover* p, bmqcrc_rollover_result* 
         a.out = p->out;
         a.ws_off = (unsigned long long*)s.off.p;
         a.ws_len = (uint32_t*)s.len.p;
-        a.off = (unsigned long long*)w->rov_dst.p;
+        a.off = (unsigned long long*)s.dst.p;
         a.ws_exp = (uint32_t*)s.exp.p;
         a.ws_out = (const uint32_t*)s.out.p;
         a.ws_rec = (uint32_t*)w->rov_rec.p;
@@ -3808,36 +3794,21 @@ int bmqcrc_partition_rollover(const bmqcrc_rollover* p, bmqcrc_rollover_result* 
         a.joff = (unsigned long long*)w->rov_joff.p;
         a.gslot = follow ? (uint32_t*)w->rov_gslot.p : nullptr;
         a.gslots = gslots;
-        a.bsum = (unsigned long long*)w->rov_bsum.p;
+        a.bsum = (unsigned long long*)s.bsum.p;
         a.ctr = (unsigned long long*)s.ctr.p;
         layout_split(n, &a.per_block, &a.nblocks);
         if (bmqcrc_launch_rollover_layout(&a, (void*)c.s)) {
             return launch_failed("rollover layout");
         }
-        // the records as the copy's messages: the descriptors are the workspace's
-        CopyArgs ca;
-        memset(&ca, 0, sizeof(ca));
-        ca.src = a.data;
-        ca.src_bytes = a.data_bytes;
-        ca.src_offsets = (const uint64_t*)a.ws_off;
-        ca.lengths = a.ws_len;
-        ca.dst = a.dst;
-        ca.dst_bytes = a.dst_bytes;
-        ca.dst_offsets = (const uint64_t*)a.off;
-        ca.out = (uint32_t*)s.out.p;
-        ca.n = n;
-        if ((rc = enqueue_copy(c, ca, w->rov_copy_first, w->rov_copy_bsum, a.ctr + kRovCtrWords))) {
+        if ((rc = s.enqueue_slot_copy(c, a.data, a.data_bytes, a.dst, a.dst_bytes, n,
+                                      kRovCtrWords))) {
             return rc;
         }
         if (bmqcrc_launch_rollover_frame(&a, (void*)c.s)) {
             return launch_failed("rollover frame");
         }
     }
-    bmqcrc_rollover_result r;
-    if ((rc = sync_result(c, o, rollover_result, result, &r))) {
-        return rc;
-    }
-    return r.refused_kind ? refused(kRolloverRefusals, r.refused_kind, r.refused_index) : 0;
+    return sync_result_or_refusal(c, o, rollover_result, result, kRolloverRefusals);
 }
 
 int bmqcrc_last_rollover(int device, void* stream, bmqcrc_rollover_result* result)

@@ -44,25 +44,23 @@
 //
 // No byte outside [journal, +60 n_records) and [data, +data_bytes) is loaded:
 // the journal is read by record index below n_records only; of the DATA window
-// the two DataHeader words are read after o + 8 <= end, the SchemaId word (at
-// o + 8, inside a header of 3 words or more) and the padding byte after
-// o + total <= end.  Every size in the format is a word count and the padding
-// brings B to a multiple of 4, so every header position in dst is a multiple
-// of 4.  Nothing is stored to dst that step 3 has not shown to lie below
-// dst_bytes: it checks every event's end.
+// step 1 reads what data_record (crc32c_journal_stage.h) reads of a record it
+// finds inside the window, and the SchemaId word at o + 8 of such a record
+// whose header has 3 words or more.  Every size in the format is a word count
+// and the padding brings B to a multiple of 4, so every header position in dst
+// is a multiple of 4.  Nothing is stored to dst that step 3 has not shown to
+// lie below dst_bytes: it checks every event's end.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "bmqcrc_internal.h"
+#include "crc32c_journal_stage.h"
 #include "crc32c_pack_layout.h"
 
 namespace bmqcrc {
 namespace {
 
-constexpr uint32_t kEventHeaderBytes = 8;
 constexpr uint32_t kHeaderDwords = kPushHeaderBytes / 4;  // 8
-constexpr uint32_t kRecMessage = 1;                       // RecordType (mqbs_filestoreprotocol.h)
-constexpr uint32_t kMagicLE = 0x6345722Au;                // bytes 2A 72 45 63 loaded as a dword
 constexpr uint32_t kFlagOutOfOrder = 4, kFlagProperties = 2;  // PushHeaderFlags
 constexpr uint32_t kEventPush = 4;                        // EventType::e_PUSH
 
@@ -91,46 +89,29 @@ __global__ __launch_bounds__(kPackThreads) void k_ppk_classify(PpkArgs a)
             const uint32_t d0 = d[0], d1 = d[1], d2 = d[2], d5 = d[5], d8 = d[8], d13 = d[13],
                            d14 = d[14];
             const uint32_t w0 = __builtin_bswap32(d0);  // type | flags | sequence number's top
-            if ((w0 >> 28) != kRecMessage || d2 == 0 || ((w0 & 0xFFFFu) == 0 && d1 == 0) ||
-                d14 != kMagicLE) {
+            uint64_t ow;
+            DataRecord dr;
+            uint32_t schema = 0;
+            if (!record_header_ok(w0, d1, d2, d14, kRecMessage)) {  // type 1 alone
                 refuse(a, BMQCRC_PPK_KIND_RECORD, m);
+            } else if (!data_window_offset(d8, a.data_file_pos, end, &ow)) {
+                refuse(a, BMQCRC_PPK_KIND_DATA_OFFSET, m);
+            } else if (!data_record(a.data, end, ow, &dr, [&](uint64_t hs) {
+                           // SchemaId: DataHeader bytes 8..9, there from 3 header words on
+                           // (12 <= hs < total: inside the record)
+                           if (hs >= 12) {
+                               schema = *(const uint32_t*)(a.data + ow + 8) & 0xFFFFu;
+                           }
+                       })) {
+                refuse(a, BMQCRC_PPK_KIND_DATA_RECORD, m);
             } else {
-                const uint64_t o = (uint64_t)__builtin_bswap32(d8) * 8;  // MessageOffsetDwords
-                if (o == 0 || o < a.data_file_pos || o - a.data_file_pos > end) {
-                    refuse(a, BMQCRC_PPK_KIND_DATA_OFFSET, m);
-                } else {
-                    const uint64_t ow = o - a.data_file_pos;  // in the window, a multiple of 8
-                    bool bad = ow + 8 > end;
-                    if (!bad) {
-                        const uint64_t hw = *(const uint64_t*)(a.data + ow);
-                        const uint32_t h0 = __builtin_bswap32((uint32_t)hw);
-                        const uint32_t h1 = __builtin_bswap32((uint32_t)(hw >> 32));
-                        const uint64_t hs = (uint64_t)(h0 >> 29) * 4;
-                        const uint64_t total = (uint64_t)(h0 & 0x1FFFFFFFu) * 4;
-                        const uint64_t opt = (uint64_t)(h1 >> 8) * 4;
-                        bad = hs == 0 || total == 0 || hs + opt >= total || ow + total > end;
-                        if (!bad) {
-                            const uint32_t pad = a.data[ow + total - 1];
-                            // SchemaId: DataHeader bytes 8..9, there from 3 header words on
-                            // (12 <= hs < total: inside the record)
-                            const uint32_t schema =
-                                hs >= 12 ? *(const uint32_t*)(a.data + ow + 8) & 0xFFFFu : 0u;
-                            bad = pad < 1 || pad > 8 || total < hs + opt + pad;
-                            if (!bad) {
-                                ok = true;
-                                app = ow + hs + opt;
-                                len = (uint32_t)(total - hs - opt - pad);
-                                exp = __builtin_bswap32(d13);  // MessageRecord @52
-                                // MessageRecord @21: CAT in the low 3 bits
-                                meta = schema | (((d5 >> 8) & 7u) << kPpkMetaCatShift) |
-                                       ((h1 & 1u) ? kPpkMetaPropsBit : 0u);
-                            }
-                        }
-                    }
-                    if (bad) {
-                        refuse(a, BMQCRC_PPK_KIND_DATA_RECORD, m);
-                    }
-                }
+                ok = true;
+                app = dr.app;
+                len = dr.len;
+                exp = __builtin_bswap32(d13);  // MessageRecord @52
+                // MessageRecord @21: CAT in the low 3 bits
+                meta = schema | (((d5 >> 8) & 7u) << kPpkMetaCatShift) |
+                       ((dr.h1 & 1u) ? kPpkMetaPropsBit : 0u);
             }
         }
         if (a.flags && (a.flags[m] & ~kFlagOutOfOrder)) {
@@ -146,45 +127,20 @@ __global__ __launch_bounds__(kPackThreads) void k_ppk_classify(PpkArgs a)
     }
 }
 
-// What layout_count takes of its args struct: the messages' application data.
-struct MessageView {
-    const unsigned long long* src_offsets;
-    const uint32_t* lengths;
-    uint64_t n;
-    unsigned long long* off;
-    unsigned long long* bsum;
-    unsigned long long* ctr;
-    uint64_t per_block;
-    uint32_t nblocks;
-};
-
 // Step 2: the shared scan over B, then event_first's shape.
 __global__ __launch_bounds__(kPackThreads) void k_ppk_count(PpkArgs a)
 {
-    const MessageView v = {a.ws_off, a.ws_len, a.n, a.off, a.bsum, a.ctr, a.per_block, a.nblocks};
+    const LayoutView v = {a.ws_off, a.ws_len, a.n, a.off, a.bsum, a.ctr, a.per_block, a.nblocks};
     const uint32_t lead = kPushHeaderBytes + a.opt_bytes;
     layout_count(v, [lead](uint64_t, uint64_t, uint32_t len) {
         return (unsigned long long)lead + len + padding(len);
     });
-    // event_first: starts at 0, strictly increasing, ends at n
-    if (a.event_first) {
-        const uint64_t stride = (uint64_t)gridDim.x * kPackThreads;
-        for (uint64_t e = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x; e <= a.n_events;
-             e += stride) {
-            const uint64_t f = a.event_first[e];
-            const bool bad = e == a.n_events ? f != a.n
-                                             : (e == 0 && f != 0) || f >= a.event_first[e + 1];
-            if (bad) {
-                refuse(a, BMQCRC_PPK_KIND_EVENT_FIRST, e);
-            }
-        }
-    }
+    event_first_shape(a, BMQCRC_PPK_KIND_EVENT_FIRST);
 }
 
 // Step 3: the events, one per thread.
 __global__ __launch_bounds__(kPackThreads) void k_ppk_check(PpkArgs a)
 {
-    __shared__ unsigned long long bpre[kPackBlocks + 1];
     // Steps 1 and 2's word: kinds up to PAYLOAD_TOO_BIG.  A higher kind is
     // raised by this pass itself and never replaces one of theirs, so the test
     // gives the same answer in every block whenever it starts.
@@ -192,67 +148,26 @@ __global__ __launch_bounds__(kPackThreads) void k_ppk_check(PpkArgs a)
     if (word != 0 && (~word >> 56) <= BMQCRC_PPK_KIND_PAYLOAD_TOO_BIG) {
         return;
     }
-    const unsigned long long pieces = block_prefix(a, bpre);
-    const unsigned long long all = bpre[a.nblocks];
-    const uint64_t stride = (uint64_t)gridDim.x * kPackThreads;
-    for (uint64_t e = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x; e < a.n_events;
-         e += stride) {
-        const uint64_t f0 = a.event_first ? a.event_first[e] : 0;
-        const uint64_t f1 = a.event_first ? a.event_first[e + 1] : a.n;
-        const unsigned long long p0 = a.off[f0] + bpre[f0 / a.per_block];  // f0 < f1 <= n
-        const unsigned long long p1 = f1 == a.n ? all : a.off[f1] + bpre[f1 / a.per_block];
-        if (kEventHeaderBytes + (p1 - p0) > a.max_event_bytes) {
-            refuse(a, BMQCRC_PPK_KIND_EVENT_TOO_BIG, e);
-        }
-        if (a.dst && kEventHeaderBytes * (e + 1) + p1 > a.dst_bytes) {
-            refuse(a, BMQCRC_PPK_KIND_DST_TOO_SMALL, e);
-        }
-    }
+    events_check(a, BMQCRC_PPK_KIND_EVENT_TOO_BIG, BMQCRC_PPK_KIND_DST_TOO_SMALL,
+                 BMQCRC_PPK_KIND_TOO_MANY_PIECES, kPpkCtrTotal, true);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (pieces > 0xFFFFFFFFull) {
-            refuse(a, BMQCRC_PPK_KIND_TOO_MANY_PIECES, 0);
-        }
         a.ctr[kSlotCtrMsgs] = a.n;
-        a.ctr[kPpkCtrTotal] = kEventHeaderBytes * a.n_events + all;
     }
 }
-
-// Last e in [lo, hi] with first[e] <= i (first[lo] <= i is given).
-__device__ __forceinline__ uint64_t event_of(const uint64_t* first, uint64_t lo, uint64_t hi,
-                                             uint64_t i)
-{
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (first[mid] <= i) {
-            lo = mid;
-        } else {
-            hi = mid - 1;
-        }
-    }
-    return lo;
-}
-
-constexpr uint32_t kSealEvents = 1024;  // k_ppk_seal: events of a block it searches in LDS
 
 // Step 4.  The word is final.
 __global__ __launch_bounds__(kPackThreads) void k_ppk_seal(PpkArgs a)
 {
-    __shared__ unsigned long long bpre[kPackBlocks + 1];
-    __shared__ uint64_t erange[2];
-    __shared__ uint64_t efirst[kSealEvents];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t lo = (uint64_t)blockIdx.x * a.per_block;
-    const uint64_t hi = min(lo + a.per_block, a.n);
-    const bool refused = a.ctr[kSlotCtrRefusal] != 0;
     if (!a.dst) {
+        unsigned long long* bpre = shared_bpre();
         // size only: where every event would start, and the total behind the last
-        if (refused || !a.event_offsets) {
+        if (a.ctr[kSlotCtrRefusal] != 0 || !a.event_offsets) {
             return;
         }
         block_prefix(a, bpre);
         const unsigned long long all = bpre[a.nblocks];
         const uint64_t stride = (uint64_t)gridDim.x * kPackThreads;
-        for (uint64_t e = (uint64_t)blockIdx.x * kPackThreads + tid; e <= a.n_events;
+        for (uint64_t e = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x; e <= a.n_events;
              e += stride) {
             const uint64_t f = e == a.n_events ? a.n : a.event_first ? a.event_first[e] : 0;
             const unsigned long long p = f == a.n ? all : a.off[f] + bpre[f / a.per_block];
@@ -260,43 +175,8 @@ __global__ __launch_bounds__(kPackThreads) void k_ppk_seal(PpkArgs a)
         }
         return;
     }
-    if (refused) {
-        // past any dst_bytes: the copy kernels refuse the message
-        for (uint64_t i = lo + tid; i < hi; i += kPackThreads) {
-            a.off[i] = ~0ull;
-        }
-        return;
-    }
-    if (tid == 0) {
-        // the events of this block's messages: the search of a message stays
-        // inside them (one or two events, usually)
-        uint64_t e0 = 0, e1 = 0;
-        if (a.event_first && lo < hi) {
-            e0 = event_of(a.event_first, 0, a.n_events - 1, lo);
-            e1 = event_of(a.event_first, e0, a.n_events - 1, hi - 1);
-        }
-        erange[0] = e0;
-        erange[1] = e1;
-    }
-    block_prefix(a, bpre);
-    const unsigned long long before = bpre[blockIdx.x];
-    const uint64_t e0 = erange[0], e1 = erange[1];
-    // the block's events' first messages, when they fit: a message's search is
-    // then a handful of LDS reads, not of dependent trips to L2
-    const bool staged = e0 != e1 && e1 - e0 < kSealEvents;
-    if (staged) {
-        for (uint64_t k = tid; k <= e1 - e0; k += kPackThreads) {
-            efirst[k] = a.event_first[e0 + k];
-        }
-    }
-    __syncthreads();
     const uint32_t lead = kPushHeaderBytes + a.opt_bytes;
-    for (uint64_t i = lo + tid; i < hi; i += kPackThreads) {
-        const uint64_t e = e0 == e1   ? e0
-                           : staged ? e0 + event_of(efirst, 0, e1 - e0, i)
-                                    : event_of(a.event_first, e0, e1, i);
-        a.off[i] = a.off[i] + before + kEventHeaderBytes * (e + 1) + lead;
-    }
+    seal_offsets(a, [lead](uint64_t) { return lead; });
 }
 
 // Step 5, after the copy.  The word is final: on a refusal the host reads kind
@@ -378,24 +258,8 @@ __global__ __launch_bounds__(kPackFrameThreads) void k_ppk_frame(PpkArgs a)
             lowest = max(lowest, ~(unsigned long long)i);
         }
     }
-    const uint64_t total = a.ctr[kPpkCtrTotal];
-    for (uint64_t e = t0; e <= a.n_events; e += stride) {
-        // event e starts 8 + 32 + O bytes before its first message's data
-        uint64_t at = total, next = total;
-        if (e < a.n_events) {
-            const uint64_t f = a.event_first ? a.event_first[e] : 0;
-            at = a.off[f] - (kEventHeaderBytes + lead);
-            if (e + 1 < a.n_events) {
-                next = a.off[a.event_first[e + 1]] - (kEventHeaderBytes + lead);
-            }
-            uint32_t* h = (uint32_t*)(a.dst + at);
-            h[0] = __builtin_bswap32((uint32_t)(next - at) & 0x7FFFFFFFu);
-            h[1] = 0x00000240u | kEventPush;  // bytes: PV 1 | PUSH, HeaderWords 2, 0, 0
-        }
-        if (a.event_offsets) {
-            a.event_offsets[e] = at;
-        }
-    }
+    // event e starts 8 + 32 + O bytes before its first message's data
+    event_headers(a, [lead](uint64_t) { return lead; }, 0x40u | kEventPush, a.ctr[kPpkCtrTotal]);
     if (bad) {
         atomicAdd(&a.ctr[kSlotCtrBad], bad);
         atomicMax(&a.ctr[kSlotCtrFirstBad], lowest);

@@ -25,8 +25,10 @@
 //      adjacent lanes store adjacent dwords; the padding bytes as byte stores;
 //      the EventHeaders and event_offsets.  It leaves at once on a refusal.
 //
-// The refusal word, pass 1's scan and the prefix of the block sums are shared
-// with crc32c_records_pack.hip and described in crc32c_pack_layout.h.
+// The refusal word, pass 1's scan, the prefix of the block sums and the event
+// split (event_first's shape, the events' checks, the search of a message's
+// event, the EventHeaders) are shared with the other packers and described in
+// crc32c_pack_layout.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -39,7 +41,7 @@ namespace {
 // byte-aligned dword: a GUID array need not be 4-byte aligned
 typedef uint32_t u32u __attribute__((aligned(1)));
 
-constexpr uint32_t kPutHeaderBytes = 36, kEventHeaderBytes = 8;
+constexpr uint32_t kPutHeaderBytes = 36;
 
 // PutHeader + application data + padding (calcNumWordsAndPadding: 1..4 bytes)
 __device__ __forceinline__ uint64_t framed_bytes(uint32_t len)
@@ -56,101 +58,24 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_count(PackArgs a)
         }
         return framed_bytes(len);
     });
-    const uint32_t tid = threadIdx.x;
-    // event_first: starts at 0, strictly increasing, ends at n
-    if (a.event_first) {
-        const uint64_t stride = (uint64_t)gridDim.x * kPackThreads;
-        for (uint64_t e = (uint64_t)blockIdx.x * kPackThreads + tid; e <= a.n_events; e += stride) {
-            const uint64_t f = a.event_first[e];
-            const bool bad = e == a.n_events ? f != a.n
-                                             : (e == 0 && f != 0) || f >= a.event_first[e + 1];
-            if (bad) {
-                refuse(a, BMQCRC_PACK_KIND_EVENT_FIRST, e);
-            }
-        }
-    }
+    event_first_shape(a, BMQCRC_PACK_KIND_EVENT_FIRST);
 }
 
 // Pass 2: the events, one per thread.  Runs only on a clean pass 1: every
 // event_first entry is then at most n.
 __global__ __launch_bounds__(kPackThreads) void k_pack_check(PackArgs a)
 {
-    __shared__ unsigned long long bpre[kPackBlocks + 1];
     if (a.ctr[kPackCtrRefusal] != 0) {
         return;
     }
-    const unsigned long long pieces = block_prefix(a, bpre);
-    const unsigned long long all = bpre[a.nblocks];
-    const uint64_t stride = (uint64_t)gridDim.x * kPackThreads;
-    for (uint64_t e = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x; e < a.n_events;
-         e += stride) {
-        const uint64_t f0 = a.event_first ? a.event_first[e] : 0;
-        const uint64_t f1 = a.event_first ? a.event_first[e + 1] : a.n;
-        const unsigned long long p0 = a.off[f0] + bpre[f0 / a.per_block];  // f0 < f1 <= n
-        const unsigned long long p1 = f1 == a.n ? all : a.off[f1] + bpre[f1 / a.per_block];
-        if (kEventHeaderBytes + (p1 - p0) > a.max_event_bytes) {
-            refuse(a, BMQCRC_PACK_KIND_EVENT_TOO_BIG, e);
-        }
-        if (kEventHeaderBytes * (e + 1) + p1 > a.dst_bytes) {
-            refuse(a, BMQCRC_PACK_KIND_DST_TOO_SMALL, e);
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (pieces > 0xFFFFFFFFull) {
-            refuse(a, BMQCRC_PACK_KIND_TOO_MANY_PIECES, 0);
-        }
-        a.ctr[kPackCtrTotal] = kEventHeaderBytes * a.n_events + all;
-    }
-}
-
-// Last e in [lo, hi] with first[e] <= i (first[lo] <= i is given).
-__device__ __forceinline__ uint64_t event_of(const uint64_t* first, uint64_t lo, uint64_t hi,
-                                             uint64_t i)
-{
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (first[mid] <= i) {
-            lo = mid;
-        } else {
-            hi = mid - 1;
-        }
-    }
-    return lo;
+    events_check(a, BMQCRC_PACK_KIND_EVENT_TOO_BIG, BMQCRC_PACK_KIND_DST_TOO_SMALL,
+                 BMQCRC_PACK_KIND_TOO_MANY_PIECES, kPackCtrTotal);
 }
 
 // Pass 3: off[i] = where message i's application data goes.
 __global__ __launch_bounds__(kPackThreads) void k_pack_place(PackArgs a)
 {
-    __shared__ unsigned long long bpre[kPackBlocks + 1];
-    __shared__ uint64_t erange[2];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t lo = (uint64_t)blockIdx.x * a.per_block;
-    const uint64_t hi = min(lo + a.per_block, a.n);
-    if (a.ctr[kPackCtrRefusal] != 0) {
-        // past any dst_bytes: the copy kernels refuse the message
-        for (uint64_t i = lo + tid; i < hi; i += kPackThreads) {
-            a.off[i] = ~0ull;
-        }
-        return;
-    }
-    if (tid == 0) {
-        // the events of this block's messages: the search of a message stays
-        // inside them (one or two events, usually)
-        uint64_t e0 = 0, e1 = 0;
-        if (a.event_first && lo < hi) {
-            e0 = event_of(a.event_first, 0, a.n_events - 1, lo);
-            e1 = event_of(a.event_first, e0, a.n_events - 1, hi - 1);
-        }
-        erange[0] = e0;
-        erange[1] = e1;
-    }
-    block_prefix(a, bpre);
-    const unsigned long long before = bpre[blockIdx.x];
-    const uint64_t e0 = erange[0], e1 = erange[1];
-    for (uint64_t i = lo + tid; i < hi; i += kPackThreads) {
-        const uint64_t e = e0 == e1 ? e0 : event_of(a.event_first, e0, e1, i);
-        a.off[i] = a.off[i] + before + kEventHeaderBytes * (e + 1) + kPutHeaderBytes;
-    }
+    seal_offsets(a, [](uint64_t) { return kPutHeaderBytes; });
 }
 
 // Step 3.  Thread t of the grid owns header dword t % 9 of message t / 9.
@@ -195,26 +120,9 @@ __global__ __launch_bounds__(kPackFrameThreads) void k_pack_frame(PackArgs a)
         }
         ((uint32_t*)(a.dst + (app - kPutHeaderBytes)))[j] = v;
     }
-    const uint64_t total = a.ctr[kPackCtrTotal];
-    for (uint64_t e = t0; e <= a.n_events; e += stride) {
-        // event e starts 8 + 36 bytes before its first message's data
-        const uint64_t at = e == a.n_events
-                                ? total
-                                : a.off[a.event_first ? a.event_first[e] : 0] -
-                                      (kEventHeaderBytes + kPutHeaderBytes);
-        if (a.event_offsets) {
-            a.event_offsets[e] = at;
-        }
-        if (e < a.n_events) {
-            const uint64_t next = e + 1 == a.n_events
-                                      ? total
-                                      : a.off[a.event_first[e + 1]] -
-                                            (kEventHeaderBytes + kPutHeaderBytes);
-            uint32_t* h = (uint32_t*)(a.dst + at);
-            h[0] = __builtin_bswap32((uint32_t)(next - at) & 0x7FFFFFFFu);
-            h[1] = 0x00000242u;  // bytes: PV 1 | type PUT 2, HeaderWords 2, 0, 0
-        }
-    }
+    // event e starts 8 + 36 bytes before its first message's data
+    event_headers(a, [](uint64_t) { return kPutHeaderBytes; }, 0x42u /* PV 1 | PUT 2 */,
+                  a.ctr[kPackCtrTotal]);
 }
 
 }  // namespace

@@ -35,8 +35,8 @@
 //
 // No byte outside [journal, +60 n_records) and [data, +data_bytes) is loaded:
 // the journal is read by record index below n_records only; of the DATA window
-// the two DataHeader words are read after o + 8 <= end and the padding byte
-// after o + total <= end.  Every offset is 64 bits wide: o = 8 x
+// step 1 reads what data_record (crc32c_journal_stage.h) reads of a selected
+// record it finds inside the window.  Every offset is 64 bits wide: 8 x
 // MessageOffsetDwords reaches 2^35, and the sums above add at most 2^31 to it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -51,8 +51,6 @@ namespace {
 
 // byte-aligned dword: a GUID or queue-key array need not be 4-byte aligned
 typedef uint32_t u32u __attribute__((aligned(1)));
-
-constexpr uint32_t kRecMessage = 1;  // RecordType::e_MESSAGE
 
 // Step 1.
 __global__ __launch_bounds__(kPackThreads) void k_recunp_classify(RecUnpackArgs a)
@@ -76,45 +74,27 @@ __global__ __launch_bounds__(kPackThreads) void k_recunp_classify(RecUnpackArgs 
         if (r < hi) {
             const uint32_t w0 = __builtin_bswap32(d[0]);  // type | flags | sequence number's top
             const uint32_t type = w0 >> 28;
-            if (type == 0 || d[2] == 0 || ((w0 & 0xFFFFu) == 0 && d[1] == 0) ||
-                d[14] != kMagicLE) {
+            if (!record_header_ok(w0, d[1], d[2], d[14], kRecAnyType)) {
                 refuse(a, BMQCRC_RECUNP_KIND_RECORD_HEADER, r);
             } else if (type == kRecMessage) {
                 // GUID @36..51, queue key @22..26
                 const bool unset = (d[9] | d[10] | d[11] | d[12]) == 0 ||
                                    ((d[5] >> 16) | (d[6] & 0xFFFFFFu)) == 0;
-                const uint64_t o = (uint64_t)__builtin_bswap32(d[8]) * 8;  // MessageOffsetDwords
+                uint64_t ow;
+                DataRecord dr;
                 if (unset) {
                     refuse(a, BMQCRC_RECUNP_KIND_MESSAGE_RECORD, r);
-                } else if (o == 0 || o < a.data_file_pos || o - a.data_file_pos > end) {
+                } else if (!data_window_offset(d[8], a.data_file_pos, end, &ow)) {
                     refuse(a, BMQCRC_RECUNP_KIND_DATA_OFFSET, r);
                 } else if (a.select && a.select[r] == 0) {
                     ++skipped;  // no byte of its DATA record is read
+                } else if (!data_record(a.data, end, ow, &dr)) {
+                    refuse(a, BMQCRC_RECUNP_KIND_DATA_RECORD, r);
                 } else {
-                    const uint64_t ow = o - a.data_file_pos;  // in the window, a multiple of 8
-                    bool bad = ow + 8 > end;
-                    if (!bad) {
-                        const uint64_t hw = *(const uint64_t*)(a.data + ow);
-                        const uint32_t h0 = __builtin_bswap32((uint32_t)hw);
-                        const uint32_t h1 = __builtin_bswap32((uint32_t)(hw >> 32));
-                        const uint64_t hs = (uint64_t)(h0 >> 29) * 4;
-                        const uint64_t total = (uint64_t)(h0 & 0x1FFFFFFFu) * 4;
-                        const uint64_t opt = (uint64_t)(h1 >> 8) * 4;
-                        bad = hs == 0 || total == 0 || hs + opt >= total || ow + total > end;
-                        if (!bad) {
-                            const uint32_t pad = a.data[ow + total - 1];
-                            bad = pad < 1 || pad > 8 || total < hs + opt + pad;
-                            if (!bad) {
-                                msg = true;
-                                a.rec_off[r] = ow + hs + opt;
-                                a.rec_len[r] = (uint32_t)(total - hs - opt - pad);
-                                a.rec_flags[r] = (uint8_t)h1;
-                            }
-                        }
-                    }
-                    if (bad) {
-                        refuse(a, BMQCRC_RECUNP_KIND_DATA_RECORD, r);
-                    }
+                    msg = true;
+                    a.rec_off[r] = dr.app;
+                    a.rec_len[r] = dr.len;
+                    a.rec_flags[r] = (uint8_t)dr.h1;
                 }
             }
             // (any other type: validated above and skipped, as the host walk skips it)

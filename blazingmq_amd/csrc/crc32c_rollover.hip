@@ -47,11 +47,11 @@
 //
 // No byte outside [journal, +60 n) and [data, +data_bytes) is loaded: the
 // journal is read by record index below n only (the hash holds such indices);
-// of the DATA window the two DataHeader words are read after o + 8 <= end and
-// the padding byte after o + total <= end, and the frame reads inside [o, o +
-// total) only.  Every size in the format is a word count, so every position in
-// dst is a multiple of 4.  Nothing is stored to dst or journal_dst that step 3
-// has not shown to lie below dst_bytes / journal_dst_bytes.
+// of the DATA window step 1 reads what data_record (crc32c_journal_stage.h)
+// reads of a record it finds inside the window, and the frame reads inside that
+// record only.  Every size in the format is a word count, so every position
+// in dst is a multiple of 4.  Nothing is stored to dst or journal_dst that
+// step 3 has not shown to lie below dst_bytes / journal_dst_bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -62,9 +62,7 @@
 namespace bmqcrc {
 namespace {
 
-// RecordType (MESSAGE is 1) and JournalOpType (mqbs_filestoreprotocol.h)
-constexpr uint32_t kRecConfirm = 2, kRecDeletion = 3, kRecQueueOp = 4, kRecJournalOp = 5;
-constexpr uint32_t kJournalOpSyncPoint = 2;
+constexpr uint32_t kJournalOpSyncPoint = 2;  // JournalOpType (mqbs_filestoreprotocol.h)
 // dwords of a record: the GUID of a MESSAGE record (bytes 36..51) and of a
 // CONFIRM record (32..47); the queue key of both lies in bytes 22..26
 constexpr uint32_t kMsgGuidDword = 9, kCfmGuidDword = 8;
@@ -164,8 +162,7 @@ __global__ __launch_bounds__(kPackThreads) void k_rov_classify(RovArgs a)
             uint32_t len = 0, rec = 0, hdr = 0, exp = 0;
             uint8_t kind = kRovDrop;
             bool header_ok = false;
-            if (type == 0 || type > kRecJournalOp || d[2] == 0 ||
-                ((w0 & 0xFFFFu) == 0 && d[1] == 0) || d[14] != kMagicLE) {
+            if (!record_header_ok(w0, d[1], d[2], d[14], kRecJournalOp)) {
                 refuse(a, BMQCRC_ROV_KIND_RECORD_HEADER, r);
             } else if (type == kRecQueueOp) {
                 const uint32_t op = __builtin_bswap32(d[8]);  // QueueOpType: PURGE 1 .. ADDITION 4
@@ -194,36 +191,19 @@ __global__ __launch_bounds__(kPackThreads) void k_rov_classify(RovArgs a)
                     if (a.follow) {
                         join_insert(a, join_key(d, kMsgGuidDword), r);
                     }
-                    const uint64_t o = (uint64_t)__builtin_bswap32(d[8]) * 8;  // MessageOffsetDwords
-                    if (o == 0 || o < a.data_file_pos || o - a.data_file_pos > end) {
+                    uint64_t ow;
+                    DataRecord dr;
+                    if (!data_window_offset(d[8], a.data_file_pos, end, &ow)) {
                         refuse(a, BMQCRC_ROV_KIND_DATA_OFFSET, r);
+                    } else if (!data_record(a.data, end, ow, &dr)) {
+                        refuse(a, BMQCRC_ROV_KIND_DATA_RECORD, r);
                     } else {
-                        const uint64_t ow = o - a.data_file_pos;  // in the window, a multiple of 8
-                        bool bad = ow + 8 > end;
-                        if (!bad) {
-                            const uint64_t hw = *(const uint64_t*)(a.data + ow);
-                            const uint32_t h0 = __builtin_bswap32((uint32_t)hw);
-                            const uint32_t h1 = __builtin_bswap32((uint32_t)(hw >> 32));
-                            const uint64_t hs = (uint64_t)(h0 >> 29) * 4;
-                            const uint64_t total = (uint64_t)(h0 & 0x1FFFFFFFu) * 4;
-                            const uint64_t opt = (uint64_t)(h1 >> 8) * 4;
-                            bad = hs == 0 || total == 0 || hs + opt >= total || ow + total > end;
-                            if (!bad) {
-                                const uint32_t pad = a.data[ow + total - 1];
-                                bad = pad < 1 || pad > 8 || total < hs + opt + pad;
-                                if (!bad) {
-                                    kind = kRovMessage;
-                                    app = ow + hs + opt;
-                                    len = (uint32_t)(total - hs - opt - pad);
-                                    rec = (uint32_t)total;  // at most 2^31 - 4
-                                    hdr = (uint32_t)(hs + opt);
-                                    exp = __builtin_bswap32(d[13]);  // MessageRecord @52
-                                }
-                            }
-                        }
-                        if (bad) {
-                            refuse(a, BMQCRC_ROV_KIND_DATA_RECORD, r);
-                        }
+                        kind = kRovMessage;
+                        app = dr.app;
+                        len = dr.len;
+                        rec = (uint32_t)dr.total;  // at most 2^31 - 4
+                        hdr = (uint32_t)dr.hdr;
+                        exp = __builtin_bswap32(d[13]);  // MessageRecord @52
                     }
                 }
             }
@@ -242,25 +222,13 @@ __global__ __launch_bounds__(kPackThreads) void k_rov_classify(RovArgs a)
     }
 }
 
-// What layout_count and block_prefix take of their args struct: the records as
-// messages, under one of the two prefixes.
-struct RecordView {
-    const unsigned long long* src_offsets;
-    const uint32_t* lengths;
-    uint64_t n;
-    unsigned long long* off;
-    unsigned long long* bsum;
-    unsigned long long* ctr;
-    uint64_t per_block;
-    uint32_t nblocks;
-};
-
-__device__ __forceinline__ RecordView bytes_view(const RovArgs& a)
+// The records as messages (LayoutView), under one of the two prefixes.
+__device__ __forceinline__ LayoutView bytes_view(const RovArgs& a)
 {
     return {a.ws_off, a.ws_len, a.n, a.off, a.bsum, a.ctr, a.per_block, a.nblocks};
 }
 
-__device__ __forceinline__ RecordView kept_view(const RovArgs& a)
+__device__ __forceinline__ LayoutView kept_view(const RovArgs& a)
 {
     return {a.ws_off, a.ws_len, a.n, a.joff, a.bsum + 2 * kPackBlocks, a.ctr, a.per_block,
             a.nblocks};

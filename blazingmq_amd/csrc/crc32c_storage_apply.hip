@@ -48,6 +48,12 @@
 // multiples of 4, so every position is one and the header copies are dword
 // copies.  A step advances by at least 72 bytes, which bounds the loop by the
 // event's size.
+//
+// The walk's DATA-record check states the clauses of data_record
+// (crc32c_journal_stage.h) but is not that function: its bound `stop` is the
+// end of the storage message inside the event, not of a caller's window, and
+// its words come from the wave's LDS ring (Window::need / be32), wave-uniform,
+// not from loads of the thread's own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -350,24 +356,12 @@ __global__ __launch_bounds__(kUnpackThreads) void k_sap_scan(SapArgs a)
     }
 }
 
-// What layout_count takes of its args struct: the msg_cap slots as messages.
-struct SlotView {
-    const unsigned long long* src_offsets;
-    const uint32_t* lengths;
-    uint64_t n;
-    unsigned long long* off;
-    unsigned long long* bsum;
-    unsigned long long* ctr;
-    uint64_t per_block;
-    uint32_t nblocks;
-};
-
 // Step 4: the shared scan over R; an unused slot, or every slot after a
 // refusal, counts for nothing.
 __global__ __launch_bounds__(kPackThreads) void k_sap_count(SapArgs a)
 {
     const uint64_t used = a.ctr[kSlotCtrRefusal] != 0 ? 0 : a.first[a.n_events];
-    const SlotView v = {a.ws_off, a.ws_len, a.msg_cap,   a.off,
+    const LayoutView v = {a.ws_off, a.ws_len, a.msg_cap,   a.off,
                         a.bsum,   a.ctr,    a.per_block, a.nblocks};
     layout_count(v, [&a, used](uint64_t i, uint64_t, uint32_t) {
         return (unsigned long long)(i < used ? a.ws_rec[i] : 0u);

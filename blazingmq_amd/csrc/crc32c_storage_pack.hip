@@ -42,8 +42,8 @@
 //
 // No byte outside [journal, +60 n_records) and [data, +data_bytes) is loaded:
 // the journal is read by record index below n_records only; of the DATA window
-// the two DataHeader words are read after o + 8 <= end and the padding byte
-// after o + total <= end, and the frame reads inside [o, o + total) only.
+// step 1 reads what data_record (crc32c_journal_stage.h) reads of a record it
+// finds inside the window, and the frame reads inside that record only.
 // Every size in the format is a word count, so every position in dst is a
 // multiple of 4.  Nothing is stored to dst that step 3 has not shown to lie
 // below dst_bytes: it checks every event's end.
@@ -57,13 +57,11 @@
 namespace bmqcrc {
 namespace {
 
-constexpr uint32_t kEventHeaderBytes = 8, kStorageHeaderBytes = 12;
+constexpr uint32_t kStorageHeaderBytes = 12;
 constexpr uint32_t kJournalBytes = 4 * kJournalRecordDwords;
 constexpr uint32_t kFrameBytes = kStorageHeaderBytes + kJournalBytes;  // in front of a payload
 constexpr uint32_t kFrameDwords = kFrameBytes / 4;                     // 18
-// RecordType (mqbs_filestoreprotocol.h) and StorageMessageType (bmqp_protocol.h)
-constexpr uint32_t kRecMessage = 1, kRecConfirm = 2, kRecDeletion = 3, kRecQueueOp = 4,
-                   kRecJournalOp = 5;
+// StorageMessageType (bmqp_protocol.h)
 constexpr uint32_t kMsgData = 1, kMsgQlist = 2, kMsgConfirm = 3, kMsgDeletion = 4,
                    kMsgJournalOp = 5, kMsgQueueOp = 6;
 
@@ -86,8 +84,7 @@ __global__ __launch_bounds__(kPackThreads) void k_spk_classify(SpkArgs a)
             const uint32_t type = w0 >> 28;
             uint64_t app = 0;
             uint32_t len = 0, rec = 0, hdr = 0, exp = 0, msg = 0;
-            if (type == 0 || type > kRecJournalOp || d[2] == 0 ||
-                ((w0 & 0xFFFFu) == 0 && d[1] == 0) || d[14] != kMagicLE) {
+            if (!record_header_ok(w0, d[1], d[2], d[14], kRecJournalOp)) {
                 refuse(a, BMQCRC_SPK_KIND_RECORD_HEADER, r);
             } else if (type == kRecQueueOp) {
                 const uint32_t op = __builtin_bswap32(d[8]);  // QueueOpType: PURGE 1 .. ADDITION 4
@@ -97,36 +94,19 @@ __global__ __launch_bounds__(kPackThreads) void k_spk_classify(SpkArgs a)
                     msg = (op & 1u) ? kMsgQueueOp : kMsgQlist;  // CREATION 2 and ADDITION 4: QLIST
                 }
             } else if (type == kRecMessage) {
-                const uint64_t o = (uint64_t)__builtin_bswap32(d[8]) * 8;  // MessageOffsetDwords
-                if (o == 0 || o < a.data_file_pos || o - a.data_file_pos > end) {
+                uint64_t ow;
+                DataRecord dr;
+                if (!data_window_offset(d[8], a.data_file_pos, end, &ow)) {
                     refuse(a, BMQCRC_SPK_KIND_DATA_OFFSET, r);
+                } else if (!data_record(a.data, end, ow, &dr)) {
+                    refuse(a, BMQCRC_SPK_KIND_DATA_RECORD, r);
                 } else {
-                    const uint64_t ow = o - a.data_file_pos;  // in the window, a multiple of 8
-                    bool bad = ow + 8 > end;
-                    if (!bad) {
-                        const uint64_t hw = *(const uint64_t*)(a.data + ow);
-                        const uint32_t h0 = __builtin_bswap32((uint32_t)hw);
-                        const uint32_t h1 = __builtin_bswap32((uint32_t)(hw >> 32));
-                        const uint64_t hs = (uint64_t)(h0 >> 29) * 4;
-                        const uint64_t total = (uint64_t)(h0 & 0x1FFFFFFFu) * 4;
-                        const uint64_t opt = (uint64_t)(h1 >> 8) * 4;
-                        bad = hs == 0 || total == 0 || hs + opt >= total || ow + total > end;
-                        if (!bad) {
-                            const uint32_t pad = a.data[ow + total - 1];
-                            bad = pad < 1 || pad > 8 || total < hs + opt + pad;
-                            if (!bad) {
-                                msg = kMsgData;
-                                app = ow + hs + opt;
-                                len = (uint32_t)(total - hs - opt - pad);
-                                rec = (uint32_t)total;  // at most 2^31 - 4
-                                hdr = (uint32_t)(hs + opt);
-                                exp = __builtin_bswap32(d[13]);  // MessageRecord @52
-                            }
-                        }
-                    }
-                    if (bad) {
-                        refuse(a, BMQCRC_SPK_KIND_DATA_RECORD, r);
-                    }
+                    msg = kMsgData;
+                    app = dr.app;
+                    len = dr.len;
+                    rec = (uint32_t)dr.total;  // at most 2^31 - 4
+                    hdr = (uint32_t)dr.hdr;
+                    exp = __builtin_bswap32(d[13]);  // MessageRecord @52
                 }
             } else {
                 msg = type == kRecConfirm ? kMsgConfirm : type == kRecDeletion ? kMsgDeletion
@@ -146,44 +126,19 @@ __global__ __launch_bounds__(kPackThreads) void k_spk_classify(SpkArgs a)
     }
 }
 
-// What layout_count takes of its args struct: the records as messages.
-struct RecordView {
-    const unsigned long long* src_offsets;
-    const uint32_t* lengths;
-    uint64_t n;
-    unsigned long long* off;
-    unsigned long long* bsum;
-    unsigned long long* ctr;
-    uint64_t per_block;
-    uint32_t nblocks;
-};
-
 // Step 2: the shared scan over B, then event_first's shape.
 __global__ __launch_bounds__(kPackThreads) void k_spk_count(SpkArgs a)
 {
-    const RecordView v = {a.ws_off, a.ws_len, a.n, a.off, a.bsum, a.ctr, a.per_block, a.nblocks};
+    const LayoutView v = {a.ws_off, a.ws_len, a.n, a.off, a.bsum, a.ctr, a.per_block, a.nblocks};
     layout_count(v, [&a](uint64_t i, uint64_t, uint32_t) {
         return (unsigned long long)kFrameBytes + a.ws_rec[i];
     });
-    // event_first: starts at 0, strictly increasing, ends at n
-    if (a.event_first) {
-        const uint64_t stride = (uint64_t)gridDim.x * kPackThreads;
-        for (uint64_t e = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x; e <= a.n_events;
-             e += stride) {
-            const uint64_t f = a.event_first[e];
-            const bool bad = e == a.n_events ? f != a.n
-                                             : (e == 0 && f != 0) || f >= a.event_first[e + 1];
-            if (bad) {
-                refuse(a, BMQCRC_SPK_KIND_EVENT_FIRST, e);
-            }
-        }
-    }
+    event_first_shape(a, BMQCRC_SPK_KIND_EVENT_FIRST);
 }
 
 // Step 3: the events, one per thread.
 __global__ __launch_bounds__(kPackThreads) void k_spk_check(SpkArgs a)
 {
-    __shared__ unsigned long long bpre[kPackBlocks + 1];
     // Steps 1 and 2's word: kinds up to PAYLOAD_TOO_BIG.  A higher kind is
     // raised by this pass itself and never replaces one of theirs, so the test
     // gives the same answer in every block whenever it starts.
@@ -191,93 +146,18 @@ __global__ __launch_bounds__(kPackThreads) void k_spk_check(SpkArgs a)
     if (word != 0 && (~word >> 56) <= BMQCRC_SPK_KIND_PAYLOAD_TOO_BIG) {
         return;
     }
-    const unsigned long long pieces = block_prefix(a, bpre);
-    const unsigned long long all = bpre[a.nblocks];
-    const uint64_t stride = (uint64_t)gridDim.x * kPackThreads;
-    for (uint64_t e = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x; e < a.n_events;
-         e += stride) {
-        const uint64_t f0 = a.event_first ? a.event_first[e] : 0;
-        const uint64_t f1 = a.event_first ? a.event_first[e + 1] : a.n;
-        const unsigned long long p0 = a.off[f0] + bpre[f0 / a.per_block];  // f0 < f1 <= n
-        const unsigned long long p1 = f1 == a.n ? all : a.off[f1] + bpre[f1 / a.per_block];
-        if (kEventHeaderBytes + (p1 - p0) > a.max_event_bytes) {
-            refuse(a, BMQCRC_SPK_KIND_EVENT_TOO_BIG, e);
-        }
-        if (kEventHeaderBytes * (e + 1) + p1 > a.dst_bytes) {
-            refuse(a, BMQCRC_SPK_KIND_DST_TOO_SMALL, e);
-        }
-    }
+    events_check(a, BMQCRC_SPK_KIND_EVENT_TOO_BIG, BMQCRC_SPK_KIND_DST_TOO_SMALL,
+                 BMQCRC_SPK_KIND_TOO_MANY_PIECES, kSpkCtrTotal);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (pieces > 0xFFFFFFFFull) {
-            refuse(a, BMQCRC_SPK_KIND_TOO_MANY_PIECES, 0);
-        }
         a.ctr[kSlotCtrMsgs] = a.n;
-        a.ctr[kSpkCtrTotal] = kEventHeaderBytes * a.n_events + all;
     }
 }
 
-// Last e in [lo, hi] with first[e] <= i (first[lo] <= i is given).
-__device__ __forceinline__ uint64_t event_of(const uint64_t* first, uint64_t lo, uint64_t hi,
-                                             uint64_t i)
-{
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (first[mid] <= i) {
-            lo = mid;
-        } else {
-            hi = mid - 1;
-        }
-    }
-    return lo;
-}
-
-constexpr uint32_t kSealEvents = 1024;  // k_spk_seal: events of a block it searches in LDS
-
-// Step 4.
+// Step 4: the frame in front of a record's application data is the
+// StorageHeader, the journal record, DataHeader and options.
 __global__ __launch_bounds__(kPackThreads) void k_spk_seal(SpkArgs a)
 {
-    __shared__ unsigned long long bpre[kPackBlocks + 1];
-    __shared__ uint64_t erange[2];
-    __shared__ uint64_t efirst[kSealEvents];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t lo = (uint64_t)blockIdx.x * a.per_block;
-    const uint64_t hi = min(lo + a.per_block, a.n);
-    if (a.ctr[kSlotCtrRefusal] != 0) {
-        // past any dst_bytes: the copy kernels refuse the message
-        for (uint64_t i = lo + tid; i < hi; i += kPackThreads) {
-            a.off[i] = ~0ull;
-        }
-        return;
-    }
-    if (tid == 0) {
-        // the events of this block's records: the search of a record stays
-        // inside them (one or two events, usually)
-        uint64_t e0 = 0, e1 = 0;
-        if (a.event_first && lo < hi) {
-            e0 = event_of(a.event_first, 0, a.n_events - 1, lo);
-            e1 = event_of(a.event_first, e0, a.n_events - 1, hi - 1);
-        }
-        erange[0] = e0;
-        erange[1] = e1;
-    }
-    block_prefix(a, bpre);
-    const unsigned long long before = bpre[blockIdx.x];
-    const uint64_t e0 = erange[0], e1 = erange[1];
-    // the block's events' first records, when they fit: a record's search is
-    // then a handful of LDS reads, not of dependent trips to L2
-    const bool staged = e0 != e1 && e1 - e0 < kSealEvents;
-    if (staged) {
-        for (uint64_t k = tid; k <= e1 - e0; k += kPackThreads) {
-            efirst[k] = a.event_first[e0 + k];
-        }
-    }
-    __syncthreads();
-    for (uint64_t i = lo + tid; i < hi; i += kPackThreads) {
-        const uint64_t e = e0 == e1   ? e0
-                           : staged ? e0 + event_of(efirst, 0, e1 - e0, i)
-                                    : event_of(a.event_first, e0, e1, i);
-        a.off[i] = a.off[i] + before + kEventHeaderBytes * (e + 1) + kFrameBytes + a.ws_hdr[i];
-    }
+    seal_offsets(a, [&a](uint64_t i) { return kFrameBytes + a.ws_hdr[i]; });
 }
 
 // Step 5, after the copy.  The word is final: on a refusal the host reads kind
@@ -363,25 +243,9 @@ __global__ __launch_bounds__(kPackFrameThreads) void k_spk_frame(SpkArgs a)
             a.out[i] = crc;
         }
     }
-    const uint64_t total = a.ctr[kSpkCtrTotal];
-    for (uint64_t e = t0; e <= a.n_events; e += stride) {
-        // event e starts 8 + 72 + header + options bytes before its first message's data
-        uint64_t at = total, next = total;
-        if (e < a.n_events) {
-            const uint64_t f = a.event_first ? a.event_first[e] : 0;
-            at = a.off[f] - a.ws_hdr[f] - (kEventHeaderBytes + kFrameBytes);
-            if (e + 1 < a.n_events) {
-                const uint64_t g = a.event_first[e + 1];
-                next = a.off[g] - a.ws_hdr[g] - (kEventHeaderBytes + kFrameBytes);
-            }
-            uint32_t* h = (uint32_t*)(a.dst + at);
-            h[0] = __builtin_bswap32((uint32_t)(next - at) & 0x7FFFFFFFu);
-            h[1] = 0x00000240u | a.event_type;  // bytes: PV 1 | type, HeaderWords 2, 0, 0
-        }
-        if (a.event_offsets) {
-            a.event_offsets[e] = at;
-        }
-    }
+    // event e starts 8 + 72 + header + options bytes before its first message's data
+    event_headers(a, [&a](uint64_t i) { return kFrameBytes + a.ws_hdr[i]; }, 0x40u | a.event_type,
+                  a.ctr[kSpkCtrTotal]);
     data = wave_sum(data);
     if ((threadIdx.x & 63u) == 0 && data) {
         atomicAdd(&a.ctr[kSpkCtrData], data);

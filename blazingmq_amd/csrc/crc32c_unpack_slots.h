@@ -1,8 +1,8 @@
 // crc32c_unpack_slots.h -- the slot pass the device unpackers share
-// (crc32c_put_unpack.hip, crc32c_records_unpack.hip; DESIGN.md sections 14, 15).
-// Device only, in the anonymous namespace like the units' own code.  A template
-// over the unit's args struct (UnpackArgs, RecUnpackArgs), of which it uses
-// msg_cap, ws_off and ws_len.
+// (crc32c_put_unpack.hip, crc32c_records_unpack.hip, crc32c_storage_apply.hip;
+// DESIGN.md sections 14, 15, 17).  Device only, in the anonymous namespace like
+// the units' own code.  A template over the unit's args struct (UnpackArgs,
+// RecUnpackArgs, SapArgs), of which it uses msg_cap, ws_off and ws_len.
 //
 // A slot is one message the call found: the placing kernel leaves its offset,
 // length and stored CRC in the workspace, the fold reads the first two of all

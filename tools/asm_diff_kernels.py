@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Compare the gfx950 instructions of every kernel in two assembly listings
-of crc32c_kernels.hip (CPU only): the check that a change left the existing
-kernels' code alone.
+of one unit, crc32c_kernels.hip or any other csrc/*.hip (CPU only): the check
+that a change left the existing kernels' code alone.
 
   hipcc -x hip --offload-arch=gfx950 --offload-device-only -O3 -std=c++17 \\
       -munsafe-fp-atomics -fuse-cuid=none -Iinclude -S \\
       blazingmq_amd/csrc/crc32c_kernels.hip -o new.s        (and old.s likewise)
-  tools/asm_diff_kernels.py old.s new.s [--drop-arg ', false']
+  tools/asm_diff_kernels.py old.s new.s [--drop-arg ', false'] [--show N]
 
 Kernels are matched by demangled name; --drop-arg removes a trailing template
 argument from the second listing's names first (a parameter added with the
