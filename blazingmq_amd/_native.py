@@ -436,6 +436,42 @@ if hasattr(lib, "bmqcrc_partition_rollover"):  # ABI 2.18 (an older build loads 
                                               ctypes.POINTER(RolloverResult), _popts]
     lib.bmqcrc_last_rollover.restype = _int
     lib.bmqcrc_last_rollover.argtypes = [_int, _vp, ctypes.POINTER(RolloverResult)]
+BMQCRC_CONFIRM_PACK_OK = 0
+BMQCRC_CONFIRM_PACK_RECORD_HEADER = 1
+BMQCRC_CONFIRM_PACK_DUPLICATE_MESSAGE = 2
+BMQCRC_CONFIRM_PACK_NULL_KEY = 3
+BMQCRC_CONFIRM_PACK_REASON = 4
+BMQCRC_CONFIRM_PACK_OVER_CONFIRMED = 5
+BMQCRC_CONFIRM_PACK_DST_TOO_SMALL = 6
+
+
+class ConfirmPack(ctypes.Structure):
+    """bmqcrc_confirm_pack (include/bmqcrc_protocol.h, ABI 2.19)."""
+    _fields_ = [("struct_size", _u32), ("reserved", _u32), ("journal", _vp),
+                ("journal_bytes", _u64), ("n_records", _u64), ("select", _vp), ("guids", _vp),
+                ("queue_keys", _vp), ("app_keys", _vp), ("reasons", _vp), ("timestamps", _vp),
+                ("n", _u64), ("timestamp", _u64), ("first_seq", _u64), ("lease_id", _u32),
+                ("reserved2", _u32), ("journal_dst", _vp), ("journal_dst_bytes", _u64),
+                ("status", _vp), ("target", _vp), ("new_index", _vp), ("left_out", _vp)]
+
+
+class ConfirmPackResult(ctypes.Structure):
+    """bmqcrc_confirm_pack_result (include/bmqcrc_protocol.h, ABI 2.19)."""
+    _fields_ = [("n_confirms", _u64), ("n_written", _u64), ("n_confirm_records", _u64),
+                ("n_deletions", _u64), ("n_not_found", _u64), ("journal_bytes", _u64),
+                ("next_seq", _u64), ("refused_kind", _u32), ("reserved", _u32),
+                ("refused_index", _u64)]
+
+    def as_dict(self):
+        return {f[0]: int(getattr(self, f[0])) for f in self._fields_ if f[0] != "reserved"}
+
+
+if hasattr(lib, "bmqcrc_confirm_records_pack"):  # ABI 2.19 (an older build loads for same-box A/B)
+    lib.bmqcrc_confirm_records_pack.restype = _int
+    lib.bmqcrc_confirm_records_pack.argtypes = [ctypes.POINTER(ConfirmPack),
+                                                ctypes.POINTER(ConfirmPackResult), _popts]
+    lib.bmqcrc_last_confirm_records.restype = _int
+    lib.bmqcrc_last_confirm_records.argtypes = [_int, _vp, ctypes.POINTER(ConfirmPackResult)]
 lib.bmqcrc_journal_scan.restype = _i64
 lib.bmqcrc_journal_scan.argtypes = [_vp, _u64, _vp, _u64, _vp, _pint, _pu64, _vp, _vp, _vp, _vp,
                                     _u64]

@@ -247,6 +247,14 @@ struct Workspace {
     SlotCopyScratch rov;
     DevBuf rov_rec, rov_hdr, rov_kind, rov_joff, rov_gslot;
     bool rov_sync = false;
+    // bmqcrc_confirm_records_pack: the part of its workspace every call zeroes
+    // (the counters; the hash of the selected MESSAGE records, 8 to 16 bytes a
+    // record; per record had, c and last, 4 each, and dead, 1), per record the
+    // refCount (4) and the kind (1), per confirm the hit (4) and the place (8),
+    // the block sums; the confirms and first_seq of the last call enqueued
+    DevBuf cfm_zero, cfm_rec, cfm_hit, cfm_off, cfm_bsum;
+    uint64_t cfm_n = 0, cfm_first_seq = 0;
+    bool cfm_any = false;
     // bmqcrc_journal_select: the part of its workspace every call zeroes (the
     // counters, the queue-key and GUID tables, the claims) and the rest (the
     // two record lists, the named DELETIONs, the states); the records of the
@@ -3816,6 +3824,185 @@ int bmqcrc_last_rollover(int device, void* stream, bmqcrc_rollover_result* resul
     return last_result(device, stream, rollover_result, result);
 }
 
+static_assert(BMQCRC_CONFIRM_PACK_RECORD_HEADER == BMQCRC_CFM_KIND_RECORD_HEADER &&
+                  BMQCRC_CONFIRM_PACK_DUPLICATE_MESSAGE == BMQCRC_CFM_KIND_DUPLICATE_MESSAGE &&
+                  BMQCRC_CONFIRM_PACK_NULL_KEY == BMQCRC_CFM_KIND_NULL_KEY &&
+                  BMQCRC_CONFIRM_PACK_REASON == BMQCRC_CFM_KIND_REASON &&
+                  BMQCRC_CONFIRM_PACK_OVER_CONFIRMED == BMQCRC_CFM_KIND_OVER_CONFIRMED &&
+                  BMQCRC_CONFIRM_PACK_DST_TOO_SMALL == BMQCRC_CFM_KIND_DST_TOO_SMALL,
+              "the kernels' refusal kinds are the public ones");
+
+// Result of the confirm pack last enqueued on c's workspace, after everything
+// enqueued on its stream (w->mu held); zeros when there was none.
+static int confirm_records_result(Ctx& c, bmqcrc_confirm_pack_result* r)
+{
+    memset(r, 0, sizeof(*r));
+    if (!c.w->cfm_any) {
+        return 0;
+    }
+    unsigned long long ctr[kCfmCtrWords] = {0};
+    r->n_confirms = c.w->cfm_n;
+    if (r->n_confirms) {
+        HIP_TRY(hipMemcpyAsync(ctr, c.w->cfm_zero.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
+    }
+    HIP_TRY(hipStreamSynchronize(c.s));
+    if (ctr[kCfmCtrRefusal]) {
+        refusal_of(ctr[kCfmCtrRefusal], &r->refused_kind, &r->refused_index);
+        return 0;
+    }
+    r->n_written = ctr[kCfmCtrWritten];
+    r->n_deletions = ctr[kCfmCtrDeletions];
+    r->n_confirm_records = r->n_written - r->n_deletions;
+    r->n_not_found = ctr[kCfmCtrNotFound];
+    r->journal_bytes = kJournalRecordBytes * r->n_written;
+    r->next_seq = c.w->cfm_first_seq + r->n_written;
+    return 0;
+}
+
+static const char* const kConfirmPackRefusals[7] = {
+    "", "BMQCRC_CONFIRM_PACK_RECORD_HEADER: record %llu has type 0 or above 5, lease id 0, "
+        "sequence number 0, a wrong magic or a QueueOpType outside 1..4",
+    "BMQCRC_CONFIRM_PACK_DUPLICATE_MESSAGE: selected MESSAGE record %llu shares its GUID and "
+    "queue key with another selected MESSAGE record",
+    "BMQCRC_CONFIRM_PACK_NULL_KEY: the GUID or the queue key of confirm %llu is all zero",
+    "BMQCRC_CONFIRM_PACK_REASON: reasons[%llu] is neither 0 (CONFIRMED) nor 1 (REJECTED)",
+    "BMQCRC_CONFIRM_PACK_OVER_CONFIRMED: the message of confirm %llu is confirmed more often "
+    "in this call than it has references left",
+    "BMQCRC_CONFIRM_PACK_DST_TOO_SMALL: the record of confirm %llu ends past journal_dst_bytes"};
+
+int bmqcrc_confirm_records_pack(const bmqcrc_confirm_pack* p, bmqcrc_confirm_pack_result* result,
+                                const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    bmqcrc_opts o;
+    int rc;
+    if ((rc = check_struct(p, "bmqcrc_confirm_pack", p ? p->reserved2 : 0,
+                           ".reserved and reserved2 must be 0")) ||
+        (rc = device_call_opts(opts, "bmqcrc_confirm_records_pack", &o))) {
+        return rc;
+    }
+    if ((rc = refuse_null({{!p->journal, "journal"},
+                           {!p->guids, "guids"},
+                           {!p->queue_keys, "queue_keys"},
+                           {!p->journal_dst && p->journal_dst_bytes != 0,
+                            "journal_dst (with journal_dst_bytes != 0)"}}))) {
+        return rc;
+    }
+    const uint64_t n = p->n, nrec = p->n_records;
+    const struct {
+        bool bad;
+        const char* what;
+    } checks[] = {
+        {((uintptr_t)p->journal & 3u) != 0, "journal must be 4-byte aligned"},
+        {((uintptr_t)p->journal_dst & 3u) != 0, "journal_dst must be 4-byte aligned"},
+        {((uintptr_t)p->timestamps & 7u) != 0, "timestamps must be 8-byte aligned"},
+        {((uintptr_t)p->target & 3u) != 0, "target must be 4-byte aligned"},
+        {((uintptr_t)p->new_index & 3u) != 0, "new_index must be 4-byte aligned"},
+        {((uintptr_t)p->left_out & 3u) != 0, "left_out must be 4-byte aligned"},
+        {nrec > 0xFFFFFFFFull, "n_records must be below 2^32"},
+        {n > 0xFFFFFFFFull, "n must be below 2^32"},
+        {p->journal_bytes != kJournalRecordBytes * nrec, "journal_bytes must be 60 n_records"},
+        {p->lease_id == 0, "lease_id must not be 0"},
+        {p->first_seq == 0 || p->first_seq > kMaxSeqNum || n > kMaxSeqNum - p->first_seq,
+         "first_seq must not be 0, and first_seq + n at most 2^48-1"}};
+    for (const auto& k : checks) {
+        if (k.bad) {
+            return fail(BMQCRC_EINVAL, k.what);
+        }
+    }
+    const NamedRange journal = {p->journal, p->journal_bytes, "[journal, journal+journal_bytes)"};
+    const NamedRange select = {p->select, p->select ? nrec : 0, "select"};
+    const NamedRange guids = {p->guids, 16 * n, "guids"};
+    const NamedRange qkeys = {p->queue_keys, 5 * n, "queue_keys"};
+    const NamedRange akeys = {p->app_keys, p->app_keys ? 5 * n : 0, "app_keys"};
+    const NamedRange reasons = {p->reasons, p->reasons ? n : 0, "reasons"};
+    const NamedRange stamps = {p->timestamps, p->timestamps ? 8 * n : 0, "timestamps"};
+    const NamedRange jdst = {p->journal_dst, p->journal_dst_bytes,
+                             "[journal_dst, journal_dst+journal_dst_bytes)"};
+    const NamedRange status = {p->status, n, "status"};
+    const NamedRange target = {p->target, 4 * n, "target"};
+    const NamedRange index = {p->new_index, 4 * n, "new_index"};
+    const NamedRange left = {p->left_out, 4 * nrec, "left_out"};
+    if ((rc = refuse_overlap({jdst, status, target, index, left},
+                             {journal, select, guids, qkeys, akeys, reasons, stamps})) ||
+        (rc = refuse_overlap({status, target, index, left}, {jdst})) ||
+        (rc = refuse_overlap({target, index, left}, {status})) ||
+        (rc = refuse_overlap({index, left}, {target})) || (rc = refuse_overlap({left}, {index}))) {
+        return rc;
+    }
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    w->cfm_n = n;
+    w->cfm_first_seq = p->first_seq;
+    w->cfm_any = true;
+    if (n) {
+        // the hash: a power of two, at least twice the records, so that a walk ends
+        const uint64_t gslots = pow2_at_least(2 * nrec);
+        const uint64_t zero_bytes = 8ull * kCfmCtrWords + 4 * gslots + 13 * nrec;
+        if ((rc = w->cfm_zero.ensure(zero_bytes)) ||
+            (rc = w->cfm_rec.ensure(5 * std::max<uint64_t>(nrec, 1))) ||
+            (rc = w->cfm_hit.ensure(4 * n)) || (rc = w->cfm_off.ensure(8 * n)) ||
+            (rc = w->cfm_bsum.ensure(8ull * 2 * kPackBlocks))) {
+            return rc;
+        }
+        HIP_TRY(hipMemsetAsync(w->cfm_zero.p, 0, zero_bytes, c.s));
+        CfmArgs a;
+        memset(&a, 0, sizeof(a));
+        a.journal = (const uint32_t*)p->journal;
+        a.n_records = nrec;
+        a.select = p->select;
+        a.guids = p->guids;
+        a.queue_keys = p->queue_keys;
+        a.app_keys = p->app_keys;
+        a.reasons = p->reasons;
+        a.timestamps = p->timestamps;
+        a.n = n;
+        a.first_seq = p->first_seq;
+        a.timestamp = p->timestamp;
+        a.lease_id = p->lease_id;
+        a.size_only = p->journal_dst ? 0u : 1u;
+        a.journal_dst = (uint32_t*)p->journal_dst;
+        a.journal_dst_bytes = p->journal_dst_bytes;
+        a.status = p->status;
+        a.target = p->target;
+        a.new_index = p->new_index;
+        a.left_out = p->left_out;
+        a.ctr = (unsigned long long*)w->cfm_zero.p;
+        a.gslot = (uint32_t*)(a.ctr + kCfmCtrWords);
+        a.gslots = gslots;
+        a.had = a.gslot + gslots;
+        a.cnt = a.had + nrec;
+        a.last = a.cnt + nrec;
+        a.dead = (uint8_t*)(a.last + nrec);
+        a.ref = (uint32_t*)w->cfm_rec.p;
+        a.kind = (uint8_t*)(a.ref + nrec);
+        a.hit = (uint32_t*)w->cfm_hit.p;
+        a.off = (unsigned long long*)w->cfm_off.p;
+        a.bsum = (unsigned long long*)w->cfm_bsum.p;
+        if (nrec) {
+            layout_split(nrec, &a.per_block, &a.nblocks);
+        }
+        layout_split(n, &a.cper_block, &a.cnblocks);
+        if (bmqcrc_launch_confirm_records_layout(&a, (void*)c.s)) {
+            return launch_failed("confirm-records layout");
+        }
+        if (!a.size_only && bmqcrc_launch_confirm_records_frame(&a, (void*)c.s)) {
+            return launch_failed("confirm-records frame");
+        }
+    }
+    return sync_result_or_refusal(c, o, confirm_records_result, result, kConfirmPackRefusals);
+}
+
+int bmqcrc_last_confirm_records(int device, void* stream, bmqcrc_confirm_pack_result* result)
+{
+    return last_result(device, stream, confirm_records_result, result);
+}
+
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,
                        uint32_t* seg_bytes)
 {
@@ -3989,7 +4176,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 18u;
+    return (2u << 16) | 19u;
 }
 
 }  // extern "C"

@@ -663,7 +663,79 @@ struct RovArgs {
     uint32_t nblocks;               // layout blocks (<= kPackBlocks)
 };
 
+// ---- bmqcrc_confirm_records_pack (crc32c_confirm_records.hip, ABI 2.19) ----
+// The classify and join grid and block are kPackBlocks x kPackThreads over
+// contiguous record ranges (layout_split over n_records), the check and seal
+// kernels' the same over contiguous confirm ranges (layout_split over n), the
+// frame kernel's kPackFrameBlocks x kPackFrameThreads.  CfmArgs::ctr words
+constexpr int kCfmCtrRefusal = kLayoutCtrRefusal;
+constexpr int kCfmCtrWritten = 1;    // records written (k_cfm_seal)
+constexpr int kCfmCtrDeletions = 2;  // DELETION records among them (k_cfm_seal)
+constexpr int kCfmCtrNotFound = 3;   // confirms without a target (k_cfm_seal)
+constexpr int kCfmCtrWords = 4;
+constexpr uint32_t kCfmNone = 0xFFFFFFFFu;  // no target, no place
+// CfmArgs::kind: what the join makes of a record of the run
+constexpr uint8_t kCfmOther = 0;
+constexpr uint8_t kCfmMessage = 1;   // a selected MESSAGE record: it is in the hash
+constexpr uint8_t kCfmConfirm = 2;   // a CONFIRM record whose reason is not AUTO_CONFIRMED
+constexpr uint8_t kCfmDeletion = 3;
+constexpr uint32_t kConfirmReasonAuto = 2;  // ConfirmReason::e_AUTO_CONFIRMED
+// BMQCRC_CONFIRM_PACK_* of bmqcrc_protocol.h, which the kernels do not include
+#define BMQCRC_CFM_KIND_RECORD_HEADER 1u
+#define BMQCRC_CFM_KIND_DUPLICATE_MESSAGE 2u
+#define BMQCRC_CFM_KIND_NULL_KEY 3u
+#define BMQCRC_CFM_KIND_REASON 4u
+#define BMQCRC_CFM_KIND_OVER_CONFIRMED 5u
+#define BMQCRC_CFM_KIND_DST_TOO_SMALL 6u
+
+struct CfmArgs {
+    const uint32_t* journal;        // device, 4-byte aligned: n_records records of 15 dwords
+    uint64_t n_records;
+    const uint8_t* select;          // device, n_records, or nullptr (every MESSAGE record)
+    const uint8_t* guids;           // device, 16 n
+    const uint8_t* queue_keys;      // device, 5 n
+    const uint8_t* app_keys;        // device, 5 n, or nullptr (the null key)
+    const uint8_t* reasons;         // device, n, or nullptr (all CONFIRMED)
+    const uint64_t* timestamps;     // device, n, or nullptr (all `timestamp`)
+    uint64_t n;                     // confirms
+    uint64_t first_seq;
+    uint64_t timestamp;
+    uint32_t lease_id;
+    uint32_t size_only;             // 1: journal_dst is null, DST_TOO_SMALL is never raised
+    uint32_t* journal_dst;          // device, 4-byte aligned
+    uint64_t journal_dst_bytes;
+    uint8_t* status;                // the caller's arrays (device; n, n, n, n_records), each may
+    uint32_t* target;               // be nullptr: written by k_cfm_frame, when nothing was
+    uint32_t* new_index;            // refused
+    uint32_t* left_out;
+    // workspace, zeroed before the launch
+    unsigned long long* ctr;        // kCfmCtrWords
+    uint32_t* gslot;                // gslots: record + 1 of a selected MESSAGE record, hashed by
+    uint64_t gslots;                // GUID and queue key; a power of two
+    uint32_t* had;                  // n_records: CONFIRM records of the run that name the message
+    uint32_t* cnt;                  // n_records: c(m), the confirms of this call that name it
+    uint32_t* last;                 // n_records: the highest such confirm + 1
+    uint8_t* dead;                  // n_records: 1: a DELETION record of the run names it
+    // workspace, written before it is read
+    uint32_t* ref;                  // n_records: the MESSAGE record's 20-bit refCount
+    uint8_t* kind;                  // n_records: kCfm*
+    uint32_t* hit;                  // n: the selected MESSAGE record with the confirm's key, live
+                                    // or not, or kCfmNone
+    unsigned long long* off;        // n: the prefix of "has a target", then the place j
+    unsigned long long* bsum;       // 2 * kPackBlocks: records written | (unused) per block
+    uint64_t per_block;             // records per block (multiple of kPackThreads)
+    uint32_t nblocks;               // blocks over the records (<= kPackBlocks, 0: no record)
+    uint32_t cnblocks;              // blocks over the confirms (<= kPackBlocks)
+    uint64_t cper_block;            // confirms per block (multiple of kPackThreads)
+};
+
 }  // namespace bmqcrc
+
+// Launchers (crc32c_confirm_records.hip).  Asynchronous on `stream`: the layout
+// decides everything, the frame stores; a size-only call launches the layout
+// alone.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_confirm_records_layout(const bmqcrc::CfmArgs* a, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_confirm_records_frame(const bmqcrc::CfmArgs* a, void* stream);
 
 // Launchers (crc32c_rollover.hip).  Asynchronous on `stream`: the layout
 // before bmqcrc_launch_copy (it writes the copy's descriptors), the frame after.

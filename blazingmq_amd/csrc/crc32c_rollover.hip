@@ -56,6 +56,7 @@
 #include <stdint.h>
 
 #include "bmqcrc_internal.h"
+#include "crc32c_join_key.h"
 #include "crc32c_journal_stage.h"
 #include "crc32c_pack_layout.h"
 
@@ -63,81 +64,11 @@ namespace bmqcrc {
 namespace {
 
 constexpr uint32_t kJournalOpSyncPoint = 2;  // JournalOpType (mqbs_filestoreprotocol.h)
-// dwords of a record: the GUID of a MESSAGE record (bytes 36..51) and of a
-// CONFIRM record (32..47); the queue key of both lies in bytes 22..26
-constexpr uint32_t kMsgGuidDword = 9, kCfmGuidDword = 8;
-
-// What the join compares: the GUID and the queue key's five bytes.
-struct JoinKey {
-    uint32_t g[4], q0, q1;
-};
-
-__device__ __forceinline__ JoinKey join_key(const uint32_t* d, uint32_t guid_dword)
+// The hash of the kept MESSAGE records (crc32c_join_key.h).  The join asks for
+// existence only.
+__device__ __forceinline__ JoinTable join_table(const RovArgs& a)
 {
-    JoinKey k;
-#pragma unroll
-    for (uint32_t j = 0; j < 4; ++j) {
-        k.g[j] = d[guid_dword + j];
-    }
-    k.q0 = d[5] >> 16;          // bytes 22, 23
-    k.q1 = d[6] & 0x00FFFFFFu;  // bytes 24..26
-    return k;
-}
-
-__device__ __forceinline__ bool same_key(const JoinKey& x, const JoinKey& y)
-{
-    return x.g[0] == y.g[0] && x.g[1] == y.g[1] && x.g[2] == y.g[2] && x.g[3] == y.g[3] &&
-           x.q0 == y.q0 && x.q1 == y.q1;
-}
-
-// Every byte of the key reaches every bit of the slot: a multiply and a fold
-// per word, and a last avalanche.
-__device__ __forceinline__ uint32_t key_hash(const JoinKey& k)
-{
-    uint32_t h = 0x9E3779B9u;
-    const uint32_t w[6] = {k.g[0], k.g[1], k.g[2], k.g[3], k.q0, k.q1};
-#pragma unroll
-    for (uint32_t j = 0; j < 6; ++j) {
-        h = (h ^ w[j]) * 0x85EBCA6Bu;
-        h ^= h >> 15;
-    }
-    h *= 0xC2B2AE35u;
-    return h ^ (h >> 16);
-}
-
-// Kept MESSAGE record r into the hash, unless its key is there already (the
-// join asks for existence only, so a chain never grows with repeats of a key).
-__device__ __forceinline__ void join_insert(const RovArgs& a, const JoinKey& k, uint64_t r)
-{
-    const uint64_t mask = a.gslots - 1;
-    uint64_t s = key_hash(k) & mask;
-    for (uint64_t step = 0; step < a.gslots; ++step, s = (s + 1) & mask) {
-        const uint32_t cur = atomicCAS(&a.gslot[s], 0u, (uint32_t)r + 1u);
-        if (cur == 0 ||
-            same_key(k, join_key(a.journal + (uint64_t)kJournalRecordDwords * (cur - 1u),
-                                 kMsgGuidDword))) {
-            return;
-        }
-    }
-}
-
-// Does a kept MESSAGE record have this key?  The walk ends at an empty slot:
-// gslots is at least twice the records, so there is one.
-__device__ __forceinline__ bool join_probe(const RovArgs& a, const JoinKey& k)
-{
-    const uint64_t mask = a.gslots - 1;
-    uint64_t s = key_hash(k) & mask;
-    for (uint64_t step = 0; step < a.gslots; ++step, s = (s + 1) & mask) {
-        const uint32_t cur = a.gslot[s];
-        if (cur == 0) {
-            return false;
-        }
-        if (same_key(k, join_key(a.journal + (uint64_t)kJournalRecordDwords * (cur - 1u),
-                                 kMsgGuidDword))) {
-            return true;
-        }
-    }
-    return false;
+    return {a.gslot, a.gslots, a.journal};
 }
 
 // Step 1.
@@ -189,7 +120,7 @@ __global__ __launch_bounds__(kPackThreads) void k_rov_classify(RovArgs a)
                 header_ok = true;
                 if (want) {
                     if (a.follow) {
-                        join_insert(a, join_key(d, kMsgGuidDword), r);
+                        join_insert(join_table(a), join_key(d, kMsgGuidDword), r);
                     }
                     uint64_t ow;
                     DataRecord dr;
@@ -245,7 +176,7 @@ __global__ __launch_bounds__(kPackThreads) void k_rov_count(RovArgs a)
             if (a.kind[i] == kRovConfirm) {
                 const JoinKey k =
                     join_key(a.journal + (uint64_t)kJournalRecordDwords * i, kCfmGuidDword);
-                a.kind[i] = join_probe(a, k) ? kRovPlain : kRovDrop;
+                a.kind[i] = join_find(join_table(a), k) ? kRovPlain : kRovDrop;
             }
         }
     }

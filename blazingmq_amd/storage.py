@@ -474,9 +474,11 @@ class PartitionWriter:
         self.dpos += total
         return off, bytes(guid)
 
-    def confirm(self, guid, queue_key, app_key=NULL_KEY):
+    def confirm(self, guid, queue_key, app_key=NULL_KEY, reason=0):
+        """`reason` is the ConfirmReason in the RecordHeader's flags: 0
+        CONFIRMED, 1 REJECTED, 2 AUTO_CONFIRMED."""
         return self._record(REC_CONFIRM, [(22, bytes(queue_key)), (27, bytes(app_key)),
-                                          (32, bytes(guid))])
+                                          (32, bytes(guid))], flags=int(reason))
 
     def deletion(self, guid, queue_key):
         return self._record(REC_DELETION, [(23, bytes(queue_key)), (28, bytes(guid))])
@@ -935,5 +937,154 @@ def last_rollover(device, stream=None):
     device's default stream."""
     r = N.RolloverResult()
     N.check(N.lib.bmqcrc_last_rollover(
+        device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
+    return r.as_dict()
+
+
+# ----------------------------------------------------------------------------
+# Device-side confirms: the CONFIRM and DELETION records of a batch.
+# ----------------------------------------------------------------------------
+CONFIRM_STATUS_CONFIRM, CONFIRM_STATUS_DELETION, CONFIRM_STATUS_NOT_FOUND = 0, 1, 2
+
+ConfirmedRecords = collections.namedtuple(
+    "ConfirmedRecords", "journal_dst status target new_index left_out result")
+
+
+def confirm_records(journal, guids, queue_keys, *, lease_id, first_seq, select=None, app_keys=None,
+                    reasons=None, timestamp=0, timestamps=None, journal_dst=None, stream=None,
+                    sync=True):
+    """Turn a batch of consumer confirms into the CONFIRM and DELETION records
+    of a device-resident partition on the GPU (``bmqcrc_confirm_records_pack``):
+    what ``FileBackedStorage::confirm`` appends through
+    ``FileStore::writeConfirmRecord`` and, when a message's count reaches
+    zero, ``writeDeletionRecord``.  There is no CRC in this call: a confirm
+    carries no payload.
+
+    The journal is the state: ``journal`` (uint8, 4-byte aligned, whole 60-byte
+    records) is the partition's run, and the outstanding count of every message
+    is derived from it on every call -- the MESSAGE record's refCount less its
+    CONFIRM records (AUTO_CONFIRMED ones excepted), nothing once a DELETION
+    record names it.  ``select`` (uint8, one byte per record, the output of
+    ``select_records``, or None for every MESSAGE record) says which MESSAGE
+    records count.  Appending ``journal_dst`` to the run and calling again
+    needs no other bookkeeping; ``journal_dst`` may be the tail of the tensor
+    ``journal`` is a slice of.
+
+    The batch is ``guids`` (uint8, 16 bytes per confirm), ``queue_keys``
+    (uint8, 5 per confirm), ``app_keys`` (uint8, 5 per confirm, or None for
+    the null key), ``reasons`` (uint8, 0 CONFIRMED or 1 REJECTED, or None) and
+    ``timestamps`` (int64 per confirm, or None for ``timestamp``).  A confirm
+    whose message is not live writes nothing (status 2); every other one writes
+    one record, sequence numbers from ``first_seq`` on under ``lease_id``: the
+    DELETION record in place of the confirm that brings the count to zero
+    (status 1), a CONFIRM record otherwise (status 0).
+
+    ``journal_dst=None`` sizes the destination exactly with a size-only call
+    first, which takes ``sync=True``.
+
+    Returns the named tuple ``(journal_dst, status, target, new_index,
+    left_out, result)``: ``status`` (uint8 per confirm), ``target`` (int32,
+    the MESSAGE record, -1 for none), ``new_index`` (int32, the record's place
+    in ``journal_dst``, -1 for none), ``left_out`` (int32 per record of the
+    run: the references a MESSAGE record has left after this call, so
+    ``left_out > 0`` is the next ``select``; None for an empty batch, which
+    launches nothing) and ``result`` the dict of
+    ``last_confirm_records`` (None with ``sync=False``); with ``sync=True``
+    ``journal_dst`` is sliced to the bytes written.  All or nothing: a
+    malformed record, two selected MESSAGE records with one key, a null GUID
+    or queue key, a message confirmed more often in one call than it has
+    references left, or a destination too small writes nothing and, with
+    ``sync=True``, raises ``BmqCrcError`` (BMQCRC_EINVAL) naming kind and
+    index.  Not meant to be captured into a graph."""
+    import torch
+    for name, t in (("journal", journal), ("guids", guids), ("queue_keys", queue_keys),
+                    ("select", select), ("app_keys", app_keys), ("reasons", reasons),
+                    ("journal_dst", journal_dst)):
+        if t is None and name not in ("journal", "guids", "queue_keys"):
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise TypeError("%s must be a contiguous %s tensor" % (name, torch.uint8))
+    dev = journal.device
+    if not journal.is_cuda:
+        raise TypeError("confirm_records takes device tensors only (journal is on %s)" % dev)
+    if timestamps is not None and not (isinstance(timestamps, torch.Tensor) and
+                                       timestamps.dtype == torch.int64 and
+                                       timestamps.is_contiguous()):
+        raise TypeError("timestamps must be a contiguous %s tensor" % torch.int64)
+    for name, t in (("guids", guids), ("queue_keys", queue_keys), ("select", select),
+                    ("app_keys", app_keys), ("reasons", reasons), ("timestamps", timestamps),
+                    ("journal_dst", journal_dst)):
+        if t is not None and t.device != dev:
+            raise TypeError("%s must be on %s like journal" % (name, dev))
+    if journal.numel() % JOURNAL_RECORD_SIZE:
+        raise ValueError("journal must hold whole 60-byte records")
+    n_records = journal.numel() // JOURNAL_RECORD_SIZE
+    if guids.numel() % 16:
+        raise ValueError("guids must hold 16 bytes per confirm")
+    n = guids.numel() // 16
+    if queue_keys.numel() != 5 * n:
+        raise ValueError("queue_keys needs 5 bytes per confirm")
+    for name, t, per in (("select", select, None), ("app_keys", app_keys, 5),
+                         ("reasons", reasons, 1), ("timestamps", timestamps, 1)):
+        if t is not None and t.numel() != (n_records if per is None else per * n):
+            raise ValueError("%s has the wrong size" % name)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    # (an empty tensor has no address: the call wants one for the required arrays)
+    spare = torch.empty(8, dtype=torch.uint8, device=dev)
+    p = N.ConfirmPack()
+    p.struct_size = ctypes.sizeof(N.ConfirmPack)
+    p.journal, p.journal_bytes = journal.data_ptr() or spare.data_ptr(), journal.numel()
+    p.n_records = n_records
+    p.select = select.data_ptr() if select is not None and n_records else None
+    p.guids = guids.data_ptr() or spare.data_ptr()
+    p.queue_keys = queue_keys.data_ptr() or spare.data_ptr()
+    for name, t in (("app_keys", app_keys), ("reasons", reasons), ("timestamps", timestamps)):
+        setattr(p, name, t.data_ptr() if t is not None and n else None)
+    p.n, p.timestamp = n, int(timestamp)
+    p.first_seq, p.lease_id = int(first_seq), int(lease_id)
+    dev_index = dev.index if dev.index is not None else -1
+    if journal_dst is None:
+        if not sync:
+            raise ValueError("journal_dst is required when sync=False: sizing it waits for a "
+                             "size-only call")
+        o = N.make_opts(device=dev_index, stream=stream.cuda_stream, flags=N.BMQCRC_F_DEVICE_PTRS)
+        r = N.ConfirmPackResult()
+        N.check(N.lib.bmqcrc_confirm_records_pack(ctypes.byref(p), ctypes.byref(r),
+                                                  ctypes.byref(o)))
+        journal_dst = torch.empty(int(r.journal_bytes), dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    target = torch.empty(n, dtype=torch.int32, device=dev)
+    new_index = torch.empty(n, dtype=torch.int32, device=dev)
+    left_out = torch.empty(n_records, dtype=torch.int32, device=dev) if n else None
+    p.journal_dst = journal_dst.data_ptr() or spare.data_ptr()
+    p.journal_dst_bytes = journal_dst.numel()
+    p.status = status.data_ptr() if n else None
+    p.target = target.data_ptr() if n else None
+    p.new_index = new_index.data_ptr() if n else None
+    p.left_out = left_out.data_ptr() if n and n_records else None
+    o = N.make_opts(device=dev_index, stream=stream.cuda_stream,
+                    flags=N.BMQCRC_F_DEVICE_PTRS | (0 if sync else N.BMQCRC_F_ASYNC))
+    r = N.ConfirmPackResult()
+    N.check(N.lib.bmqcrc_confirm_records_pack(ctypes.byref(p), ctypes.byref(r), ctypes.byref(o)))
+    if not sync:
+        return ConfirmedRecords(journal_dst, status, target, new_index, left_out, None)
+    return ConfirmedRecords(journal_dst[:int(r.journal_bytes)], status, target, new_index,
+                            left_out, r.as_dict())
+
+
+def last_confirm_records(device, stream=None):
+    """The result of the previous ``confirm_records`` on (device, stream)
+    (bmqcrc_last_confirm_records), as a dict; waits for it.  ``n_confirms``;
+    ``n_written`` records, of which ``n_confirm_records`` CONFIRM and
+    ``n_deletions`` DELETION records; ``n_not_found`` confirms without a live
+    message; ``journal_bytes`` written (or, after a size-only call, needed);
+    ``next_seq``, the sequence number behind the last record; ``refused_kind``
+    (0, ``BMQCRC_CONFIRM_PACK_OK``, or the kind) and ``refused_index`` (a
+    record or a confirm, by kind).  After a refused call only ``n_confirms``
+    and the two ``refused_*`` are set.  ``stream=None`` is the device's default
+    stream."""
+    r = N.ConfirmPackResult()
+    N.check(N.lib.bmqcrc_last_confirm_records(
         device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
     return r.as_dict()

@@ -1305,6 +1305,151 @@ int bmqcrc_partition_rollover(const bmqcrc_rollover* p, bmqcrc_rollover_result* 
  * stream); waits for it.  `result` may be NULL. */
 int bmqcrc_last_rollover(int device, void* stream, bmqcrc_rollover_result* result);
 
+/* ABI 2.19.  The consumer's confirm: a batch of confirms, in device memory,
+ * against the journal run of a device-resident partition becomes ON THE DEVICE
+ * the CONFIRM and DELETION records the reference would append -- the path
+ * QueueHandle::confirmMessage -> FileBackedStorage::confirm ->
+ * FileStore::writeConfirmRecord and, when a message's count reaches zero,
+ * FileBackedStorage::remove -> FileStore::writeDeletionRecord -- byte for byte,
+ * in one asynchronous call.  THIS CALL HAS NO CRC IN IT: a confirm carries no
+ * payload.  It is here because a device-resident partition that cannot record
+ * a confirm cannot free anything.
+ *
+ * The journal is the state.  Nothing persists between calls: the outstanding
+ *   count of every message is derived from the run, as recovery derives it
+ *   (processMessageRecord / processConfirmRecord).  Record r is
+ *   journal[60 r .. 60 r + 60), r = 0 .. n_records - 1.  select[r] != 0 selects
+ *   MESSAGE record r (the output of bmqcrc_journal_select; on other records it
+ *   is ignored); select == NULL selects every MESSAGE record.  With key = (GUID,
+ *   queue key) -- bytes 36..51 and 22..26 of a MESSAGE record, 32..47 and 22..26
+ *   of a CONFIRM record, 28..43 and 23..27 of a DELETION record:
+ *   - a MESSAGE record m is LIVE if it is selected and no DELETION record
+ *     anywhere in the run has its key;
+ *   - had(m) is the number of CONFIRM records in the run with m's key whose
+ *     ConfirmReason (the low 12 bits of the RecordHeader's flags) is not
+ *     AUTO_CONFIRMED (2);
+ *   - left(m) = max(refCount(m) - had(m), 0), refCount the 20-bit field
+ *     (byte 20 above the RecordHeader's 12 flag bits); 0 when m is not live;
+ *   - CONFIRM and DELETION records that name no selected MESSAGE record are
+ *     ignored, as the reference logs and ignores them.
+ *   Appending the call's output to the run and calling again needs no other
+ *   bookkeeping: journal_dst may be journal + 60 n_records of one allocation.
+ * The batch.  Confirm i = 0 .. n - 1 is guids[16 i .. +16), queue_keys[5 i ..
+ *   +5), app_keys[5 i .. +5) (NULL: the null key), reasons[i] (0 CONFIRMED or 1
+ *   REJECTED; NULL: 0) and timestamps[i] (NULL: `timestamp` for all).
+ * What is written.  target(i) is the live MESSAGE record with confirm i's key,
+ *   or none; c(m) the confirms of this call whose target is m; last(m) the
+ *   highest of them.
+ *   - No target: nothing is written, status[i] = 2 (the reference's
+ *     e_GUID_NOT_FOUND, normal traffic after a consumer reconnects).
+ *   - Otherwise confirm i writes one record at journal_dst + 60 j, j the number
+ *     of confirms below i that have a target, with sequence number first_seq +
+ *     j, lease_id and confirm i's timestamp:
+ *     a DELETION record when i == last(m) and c(m) == left(m) (status[i] = 1):
+ *       flags 0, the queue key at byte 23, the GUID at byte 28 -- the reference
+ *       does not record the confirm that brings the count to zero and writes
+ *       the DELETION in its place;
+ *     a CONFIRM record otherwise (status[i] = 0): the reason in the flags, the
+ *       queue key at byte 22, the app key at 27, the GUID at 32.
+ *     Every other byte behind the RecordHeader is zero, the magic 0x2A724563 at 56.
+ * Outputs, each may be NULL: status[n]; target[n] (the record index,
+ *   0xFFFFFFFF for none); new_index[n] (j, or 0xFFFFFFFF); left_out[n_records]
+ *   (left(m) - c(m) for MESSAGE records, 0 elsewhere: left_out > 0 is the next
+ *   select).
+ * Size only.  journal_dst == NULL with journal_dst_bytes == 0: everything is
+ *   decided, nothing is stored (no output array either) and the result says
+ *   what a real call would write.
+ * All or nothing, decided on the device.  One violation anywhere refuses the
+ *   call, and a refused call writes nothing.  The lowest kind wins and within
+ *   it the lowest index (BMQCRC_CONFIRM_PACK_* below), whatever the order the
+ *   device works in.  A synchronous call returns BMQCRC_EINVAL naming kind and
+ *   index; after an asynchronous call bmqcrc_last_confirm_records reports them.
+ * What differs from the reference.
+ *   - Over-confirming within one call (c(m) > left(m)) is a refusal.  The
+ *     reference would apply the first left(m) confirms and answer
+ *     e_GUID_NOT_FOUND to the rest; deciding "first" needs each confirm's rank
+ *     among the confirms of its message, which is not built.  Across calls the
+ *     behaviour is the reference's: the later confirm finds no live message.
+ *   - A mismatched app key is not detected: the per-app virtual storage stays
+ *     with the caller, app_keys are copied into the records and nothing more.
+ *   - The DELETION record takes the zeroing confirm's timestamp, where the
+ *     reference reads the clock again.
+ *   - There is no auto-confirm and no rollover-if-needed.
+ *   - Nothing is replicated: the output goes to bmqcrc_storage_event_pack.
+ * Options.  Device pointers only: BMQCRC_F_DEVICE_PTRS is required,
+ *   BMQCRC_F_ASYNC allowed; any other flag, ndevices > 1, a wrong struct_size or
+ *   a non-zero reserved field; journal, guids or queue_keys null; journal_dst
+ *   null with journal_dst_bytes != 0; journal, journal_dst, target, new_index or
+ *   left_out not 4-byte aligned, timestamps not 8-byte aligned; journal_bytes !=
+ *   60 n_records; n or n_records >= 2^32; lease_id 0; first_seq 0 or first_seq
+ *   + n above 2^48 - 1; journal_dst or an output array meeting an input or one
+ *   another is BMQCRC_EINVAL, answered on the host before the device lookup.
+ *   n == 0 launches nothing, writes nothing and reports zeros.
+ * *result (may be NULL) is written by a synchronous call only.
+ * State.  As bmqcrc_partition_rollover: takes the workspace mutex of (device,
+ *   stream); restores the caller's current device; allocates its own workspace
+ *   on first use and when the call grows (18 bytes per record and 8 to 16 more
+ *   for the hash, 12 per confirm), which bmqcrc_reserve does not cover; is not
+ *   meant to be captured into a hipGraph; is deterministic.  The shape
+ *   prediction and the records of every other bmqcrc_last_* call are never
+ *   touched. */
+#define BMQCRC_CONFIRM_PACK_OK 0
+#define BMQCRC_CONFIRM_PACK_RECORD_HEADER 1      /* BMQCRC_ROLLOVER_RECORD_HEADER's conditions, on every
+                                                    record of the run.  Index: the record */
+#define BMQCRC_CONFIRM_PACK_DUPLICATE_MESSAGE 2  /* two selected MESSAGE records share a key.  Index: the
+                                                    lowest record among all that share theirs */
+#define BMQCRC_CONFIRM_PACK_NULL_KEY 3           /* a confirm whose GUID or queue key is all zero.  Index:
+                                                    the confirm */
+#define BMQCRC_CONFIRM_PACK_REASON 4             /* reasons[i] above 1.  Index: the confirm */
+#define BMQCRC_CONFIRM_PACK_OVER_CONFIRMED 5     /* c(m) > left(m).  Index: the lowest confirm whose
+                                                    target is such a message */
+#define BMQCRC_CONFIRM_PACK_DST_TOO_SMALL 6      /* index: the lowest confirm whose record ends past
+                                                    journal_dst_bytes */
+
+typedef struct bmqcrc_confirm_pack {
+    uint32_t struct_size, reserved;       /* sizeof, 0 */
+    const void* journal;                  /* device, 4-byte aligned: n_records 60-byte records, the record run */
+    uint64_t journal_bytes;               /* == 60 * n_records */
+    uint64_t n_records;                   /* < 2^32 */
+    const uint8_t* select;                /* device, n_records, may be NULL (every MESSAGE record) */
+    const uint8_t* guids;                 /* device, 16 n */
+    const uint8_t* queue_keys;            /* device, 5 n */
+    const uint8_t* app_keys;              /* device, 5 n, may be NULL (the null key) */
+    const uint8_t* reasons;               /* device, n, may be NULL (all CONFIRMED) */
+    const uint64_t* timestamps;           /* device, n, may be NULL (`timestamp` for all) */
+    uint64_t n;                           /* confirms, < 2^32 */
+    uint64_t timestamp;
+    uint64_t first_seq;                   /* sequence number of the first record written, not 0 */
+    uint32_t lease_id;                    /* primary lease id, not 0 */
+    uint32_t reserved2;                   /* 0 */
+    void* journal_dst;                    /* device, 4-byte aligned: the 60-byte records back to back;
+                                             NULL (journal_dst_bytes 0): size only */
+    uint64_t journal_dst_bytes;
+    uint8_t* status;                      /* device, n, may be NULL: 0 CONFIRM, 1 DELETION, 2 not found */
+    uint32_t* target;                     /* device, n, may be NULL */
+    uint32_t* new_index;                  /* device, n, may be NULL */
+    uint32_t* left_out;                   /* device, n_records, may be NULL */
+} bmqcrc_confirm_pack;
+
+/* All fields zero before the first call on (device, stream); after a refused
+ * call only n_confirms and the refused_* fields are set. */
+typedef struct bmqcrc_confirm_pack_result {
+    uint64_t n_confirms;                  /* n */
+    uint64_t n_written;                   /* records: n_confirm_records + n_deletions */
+    uint64_t n_confirm_records, n_deletions, n_not_found;
+    uint64_t journal_bytes;               /* 60 n_written */
+    uint64_t next_seq;                    /* first_seq + n_written */
+    uint32_t refused_kind, reserved;
+    uint64_t refused_index;               /* a record or a confirm, by kind */
+} bmqcrc_confirm_pack_result;
+
+int bmqcrc_confirm_records_pack(const bmqcrc_confirm_pack* p, bmqcrc_confirm_pack_result* result,
+                                const bmqcrc_opts* opts);
+
+/* ABI 2.19.  Result of the previous bmqcrc_confirm_records_pack on (device,
+ * stream); waits for it.  `result` may be NULL. */
+int bmqcrc_last_confirm_records(int device, void* stream, bmqcrc_confirm_pack_result* result);
+
 /* ---- cluster state ledger (mqbc_clusterstateledgerprotocol.h:76,272) ------ */
 
 /* mqbc::ClusterStateLedgerUtilRc values (mqbc_clusterstateledgerutil.h:65-124)

@@ -1,0 +1,595 @@
+"""Consumer confirms recorded on the GPU (bmqcrc_confirm_records_pack, ABI
+2.19).  The oracle throughout is tests/confirm_records_model.py.  Every raw
+call hands the library a sentinel-filled destination and output arrays with
+guard bytes and elements behind them: the guards are checked after every call,
+and every byte and element after a refused or size-only one."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+from blazingmq_amd import (ConfirmEventBuilder, PushMessageIterator,
+                           _native as N, apply_events, confirm_arrays, confirm_records,
+                           last_confirm_records, last_copy, last_journal_select, last_launch,
+                           last_push_pack, last_put_pack, last_put_unpack, last_records_pack,
+                           last_records_unpack, last_rollover, last_storage_apply,
+                           last_storage_pack, pack_push_events, pack_records,
+                           pack_storage_events, rollover_records, select_records)
+from blazingmq_amd import Crc32c
+from blazingmq_amd import storage as S
+import confirm_records_cases as C
+import confirm_records_model as M
+import device_views as V
+import put_pack_model as P
+from records_pack_model import random_meta
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 8      # elements behind every output array
+SLACK = 64     # bytes behind every input buffer and the destination
+SENTINEL = 0xC3
+JH = S.PartitionWriter.JOURNAL_HEADER
+CANARY = {"status": (np.uint8, 0x5A), "target": (np.uint32, 0x5A5A5A5A),
+          "new_index": (np.uint32, 0xA5A5A5A5), "left_out": (np.uint32, 0x3C3C3C3C)}
+KINDS = ("OK", "RECORD_HEADER", "DUPLICATE_MESSAGE", "NULL_KEY", "REASON", "OVER_CONFIRMED",
+         "DST_TOO_SMALL")
+KIND_NAME = {k: ("BMQCRC_CONFIRM_PACK_" + n).encode() for k, n in enumerate(KINDS) if k}
+KEYS = [bytes([0x26, 0xda, 0xcd, 0xc9, 0x74 + k]) for k in range(4)]
+BATCH = ("guids", "queue_keys", "app_keys", "reasons", "timestamps")
+# the base pointers the ABI permits: 4-byte ones at +4, the 8-byte one at +8, bytes at +1
+PHASES = {"journal": 4, "journal_dst": 4, "select": 1, "guids": 1, "queue_keys": 1,
+          "app_keys": 1, "reasons": 1, "timestamps": 8, "status": 1, "target": 4, "new_index": 4,
+          "left_out": 4}
+
+
+def _side_stream(cuda):
+    """A stream of its own from the high-priority pool (the default pool's
+    streams carry planner history that tests elsewhere rely on)."""
+    import torch
+    return torch.cuda.Stream(cuda, priority=-1)
+
+
+def _t(cuda, a, dtype):
+    import torch
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if dtype == np.uint32:
+        a = a.view(np.int32)
+    return torch.from_numpy(a).to(cuda)
+
+
+def _dev(cuda, buf, place, name):
+    """`buf` on the device as a view of a longer allocation: one that starts
+    with it, or with `place` (a device_views.Placer) one that holds it at the
+    phase the placer has for `name`."""
+    import torch
+    buf = np.array(buf)  # (a copy: shared inputs are read-only)
+    if place is not None:
+        return place.put(name, buf)
+    raw = buf.reshape(-1).view(np.uint8)
+    back = torch.full((raw.size + SLACK,), 0xEE, dtype=torch.uint8, device=cuda)
+    back[:raw.size] = torch.from_numpy(raw).to(cuda)
+    return back[:raw.size].view({np.dtype(np.int64): torch.int64}.get(buf.dtype, torch.uint8))
+
+
+def _filled(cuda, place, name, count, dt, value):
+    import torch
+    if place is not None:
+        return place.fill(name, count, dt, value)
+    fill = np.array([value], np.uint64).astype(dt)
+    return torch.from_numpy(np.repeat(fill, count).view(
+        {np.uint32: np.int32}.get(dt, dt))).to(cuda)
+
+
+def _raw(cuda, run, batch, kw, sync=True, stream=None, skip=(), phases=None):
+    """One bmqcrc_confirm_records_pack over device tensors into a
+    sentinel-filled destination and arrays.  `kw`: lease_id, first_seq,
+    timestamp, select, journal_dst_bytes (None: a size-only call, journal_dst
+    NULL).  Returns (rc, error text, result of the call or of
+    bmqcrc_last_confirm_records, everything written on the host with its
+    guards).  `phases` maps every pointer of the call to the phase of its base;
+    the sentinel margins around each are checked after the call."""
+    import torch
+    place = V.Placer(cuda, phases) if phases is not None else None
+    stream = stream or torch.cuda.current_stream(cuda)
+    n_records, n = len(run) // 60, len(batch["guids"]) // 16
+    room = kw.get("journal_dst_bytes")
+    with torch.cuda.stream(stream):
+        d_in = {"journal": _dev(cuda, np.asarray(run, np.uint8), place, "journal")}
+        if kw.get("select") is not None:
+            d_in["select"] = _dev(cuda, np.asarray(kw["select"], np.uint8), place, "select")
+        for name in BATCH:
+            if batch.get(name) is not None:
+                dt = np.int64 if name == "timestamps" else np.uint8
+                d_in[name] = _dev(cuda, np.asarray(batch[name], dt), place, name)
+        arr = {"journal_dst": _filled(cuda, place, "journal_dst", (room or 0) + SLACK, np.uint8,
+                                      SENTINEL)}
+        for name, (dt, value) in CANARY.items():
+            if name not in skip:
+                count = n_records if name == "left_out" else n
+                arr[name] = _filled(cuda, place, name, count + GUARD, dt, value)
+        # (an empty tensor has no address: the call wants one)
+        spare = torch.zeros(8, dtype=torch.uint8, device=cuda)
+        p = N.ConfirmPack()
+        p.struct_size = ctypes.sizeof(N.ConfirmPack)
+        p.journal, p.journal_bytes = d_in["journal"].data_ptr() or spare.data_ptr(), len(run)
+        p.n_records, p.n = n_records, n
+        p.select = d_in["select"].data_ptr() if "select" in d_in and n_records else None
+        p.guids = d_in["guids"].data_ptr() or spare.data_ptr()
+        p.queue_keys = d_in["queue_keys"].data_ptr() or spare.data_ptr()
+        for name in BATCH[2:]:
+            setattr(p, name, d_in[name].data_ptr() if name in d_in and n else None)
+        p.timestamp, p.first_seq, p.lease_id = kw.get("timestamp", 0), kw["first_seq"], kw["lease_id"]
+        p.journal_dst = arr["journal_dst"].data_ptr() if room is not None else None
+        p.journal_dst_bytes = room or 0
+        for name in CANARY:
+            setattr(p, name, arr[name].data_ptr() if name in arr else None)
+        o = N.make_opts(device=cuda.index, stream=stream.cuda_stream,
+                        flags=N.BMQCRC_F_DEVICE_PTRS | (0 if sync else N.BMQCRC_F_ASYNC))
+        r = N.ConfirmPackResult()
+        rc = N.lib.bmqcrc_confirm_records_pack(ctypes.byref(p), ctypes.byref(r), ctypes.byref(o))
+        err = N.lib.bmqcrc_last_error()
+        res = r.as_dict() if sync else last_confirm_records(cuda.index, stream)
+        host = {name: t.cpu().numpy() for name, t in arr.items()}
+        if place is not None:
+            place.check()
+    for name, (dt, _) in CANARY.items():
+        if name in host:
+            host[name] = host[name].view(dt)
+    return rc, err, res, host
+
+
+def _untouched(name, a):
+    return bool((a == (CANARY[name][1] if name in CANARY else SENTINEL)).all())
+
+
+def _check(cuda, run, batch, kw, sync=True, stream=None, skip=(), phases=None):
+    """The call against the model: a refusal identical and nothing written, or
+    every destination byte, array entry and result field.  `journal_dst_bytes`
+    "exact" is what the model says the call writes, None a size-only call.
+    Returns (model, host)."""
+    kw = dict(kw)
+    mkw = {k: kw.get(k) for k in ("lease_id", "first_seq", "select", "journal_dst_bytes")}
+    mkw["timestamp"] = kw.get("timestamp", 0)
+    mbatch = {k: batch.get(k) for k in BATCH}
+    if kw.get("journal_dst_bytes") == "exact":
+        sized = M.confirm_records(run, **mbatch, **dict(mkw, journal_dst_bytes=None))
+        kw["journal_dst_bytes"] = mkw["journal_dst_bytes"] = \
+            sized.result["journal_bytes"] if isinstance(sized, M.Confirmed) else 600
+    m = M.confirm_records(run, **mbatch, **mkw)
+    rc, err, res, host = _raw(cuda, run, batch, kw, sync=sync, stream=stream, skip=skip,
+                              phases=phases)
+    n = len(batch["guids"]) // 16
+    if isinstance(m, M.Refusal):
+        if sync:
+            assert rc == N.BMQCRC_EINVAL and KIND_NAME[m.kind] in err, (rc, err, m)
+            assert b"nothing was written" in err and (b"%d" % m.index) in err, (err, m)
+        else:
+            assert rc == 0, err
+        assert res == M.refused_result(m, n), (res, m)
+        for name, a in host.items():
+            assert _untouched(name, a), name
+        return m, host
+    assert rc == 0, err
+    assert res == m.result, (res, m.result)
+    if kw.get("journal_dst_bytes") is None or n == 0:     # size only, or nothing launched
+        for name, a in host.items():
+            assert _untouched(name, a), name
+        return m, host
+    for name, want in (("journal_dst", m.journal), ("status", m.status), ("target", m.target),
+                       ("new_index", m.new_index), ("left_out", m.left_out)):
+        if name in skip:
+            continue
+        assert np.array_equal(host[name][:len(want)], want), name
+        assert _untouched(name, host[name][len(want):]), name
+    return m, host
+
+
+def _batch(pairs, rng=None, plain=False):
+    """The batch of (guid, queue key) pairs; with `rng` app keys, reasons and
+    timestamps of its own, `plain` leaves those three NULL."""
+    n = len(pairs)
+    b = dict(guids=np.frombuffer(b"".join(g for g, _ in pairs), np.uint8).copy(),
+             queue_keys=np.frombuffer(b"".join(k for _, k in pairs), np.uint8).copy())
+    if not plain:
+        rng = rng or np.random.default_rng(n)
+        b["app_keys"] = rng.integers(0, 256, 5 * n, dtype=np.uint8)
+        b["reasons"] = rng.integers(0, 2, n, dtype=np.uint8)
+        b["timestamps"] = rng.integers(0, 1 << 62, n, dtype=np.int64)
+    return b
+
+
+@functools.lru_cache(maxsize=None)
+def _messages(n):
+    """(run of a CREATION record and n MESSAGE records of refCount 1 in four
+    queues, their (guid, key) pairs, the next sequence number).  Shared, never
+    modified."""
+    w = S.PartitionWriter(lease_id=4)
+    pairs = []
+    for i in range(n):
+        pairs.append((w.message(b"", KEYS[i % 4], guid=(0x4000 + i).to_bytes(16, "little"))[1],
+                      KEYS[i % 4]))
+    j, _ = w.files()
+    run = j[JH:]
+    run.setflags(write=False)
+    return run, tuple(pairs), w.seq + 1
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1023, 1025])
+def test_batch_sizes_against_1025_messages(cuda, n):
+    run, pairs, seq = _messages(1025)
+    rng = np.random.default_rng(n)
+    order = rng.permutation(1025)[:n]
+    kw = dict(lease_id=4, first_seq=seq, journal_dst_bytes="exact")
+    m, _ = _check(cuda, run, _batch([pairs[i] for i in order], rng), kw)
+    assert m.result["n_deletions"] == n
+
+
+@functools.lru_cache(maxsize=None)
+def _mixed(n=3000, seed=21):
+    """(run of n records of every type, the next sequence number): messages of
+    refCount 1..3 in four queues, CONFIRM records (every fourth AUTO_CONFIRMED)
+    and DELETION records of earlier and of LATER messages, QUEUE_OP and
+    JOURNAL_OP records.  Shared, never modified."""
+    rng = np.random.default_rng(seed)
+    w = S.PartitionWriter(lease_id=9)
+    msgs, k = [], 0
+    while len(w.recs) < n:
+        roll = int(rng.integers(0, 10))
+        if roll < 5 or not msgs:
+            key = KEYS[int(rng.integers(0, 4))]
+            guid = (0x77000000 + len(msgs)).to_bytes(16, "big")
+            w.message(b"", key, guid=guid, ref_count=int(rng.integers(1, 4)))
+            msgs.append((guid, key))
+        elif roll < 7:
+            k += 1
+            w.confirm(*msgs[int(rng.integers(0, len(msgs)))],
+                      reason=2 if k % 4 == 0 else int(rng.integers(0, 2)))
+        elif roll == 7:
+            if rng.random() < 0.5:
+                w.deletion(*msgs[int(rng.integers(0, len(msgs)))])
+            else:   # of the message that comes five messages on, should its key be the first
+                w.deletion((0x77000000 + len(msgs) + 5).to_bytes(16, "big"), KEYS[0])
+        elif roll == 8:
+            w.queue_op(int(rng.integers(1, 5)), KEYS[int(rng.integers(0, 4))])
+        else:
+            w.sync_point()
+    run = w.files()[0][JH:]
+    assert run.size == 60 * n
+    run.setflags(write=False)
+    return run, w.seq + 1
+
+
+@functools.lru_cache(maxsize=None)
+def _mixed_messages():
+    """The mixed run's MESSAGE records as (guid, key, references left, named by
+    a DELETION record), the third by the model's own recovery (a call with one
+    confirm that names nothing)."""
+    run, seq = _mixed()
+    left = M.confirm_records(run, **_batch([(b"\x01" * 16, KEYS[0])], plain=True), lease_id=9,
+                             first_seq=seq).left_out
+    recs = run.reshape(-1, 60)
+    deleted = {(d[28:44].tobytes(), d[23:28].tobytes()) for d in recs[recs[:, 0] >> 4 == 3]}
+    return tuple((g, k, int(left[r]), (g, k) in deleted)
+                 for r in np.flatnonzero(recs[:, 0] >> 4 == 1)
+                 for g, k in [(recs[r, 36:52].tobytes(), recs[r, 22:27].tobytes())])
+
+
+@pytest.mark.parametrize("select", ["all", "none", "second", None])
+def test_mixed_records_over_three_blocks(cuda, select):
+    run, seq = _mixed()
+    msgs = _mixed_messages()
+    n_records = run.size // 60
+    assert n_records == 3000
+    sel = {"all": np.ones(n_records, np.uint8), "none": np.zeros(n_records, np.uint8),
+           "second": (np.arange(n_records) % 2).astype(np.uint8), None: None}[select]
+    rng = np.random.default_rng(5)
+    pairs = []
+    for g, k, left, _ in msgs:      # never more of one than it has left
+        pairs += [(g, k)] * int(rng.integers(0, left + 1))
+    pairs += [(bytes(rng.integers(1, 256, 16, dtype=np.uint8)), KEYS[1]) for _ in range(40)]
+    pairs += [(g, k) for g, k, _, dead in msgs if dead][:40]         # gone: a DELETION names them
+    pairs = [pairs[i] for i in rng.permutation(len(pairs))]
+    assert len(pairs) > 1024
+    kw = dict(lease_id=9, first_seq=seq, timestamp=5, select=sel, journal_dst_bytes="exact")
+    m, _ = _check(cuda, run, _batch(pairs, rng), kw)
+    assert isinstance(m, M.Confirmed)
+    if select in ("all", None):
+        assert m.result["n_deletions"] > 100 and m.result["n_confirm_records"] > 100
+        assert m.result["n_not_found"] >= 40
+    if select == "none":
+        assert m.result["n_written"] == 0 and not m.left_out.any()
+
+
+@pytest.mark.parametrize("times", [2000, 2001])
+def test_one_message_confirmed_2000_times(cuda, times):
+    w = S.PartitionWriter(lease_id=2)
+    guid = w.message(b"", KEYS[0], ref_count=2000)[1]
+    run = w.files()[0][JH:]
+    kw = dict(lease_id=2, first_seq=2, journal_dst_bytes=60 * times)
+    m, host = _check(cuda, run, _batch([(guid, KEYS[0])] * times), kw)
+    if times == 2001:
+        assert m == M.Refusal(M.OVER_CONFIRMED, 0)
+        return
+    assert m.result["n_confirm_records"] == 1999 and m.result["n_deletions"] == 1
+    assert m.status.tolist() == [0] * 1999 + [1]
+    assert host["journal_dst"][60 * 1999] >> 4 == 3
+
+
+@pytest.mark.parametrize("byte", [0, 15])
+def test_guids_that_differ_in_one_byte_only(cuda, byte):
+    w = S.PartitionWriter(lease_id=2)
+    pairs = []
+    for b in range(256):
+        guid = bytearray(b"\x5A" * 16)
+        guid[byte] = b
+        pairs.append((w.message(b"", KEYS[1], guid=bytes(guid))[1], KEYS[1]))
+    run = w.files()[0][JH:]
+    order = np.random.default_rng(byte).permutation(256)
+    kw = dict(lease_id=2, first_seq=w.seq + 1, journal_dst_bytes="exact")
+    m, _ = _check(cuda, run, _batch([pairs[i] for i in order]), kw)
+    assert m.target.tolist() == order.tolist() and m.result["n_deletions"] == 256
+
+
+def test_the_hand_worked_case_and_the_same_guid_under_two_queue_keys(cuda):
+    kw = dict(C.KW, journal_dst_bytes=240)
+    m, host = _check(cuda, C.run(), C.batch(), kw)
+    assert host["journal_dst"][:240].tobytes() == C.expected_bytes().tobytes()
+    assert host["target"][:6].tolist() == C.EXPECTED_TARGET       # G0 under key A and under key B
+    assert host["status"][:6].tolist() == C.EXPECTED_STATUS
+    assert host["left_out"][:10].tolist() == C.EXPECTED_LEFT
+
+
+def test_messages_one_confirm_short_of_their_count_in_the_run(cuda):
+    w = S.PartitionWriter(lease_id=2)
+    pairs = []
+    for i in range(70):
+        key = KEYS[i % 4]
+        guid = w.message(b"", key, ref_count=1 + i % 4)[1]
+        for _ in range(i % 4):
+            w.confirm(guid, key)
+        pairs.append((guid, key))
+    run = w.files()[0][JH:]
+    kw = dict(lease_id=2, first_seq=w.seq + 1, journal_dst_bytes="exact")
+    m, _ = _check(cuda, run, _batch(pairs), kw)
+    assert m.status.tolist() == [1] * 70
+
+
+@pytest.mark.parametrize("where", ["first", "last"])
+def test_a_stale_guid_at_either_end(cuda, where):
+    run, pairs, seq = _messages(1025)
+    stale = (b"\xFE" * 16, KEYS[0])
+    chosen = list(pairs[100:165])
+    chosen = [stale] + chosen if where == "first" else chosen + [stale]
+    kw = dict(lease_id=4, first_seq=seq, journal_dst_bytes="exact")
+    m, _ = _check(cuda, run, _batch(chosen), kw)
+    assert m.status[0 if where == "first" else -1] == 2 and m.result["n_written"] == 65
+
+
+@pytest.mark.parametrize("skip", list(CANARY) + ["all", "batch"])
+def test_each_output_and_each_optional_input_null(cuda, skip):
+    run, pairs, seq = _messages(1025)
+    kw = dict(lease_id=4, first_seq=seq, timestamp=77, journal_dst_bytes="exact")
+    b = _batch(list(pairs[:130]) + [(b"\x01" * 16, KEYS[2])], plain=skip == "batch")
+    _check(cuda, run, b, kw, skip=tuple(CANARY) if skip == "all" else (skip,))
+
+
+def test_size_only_then_the_real_call(cuda):
+    run, seq = _mixed()
+    pairs = [(g, k) for g, k, left, _ in _mixed_messages() if left]
+    b = _batch(pairs)
+    kw = dict(lease_id=9, first_seq=seq)
+    sized, _ = _check(cuda, run, b, dict(kw, journal_dst_bytes=None))
+    _check(cuda, run, b, dict(kw, journal_dst_bytes=None), sync=False)
+    need = sized.result["journal_bytes"]
+    assert need == 60 * len(pairs)
+    _check(cuda, run, b, dict(kw, journal_dst_bytes=need))
+    m, _ = _check(cuda, run, b, dict(kw, journal_dst_bytes=need - 1))
+    assert m == M.Refusal(M.DST_TOO_SMALL, len(pairs) - 1)
+
+
+def test_the_destination_is_the_tail_of_the_runs_own_allocation(cuda):
+    import torch
+    run, pairs, seq = _messages(1025)
+    chosen = [pairs[i] for i in np.random.default_rng(3).permutation(1025)[:300]]
+    b = _batch(chosen, plain=True)
+    want = M.confirm_records(run, **b, lease_id=4, first_seq=seq, journal_dst_bytes=60 * 300)
+    whole = torch.full((run.size + 60 * 300 + SLACK,), SENTINEL, dtype=torch.uint8, device=cuda)
+    whole[:run.size] = torch.from_numpy(np.array(run)).to(cuda)
+    r = confirm_records(whole[:run.size], _t(cuda, b["guids"], np.uint8),
+                        _t(cuda, b["queue_keys"], np.uint8), lease_id=4, first_seq=seq,
+                        journal_dst=whole[run.size:run.size + 60 * 300])
+    assert r.result == want.result
+    got = whole.cpu().numpy()
+    assert np.array_equal(got[:run.size], run)
+    assert np.array_equal(got[run.size:run.size + 60 * 300], want.journal)
+    assert (got[run.size + 60 * 300:] == SENTINEL).all()
+    # ... and the grown run is the next call's: every one of them is gone now
+    again = confirm_records(whole[:run.size + 60 * 300], _t(cuda, b["guids"], np.uint8),
+                            _t(cuda, b["queue_keys"], np.uint8), lease_id=4,
+                            first_seq=r.result["next_seq"])
+    assert again.result["n_not_found"] == 300 and again.journal_dst.numel() == 0
+    assert int((again.left_out.cpu() > 0).sum()) == 1025 - 300
+
+
+@pytest.mark.parametrize("sync", [True, False], ids=["sync", "async"])
+@pytest.mark.parametrize("r", C.refused(), ids=lambda r: r.name)
+def test_every_refusal(cuda, r, sync):
+    kw = dict(C.KW, journal_dst_bytes=240)
+    kw.update(r.kw)
+    m, _ = _check(cuda, r.run, r.batch, kw, sync=sync)
+    assert m == M.Refusal(r.kind, r.index)
+
+
+@pytest.mark.parametrize("sync", [True, False], ids=["sync", "async"])
+def test_a_violation_in_the_last_record_of_the_last_block_and_in_the_last_confirm(cuda, sync):
+    run, seq = _mixed()
+    _, pairs, _ = _messages(1025)
+    b = _batch(list(pairs), plain=True)      # none of them is in the mixed run: 1,025 not found
+    kw = dict(lease_id=9, first_seq=seq, journal_dst_bytes=60)
+    bad = np.array(run)
+    bad[60 * 2999 + 59] ^= 1                 # the magic of record 2,999
+    m, _ = _check(cuda, bad, b, kw, sync=sync)
+    assert m == M.Refusal(M.RECORD_HEADER, 2999)
+    null = dict(b, guids=b["guids"].copy())
+    null["guids"][-16:] = 0
+    m, _ = _check(cuda, run, null, kw, sync=sync)
+    assert m == M.Refusal(M.NULL_KEY, 1024)
+    reasons = np.zeros(1025, np.uint8)
+    reasons[-1] = 2
+    m, _ = _check(cuda, run, dict(b, reasons=reasons), kw, sync=sync)
+    assert m == M.Refusal(M.REASON, 1024)
+    # the last record a second MESSAGE record of record 0's key
+    recs = np.array(run).reshape(-1, 60)
+    first = int(np.flatnonzero(recs[:, 0] >> 4 == 1)[0])
+    recs[2999, :2], recs[2999, 20:56] = recs[first, :2], recs[first, 20:56]
+    m, _ = _check(cuda, recs.reshape(-1), b, kw, sync=sync)
+    assert m == M.Refusal(M.DUPLICATE_MESSAGE, first)
+    # the last confirm's record is the one that does not fit
+    run2, pairs2, seq2 = _messages(1025)
+    m, _ = _check(cuda, run2, b, dict(lease_id=4, first_seq=seq2, journal_dst_bytes=60 * 1025 - 1),
+                  sync=sync)
+    assert m == M.Refusal(M.DST_TOO_SMALL, 1024)
+
+
+def test_every_base_pointer_at_the_smallest_alignment_the_abi_permits(cuda):
+    run, pairs, seq = _messages(1025)
+    rng = np.random.default_rng(11)
+    b = _batch([pairs[i] for i in rng.permutation(1025)[:200]] + [(b"\x09" * 16, KEYS[3])], rng)
+    kw = dict(lease_id=4, first_seq=seq, select=np.ones(1025, np.uint8), journal_dst_bytes="exact")
+    _check(cuda, run, b, kw, phases=PHASES)
+    _check(cuda, C.run(), C.batch(), dict(C.KW, select=np.ones(10, np.uint8),
+                                          journal_dst_bytes=179), phases=PHASES)   # refused
+
+
+def test_state(cuda):
+    import torch
+    rng = np.random.default_rng(56)
+    host = rng.integers(0, 256, size=1 << 18, dtype=np.uint8)
+    arena = torch.from_numpy(host).to(cuda)
+    lens = rng.integers(1, 1025, size=3001).astype(np.uint32)
+    offs = (rng.random(lens.size) * (host.size - 1100)).astype(np.int64)
+    d_off, d_len = _t(cuda, offs, np.int64), _t(cuda, lens, np.uint32)
+    qkeys, guids = random_meta(rng, 30)
+    run, pairs, seq = _messages(1025)
+    b = _batch(list(pairs[:300]))
+    kw = dict(lease_id=4, first_seq=seq, journal_dst_bytes="exact")
+    s = _side_stream(cuda)
+
+    def records():
+        return (last_launch(cuda.index, s, offsets=True), last_copy(cuda.index, s),
+                last_put_pack(cuda.index, s), last_records_pack(cuda.index, s),
+                last_put_unpack(cuda.index, s), last_records_unpack(cuda.index, s),
+                last_journal_select(cuda.index, s), last_storage_apply(cuda.index, s),
+                last_storage_pack(cuda.index, s), last_push_pack(cuda.index, s),
+                last_rollover(cuda.index, s))
+    with torch.cuda.stream(s):
+        # none yet on s
+        assert last_confirm_records(cuda.index, s) == M.refused_result(M.Refusal(0, 0), 0)
+        Crc32c.calculate_batch(arena, d_off, d_len, stream=s)
+        dst, jour, _, _, _ = pack_records(
+            arena, d_off[:30], d_len[:30], _t(cuda, qkeys, np.uint8), _t(cuda, guids, np.uint8),
+            file_key=b"\x11\x22\x33\x44\x55", lease_id=3, first_seq=2, data_file_pos=40, stream=s)
+        select_records(jour, data_file_bytes=40 + dst.numel(), stream=s)
+        rollover_records(jour, dst, data_file_pos=40, new_data_file_pos=40, stream=s)
+        pack_storage_events(jour, dst, journal_pos=JH, data_file_pos=40, partition_id=1, stream=s)
+        pack_push_events(jour, dst, data_file_pos=40,
+                         queue_ids=_t(cuda, np.arange(30), np.int32), stream=s)
+        before = records()
+        _check(cuda, run, b, kw, stream=s)
+        _check(cuda, run, b, kw, stream=s, sync=False)
+        _check(cuda, run, b, dict(kw, journal_dst_bytes=100), stream=s)   # a refused one
+        _check(cuda, run, b, dict(kw, journal_dst_bytes=None), stream=s)  # a size-only one
+        assert records() == before
+        out = Crc32c.calculate_batch(arena, d_off, d_len, stream=s)
+    s.synchronize()
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), P.host_crcs(host, offs, lens))
+
+
+# ---- the pipeline ------------------------------------------------------------
+
+def test_a_messages_whole_life_on_one_device(cuda):
+    # pack_records(ref_counts=2) -> pack_push_events -> the GUIDs read back by
+    # PushMessageIterator -> ConfirmEventBuilder -> confirm_arrays ->
+    # confirm_records twice, once per app -> pack_storage_events over the appended
+    # records -> apply_events on a replica -> select_records selects nothing ->
+    # rollover_records(keep=select, FOLLOW): an empty run and its sync point
+    import torch
+    rng = np.random.default_rng(19)
+    n = 200
+    lens = rng.integers(1, 301, size=n).astype(np.uint32)
+    soff = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    src = rng.integers(0, 256, size=int(lens.sum()), dtype=np.uint8)
+    qkeys, guids = random_meta(rng, n)
+    qkeys[:] = np.frombuffer(KEYS[0], np.uint8)
+    w = S.PartitionWriter(lease_id=7, partition_id=2)
+    w.queue_op(S.OP_CREATION, KEYS[0])
+    head = _t(cuda, np.frombuffer(w.recs[0], np.uint8).copy(), np.uint8)
+    data, jour, _, _, _ = pack_records(
+        _t(cuda, src, np.uint8), _t(cuda, soff, np.int64), _t(cuda, lens, np.uint32),
+        _t(cuda, qkeys, np.uint8), _t(cuda, guids, np.uint8), file_key=b"\x11\x22\x33\x44\x55",
+        lease_id=7, first_seq=2, data_file_pos=40,
+        ref_counts=_t(cuda, np.full(n, 2), np.uint32))
+    journal = torch.cat([head, jour])
+    # delivery, to one consumer of each app
+    records = _t(cuda, np.arange(1, n + 1, dtype=np.uint32), np.uint32)
+    push = pack_push_events(journal, data, data_file_pos=40, records=records,
+                            queue_ids=_t(cuda, np.full(n, 3), np.int32))
+    assert push.result["n_bad"] == 0
+    delivered = [m["guid"] for m in PushMessageIterator(push.events.cpu().numpy())]
+    assert delivered == [g.tobytes() for g in guids]
+    # the consumers' answers
+    apps = (b"\xA1" * 5, b"\xA2" * 5)
+    handles = {(3, 1): (KEYS[0], apps[0]), (3, 2): (KEYS[0], apps[1])}
+    seq = n + 2
+    appended, run0 = [], journal.cpu().numpy()
+    for sub in (1, 2):
+        builder = ConfirmEventBuilder()
+        for g in (delivered if sub == 1 else delivered[::-1]):
+            builder.append_message(3, sub, g)
+        g_, q_, a_ = confirm_arrays([builder.blob()], handles)
+        c = confirm_records(journal, _t(cuda, g_, np.uint8), _t(cuda, q_, np.uint8),
+                            app_keys=_t(cuda, a_, np.uint8), lease_id=7, first_seq=seq,
+                            timestamp=1000 + sub)
+        want = dict(n_confirms=n, n_written=n, n_confirm_records=n if sub == 1 else 0,
+                    n_deletions=0 if sub == 1 else n, n_not_found=0, journal_bytes=60 * n,
+                    next_seq=seq + n, refused_kind=0, refused_index=0)
+        assert c.result == want
+        left = c.left_out.cpu().numpy()
+        assert left[0] == 0 and (left[1:n + 1] == 2 - sub).all()
+        model = M.confirm_records(journal.cpu().numpy(), g_, q_, app_keys=a_, lease_id=7,
+                                  first_seq=seq, timestamp=1000 + sub)
+        assert np.array_equal(c.journal_dst.cpu().numpy(), model.journal)
+        seq = c.result["next_seq"]
+        appended.append(c.journal_dst)
+        journal = torch.cat([journal, c.journal_dst])   # the next call's run holds this one's output
+    assert journal.numel() == run0.size + 120 * n
+    # replication of what was appended, and a replica that applies it
+    tail = torch.cat(appended)
+    p = pack_storage_events(tail, data, journal_pos=JH + 60 * (n + 1), data_file_pos=40,
+                            partition_id=2)
+    assert p.result["n_msgs"] == 2 * n and p.result["n_data"] == 0
+    replica = apply_events(p.events, p.event_offsets, partition_id=2,
+                           journal_pos=JH + 60 * (n + 1), data_file_pos=40 + data.numel(),
+                           lease_id=7, seq=n + 1)
+    assert torch.equal(replica.journal, tail)
+    assert replica.result["head_seq"] == seq - 1
+    # nothing is outstanding: recovery selects nothing, on the device and on the host
+    w.seq = seq - 1
+    w.sync_point()
+    sync = _t(cuda, np.frombuffer(w.recs[-1], np.uint8).copy(), np.uint8)
+    journal = torch.cat([journal, sync])
+    n_records = journal.numel() // 60
+    select, sel = select_records(journal, data_file_bytes=40 + data.numel())
+    assert sel["recovery_rc"] == 0 and sel["n_selected"] == 0 and sel["n_deleted"] == n
+    assert not select.any()
+    files = w.files()
+    jfile = np.concatenate([files[0][:JH], journal.cpu().numpy()])
+    dfile = np.concatenate([files[1][:40], data.cpu().numpy()])
+    scan = S.scan_partition(jfile, dfile)
+    assert scan["recovery_rc"] == 0 and len(scan["record_offset"]) == 0
+    r = rollover_records(journal, data, data_file_pos=40, new_data_file_pos=40, keep=select,
+                         confirm_mode=S.CONFIRMS_FOLLOW_MESSAGES, sync_point=n_records - 1,
+                         timestamp=99)
+    assert (r.result["n_kept"], r.result["n_messages"], r.result["data_bytes"]) == (0, 0, 0)
+    assert r.journal_dst.numel() == 60 and r.journal_dst[0] >> 4 == 5
