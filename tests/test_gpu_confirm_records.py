@@ -21,6 +21,7 @@ from blazingmq_amd import storage as S
 import confirm_records_cases as C
 import confirm_records_model as M
 import device_views as V
+import join_collisions as J
 import put_pack_model as P
 from records_pack_model import random_meta
 
@@ -410,6 +411,66 @@ def test_the_destination_is_the_tail_of_the_runs_own_allocation(cuda):
                             first_seq=r.result["next_seq"])
     assert again.result["n_not_found"] == 300 and again.journal_dst.numel() == 0
     assert int((again.left_out.cpu() > 0).sum()) == 1025 - 300
+
+
+# ---- keys chosen to collide in the JoinTable (join_collisions.py) -------------
+
+def _crafted_kw(c, **more):
+    return dict(lease_id=c.info["lease_id"], first_seq=c.info["next_seq"],
+                journal_dst_bytes="exact", **more)
+
+
+def test_one_chain_across_the_tables_end(cuda):
+    """200 messages with one home eight slots before the table's end, CONFIRM
+    and DELETION records of the run among them (all three key extractions),
+    every queue-key byte 0x80 or more; 40 absent keys walk the whole chain and
+    10 from mid-chain.  Twice: the outputs are equal."""
+    c = J.confirm_chain()
+    pairs, names = J.confirm_chain_batch()
+    b = _batch(pairs)
+    m, host = _check(cuda, c.run, b, _crafted_kw(c))
+    assert isinstance(m, M.Confirmed)
+    assert (m.result["n_not_found"], m.result["n_written"]) == (50, 180)
+    assert host["target"][:len(pairs)].tolist() == [M.NONE if r is None else r for r in names]
+    _, again = _check(cuda, c.run, b, _crafted_kw(c))
+    assert sorted(again) == sorted(host)
+    assert all(np.array_equal(host[name], again[name]) for name in host)
+
+
+def test_a_chain_longer_than_a_block(cuda):
+    c = J.confirm_long()
+    order = J.long_order()
+    m, host = _check(cuda, c.run, _batch([J.split(c.keys[i]) for i in order]), _crafted_kw(c))
+    assert m.result["n_deletions"] == J.LONG
+    assert host["target"][:J.LONG].tolist() == (order + 1).tolist()
+
+
+@pytest.mark.parametrize("swapped", [False, True], ids=["low_first", "high_first"])
+def test_near_pairs_in_one_chain(cuda, swapped):
+    """Per key byte two messages that differ in bit 0x80 of it only, all 42 in
+    one chain: the first of each is confirmed, its twin is left alone."""
+    c = J.confirm_pairs(swapped)
+    firsts = [a for a, _ in c.info["pairs"]]
+    m, host = _check(cuda, c.run, _batch([J.split(a) for a in firsts]), _crafted_kw(c))
+    assert m.result["n_deletions"] == J.PAIRS == 21
+    assert host["target"][:J.PAIRS].tolist() == list(range(1, 43, 2))
+    assert host["left_out"][:43].tolist() == [0] + [0, 1] * J.PAIRS
+
+
+def test_a_duplicate_behind_a_chain(cuda):
+    c = J.confirm_duplicate()
+    m, _ = _check(cuda, c.run, _batch([J.split(c.keys[0])]), _crafted_kw(c))
+    assert m == M.Refusal(M.DUPLICATE_MESSAGE, J.BEHIND)
+
+
+def test_select_leaves_one_collider_in_the_table(cuda):
+    c = J.confirm_chain()
+    pairs, _ = J.confirm_chain_batch()
+    select, only = J.confirm_chain_select()
+    m, host = _check(cuda, c.run, _batch(pairs), _crafted_kw(c, select=select))
+    assert (m.result["n_not_found"], m.result["n_written"]) == (len(pairs) - 1, 1)
+    target = host["target"][:len(pairs)]
+    assert target[target != M.NONE].tolist() == [only]
 
 
 @pytest.mark.parametrize("sync", [True, False], ids=["sync", "async"])

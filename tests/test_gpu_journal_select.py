@@ -14,6 +14,7 @@ from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, last_copy, last_jo
                            last_records_unpack, pack_events, pack_records, select_records, synth,
                            unpack_events, unpack_records)
 from blazingmq_amd import storage as S
+import join_collisions as J
 import journal_select_cases as C
 import journal_select_model as M
 import put_pack_model as P
@@ -142,6 +143,68 @@ def test_queue_cap_counts_distinct_keys(cuda):
         assert res["refused_kind"] == 0
     _hold(cuda, j, d, queue_cap=3)
     _hold(cuda, j, d, queue_cap=1 << 40)
+
+
+# ---- keys chosen to collide in the two tables (join_collisions.py) ------------
+
+def _same(a, b):
+    return a[1] == b[1] and np.array_equal(a[0], b[0])
+
+
+def _all_three(res):
+    return res["recovery_rc"] == 0 and min(res["n_selected"], res["n_deleted"],
+                                            res["n_purged"]) > 0
+
+
+def test_many_queues_with_one_home(cuda):
+    """300 queue keys (every byte 0x80 or more) whose home is four slots before
+    the end of the 1,024 slots a queue_cap of 300 gives: one block's threads
+    publish one chain of 300 at once.  Queue DELETIONs with a re-CREATION,
+    PURGEs, an ADDITION and deleted messages among them.  Twice: equal."""
+    j, d, keys, _, _ = J.select_queues(True)
+    first = _hold(cuda, j, d, queue_cap=J.QUEUES)
+    assert _all_three(first[1])
+    assert _same(first, _hold(cuda, j, d, queue_cap=J.QUEUES))
+
+
+def test_many_queues_with_one_home_under_csl(cuda):
+    """The same keys without the queue DELETIONs, which the reference fails
+    under CSL: without CSL, with all 300 keys as queue_keys, with one of them
+    withheld (its CREATION is the host walk's failing record)."""
+    j, d, keys, _, _ = J.select_queues(False)
+    assert _all_three(_hold(cuda, j, d, queue_cap=J.QUEUES)[1])
+    assert _all_three(_hold(cuda, j, d, True, keys, queue_cap=J.QUEUES)[1])
+    short = keys[:J.WITHHELD] + keys[J.WITHHELD + 1:]
+    _, res = _hold(cuda, j, d, True, short, queue_cap=J.QUEUES)
+    assert res["recovery_rc"] == S.RC_INVALID_QUEUE_KEY and res["n_selected"] == 0
+
+
+@pytest.mark.parametrize("deletions", [True, False], ids=["queue_deletions", "csl"])
+def test_queue_cap_one_below_the_colliding_keys(cuda, deletions):
+    import torch
+    j, d, keys, _, _ = J.select_queues(deletions)
+    run = _dev(cuda, M.record_run(j)[0])
+    n = run.numel() // 60
+    kw = dict(data_file_bytes=d.size, with_csl=not deletions, queue_keys=() if deletions else keys)
+    with pytest.raises(BmqCrcError) as e:
+        select_records(run, queue_cap=J.QUEUES - 1, **kw)
+    assert e.value.rc == N.BMQCRC_EINVAL and "queue_cap" in str(e.value)
+    assert "BMQCRC_JSEL_TOO_MANY_QUEUES" in str(e.value)
+    res = last_journal_select(cuda.index, torch.cuda.current_stream(cuda))
+    assert res == dict(n_records=n, first_record=n, n_selected=0, n_deleted=0, n_purged=0,
+                       error_record=n, recovery_rc=0, refused_kind=1)
+
+
+def test_deletions_in_one_guid_chain(cuda):
+    """300 DELETION records in one chain across the end of the GUID table's
+    2,048 slots, the MESSAGE records they name walking it: two DELETIONs of one
+    GUID, a DELETION below its MESSAGE, one of no message, one GUID under two
+    MESSAGE records, and 30 undeleted messages that walk to the empty slot from
+    the chain's start and from mid-chain.  Twice: equal."""
+    j, d, _, _, _, _, want = J.select_guid_chain()
+    first = _hold(cuda, j, d)
+    assert first[1]["recovery_rc"] == 0 and {k: first[1][k] for k in want} == want
+    assert _same(first, _hold(cuda, j, d))
 
 
 def test_empty_run(cuda):

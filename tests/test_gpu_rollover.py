@@ -19,6 +19,7 @@ from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, apply_events, last
 from blazingmq_amd import storage as S
 from blazingmq_amd import synth
 import device_views as V
+import join_collisions as J
 import put_pack_model as P
 import put_unpack_model as PU
 import rollover_cases as C
@@ -427,6 +428,59 @@ def test_the_join_cases_of_the_model_test(cuda):
     run, d, keep, want = C.join_partition()
     kept = _follow(cuda, run, d, keep)
     assert np.flatnonzero(kept).tolist() == want
+
+
+# ---- keys chosen to collide in the JoinTable (join_collisions.py) -------------
+
+def _confirms_kept(cuda, c):
+    """Which CONFIRM records of the crafted run `c` are rolled, in run order;
+    the set restatement of the join (J.survivors) agrees."""
+    kept = _follow(cuda, c.run, c.data, c.info["keep"])[_types(c.run) == 2].tolist()
+    assert kept == J.survivors(c.run, c.info["keep"])
+    return kept
+
+
+def test_one_chain_across_the_tables_end(cuda):
+    """200 messages with one home eight slots before the table's end (every
+    queue-key byte 0x80 or more), every second one kept: the table holds a
+    chain of 100 that the dropped messages' CONFIRM records walk to its end.
+    Twice: the outputs are equal."""
+    c = J.rollover_chain()
+    kept = _confirms_kept(cuda, c)
+    assert len(kept) == J.CHAIN and sum(kept) == J.CHAIN // 2
+    kw = _kw(keep=c.info["keep"], confirm_mode=1)
+    (_, host), (_, again) = _check(cuda, c.run, c.data, kw), _check(cuda, c.run, c.data, kw)
+    assert sorted(again) == sorted(host)
+    assert all(np.array_equal(host[name], again[name]) for name in host)
+
+
+def test_a_chain_longer_than_a_block(cuda):
+    assert sum(_confirms_kept(cuda, J.rollover_long())) == J.LONG == 1100
+
+
+@pytest.mark.parametrize("swapped", [False, True], ids=["low_first", "high_first"])
+def test_near_pairs_in_one_chain(cuda, swapped):
+    """Per key byte two messages that differ in bit 0x80 of it only, the first
+    of each kept, all 21 kept ones in one chain: the twin's CONFIRM record
+    meets its twin in the table and is dropped."""
+    c = J.rollover_pairs(swapped)
+    kept = _confirms_kept(cuda, c)
+    assert len(kept) == 2 * J.PAIRS and sum(kept) == J.PAIRS == 21
+    confirms = np.asarray(c.run).reshape(-1, 60)[_types(c.run) == 2]
+    assert {r[32:48].tobytes() + r[22:27].tobytes() for r in confirms[kept]} == \
+        {first for first, _ in c.info["pairs"]}
+
+
+def test_a_duplicate_behind_a_chain(cuda):
+    c = J.rollover_duplicate()
+    m, _ = _check(cuda, c.run, c.data, _kw(keep=c.info["keep"], confirm_mode=1))
+    assert m.result["n_messages"] == J.BEHIND + 1 and m.result["n_kept"] == J.BEHIND + 3
+
+
+def test_keep_leaves_one_collider_in_the_table(cuda):
+    c = J.rollover_chain(137)
+    kept = _confirms_kept(cuda, c)
+    assert sum(kept) == 1 and c.info["n_kept_messages"] == 1
 
 
 # ---- verify on rollover ------------------------------------------------------
