@@ -23,6 +23,7 @@ import confirm_records_model as M
 import device_views as V
 import join_collisions as J
 import put_pack_model as P
+import test_grid_regimes as G
 from records_pack_model import random_meta
 
 pytestmark = pytest.mark.gpu
@@ -144,20 +145,30 @@ def _untouched(name, a):
     return bool((a == (CANARY[name][1] if name in CANARY else SENTINEL)).all())
 
 
-def _check(cuda, run, batch, kw, sync=True, stream=None, skip=(), phases=None):
+def _model(run, batch, kw):
+    """M.confirm_records' answer to the call `kw` describes ("exact": size only)."""
+    mkw = {k: kw.get(k) for k in ("lease_id", "first_seq", "select", "journal_dst_bytes")}
+    mkw["timestamp"] = kw.get("timestamp", 0)
+    if mkw["journal_dst_bytes"] == "exact":
+        mkw["journal_dst_bytes"] = None
+    return M.confirm_records(run, **{k: batch.get(k) for k in BATCH}, **mkw)
+
+
+def _check(cuda, run, batch, kw, sync=True, stream=None, skip=(), phases=None, model=None):
     """The call against the model: a refusal identical and nothing written, or
     every destination byte, array entry and result field.  `journal_dst_bytes`
     "exact" is what the model says the call writes, None a size-only call.
-    Returns (model, host)."""
+    `model` is _model's answer to this very call when the caller has it already
+    (a size-only call's answer serves for "exact" and the other way round: only
+    DST_TOO_SMALL looks at the size); the model is not run then.  Returns
+    (model, host)."""
     kw = dict(kw)
-    mkw = {k: kw.get(k) for k in ("lease_id", "first_seq", "select", "journal_dst_bytes")}
-    mkw["timestamp"] = kw.get("timestamp", 0)
-    mbatch = {k: batch.get(k) for k in BATCH}
+    sized = model if model is not None else \
+        _model(run, batch, kw) if kw.get("journal_dst_bytes") == "exact" else None
     if kw.get("journal_dst_bytes") == "exact":
-        sized = M.confirm_records(run, **mbatch, **dict(mkw, journal_dst_bytes=None))
-        kw["journal_dst_bytes"] = mkw["journal_dst_bytes"] = \
+        kw["journal_dst_bytes"] = \
             sized.result["journal_bytes"] if isinstance(sized, M.Confirmed) else 600
-    m = M.confirm_records(run, **mbatch, **mkw)
+    m = model if model is not None else _model(run, batch, kw)
     rc, err, res, host = _raw(cuda, run, batch, kw, sync=sync, stream=stream, skip=skip,
                               phases=phases)
     n = len(batch["guids"]) // 16
@@ -227,9 +238,9 @@ def test_batch_sizes_against_1025_messages(cuda, n):
 
 
 @functools.lru_cache(maxsize=None)
-def _mixed(n=3000, seed=21):
+def _mixed(n=3000, seed=21, refs=3):
     """(run of n records of every type, the next sequence number): messages of
-    refCount 1..3 in four queues, CONFIRM records (every fourth AUTO_CONFIRMED)
+    refCount 1..`refs` in four queues, CONFIRM records (every fourth AUTO_CONFIRMED)
     and DELETION records of earlier and of LATER messages, QUEUE_OP and
     JOURNAL_OP records.  Shared, never modified."""
     rng = np.random.default_rng(seed)
@@ -240,7 +251,7 @@ def _mixed(n=3000, seed=21):
         if roll < 5 or not msgs:
             key = KEYS[int(rng.integers(0, 4))]
             guid = (0x77000000 + len(msgs)).to_bytes(16, "big")
-            w.message(b"", key, guid=guid, ref_count=int(rng.integers(1, 4)))
+            w.message(b"", key, guid=guid, ref_count=int(rng.integers(1, refs + 1)))
             msgs.append((guid, key))
         elif roll < 7:
             k += 1
@@ -262,11 +273,11 @@ def _mixed(n=3000, seed=21):
 
 
 @functools.lru_cache(maxsize=None)
-def _mixed_messages():
+def _mixed_messages(n=3000, seed=21, refs=3):
     """The mixed run's MESSAGE records as (guid, key, references left, named by
     a DELETION record), the third by the model's own recovery (a call with one
     confirm that names nothing)."""
-    run, seq = _mixed()
+    run, seq = _mixed(n, seed, refs)
     left = M.confirm_records(run, **_batch([(b"\x01" * 16, KEYS[0])], plain=True), lease_id=9,
                              first_seq=seq).left_out
     recs = run.reshape(-1, 60)
@@ -511,6 +522,178 @@ def test_a_violation_in_the_last_record_of_the_last_block_and_in_the_last_confir
     m, _ = _check(cuda, run2, b, dict(lease_id=4, first_seq=seq2, journal_dst_bytes=60 * 1025 - 1),
                   sync=sync)
     assert m == M.Refusal(M.DST_TOO_SMALL, 1024)
+
+
+# ---- past one tile per block, past one wave of block sums, past the frame grid
+# (test_grid_regimes.py names the regimes and pins the sizes) ---------------------
+
+def _unknown(rng, count, key):
+    """`count` pairs of GUIDs no run here holds (no zero byte: the runs' GUIDs
+    are small integers) under `key`."""
+    return [(g.tobytes(), key) for g in rng.integers(1, 256, (count, 16), dtype=np.uint8)]
+
+
+def _shuffled(rng, pairs):
+    return [pairs[i] for i in rng.permutation(len(pairs))]
+
+
+@functools.lru_cache(maxsize=None)
+def _many_records_case():
+    """(run, kw, batch): N_TILES mixed records, two tiles per record block, and
+    about 40,000 confirms -- of three messages in eight, never more of one than it
+    has left -- among them 1,100 unknown GUIDs and 1,100 messages a DELETION
+    record names (test_mixed_records_over_three_blocks adds 40 of each: at this
+    size that leaves a call without `select` under 1,000 not found)."""
+    run, seq = _mixed(G.N_TILES, 23)
+    msgs = _mixed_messages(G.N_TILES, 23)
+    rng = np.random.default_rng(6)
+    pairs = []
+    for g, k, left, _ in msgs:
+        if rng.random() < 3 / 8:
+            pairs += [(g, k)] * int(rng.integers(0, left + 1))
+    pairs += _unknown(rng, 1100, KEYS[1])
+    pairs += [(g, k) for g, k, _, dead in msgs if dead][:1100]
+    kw = dict(lease_id=9, first_seq=seq, timestamp=5, journal_dst_bytes="exact")
+    return run, kw, _batch(_shuffled(rng, pairs), rng)
+
+
+@functools.lru_cache(maxsize=None)
+def _many_confirms_case():
+    """(run, kw, batch): N_FEW mixed records of refCount 1..30 in 40 blocks, and
+    N_TILES confirms in 129 blocks of two tiles: every message confirmed up to
+    as often as it has references left, 1,100 messages a DELETION record names,
+    unknown GUIDs for the rest."""
+    run, seq = _mixed(G.N_FEW, 24, 30)
+    msgs = _mixed_messages(G.N_FEW, 24, 30)
+    rng = np.random.default_rng(7)
+    pairs = []
+    for g, k, left, _ in msgs:
+        pairs += [(g, k)] * int(rng.integers(0, left + 1))
+    pairs += [(g, k) for g, k, _, dead in msgs if dead][:1100]
+    assert 100000 < len(pairs) < G.N_TILES - 50000
+    pairs += _unknown(rng, G.N_TILES - len(pairs), KEYS[2])
+    kw = dict(lease_id=9, first_seq=seq, timestamp=5, journal_dst_bytes="exact")
+    return run, kw, _batch(_shuffled(rng, pairs), rng)
+
+
+@functools.lru_cache(maxsize=None)
+def _many_confirms_model():
+    run, kw, b = _many_confirms_case()
+    return _model(run, b, kw)
+
+
+def _not_vacuous(m):
+    assert isinstance(m, M.Confirmed)
+    assert min(m.result["n_confirm_records"], m.result["n_deletions"],
+               m.result["n_not_found"]) > 1000, m.result
+    assert int((m.left_out != 0).sum()) > 1000
+
+
+@pytest.mark.parametrize("select", [None, "second"])
+def test_two_tiles_of_records_per_block_and_confirms_past_the_frames_dwords(cuda, select):
+    """Records in regime D (stage()'s second tile, k_cfm_join's record loop a
+    second time), confirms in regime A (the frame's dword loop a second time);
+    the record grid is the wider one in k_cfm_join."""
+    run, kw, b = _many_records_case()
+    n = len(b["guids"]) // 16
+    assert G.regime(run.size // 60)[:2] == (129, 2048)
+    assert G.regime(n).dwords_past_grid and G.regime(n).nblocks < 64
+    sel = (np.arange(G.N_TILES) % 2).astype(np.uint8) if select else None
+    want = _model(run, b, dict(kw, select=sel))
+    _not_vacuous(want)
+    _check(cuda, run, b, dict(kw, select=sel), model=want)
+
+
+def test_two_tiles_of_confirms_per_block_against_few_records(cuda):
+    """Confirms in regime D (layout_count's carry and block_prefix's cross-wave
+    leg over the confirms), records in 40 blocks: cnblocks is far above nblocks
+    in k_cfm_join."""
+    run, kw, b = _many_confirms_case()
+    assert len(b["guids"]) // 16 == G.N_TILES and run.size // 60 == G.N_FEW
+    assert G.regime(G.N_TILES)[:2] == (129, 2048) and G.regime(G.N_FEW).nblocks == 40
+    want = _many_confirms_model()
+    _not_vacuous(want)
+    _check(cuda, run, b, kw, model=want)
+
+
+def test_records_and_confirms_past_the_frame_grid(cuda):
+    """Both in regime E: every one of k_cfm_frame's three loops takes a second
+    step (confirm and record 524,288 are thread 0's).  Every confirm deletes.
+    The size-only call reports what the full call reports."""
+    run, pairs, seq = _messages(G.N_FRAME)
+    assert run.size // 60 == G.N_FRAME and G.regime(G.N_FRAME).units_past_grid
+    rng = np.random.default_rng(8)
+    b = _batch(_shuffled(rng, pairs), rng)
+    kw = dict(lease_id=4, first_seq=seq, journal_dst_bytes="exact")
+    want = _model(run, b, kw)
+    assert want.result["n_deletions"] == G.N_FRAME and not want.left_out.any()
+    full, host = _check(cuda, run, b, kw, model=want)
+    assert host["left_out"].size == G.N_FRAME + GUARD
+    sized, _ = _check(cuda, run, b, dict(kw, journal_dst_bytes=None), model=want)
+    assert sized.result == full.result
+
+
+def _over_confirmed_by_the_last_confirm_of_the_last_block():
+    """N_TILES confirms of which all but three name nothing; message 3 of
+    1,025 (refCount 1) is confirmed in the second tile of block 0 and again by
+    the last confirm of the last block: the first of the two is named."""
+    run, pairs, seq = _messages(1025)
+    rng = np.random.default_rng(9)
+    chosen = _unknown(rng, G.N_TILES, KEYS[0])
+    chosen[1024 + 7] = chosen[-1] = pairs[3]
+    chosen[2048 + 1] = pairs[4]
+    kw = dict(lease_id=4, first_seq=seq, journal_dst_bytes="exact")
+    return run, _batch(chosen, rng), kw, M.Refusal(M.OVER_CONFIRMED, 1024 + 7)
+
+
+def _duplicate_message_in_two_tiles_of_one_block():
+    """The first MESSAGE record of block 3 of N_TILES records again in the
+    block's second tile."""
+    run, kw, _ = _many_records_case()
+    recs = np.array(run).reshape(-1, 60)
+    lo = 3 * G.regime(G.N_TILES).per_block
+    first = lo + int(np.flatnonzero(recs[lo:lo + 1024, 0] >> 4 == 1)[0])
+    twin = lo + 1024 + 11
+    recs[twin, :2], recs[twin, 20:56] = recs[first, :2], recs[first, 20:56]
+    b = _batch(_unknown(np.random.default_rng(10), 1025, KEYS[3]), plain=True)
+    return recs.reshape(-1), b, kw, M.Refusal(M.DUPLICATE_MESSAGE, first)
+
+
+def _destination_one_record_short():
+    """The last of N_TILES confirms that writes a record, behind the sums of
+    129 blocks of two tiles, is the one that does not fit."""
+    run, kw, b = _many_confirms_case()
+    want = _many_confirms_model()
+    last = int(np.flatnonzero(want.new_index != M.NONE)[-1])
+    assert last > G.N_TILES - 1024          # in the last block
+    short = dict(kw, journal_dst_bytes=want.result["journal_bytes"] - 60)
+    return run, b, short, M.Refusal(M.DST_TOO_SMALL, last)
+
+
+def _null_key_in_a_second_tile_above_a_reason():
+    """A null GUID in the second tile of confirm block 5 and a reason of 2 at
+    confirm 100: NULL_KEY is the lower kind."""
+    run, kw, b = _many_confirms_case()
+    at = 5 * G.regime(G.N_TILES).per_block + 1024 + 9
+    bad = dict(b, guids=b["guids"].copy(), reasons=b["reasons"].copy())
+    bad["guids"][16 * at:16 * at + 16] = 0
+    bad["reasons"][100] = 2
+    return run, bad, kw, M.Refusal(M.NULL_KEY, at)
+
+
+@pytest.mark.parametrize("case", [
+    _over_confirmed_by_the_last_confirm_of_the_last_block,
+    _duplicate_message_in_two_tiles_of_one_block, _destination_one_record_short,
+    _null_key_in_a_second_tile_above_a_reason], ids=lambda f: f.__name__.strip("_"))
+def test_refusals_across_tiles_and_blocks(cuda, case):
+    """What the model refuses past one tile per block, synchronous and
+    asynchronous, with nothing written."""
+    run, b, kw, expected = case()
+    want = _model(run, b, kw)
+    assert want == expected
+    for sync in (True, False):
+        m, _ = _check(cuda, run, b, kw, sync=sync, model=want)
+        assert m == expected
 
 
 def test_every_base_pointer_at_the_smallest_alignment_the_abi_permits(cuda):

@@ -9,6 +9,7 @@ import pytest
 
 import device_views as V
 import oracle
+import test_grid_regimes as G
 from blazingmq_amd import BmqCrcError, Crc32c, _native as N, last_copy, last_launch
 
 pytestmark = pytest.mark.gpu
@@ -368,3 +369,41 @@ def test_long_runs_of_empty_messages(cuda):
     seeds = _seeds(rng, lens.size)
     got, _ = _check(cuda, src, soff, lens, doff, int(doff[-1] + lens[-1]) + 16, seeds)
     assert np.array_equal(got[lens == 0], seeds[lens == 0])
+
+
+def _two_tiles_per_block():
+    # N_TILES messages of 0..300 bytes with runs of 600 empties (one across a
+    # tile's end, one across a block's, one at the batch's end); sources at
+    # index mod 16; a third of the destinations end to end with their
+    # predecessor (neighbours share 16-byte pieces), the others at the next
+    # offset with the misalignment a permutation gives them
+    rng = np.random.default_rng(34)
+    n = G.N_TILES
+    lens = rng.integers(0, 301, size=n)
+    for at in (700, 2048 - 300, 100 * 2048 + 1024 - 300, n - 600):
+        lens[at:at + 600] = 0
+    smis = np.arange(n) % 16
+    dmis = rng.permutation(n) % 16
+    packed = rng.random(n) < 1 / 3
+    soff, doff, s, d = np.zeros(n, np.int64), np.zeros(n, np.int64), 0, 7
+    for i, ln in enumerate(lens.tolist()):
+        s = (s + 15) // 16 * 16 + int(smis[i])
+        if not packed[i]:
+            d += (int(dmis[i]) - d) % 16
+        soff[i], doff[i] = s, d
+        s += ln
+        d += ln
+    src = rng.integers(0, 256, size=s + 16, dtype=np.uint8)
+    return src, soff, lens, doff, d + 16, _seeds(rng, n)
+
+
+def test_two_tiles_per_block_called_directly(cuda):
+    """256 * 1,024 + 1,025 messages: the copy's own count and scan kernels run
+    two tiles per block (layout_split gives 129 blocks of 2,048), which the
+    suite reached through the packers only."""
+    import torch
+    assert G.regime(G.N_TILES)[:2] == (129, 2048)
+    src, soff, lens, doff, size, seeds = _two_tiles_per_block()
+    assert set((doff % 16).tolist()) == set(range(16)) and int((lens == 0).sum()) > 2400
+    _check(cuda, src, soff, lens, doff, size, seeds)
+    assert last_copy(cuda.index, torch.cuda.current_stream(cuda)) == (G.N_TILES, 0, G.N_TILES)

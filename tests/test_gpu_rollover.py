@@ -24,6 +24,7 @@ import put_pack_model as P
 import put_unpack_model as PU
 import rollover_cases as C
 import rollover_model as M
+import test_grid_regimes as G
 from records_pack_model import random_meta
 
 pytestmark = pytest.mark.gpu
@@ -144,20 +145,28 @@ def _untouched(name, a):
     return bool((a == (CANARY[name] if name in CANARY else SENTINEL)).all())
 
 
-def _check(cuda, run, data, kw, sync=True, stream=None, skip=(), phases=None):
+def _check(cuda, run, data, kw, sync=True, stream=None, skip=(), phases=None, model=None):
     """The call against the model: a refusal identical and nothing written, or
     every destination byte, array entry and result field.  `dst_bytes` /
-    `journal_dst_bytes` None is the exact size.  Returns (model, host)."""
+    `journal_dst_bytes` None is the exact size.  `model` is M.rollover's answer
+    to this very call when the caller has it already (a size left None: its
+    answer with room to spare); the model is not run then.  Returns (model,
+    host)."""
     kw = dict(kw)
     exact = [k for k in ("dst_bytes", "journal_dst_bytes") if kw[k] is None]
-    if exact:
+    if model is not None:
+        for k in exact:
+            kw[k] = model.result[{"dst_bytes": "data_bytes",
+                                  "journal_dst_bytes": "journal_bytes"}[k]] \
+                if isinstance(model, M.Rolled) else 4096
+    elif exact:
         big = dict(kw)
         big.update({k: 1 << 40 for k in exact})
         m = M.rollover(run, data, crc32c=CRC, **big)
         for k in exact:
             kw[k] = m.result[{"dst_bytes": "data_bytes", "journal_dst_bytes": "journal_bytes"}[k]] \
                 if isinstance(m, M.Rolled) else 4096
-    m = M.rollover(run, data, crc32c=CRC, **kw)
+    m = model if model is not None else M.rollover(run, data, crc32c=CRC, **kw)
     rc, err, res, host = _raw(cuda, run, data, kw, sync=sync, stream=stream, skip=skip,
                               phases=phases)
     n = len(run) // 60
@@ -183,13 +192,13 @@ def _check(cuda, run, data, kw, sync=True, stream=None, skip=(), phases=None):
 
 
 @functools.lru_cache(maxsize=None)
-def _records(n, seed=7, options=False, lengths=None):
+def _records(n, seed=7, options=False, lengths=None, confirm_every=3):
     """(record run of n records, DATA file): two queues' CREATIONs, then
     messages of 0..40 bytes (or of `lengths`, in turn) alternating between the
-    queues, every third followed by its CONFIRM, every ninth by its DELETION
-    too, in front of every 16th a queue ADDITION, PURGE or DELETION or a sync
-    point; with `options` DATA headers of 3 and 5 words with 0..2 option words.
-    Shared, never modified."""
+    queues, every third (every `confirm_every`-th) followed by its CONFIRM,
+    every third of those by its DELETION too, in front of every 16th a queue
+    ADDITION, PURGE or DELETION or a sync point; with `options` DATA headers of
+    3 and 5 words with 0..2 option words.  Shared, never modified."""
     rng = np.random.default_rng(seed)
     w = S.PartitionWriter(lease_id=4, partition_id=1)
     w.queue_op(S.OP_CREATION, QK)
@@ -220,9 +229,9 @@ def _records(n, seed=7, options=False, lengths=None):
                           bytes(rng.integers(0, 256, size=lead - 8, dtype=np.uint8)) + app +
                           bytes([pad]) * pad)
             w.dpos = before + total
-        if k % 3 == 0 and len(w.recs) < n:
+        if k % confirm_every == 0 and len(w.recs) < n:
             w.confirm(guid, key)
-        if k % 9 == 0 and len(w.recs) < n:
+        if k % (3 * confirm_every) == 0 and len(w.recs) < n:
             w.deletion(guid, key)
         k += 1
     j, d = w.files()
@@ -380,6 +389,173 @@ def test_a_violation_in_the_last_record_of_the_last_block(cuda):
     keep[last] = 0
     m, _ = _check(cuda, bad, d, _kw(keep=keep))
     assert isinstance(m, M.Rolled)
+
+
+# ---- past one tile per block, past one wave of block sums, past the frame grid
+# (test_grid_regimes.py names the regimes and pins the sizes) ---------------------
+
+@functools.lru_cache(maxsize=None)
+def _large(n):
+    """The run of n records the tests below share, and its DATA file: the
+    first n records of one run of N_FRAME, written once (seconds of host time,
+    more than every device call here together), with the whole DATA file (a
+    shorter run leaves its end unread).  Varied DATA
+    record sizes (`options`), so that a shifted position shows; a CONFIRM behind
+    every seventh message only, so that with every second record kept more than
+    100,000 of N_TILES records are kept MESSAGE records."""
+    run, d = _records(G.N_FRAME, seed=289, options=True, confirm_every=7)
+    return run[:60 * n], d
+
+
+def _large_kw(n, how, mode, sync=True, window=False):
+    run, _ = _large(n)
+    return _kw(keep=_keep(run, how) if how else None, confirm_mode=mode,
+               sync_point=_last_sync(run) if sync else None,
+               data_file_pos=40 if window else 0, new_data_file_pos=4096)
+
+
+@functools.lru_cache(maxsize=None)
+def _large_model(n, how, mode, sync=True, window=False):
+    """The model's answer to _large_kw's call with room to spare, run once."""
+    run, d = _large(n)
+    kw = dict(_large_kw(n, how, mode, sync, window), dst_bytes=1 << 40, journal_dst_bytes=1 << 40)
+    return M.rollover(run, d[40:] if window else d, crc32c=CRC, **kw)
+
+
+def _every_whole_tile_block_holds_every_type(run):
+    """Every layout block that owns a whole tile or more (N_WAVES leaves its
+    last block one record) holds records of all five types."""
+    t = _types(run)
+    r = G.regime(t.size)
+    for b in range(r.nblocks):
+        mine = t[b * r.per_block:(b + 1) * r.per_block]
+        assert mine.size < 1024 or set(mine.tolist()) == {1, 2, 3, 4, 5}, b
+
+
+def _confirms_kept_and_dropped(run, m):
+    confirms = _types(run) == 2
+    kept = m.new_index[confirms] != M.NOT_KEPT
+    return int(kept.sum()), int((~kept).sum())
+
+
+@pytest.mark.parametrize("n,mode", [(G.N_WAVES, 1), (G.N_TILES, 0), (G.N_TILES, 1),
+                                    (G.N_FRAME, 1)],
+                         ids=["waves-follow", "tiles-as_kept", "tiles-follow", "frame-follow"])
+def test_every_second_record_kept_past_one_tile_per_block(cuda, n, mode):
+    """N_WAVES: the frame's dword loop steps twice and the block sums of both
+    prefixes cross waves.  N_TILES: two tiles per block -- stage()'s second
+    tile, both layout_count carries, the join over two tiles.  N_FRAME: three
+    tiles, and the frame's per-record loop steps twice (record 524,288)."""
+    run, d = _large(n)
+    r = G.regime(n)
+    assert r.dwords_past_grid and r.cross_wave
+    assert (r.per_block > 1024) == (n >= G.N_TILES) and r.units_past_grid == (n == G.N_FRAME)
+    _every_whole_tile_block_holds_every_type(run)
+    want = _large_model(n, "second", mode)
+    assert isinstance(want, M.Rolled) and want.result["n_bad"] == 0
+    if mode:
+        kept, dropped = _confirms_kept_and_dropped(run, want)
+        assert 10 * kept >= kept + dropped and 10 * dropped >= kept + dropped
+    if n == G.N_TILES:
+        assert want.result["n_messages"] > 100000
+    # (N_FRAME: record 524,288 is the only one of the frame's second step; a
+    # step not taken leaves the canaries in its new_index and out entries)
+    m, _ = _check(cuda, run, d, _large_kw(n, "second", mode), model=want)
+    assert m is want
+
+
+def test_all_256_blocks_of_one_tile_with_everything_kept(cuda):
+    run, d = _large(G.N_FULL)
+    assert G.regime(G.N_FULL)[:2] == (256, 1024)
+    _every_whole_tile_block_holds_every_type(run)
+    want = _large_model(G.N_FULL, "all", 0, sync=False)
+    assert want.result["n_messages"] == int((_types(run) == 1).sum()) > 100000
+    assert want.result["n_kept"] == int((_types(run) != 5).sum())
+    _check(cuda, run, d, _large_kw(G.N_FULL, "all", 0, sync=False), model=want)
+
+
+def test_a_window_over_two_tiles_per_block_with_no_keep_array(cuda):
+    run, d = _large(G.N_TILES)
+    want = _large_model(G.N_TILES, None, 0, window=True)
+    assert isinstance(want, M.Rolled) and want.result["n_messages"] > 100000
+    assert want.result["n_messages"] == int((_types(run) == 1).sum())
+    _check(cuda, run, d[40:], _large_kw(G.N_TILES, None, 0, window=True), model=want)
+
+
+def _refusal_in_the_second_tile():
+    """(a) the magic of record 1,024 + 5, in the second tile of block 0, and of
+    record 2,048 + 3, in the first tile of block 1: the lower one is named."""
+    run, d = _large(G.N_TILES)
+    bad = run.copy()
+    for i in (1024 + 5, 2048 + 3):
+        bad[60 * i + 59] ^= 0xFF
+    return bad, d, {}, M.Refusal(M.RECORD_HEADER, 1029)
+
+
+def _refusal_kinds_across_blocks():
+    """(b) a kept MESSAGE record's DATA record below record 100 (its last
+    padding byte 9: DATA_RECORD) and the header of record 200,001: the lower
+    kind wins over the lower index."""
+    run, d = _large(G.N_TILES)
+    victim = [i for i in range(1, 100, 2) if int(run[60 * i]) >> 4 == 1][3]
+    o = 8 * int.from_bytes(run[60 * victim + 32:60 * victim + 36].tobytes(), "big")
+    data = d.copy()
+    data[o + 4 * (int.from_bytes(d[o:o + 4].tobytes(), "big") & 0x1FFFFFFF) - 1] = 9
+    alone = M.rollover(run[:60 * 100], data, crc32c=CRC,
+                       **_kw(keep=_keep(run[:60 * 100], "second"), dst_bytes=1 << 40,
+                             journal_dst_bytes=1 << 40))
+    assert alone == M.Refusal(M.DATA_RECORD, victim)
+    bad = run.copy()
+    bad[60 * 200001 + 8:60 * 200001 + 12] = 0        # primaryLeaseId 0
+    return bad, data, {}, M.Refusal(M.RECORD_HEADER, 200001)
+
+
+def _refusal_in_the_last_record_of_the_last_block():
+    """(c) the magic of record n - 1, the 1,025th record of block 128."""
+    run, d = _large(G.N_TILES)
+    r = G.regime(G.N_TILES)
+    assert G.N_TILES - 1 - (r.nblocks - 1) * r.per_block == 1024
+    bad = run.copy()
+    bad[60 * (G.N_TILES - 1) + 59] ^= 0xFF
+    return bad, d, {}, M.Refusal(M.RECORD_HEADER, G.N_TILES - 1)
+
+
+def _journal_destination_one_record_short():
+    """(d) journal_dst one record short: the sync point behind the kept
+    records of all 129 blocks is what no longer fits, named as record n."""
+    run, d = _large(G.N_TILES)
+    want = _large_model(G.N_TILES, "second", 1)
+    short = dict(journal_dst_bytes=want.result["journal_bytes"] - 60,
+                 dst_bytes=want.result["data_bytes"])
+    return run, d, short, M.Refusal(M.DST_TOO_SMALL, G.N_TILES)
+
+
+def _data_destination_one_byte_short():
+    """(d) dst one byte short: the last kept MESSAGE record's DATA record ends
+    one byte past it."""
+    run, d = _large(G.N_TILES)
+    want = _large_model(G.N_TILES, "second", 1)
+    short = dict(journal_dst_bytes=want.result["journal_bytes"],
+                 dst_bytes=want.result["data_bytes"] - 1)
+    last = np.flatnonzero((_types(run) == 1) & (want.new_index != M.NOT_KEPT))[-1]
+    return run, d, short, M.Refusal(M.DST_TOO_SMALL, int(last))
+
+
+@pytest.mark.parametrize("case", [
+    _refusal_in_the_second_tile, _refusal_kinds_across_blocks,
+    _refusal_in_the_last_record_of_the_last_block, _journal_destination_one_record_short,
+    _data_destination_one_byte_short], ids=lambda f: f.__name__.strip("_"))
+def test_refusals_across_tiles_and_blocks(cuda, case):
+    """Over N_TILES records, every second kept, FOLLOW: what the model refuses,
+    synchronous and asynchronous, with nothing written."""
+    run, data, sizes, expected = case()
+    kw = dict(_large_kw(G.N_TILES, "second", 1), **sizes)
+    room = {k: kw[k] if kw[k] is not None else 1 << 40 for k in ("dst_bytes", "journal_dst_bytes")}
+    want = M.rollover(run, data, crc32c=CRC, **dict(kw, **room))
+    assert want == expected
+    for sync in (True, False):
+        m, _ = _check(cuda, run, data, kw, sync=sync, model=want)
+        assert m == expected
 
 
 # ---- the join ----------------------------------------------------------------

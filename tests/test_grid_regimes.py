@@ -1,0 +1,116 @@
+"""The sizes at which the device calls' shared grids change what they run, and
+the sizes the large GPU tests use to get there (no GPU needed).
+
+Every device call splits its units -- messages, records, confirms -- with
+layout_split (bmqcrc_host.cpp): at most kPackBlocks blocks of whole
+kPackThreads tiles each.  A frame kernel of kPackFrameBlocks x
+kPackFrameThreads threads then strides over 15 dwords per unit and over the
+units.  Above certain sizes the same code runs loops it never enters below:
+
+  A  15 n > frame grid     the frame kernels' dword loop takes a second step
+  B  more than 64 blocks   block_prefix's cross-wave leg (before += wsum[0][w])
+  C  kPackBlocks blocks    the whole layout grid, one tile each
+  D  per_block > one tile  stage()'s second tile, layout_count's carry from tile
+                           to tile inside a block
+  E  n > frame grid        the frame kernels' per-unit loops take a second step
+
+`layout_split` is restated here and the four constants are read from the text
+of bmqcrc_internal.h, so a changed constant fails this file instead of letting
+test_gpu_rollover.py, test_gpu_confirm_records.py and test_gpu_copy.py, which
+import the sizes below, quietly stop reaching their regimes."""
+import collections
+import os
+import re
+
+import pytest
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                      "blazingmq_amd", "csrc", "bmqcrc_internal.h")
+
+N_WAVES = 65537 + 1024          # A and B: 66 blocks of one tile
+N_FULL = 262144                 # C (A and B too): 256 blocks of one tile
+N_TILES = 256 * 1024 + 1025     # D: 129 blocks of two tiles
+N_FRAME = 524289                # E: 171 blocks of three tiles; unit 524,288 is frame thread 0's
+N_FEW = 40000                   # A alone: 40 blocks of one tile, one wave of block sums
+RECORD_DWORDS = 15              # kJournalRecordDwords: a journal record is 60 bytes
+
+Regime = collections.namedtuple(
+    "Regime", "nblocks per_block dwords_past_grid units_past_grid cross_wave")
+
+
+def constants():
+    """kPackThreads, kPackBlocks, kPackFrameThreads, kPackFrameBlocks and
+    kJournalRecordDwords as bmqcrc_internal.h spells them."""
+    with open(HEADER) as f:
+        text = f.read()
+    found = {}
+    for name in ("kPackThreads", "kPackBlocks", "kPackFrameThreads", "kPackFrameBlocks",
+                 "kJournalRecordDwords"):
+        m = re.findall(r"constexpr (?:int|uint32_t) %s = (\d+);" % name, text)
+        assert len(m) == 1, (name, m)
+        found[name] = int(m[0])
+    return found
+
+
+def layout_split(n, threads, blocks):
+    """(per_block, nblocks) as bmqcrc_host.cpp's layout_split gives them, n > 0."""
+    tiles = (n + threads - 1) // threads
+    nb = min(tiles, blocks)
+    tiles_per = (tiles + nb - 1) // nb
+    return tiles_per * threads, (tiles + tiles_per - 1) // tiles_per
+
+
+def regime(n):
+    """What a call over n units runs, by today's header."""
+    k = constants()
+    per_block, nblocks = layout_split(n, k["kPackThreads"], k["kPackBlocks"])
+    grid = k["kPackFrameThreads"] * k["kPackFrameBlocks"]
+    return Regime(nblocks, per_block, k["kJournalRecordDwords"] * n > grid, n > grid,
+                  nblocks > 64)
+
+
+def test_the_constants_the_sizes_were_derived_from():
+    assert constants() == dict(kPackThreads=1024, kPackBlocks=256, kPackFrameThreads=256,
+                               kPackFrameBlocks=2048, kJournalRecordDwords=RECORD_DWORDS)
+
+
+@pytest.mark.parametrize("n,want", [
+    (N_FEW, Regime(40, 1024, True, False, False)),
+    (N_WAVES, Regime(66, 1024, True, False, True)),
+    (N_FULL, Regime(256, 1024, True, False, True)),
+    (N_TILES, Regime(129, 2048, True, False, True)),
+    (N_FRAME, Regime(171, 3072, True, True, True)),
+], ids=["N_FEW", "N_WAVES", "N_FULL", "N_TILES", "N_FRAME"])
+def test_each_size_reaches_the_regime_it_claims(n, want):
+    assert regime(n) == want
+
+
+def test_the_first_size_of_every_regime():
+    # A: 15 n > 524,288
+    assert not regime(34952).dwords_past_grid and regime(34953).dwords_past_grid
+    # B: a 65th block, whose sum lies in the second wave of block_prefix
+    assert regime(65536) == Regime(64, 1024, True, False, False)
+    assert regime(65537) == Regime(65, 1024, True, False, True)
+    # C and D: the last size with one tile per block, the first with two
+    assert regime(N_FULL - 1023)[:2] == (256, 1024)
+    assert regime(N_FULL)[:2] == (256, 1024)
+    assert regime(N_FULL + 1)[:2] == (129, 2048)
+    # E: unit 524,288 is the first that a frame thread reaches in its second step
+    assert not regime(N_FRAME - 1).units_past_grid and regime(N_FRAME).units_past_grid
+    assert regime(N_FRAME - 1)[:2] == (256, 2048) and regime(N_FRAME)[:2] == (171, 3072)
+
+
+def test_every_block_of_the_large_sizes_owns_units():
+    # no empty block, and the last block ends the call: a refusal "in the last
+    # record of the last block" is record n - 1 of block nblocks - 1
+    for n in (N_FEW, N_WAVES, N_FULL, N_TILES, N_FRAME):
+        r = regime(n)
+        assert (r.nblocks - 1) * r.per_block < n <= r.nblocks * r.per_block
+
+
+def test_layout_split_below_one_grid_of_tiles():
+    # what the older tests run at: their sizes stay in the first regime
+    assert layout_split(1, 1024, 256) == (1024, 1)
+    assert layout_split(1025, 1024, 256) == (1024, 2)
+    assert layout_split(3000, 1024, 256) == (1024, 3)
+    assert not regime(3000).dwords_past_grid
