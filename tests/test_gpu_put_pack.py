@@ -3,6 +3,7 @@ The oracle throughout is the concatenated PutEventBuilder(defer_crc=False)
 bytes plus host CRCs: every check compares the packed bytes byte for byte,
 `out`, `event_offsets`, and the canary behind the total."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -10,7 +11,10 @@ import pytest
 from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, last_copy, last_launch,
                            last_put_pack, pack_events)
 import device_views as V
-from put_pack_model import host_crcs, layout, model_bytes, oracle_events, random_meta
+import pack_pool
+import test_grid_regimes as G
+from put_pack_model import (EVT, HDR, host_crcs, layout, model_bytes, model_bytes_fast,
+                            oracle_events, pad_of, pool_crcs, pooled_crcs, random_meta)
 
 pytestmark = pytest.mark.gpu
 
@@ -66,22 +70,30 @@ def _check_placed(cuda, place, src, soff, lens, qids, guids, flags, ef, slack, m
     return host[:total]
 
 
-def _check(cuda, src, soff, lens, qids, guids, flags=None, ef=None, slack=64, phases=None, **kw):
+def _check(cuda, src, soff, lens, qids, guids, flags=None, ef=None, slack=64, phases=None,
+           model=None, inputs=None, **kw):
     """One pack into a canary destination against the oracle.  Returns the
     packed bytes (host).  `phases` maps every pointer of the call (src,
     src_offsets, lengths, queue_ids, guids, flags, event_first, dst,
     event_offsets, out) to the phase of its base: the call then goes through
     the raw entry point and the sentinel margins around every buffer are
-    checked; None: the wrapper, every buffer at the start of an allocation."""
+    checked; None: the wrapper, every buffer at the start of an allocation.
+    `model` is (expected bytes, event offsets, CRCs) of this very call when the
+    caller has them already: the oracle and the host CRCs are not run then.
+    `inputs` is _inputs' answer for these arguments, already on the device."""
     import torch
     if phases is not None:
         return _check_placed(cuda, V.Placer(cuda, phases), src, soff, lens, qids, guids, flags, ef,
                              slack, **kw)
     # (n = 0 writes nothing, not even an empty event)
-    exp = np.concatenate(oracle_events(src, soff, lens, qids, guids, flags, ef)) if len(lens) \
-        else np.zeros(0, np.uint8)
+    if model is not None:
+        exp, want_ev, want_crcs = model
+    else:
+        exp = np.concatenate(oracle_events(src, soff, lens, qids, guids, flags, ef)) \
+            if len(lens) else np.zeros(0, np.uint8)
+        want_ev, want_crcs = layout(lens, ef)[1], host_crcs(src, soff, lens)
     total = exp.size
-    d = _inputs(cuda, src, soff, lens, qids, guids, flags, ef)
+    d = inputs if inputs is not None else _inputs(cuda, src, soff, lens, qids, guids, flags, ef)
     dst = torch.full((total + slack,), FILL, dtype=torch.uint8, device=cuda)
     out = torch.full((len(lens),), FILL32, dtype=torch.int32, device=cuda)
     rdst, evoff, rout = pack_events(dst=dst, out=out, **d, **kw)
@@ -94,10 +106,10 @@ def _check(cuda, src, soff, lens, qids, guids, flags=None, ef=None, slack=64, ph
     diff = np.nonzero(host[:total] != exp)[0]
     assert diff.size == 0, (diff.size, [int(i) for i in diff[:8]])
     assert np.all(host[total:] == FILL)
-    assert np.array_equal(out.cpu().numpy().view(np.uint32), host_crcs(src, soff, lens))
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), want_crcs)
     if len(lens):
-        assert np.array_equal(evoff.cpu().numpy(), layout(lens, ef)[1])
-    assert torch.equal(d["src"].cpu(), torch.from_numpy(src))  # the source is only read
+        assert np.array_equal(evoff.cpu().numpy(), want_ev)
+    assert np.array_equal(d["src"].cpu().numpy(), src)  # the source is only read
     return host[:total]
 
 
@@ -123,15 +135,19 @@ def _raw(cuda, d, n, n_events, dst, dst_bytes, out, evoff, flags=N.BMQCRC_F_DEVI
 
 
 def _refused(cuda, kind, index, src, soff, lens, qids, guids, flags=None, ef=None,
-             dst_bytes=None, phases=None, **kw):
+             dst_bytes=None, phases=None, size=None, inputs=None, **kw):
     """The call is refused with (kind, index), synchronously and asynchronously,
     and the whole dst, out and event_offsets keep their canaries.  `phases`:
-    as in _check."""
+    as in _check.  `size` is the destination's, when the caller has the layout
+    already (no less than every event of these lengths takes); `inputs` is
+    _inputs' answer for these arguments, already on the device."""
     import torch
     n, n_events = len(lens), 1 if ef is None else len(ef) - 1
     place = V.Placer(cuda, phases) if phases is not None else None
-    d = _inputs(cuda, src, soff, lens, qids, guids, flags, ef, place)
-    size = int(layout(lens, None)[1][-1]) + 8 * n_events + 64
+    d = inputs if inputs is not None else \
+        _inputs(cuda, src, soff, lens, qids, guids, flags, ef, place)
+    if size is None:
+        size = int(layout(lens, None)[1][-1]) + 8 * n_events + 64
     stream = torch.cuda.current_stream(cuda)
     name = {1: b"SRC_RANGE", 2: b"EVENT_FIRST", 3: b"EVENT_TOO_BIG", 4: b"DST_TOO_SMALL"}[kind]
     for flags_ in (N.BMQCRC_F_DEVICE_PTRS, N.BMQCRC_F_DEVICE_PTRS | N.BMQCRC_F_ASYNC):
@@ -393,3 +409,224 @@ def test_crossing_4_gib(cuda):
     assert bool((dst[total:] == FILL).all())
     crc11 = host_crcs(src, soff[:11], lens[:11])
     assert np.array_equal(out.cpu().numpy().view(np.uint32), crc11[np.arange(n) % 11])
+
+
+# ---- past one tile per block (DESIGN.md sections 12 and 20) -------------------
+#
+# One set of N_FRAME messages (pack_pool.py: variable lengths, every padding
+# count and an empty message in every tile, one message of 70,000 bytes every
+# 3,001), built once; the smaller sizes are its prefixes.  The expected bytes
+# come from model_bytes_fast, which test_put_pack_model.py holds to the loop
+# model and to PutEventBuilder, once per (size, events).  The caches below live
+# as long as the session, as test_gpu_rollover.py's do: some 150 MB on the host
+# (the inputs and five images of 6 to 48 MB) and 25 MB on the device.
+
+@functools.lru_cache(maxsize=None)
+def _large():
+    """((src, soff, lens, qids, guids, flags) of N_FRAME messages, their CRCs
+    from one CRC per pool pair).  Shared, never modified."""
+    src, soff, lens, ix = pack_pool.messages(G.N_FRAME)
+    case = (src, soff, lens) + random_meta(np.random.default_rng(21), G.N_FRAME)
+    crcs = pooled_crcs(pool_crcs(*pack_pool.pool()), ix)
+    for a in case + (crcs,):
+        a.setflags(write=False)
+    return case, crcs
+
+
+@functools.lru_cache(maxsize=None)
+def _large_dev(cuda):
+    return _inputs(cuda, *(np.array(a) for a in _large()[0]), None)
+
+
+def _events_of(n, per):
+    return None if per is None else np.append(np.arange(0, n, per), n)
+
+
+def _first(cuda, n, ef=None):
+    """(the first n messages on the host, the same on the device with `ef`)."""
+    case = _large()[0]
+    dev = {k: v if k == "src" else v[:n] for k, v in _large_dev(cuda).items()
+           if k != "event_first"}
+    dev["event_first"] = _t(cuda, ef, np.int64) if ef is not None else None
+    return (case[0],) + tuple(a[:n] for a in case[1:]), dev
+
+
+def _patched(dev, **changes):
+    """`dev` with clones of the named tensors, entry i set to v for every
+    (i, v) of the name's dict."""
+    out = dict(dev)
+    for name, entries in changes.items():
+        out[name] = dev[name].clone()
+        for i, v in entries.items():
+            out[name][i] = v
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _expected(n, per):
+    """(expected bytes, event offsets, CRCs) of the first n messages in events
+    of `per` messages (None: one event)."""
+    case, crcs = _large()
+    host = (case[0],) + tuple(a[:n] for a in case[1:])
+    ef = _events_of(n, per)
+    img = model_bytes_fast(*host, ef, crcs[:n])
+    ev = layout(host[2], ef)[1]
+    # the framed totals are the model's
+    assert img.size == int(ev[-1]) == EVT * (ev.size - 1) + int(
+        (HDR + host[2] + pad_of(host[2])).sum())
+    return img, ev, crcs[:n]
+
+
+@functools.lru_cache(maxsize=None)
+def _event_offsets(n, per):
+    return layout(_large()[0][2][:n], _events_of(n, per))[1]
+
+
+LARGE = [(G.N_WAVES, 3), (G.N_FULL, None), (G.N_TILES, 3), (G.N_TILES, 1), (G.N_FRAME, 1)]
+LARGE_IDS = ["N_WAVES-events_of_3", "N_FULL-one_event", "N_TILES-events_of_3",
+             "N_TILES-own_events", "N_FRAME-own_events"]
+
+
+@pytest.mark.parametrize("n,per", LARGE, ids=LARGE_IDS)
+def test_past_one_tile_per_block(cuda, n, per):
+    # N_WAVES: 66 blocks, some 342 events a block, two of three block seams
+    # inside an event.  N_FULL: all 256 blocks under one event.  N_TILES: two
+    # tiles a block; with an event per message a block spans 2,048 events and
+    # seal_offsets searches event_first in global memory, not in LDS.  N_FRAME:
+    # three steps of the shape check and of events_check, two of
+    # event_headers, and k_pack_frame's per-message regime.
+    model = _expected(n, per)
+    assert int(np.diff(model[1]).max()) <= CAP
+    ef = _events_of(n, per)
+    host, dev = _first(cuda, n, ef)
+    _check(cuda, *host, ef=ef, model=model, inputs=dev)
+
+
+def test_past_one_tile_per_block_on_a_side_stream(cuda):
+    import torch
+    n = G.N_TILES
+    ef = _events_of(n, 3)
+    host, dev = _first(cuda, n, ef)
+    torch.cuda.synchronize(cuda)
+    s = torch.cuda.Stream(cuda, priority=-1)
+    with torch.cuda.stream(s):
+        _check(cuda, *host, ef=ef, model=_expected(n, 3), inputs=dev, sync=False, stream=s)
+
+
+def test_event_first_refused_in_a_late_step_of_the_shape_loop(cuda):
+    # one event per message at N_FRAME: 175,104 threads over 524,290 entries
+    n = G.N_FRAME
+    threads = G.regime(n).nblocks * 1024
+    assert 2 * threads < n < 3 * threads
+    good = _events_of(n, 1)
+    size = int(_event_offsets(n, 1)[-1]) + 64
+    host, dev = _first(cuda, n)
+
+    def refused(index, entries):
+        ef = good.copy()
+        for e, v in entries.items():
+            ef[e] = v
+        _refused(cuda, N.BMQCRC_PUT_PACK_EVENT_FIRST, index, *host, ef=ef, size=size,
+                 inputs=dict(dev, event_first=_t(cuda, ef, np.int64)))
+
+    late = 2 * threads + 50000          # read in the third step alone
+    refused(late, {late: late + 1})     # equal to the next entry
+    refused(n, {n: n + 1})              # the last entry is not n
+    # a high entry of an early thread's third step, a lower one of a later
+    # thread's second step: the lower index
+    high, low = 2 * threads + 10, threads + 170000
+    refused(low, {high: high + 1, low: low + 1})
+    assert np.array_equal(dev["src"].cpu().numpy(), host[0])
+
+
+def test_source_range_refused_past_one_tile_per_block(cuda):
+    n = G.N_TILES
+    per_block = G.regime(n).per_block
+    ef = _events_of(n, 3)
+    size = int(_event_offsets(n, 3)[-1]) + 64
+    host, dev = _first(cuda, n, ef)
+    declared = pack_pool.SRC_BYTES  # smaller than the tensor: a broken check stays inside it
+    assert host[0].size >= declared + 64
+
+    def refused(kind, index, at, inputs=dev):
+        bad = _patched(inputs, src_offsets={i: declared - 10 for i in at},
+                       lengths={i: 11 for i in at})   # one byte past
+        _refused(cuda, kind, index, *host, ef=ef, size=size, inputs=bad, src_bytes=declared)
+
+    # in the second tile of block 0, below one in block 1
+    assert 1024 <= 1030 < per_block <= 2100
+    refused(N.BMQCRC_PUT_PACK_SRC_RANGE, 1030, (1030, 2100))
+    # the last message of the last block
+    refused(N.BMQCRC_PUT_PACK_SRC_RANGE, n - 1, (n - 1,))
+    # with a bad event_first entry at a lower index: kind 1 wins over kind 2
+    bad_ef = ef.copy()
+    bad_ef[7] = bad_ef[8]
+    refused(N.BMQCRC_PUT_PACK_SRC_RANGE, 150000, (150000,),
+            dict(dev, event_first=_t(cuda, bad_ef, np.int64)))
+    _refused(cuda, N.BMQCRC_PUT_PACK_EVENT_FIRST, 7, *host, ef=bad_ef, size=size,
+             inputs=dict(dev, event_first=_t(cuda, bad_ef, np.int64)))
+    assert np.array_equal(dev["src"].cpu().numpy(), host[0])
+
+
+def test_event_size_cap_past_one_tile_per_block(cuda):
+    # events of 3 at N_TILES with two messages made the longest of all: each is
+    # the first of its event and lies in the second tile of a block behind the
+    # 64th, where p0 is off[f0], with the tile carry in it, plus bpre[f0 / 2048]
+    n = G.N_TILES
+    per_block = G.regime(n).per_block
+    ef = _events_of(n, 3)
+    ia, ib = 70 * per_block + 1525, 100 * per_block + 1024
+    for i in (ia, ib):
+        assert i % 3 == 0 and i % per_block >= 1024 and i // per_block > 64
+    host, dev = _first(cuda, n, ef)
+    src, soff, lens = host[0], host[1].copy(), host[2].copy()
+    soff[[ia, ib]], lens[[ia, ib]] = (5, 9), (80000, 90000)
+    dev = _patched(dev, src_offsets={ia: 5, ib: 9}, lengths={ia: 80000, ib: 90000})
+    ev = layout(lens, ef)[1]
+    sizes = np.diff(ev)
+    order = np.argsort(sizes)
+    assert [int(e) for e in order[-2:]] == [ia // 3, ib // 3] and \
+        sizes[order[-3]] < sizes[ia // 3] - 4 and sizes[ia // 3] < sizes[ib // 3] - 4
+    case = (src, soff, lens) + host[3:]
+    size = int(ev[-1]) + 64
+    # one event over the cap, then two: the lower index
+    _refused(cuda, N.BMQCRC_PUT_PACK_EVENT_TOO_BIG, ib // 3, *case, ef=ef, size=size, inputs=dev,
+             max_event_bytes=int(sizes[ib // 3]) - 4)
+    _refused(cuda, N.BMQCRC_PUT_PACK_EVENT_TOO_BIG, ia // 3, *case, ef=ef, size=size, inputs=dev,
+             max_event_bytes=int(sizes[ia // 3]) - 4)
+    # the cap exactly the largest event
+    crcs = _large()[1][:n].copy()
+    crcs[[ia, ib]] = host_crcs(src, soff[[ia, ib]], lens[[ia, ib]])
+    img = model_bytes_fast(*case, ef, crcs)
+    _check(cuda, *case, ef=ef, model=(img, ev, crcs), inputs=dev,
+           max_event_bytes=int(sizes[ib // 3]))
+
+
+def test_destination_size_past_one_tile_per_block(cuda):
+    n = G.N_TILES
+    ef = _events_of(n, 3)
+    ev = _event_offsets(n, 3)
+    total, n_events = int(ev[-1]), ev.size - 1
+    host, dev = _first(cuda, n, ef)
+    kind = N.BMQCRC_PUT_PACK_DST_TOO_SMALL
+    _refused(cuda, kind, n_events - 1, *host, ef=ef, size=total + 64, inputs=dev,
+             dst_bytes=total - 4)
+    # halfway through the image: the first event that ends past it, while
+    # every later one, in every block of the check grid, refuses as well
+    half = total // 2
+    first = int(np.searchsorted(ev[1:], half, side="right"))
+    assert ev[first] <= half < ev[first + 1] and n_events // 3 < first < 2 * n_events // 3
+    _refused(cuda, kind, first, *host, ef=ef, size=total + 64, inputs=dev, dst_bytes=half)
+    _check(cuda, *host, ef=ef, model=_expected(n, 3), inputs=dev, slack=0)  # dst_bytes == total
+    # one event per message at N_FRAME: some 260,000 events refuse, over three
+    # steps of every block of the check grid
+    n = G.N_FRAME
+    ef = _events_of(n, 1)
+    ev = _event_offsets(n, 1)
+    total = int(ev[-1])
+    half = total // 2
+    first = int(np.searchsorted(ev[1:], half, side="right"))
+    assert ev[first] <= half < ev[first + 1] and n - first > 200000
+    host, dev = _first(cuda, n, ef)
+    _refused(cuda, kind, first, *host, ef=ef, size=total + 64, inputs=dev, dst_bytes=half)
+    assert np.array_equal(dev["src"].cpu().numpy(), host[0])

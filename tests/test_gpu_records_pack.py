@@ -4,6 +4,7 @@ the CPU tests hold to PartitionWriter and to the reference's fixture: every
 check compares both destinations byte for byte, `out`, `record_offsets`, and
 the canaries behind both totals."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -12,9 +13,12 @@ from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, last_copy, last_la
                            last_put_pack, last_records_pack, pack_events, pack_records)
 from blazingmq_amd import storage as S
 import device_views as V
+import pack_pool
 import put_pack_model as P
-from records_pack_model import (DH, REC, golden_case, host_crcs, layout, model_bytes,
-                                random_meta, wrap_partition)
+import test_grid_regimes as G
+from records_pack_model import (DH, REC, data_bytes_fast, golden_case, host_crcs,
+                                journal_bytes_fast, layout, model_bytes, pad_of, pool_crcs,
+                                pooled_crcs, random_meta, wrap_partition)
 
 pytestmark = pytest.mark.gpu
 
@@ -70,23 +74,29 @@ def _result(n, total, n_bad=0, first_bad=None, kind=0, index=0):
 
 
 def _check(cuda, src, soff, lens, qkeys, guids, kw=KW, slack=64, sync=True, stream=None,
-           n_bad=0, first_bad=None, phases=None):
+           n_bad=0, first_bad=None, phases=None, model=None, inputs=None):
     """One pack into canary destinations against the model.  Returns the
     packed (DATA, journal) bytes (host).  `phases` maps every pointer of the
     call (src, src_offsets, lengths, queue_keys, guids, the optional arrays,
     dst, journal_dst, record_offsets, out) to the phase of its base: the call
     then goes through the raw entry point (synchronous, on the current stream)
     and the sentinel margins around every buffer are checked; None: the
-    wrapper, every buffer at the start of an allocation."""
+    wrapper, every buffer at the start of an allocation.  `model` is (DATA
+    bytes, journal bytes, CRCs) of this very call when the caller has them
+    already: the model and the host CRCs are not run then.  `inputs` is
+    _inputs' answer for these arguments, already on the device."""
     import torch
     place = V.Placer(cuda, phases) if phases is not None else None
     n = len(lens)
-    crcs = host_crcs(src, soff, lens)
-    stored = crcs if kw.get("expected") is None else np.asarray(kw["expected"], np.uint32)
-    model_kw = {k: v for k, v in kw.items() if k != "expected"}
-    exp_d, exp_j = model_bytes(src, soff, lens, qkeys, guids, stored, **model_kw)
+    if model is not None:
+        exp_d, exp_j, crcs = model
+    else:
+        crcs = host_crcs(src, soff, lens)
+        stored = crcs if kw.get("expected") is None else np.asarray(kw["expected"], np.uint32)
+        model_kw = {k: v for k, v in kw.items() if k != "expected"}
+        exp_d, exp_j = model_bytes(src, soff, lens, qkeys, guids, stored, **model_kw)
     total = exp_d.size
-    d = _inputs(cuda, src, soff, lens, qkeys, guids, kw, place)
+    d = inputs if inputs is not None else _inputs(cuda, src, soff, lens, qkeys, guids, kw, place)
     if place is not None:
         assert sync and stream is None
         dst = place.fill("dst", total + slack, np.uint8, FILL)
@@ -116,7 +126,7 @@ def _check(cuda, src, soff, lens, qkeys, guids, kw=KW, slack=64, sync=True, stre
         assert np.all(got[exp.size:] == FILL)
     assert np.array_equal(out.cpu().numpy().view(np.uint32), crcs)
     assert np.array_equal(roff.cpu().numpy(), layout(lens)[1])
-    assert torch.equal(d["src"].cpu(), torch.from_numpy(np.asarray(src)))  # only read
+    assert np.array_equal(d["src"].cpu().numpy(), np.asarray(src))  # only read
     return host_d[:total], host_j[:REC * n]
 
 
@@ -145,14 +155,16 @@ def _raw(cuda, d, kw, n, dst, dst_bytes, jour, roff, out, flags, src_bytes=None)
 
 
 def _refused(cuda, kind, index, src, soff, lens, qkeys, guids, kw=KW, dst_bytes=None,
-             src_bytes=None, size=None, phases=None):
+             src_bytes=None, size=None, phases=None, inputs=None):
     """The call is refused with (kind, index), synchronously and asynchronously,
     and dst, journal_dst, out and record_offsets keep their canaries whole.
-    `phases`: as in _check."""
+    `phases`: as in _check.  `inputs` is _inputs' answer for these arguments,
+    already on the device."""
     import torch
     n = len(lens)
     place = V.Placer(cuda, phases) if phases is not None else None
-    d = _inputs(cuda, src, soff, lens, qkeys, guids, kw, place)
+    d = inputs if inputs is not None else \
+        _inputs(cuda, src, soff, lens, qkeys, guids, kw, place)
     if size is None:
         size = int(layout(lens)[1][-1]) + 64
     stream = torch.cuda.current_stream(cuda)
@@ -466,3 +478,224 @@ def test_put_events_to_verified_partition(cuda):
     got = S.verify_partition(jf, df)
     assert (got["recovery_rc"], got["n_messages"], got["n_bad"]) == (0, n, 1)
     assert list(got["bad_record_offsets"]) == [44 + 60 + REC * victim]
+
+
+# ---- past one tile per block (DESIGN.md sections 13 and 20) -------------------
+#
+# One set of N_FRAME messages (pack_pool.py: variable lengths, every padding
+# count and an empty message in every tile, one message of 70,000 bytes every
+# 3,001), built once; the smaller sizes are its prefixes.  The expected bytes
+# come from data_bytes_fast and journal_bytes_fast, which
+# test_records_pack_model.py holds to the loop model and to PartitionWriter.
+# The caches below live as long as the session, as test_gpu_rollover.py's do:
+# some 80 MB on the host (the inputs, two DATA images of 32 MB) and 30 MB on
+# the device.
+
+MAX_FILE = 8 * 0xFFFFFFFF  # kRecMaxFileBytes: where MessageOffsetDwords stops
+
+
+@functools.lru_cache(maxsize=None)
+def _large():
+    """((src, soff, lens, qkeys, guids) of N_FRAME messages, KW with every
+    optional array but `expected`, their CRCs from one CRC per pool pair).
+    Shared, never modified."""
+    src, soff, lens, ix = pack_pool.messages(G.N_FRAME)
+    rng = np.random.default_rng(22)
+    case = (src, soff, lens) + random_meta(rng, G.N_FRAME)
+    kw = _all_options(rng, G.N_FRAME)
+    crcs = pooled_crcs(pool_crcs(*pack_pool.pool()), ix)
+    for a in case + (crcs,) + tuple(kw[k] for k in OPTIONAL if k in kw):
+        a.setflags(write=False)
+    return case, kw, crcs
+
+
+@functools.lru_cache(maxsize=None)
+def _large_dev(cuda):
+    case, kw, _ = _large()
+    return _inputs(cuda, *(np.array(a) for a in case),
+                   {k: np.array(kw[k]) for k in OPTIONAL if k in kw})
+
+
+@functools.lru_cache(maxsize=None)
+def _large_data(with_flags):
+    """(the DATA bytes of all N_FRAME records, Q).  The first n records' bytes
+    are the first Q[n] of them."""
+    case, kw, _ = _large()
+    data = data_bytes_fast(*case[:3], kw["data_flags"] if with_flags else None)
+    Q = layout(case[2])[1]
+    assert data.size == int(Q[-1]) == int((DH + case[2] + pad_of(case[2])).sum())  # the model's total
+    return data, Q
+
+
+def _first(cuda, n, options=True, expected=None, **scalars):
+    """The first n messages: (host case, keywords with `scalars` changed, the
+    device inputs, (DATA bytes, journal bytes, CRCs) expected)."""
+    case, kw, crcs = _large()
+    host = (case[0],) + tuple(a[:n] for a in case[1:])
+    kw = {k: (v[:n] if k in OPTIONAL else v) for k, v in kw.items() if options or k not in OPTIONAL}
+    kw.update(scalars)
+    dev = {}
+    for k, v in _large_dev(cuda).items():
+        if k in OPTIONAL:
+            dev[k] = v[:n] if options and v is not None else None
+        else:
+            dev[k] = v if k == "src" else v[:n]
+    stored = crcs[:n]
+    if expected is not None:
+        kw["expected"] = stored = expected
+        dev["expected"] = _t(cuda, expected, np.uint32)
+    data, Q = _large_data(options)
+    jour = journal_bytes_fast(host[2], host[3], host[4], stored,
+                              **{k: v for k, v in kw.items() if k not in ("data_flags", "expected")})
+    return host, kw, dev, (data[:int(Q[n])], jour, crcs[:n])
+
+
+def _patched(dev, **changes):
+    """`dev` with clones of the named tensors, entry i set to v for every
+    (i, v) of the name's dict."""
+    out = dict(dev)
+    for name, entries in changes.items():
+        out[name] = dev[name].clone()
+        for i, v in entries.items():
+            out[name][i] = v
+    return out
+
+
+@pytest.mark.parametrize("n", [G.N_WAVES, G.N_FULL, G.N_TILES, G.N_FRAME],
+                         ids=["N_WAVES", "N_FULL", "N_TILES", "N_FRAME"])
+def test_past_one_tile_per_block(cuda, n):
+    # N_WAVES: block_prefix's cross-wave leg and the journal loop's later steps.
+    # N_FULL: all 256 blocks; the DataHeader loop's second step; the sequence
+    # number's high half changes inside the call.  N_TILES: two tiles a block.
+    # N_FRAME: three, and both per-message regimes of k_rec_frame.
+    first_seq = (1 << 32) - 1000 if n == G.N_FULL else 2
+    host, kw, dev, model = _first(cuda, n, first_seq=first_seq)
+    _check(cuda, *host, kw, model=model, inputs=dev)
+
+
+def test_a_file_filled_to_its_last_addressable_byte(cuda):
+    n = G.N_TILES
+    total = int(_large_data(True)[1][n])
+    host, kw, dev, model = _first(cuda, n, data_file_pos=MAX_FILE - total)
+    data, jour = _check(cuda, *host, kw, model=model, inputs=dev)  # record_offsets[n] included
+    last = jour[REC * (n - 1):]
+    assert int.from_bytes(last[32:36].tobytes(), "big") + \
+        int(layout(host[2])[0][-1]) // 8 == 0xFFFFFFFF
+    # one byte of file less
+    _refused(cuda, N.BMQCRC_REC_PACK_DATA_FILE_FULL, n - 1, *host,
+             dict(_scalars(kw), data_file_pos=MAX_FILE - total + 8), size=total + 64, inputs=dev)
+
+
+def test_past_one_tile_per_block_without_the_optional_arrays(cuda):
+    host, kw, dev, model = _first(cuda, G.N_TILES, options=False)
+    assert not any(k in kw for k in OPTIONAL) and all(dev[k] is None for k in OPTIONAL)
+    _check(cuda, *host, kw, model=model, inputs=dev)
+
+
+def test_past_one_tile_per_block_on_a_side_stream(cuda):
+    import torch
+    host, kw, dev, model = _first(cuda, G.N_TILES)
+    torch.cuda.synchronize(cuda)
+    s = _side_stream(cuda)
+    with torch.cuda.stream(s):
+        _check(cuda, *host, kw, model=model, inputs=dev, sync=False, stream=s)
+
+
+CRC_DWORD = 13  # of a journal record's 15: the stored CRC, bytes 52..55
+
+
+def _crc_dword(m):
+    """The index of record m's CRC dword among the journal's: the thread of
+    k_rec_frame's journal loop that compares it, modulo the grid."""
+    return G.RECORD_DWORDS * m + CRC_DWORD
+
+
+def _crc_wave(m):
+    """The wave and step of k_rec_frame's journal loop that holds record m's
+    CRC dword: 64 consecutive dwords, and the grid is a multiple of 64."""
+    return _crc_dword(m) // 64
+
+
+def test_expected_mismatches_in_every_step_of_the_journal_loop(cuda):
+    n = G.N_FRAME
+    grid = G.constants()["kPackFrameThreads"] * G.constants()["kPackFrameBlocks"]
+    crcs = _large()[2]
+    # every 1,000th record (999, 1,999, ...), the record after one of them,
+    # whose CRC dword lies in the same wave, and the last record, the only one
+    # past the frame grid's first step of records
+    pair = 200999
+    assert _crc_wave(pair) == _crc_wave(pair + 1) and pair % 1000 == 999
+    bad = np.concatenate([np.arange(999, n, 1000), [pair + 1, n - 1]])
+    assert np.unique(bad).size == bad.size == n // 1000 + 2 and n - 1 == grid
+    steps = {_crc_dword(int(m)) // grid for m in bad}
+    assert steps == set(range(G.RECORD_DWORDS + 1))  # a mismatch in every step, the 16th too
+    wrong = crcs.copy()
+    wrong[bad] ^= (1 << (bad % 32)).astype(np.uint32)
+    host, kw, dev, model = _first(cuda, n, expected=wrong)
+    data, jour = _check(cuda, *host, kw, model=model, inputs=dev, n_bad=bad.size, first_bad=999)
+    stored = jour.reshape(n, REC)[:, 52:56]
+    assert np.array_equal(stored, wrong.astype(">u4").view(np.uint8).reshape(n, 4))
+    # the only mismatch at record 524,288
+    wrong = crcs.copy()
+    wrong[grid] ^= 0x80000000
+    host, kw, dev, model = _first(cuda, n, expected=wrong)
+    _check(cuda, *host, kw, model=model, inputs=dev, n_bad=1, first_bad=grid)
+
+
+def test_bounds_found_by_bisection_in_a_late_block_of_two_tiles(cuda):
+    # k_rec_place searches off[] as pass 1 left it, block-local with the tile
+    # carry in it, in the one block with before <= bound < after
+    n = G.N_TILES
+    per_block = G.regime(n).per_block
+    host, kw, dev, _ = _first(cuda, n)
+    kw = _scalars(kw)
+    Q = _large_data(True)[1][:n + 1]
+    total = int(Q[-1])
+    lo = 100 * per_block
+    assert per_block == 2048 and lo // per_block > 64 and lo + per_block < n
+    ks = (lo, lo + 1023, lo + 1024, lo + 2047)
+
+    def refused(kind, index, dst_bytes=total + 64, room=None):
+        _refused(cuda, kind, index, *host,
+                 kw if room is None else dict(kw, data_file_pos=MAX_FILE - room),
+                 dst_bytes=dst_bytes, size=total + 64, inputs=dev)
+
+    small, full = N.BMQCRC_REC_PACK_DST_TOO_SMALL, N.BMQCRC_REC_PACK_DATA_FILE_FULL
+    for k in ks:
+        refused(small, k, int(Q[k + 1]) - 8)
+    refused(small, lo, int(Q[lo]))            # the bound is the block's `before`
+    refused(small, lo - 1, int(Q[lo]) - 8)    # the previous block's last record
+    refused(small, n - 1, total - 8)
+    for k in ks:
+        refused(full, k, room=int(Q[k + 1]) - 8)
+    # both bounds, in different blocks, the file's in the earlier one: kind 3
+    k_dst, k_file = 120 * per_block + 1030, 50 * per_block + 7
+    refused(small, k_dst, int(Q[k_dst + 1]) - 8, room=int(Q[k_file + 1]) - 8)
+    assert np.array_equal(dev["src"].cpu().numpy(), host[0])
+
+
+def test_message_refusals_past_one_tile_per_block(cuda):
+    n = G.N_TILES
+    per_block = G.regime(n).per_block
+    host, kw, dev, _ = _first(cuda, n)
+    kw = _scalars(kw)
+    size = int(_large_data(True)[1][n]) + 64
+    declared = pack_pool.SRC_BYTES  # smaller than the tensor: a broken check stays inside it
+    assert host[0].size >= declared + 64
+
+    def out_of_range(index, at):
+        bad = _patched(dev, src_offsets={i: declared - 10 for i in at},
+                       lengths={i: 11 for i in at})   # one byte past
+        _refused(cuda, N.BMQCRC_REC_PACK_SRC_RANGE, index, *host, kw, size=size, inputs=bad,
+                 src_bytes=declared)
+
+    # in the second tile of block 0, below one in block 1
+    assert 1024 <= 1030 < per_block <= 2100
+    out_of_range(1030, (1030, 2100))
+    out_of_range(n - 1, (n - 1,))             # the last record of the last block
+    # a length the DataHeader cannot hold, out of the source's range as well:
+    # kind 1.  The call is refused before anything is read.
+    bad = _patched(dev, lengths={200001: -(1 << 31)})   # 2^31 as the tensor's int32
+    _refused(cuda, N.BMQCRC_REC_PACK_RECORD_TOO_BIG, 200001, *host, kw, size=size, inputs=bad,
+             src_bytes=declared)
+    assert np.array_equal(dev["src"].cpu().numpy(), host[0])

@@ -16,8 +16,9 @@ units.  Above certain sizes the same code runs loops it never enters below:
 
 `layout_split` is restated here and the four constants are read from the text
 of bmqcrc_internal.h, so a changed constant fails this file instead of letting
-test_gpu_rollover.py, test_gpu_confirm_records.py and test_gpu_copy.py, which
-import the sizes below, quietly stop reaching their regimes."""
+test_gpu_rollover.py, test_gpu_confirm_records.py, test_gpu_copy.py,
+test_gpu_put_pack.py and test_gpu_records_pack.py, which import the sizes
+below, quietly stop reaching their regimes."""
 import collections
 import os
 import re
@@ -106,6 +107,44 @@ def test_every_block_of_the_large_sizes_owns_units():
     for n in (N_FEW, N_WAVES, N_FULL, N_TILES, N_FRAME):
         r = regime(n)
         assert (r.nblocks - 1) * r.per_block < n <= r.nblocks * r.per_block
+
+
+def seal_events():
+    """kSealEvents as crc32c_pack_layout.h spells it."""
+    with open(os.path.join(os.path.dirname(HEADER), "crc32c_pack_layout.h")) as f:
+        m = re.findall(r"constexpr uint32_t kSealEvents = (\d+);", f.read())
+    assert len(m) == 1, m
+    return int(m[0])
+
+
+def steps(entries, threads):
+    """Steps of a grid-stride loop of `threads` threads over `entries` entries."""
+    return (entries + threads - 1) // threads
+
+
+def test_what_the_put_and_record_packers_reach():
+    # test_gpu_put_pack.py and test_gpu_records_pack.py: their frame kernels
+    # stride over 9 and 3 dwords per message, not 15
+    k = constants()
+    grid = k["kPackFrameThreads"] * k["kPackFrameBlocks"]
+    assert steps(9 * 58254, grid) == 1 and steps(9 * 58255, grid) == 2      # PutHeader
+    assert steps(3 * 174762, grid) == 1 and steps(3 * 174763, grid) == 2    # DataHeader
+    for n in (N_WAVES, N_FULL, N_TILES, N_FRAME):
+        assert steps(9 * n, grid) >= 2, n
+    assert steps(3 * N_WAVES, grid) == 1 and steps(3 * N_FULL, grid) == 2
+    # one event per message at N_FRAME: event_first's N_FRAME + 1 entries over
+    # the layout grid, the events over k_pack_check's grid, the EventHeaders
+    # over the frame grid
+    r = regime(N_FRAME)
+    assert steps(N_FRAME + 1, r.nblocks * k["kPackThreads"]) == 3
+    assert steps(N_FRAME, k["kPackBlocks"] * k["kPackThreads"]) == 3
+    assert steps(N_FULL, k["kPackBlocks"] * k["kPackThreads"]) == 1
+    assert steps(N_FRAME + 1, grid) == 2 and steps(N_FRAME - 1, grid) == 1
+    # seal_offsets at N_TILES: a block of single-message events is past the
+    # events it searches in LDS, a block of 3-message events is not
+    per_block = regime(N_TILES).per_block
+    assert seal_events() == 1024
+    assert per_block - 1 >= seal_events() > (per_block + 2) // 3 + 1
 
 
 def test_layout_split_below_one_grid_of_tiles():

@@ -5,8 +5,9 @@ import numpy as np
 import pytest
 
 from blazingmq_amd.put_event import PutMessageIterator
-from put_pack_model import (EVT, HDR, host_crcs, layout, model_bytes, oracle_events, pad_of,
-                            random_meta)
+import pack_pool
+from put_pack_model import (EVT, HDR, host_crcs, layout, model_bytes, model_bytes_fast,
+                            oracle_events, pad_of, pool_crcs, pooled_crcs, random_meta)
 
 LENS = np.arange(68)  # 0..67: every padding count, many times over
 CUTS = [None, [0, 68], [0, 1, 68], [0, 1, 2, 67, 68], [0, 17, 18, 40, 68], list(range(69))]
@@ -58,6 +59,49 @@ def test_model_through_the_native_walk(cuts):
             assert m["app_data"] == src[int(soff[i]):int(soff[i]) + int(lens[i])].tobytes()
             n_msgs += 1
         assert n_msgs == ef[e + 1] - ef[e]
+
+
+N_POOLED = pack_pool.POOL + 1100  # every pool pair, the long one included, and a second lap
+
+
+def _pooled_case():
+    src, soff, lens, ix = pack_pool.messages(N_POOLED)
+    rng = np.random.default_rng(2)
+    return (src, soff, lens) + random_meta(rng, N_POOLED), ix
+
+
+@pytest.mark.parametrize("cuts,with_flags", [
+    (None, True),
+    ([0, N_POOLED], False),
+    (list(range(0, N_POOLED, 3)) + [N_POOLED], True),        # events of 3, the last shorter
+    (list(range(N_POOLED + 1)), False),                       # every message its own event
+    ([0, 1, 2, 1024, 1025, 1500, 1501, 2048, N_POOLED - 1, N_POOLED], True)])
+def test_fast_model_is_the_loop_model_and_the_builder(cuts, with_flags):
+    (src, soff, lens, qids, guids, flags), ix = _pooled_case()
+    assert set(pad_of(lens)) == {1, 2, 3, 4} and (lens == 0).any()
+    assert int(lens[pack_pool.LONG_VISIT]) == pack_pool.LONG
+    if not with_flags:
+        flags = None
+    crcs = pooled_crcs(pool_crcs(*pack_pool.pool()), ix)
+    assert np.array_equal(crcs, host_crcs(src, soff, lens))
+    fast = model_bytes_fast(src, soff, lens, qids, guids, flags, cuts, crcs)
+    assert np.array_equal(fast, model_bytes(src, soff, lens, qids, guids, flags, cuts, crcs))
+    assert np.array_equal(fast, np.concatenate(
+        oracle_events(src, soff, lens, qids, guids, flags, cuts)))
+
+
+def test_fast_model_of_nothing_and_of_one():
+    src, soff, lens, ix = pack_pool.messages(1)
+    qids, guids, flags = random_meta(np.random.default_rng(3), 1)
+    crcs = host_crcs(src, soff, lens)
+    assert np.array_equal(model_bytes_fast(src, soff, lens, qids, guids, flags, None, crcs),
+                          model_bytes(src, soff, lens, qids, guids, flags, None, crcs))
+    none = (src, soff[:0], lens[:0], qids[:0], guids[:0], None, None, crcs[:0])
+    assert np.array_equal(model_bytes_fast(*none), model_bytes(*none))  # an empty event
+
+
+def test_the_pool_holds_what_the_large_cases_rely_on():
+    pack_pool.check_properties(pad_of)
 
 
 def test_event_formulas():

@@ -7,8 +7,10 @@ import pytest
 
 from blazingmq_amd import pack_records  # noqa: F401  (ABI 2.11: absent before it)
 from blazingmq_amd import storage as S
+import pack_pool
 from records_pack_model import (DH, REC, golden_case, host_crcs, layout, model_bytes,
-                                oracle_bytes, pad_of, random_meta, wrap_partition)
+                                model_bytes_fast, oracle_bytes, pad_of, pool_crcs, pooled_crcs,
+                                random_meta, wrap_partition)
 
 LENS = np.arange(40)  # 0..39: every padding count five times
 KW = dict(file_key=bytes(5), lease_id=7, first_seq=2, data_file_pos=40, timestamp=0x6720EAB4)
@@ -50,6 +52,59 @@ def test_model_is_byte_for_byte_the_partition_writer(variant):
     odata, ojour = oracle_bytes(src, soff, lens, qkeys, guids, crcs, **kw)
     assert np.array_equal(data, odata) and np.array_equal(jour, ojour)
     assert data.size == int(layout(lens)[1][-1]) and jour.size == REC * n
+
+
+N_POOLED = pack_pool.POOL + 1100  # every pool pair, the long one included, and a second lap
+
+
+@pytest.mark.parametrize("variant", ["plain", "ref_counts", "data_flags", "timestamps", "all",
+                                     "expected", "seq_past_32_bits", "offset_across_2_31"])
+def test_fast_model_is_the_loop_model_and_the_partition_writer(variant):
+    src, soff, lens, ix = pack_pool.messages(N_POOLED)
+    n = N_POOLED
+    rng = np.random.default_rng(4)
+    qkeys, guids = random_meta(rng, n)
+    assert set(pad_of(lens)) == set(range(1, 9)) and (lens == 0).any()
+    assert int(lens[pack_pool.LONG_VISIT]) == pack_pool.LONG
+    kw = dict(KW)
+    if variant in ("ref_counts", "all"):
+        kw["ref_counts"] = rng.choice(np.array([1, 2, 4095, 4096, (1 << 20) - 1], np.uint32), n)
+    if variant in ("data_flags", "all"):
+        kw["data_flags"] = rng.integers(0, 256, size=n, dtype=np.uint8)
+    if variant in ("timestamps", "all"):
+        kw["timestamps"] = rng.integers(1, 1 << 62, size=n, dtype=np.int64)
+    if variant == "all":
+        kw.update(file_key=b"\x9a\x00\xff\x01\x7e", lease_id=0xFEDCBA98)
+    if variant in ("seq_past_32_bits", "all"):
+        kw["first_seq"] = (1 << 32) - 1000       # the high half changes inside the run
+    Q = layout(lens)[1]
+    if variant == "offset_across_2_31":
+        kw["data_file_pos"] = (1 << 34) - int(Q[n // 2])
+    crcs = pooled_crcs(pool_crcs(*pack_pool.pool()), ix)
+    assert np.array_equal(crcs, host_crcs(src, soff, lens))
+    stored = crcs
+    if variant == "expected":
+        stored = crcs ^ (np.arange(n) % 7 == 3).astype(np.uint32)  # not the computed CRC
+        assert int((stored != crcs).sum()) > 500
+    data, jour = model_bytes_fast(src, soff, lens, qkeys, guids, stored, **kw)
+    if variant == "offset_across_2_31":
+        dw = jour.reshape(n, REC)[:, 32:36]
+        assert dw[0, 0] == 0x7F and dw[n // 2 - 1, 0] == 0x7F and dw[n // 2, 0] == 0x80
+    for other in (model_bytes, oracle_bytes):
+        d, j = other(src, soff, lens, qkeys, guids, stored, **kw)
+        assert np.array_equal(data, d) and np.array_equal(jour, j), other.__name__
+    assert data.size == int(Q[-1]) and jour.size == REC * n
+
+
+def test_fast_model_of_nothing():
+    src, soff, lens, ix = pack_pool.messages(0)
+    data, jour = model_bytes_fast(src, soff, lens, np.zeros((0, 5), np.uint8),
+                                  np.zeros((0, 16), np.uint8), np.zeros(0, np.uint32), **KW)
+    assert data.size == 0 and jour.size == 0
+
+
+def test_the_pool_holds_what_the_large_cases_rely_on():
+    pack_pool.check_properties(pad_of)
 
 
 def test_defaults_of_the_writer_are_todays_bytes():
