@@ -130,3 +130,104 @@ def refused_result(r, n_events):
     """The result struct's fields after the refusal `r`."""
     return dict(n_events=n_events, n_msgs=0, n_data=0, total_bytes=0, n_bad=0, first_bad=0,
                 refused_kind=r.kind, refused_index=r.index)
+
+
+# ---- the same without a Python loop per record ---------------------------------
+
+def _be32s(rows):
+    """The big-endian 32-bit values of (k, 4) uint8 rows, as int64."""
+    return np.ascontiguousarray(rows, np.uint8).view(">u4")[:, 0].astype(np.int64)
+
+
+def storage_events_fast(journal, data, *, journal_pos, data_file_pos, partition_id,
+                        event_first=None, flags=None, event_type=0,
+                        storage_protocol_version=E.STORAGE_PROTOCOL_VERSION, max_event_bytes=0,
+                        max_payload_bytes=0, dst_bytes=None, crc32c=None, record_crcs=None):
+    """``pack`` in numpy alone, for records that are well formed (asserted):
+    the StorageHeaders and journal records as an (n, 72) array scattered to
+    their offsets, the DATA records by one gather of dwords.  Of the refusals
+    it knows PAYLOAD_TOO_BIG, EVENT_TOO_BIG and DST_TOO_SMALL (``dst_bytes``
+    None: room for everything).  The CRCs are ``record_crcs`` (one per record,
+    computed once by the caller) or ``crc32c`` of every MESSAGE record's
+    application data."""
+    from put_pack_model import be_bytes, byte_runs, scatter_frames
+    recs = np.asarray(journal, np.uint8).reshape(-1, 60)
+    data = np.asarray(data, np.uint8)
+    n = recs.shape[0]
+    assert n > 0
+    rtype = (recs[:, 0] >> 4).astype(np.int64)
+    seq = recs[:, 2:8].astype(np.int64)
+    op = _be32s(recs[:, 32:36])
+    assert rtype.min() >= 1 and rtype.max() <= 5 and _be32s(recs[:, 8:12]).min() > 0
+    assert seq.any(axis=1).all() and bool((recs[:, 56:60] == np.frombuffer(MAGIC, np.uint8)).all())
+    types = np.array([0, E.MSG_DATA, E.MSG_CONFIRM, E.MSG_DELETION, 0, E.MSG_JOURNAL_OP],
+                     np.uint8)[rtype]
+    queue_op = rtype == 4
+    assert bool(((op[queue_op] >= 1) & (op[queue_op] <= 4)).all())
+    types[queue_op] = np.where(op[queue_op] & 1, E.MSG_QUEUE_OP, E.MSG_QLIST)
+    is_data = rtype == 1
+    where = np.flatnonzero(is_data)
+    at = 8 * op[where] - data_file_pos
+    assert at.size == 0 or (at.min() >= 0 and 8 * op[where].min() > 0 and
+                            at.max() + 8 <= data.size)
+    h0 = _be32s(data[at[:, None] + np.arange(4)])
+    h1 = _be32s(data[at[:, None] + 4 + np.arange(4)])
+    hs, rec, opt = (h0 >> 29) * 4, (h0 & 0x1FFFFFFF) * 4, (h1 >> 8) * 4
+    assert bool(((hs > 0) & (hs + opt < rec) & (at + rec <= data.size)).all())
+    pad = data[at + rec - 1].astype(np.int64)
+    assert bool(((pad >= 1) & (pad <= 8) & (rec >= hs + opt + pad)).all())
+    length = rec - hs - opt - pad
+    size = np.zeros(n, np.int64)
+    size[where] = rec
+    first = np.array([0, n], np.int64) if event_first is None else np.asarray(
+        event_first).astype(np.int64)
+    n_events = first.size - 1
+    assert first[0] == 0 and first[-1] == n and bool((np.diff(first) > 0).all())
+    before = np.concatenate([[0], np.cumsum(72 + size)])
+    offsets = 8 * np.arange(n_events + 1) + before[first]
+    big = np.flatnonzero(60 + size > (max_payload_bytes or E.MAX_PAYLOAD_SIZE_SOFT))
+    if big.size:
+        return Refusal(PAYLOAD_TOO_BIG, int(big[0]))
+    big = np.flatnonzero(np.diff(offsets) > (max_event_bytes or E.MAX_EVENT_SIZE_SOFT))
+    if big.size:
+        return Refusal(EVENT_TOO_BIG, int(big[0]))
+    if dst_bytes is not None and offsets[-1] > dst_bytes:
+        return Refusal(DST_TOO_SMALL, int(np.flatnonzero(offsets[1:] > dst_bytes)[0]))
+    event = np.searchsorted(first, np.arange(n), side="right") - 1
+    pos = before[:-1] + 8 * (event + 1)
+    events = np.zeros(int(offsets[-1]), np.uint8)
+    heads = np.zeros((n_events, 8), np.uint8)
+    heads[:, 0:4] = be_bytes(np.diff(offsets), 4)
+    heads[:, 4] = (E.PROTOCOL_VERSION << 6) | (event_type or E.EVENT_TYPE_STORAGE)
+    heads[:, 5] = 2
+    scatter_frames(events, offsets[:-1], heads)
+    f = np.asarray(flags).astype(np.int64) & 0x1F if flags is not None else np.zeros(n, np.int64)
+    frames = np.zeros((n, 72), np.uint8)
+    frames[:, 0:4] = be_bytes((f << 27) | ((72 + size) // 4), 4)
+    frames[:, 4] = ((storage_protocol_version & 3) << 4) | 3
+    frames[:, 5] = types
+    frames[:, 6:8] = be_bytes(np.full(n, int(partition_id)), 2)
+    frames[:, 8:12] = be_bytes((int(journal_pos) + 60 * np.arange(n, dtype=np.int64)) // 4, 4)
+    frames[:, 12:] = recs
+    scatter_frames(events, pos, frames)
+    # the DATA records, whole, as dwords: they start on multiples of 8 of the
+    # file and their sizes are word counts (the window may start anywhere)
+    owner, to = byte_runs((pos[where] + 72) // 4, rec // 4)
+    within = to - ((pos[where] + 72) // 4)[owner]
+    source = at[owner] + 4 * within
+    dwords = np.stack([data[source + k] for k in range(4)], axis=1)
+    events.view(np.uint32)[to] = np.ascontiguousarray(dwords).view(np.uint32)[:, 0]
+    expected = np.zeros(n, np.uint32)
+    expected[where] = _be32s(recs[where, 52:56])
+    if record_crcs is not None:
+        crcs = np.array(record_crcs, np.uint32)
+        assert crcs.size == n and not crcs[~is_data].any()
+    else:
+        crcs = np.zeros(n, np.uint32)
+        crcs[where] = [crc32c(data[a:a + ln].tobytes())
+                       for a, ln in zip((at + hs + opt).tolist(), length.tolist())]
+    wrong = np.flatnonzero(is_data & (expected != crcs))
+    result = dict(n_events=n_events, n_msgs=n, n_data=int(where.size),
+                  total_bytes=int(offsets[-1]), n_bad=int(wrong.size),
+                  first_bad=int(wrong[0]) if wrong.size else n, refused_kind=0, refused_index=0)
+    return Packed(events, offsets.astype(np.uint64), types, crcs, expected, result)

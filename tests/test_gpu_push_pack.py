@@ -23,6 +23,8 @@ import push_pack_model as M
 import put_pack_model as P
 import put_unpack_model as PU
 import device_views as V
+import record_pool as R
+import test_grid_regimes as G
 
 pytestmark = pytest.mark.gpu
 
@@ -112,8 +114,9 @@ def _raw(cuda, run, data, kw, sync=True, stream=None, skip=(), phases=None):
         if kw["dst_bytes"] is not None and place is not None:
             arr["dst"] = place.fill("dst", kw["dst_bytes"] + SLACK, np.uint8, SENTINEL)
         elif kw["dst_bytes"] is not None:
-            arr["dst"] = torch.full((kw["dst_bytes"] + SLACK,), SENTINEL, dtype=torch.uint8,
-                                    device=cuda)
+            # (`dst_alloc`: a destination declared shorter than its allocation)
+            size = max(kw["dst_bytes"], kw.get("dst_alloc", 0))
+            arr["dst"] = torch.full((size + SLACK,), SENTINEL, dtype=torch.uint8, device=cuda)
         for name, dt in NP.items():
             if name in skip:
                 continue
@@ -713,3 +716,372 @@ def test_put_in_to_push_out_on_one_device(cuda):
         assert m["payload"] == buf[at:at + ln].tobytes()
         assert m["guid"] == pm["guids"][i].tobytes() and m["queue_id"] == int(pm["queue_ids"][i])
     assert np.array_equal(p.crcs.cpu().numpy().view(np.uint32), pm["crcs"])
+
+
+# ---- past one tile per block ----------------------------
+#
+# N_FRAME messages over record_pool.py's journal of N_FRAME records: message m
+# names MESSAGE record msgs[(m * STEP + 5) % len(msgs)], so neighbours name
+# records far apart and past len(msgs) messages the records repeat; the smaller
+# sizes are prefixes.  Messages LONG_MESSAGES name the two records longer than a
+# chunk of the copy instead.  Queue ids, RDA counters and sub-queue ids are
+# random, the flags 0 or 4.  The expected bytes are push_events_fast's, which
+# test_push_pack_model.py holds to the loop model and to PushEventBuilder.  A
+# model is built for the case that needs it and dropped with it.
+
+LONG_MESSAGES = (1024 + 476, 70 * 2048 + 1024 + 300)    # second tiles of blocks 0 and 70 at N_TILES
+
+
+@functools.lru_cache(maxsize=None)
+def _large_inputs():
+    """(records, queue_ids, flags, rda, sub_ids, application bytes) of N_FRAME
+    messages.  Shared, never modified."""
+    n = G.N_FRAME
+    rng = np.random.default_rng(31)
+    p = R.pool()
+    records = R.push_records(n).astype(np.uint32)
+    records[list(LONG_MESSAGES)] = p.long
+    qids = rng.integers(-2**31, 2**31, size=n, dtype=np.int64).astype(np.int32)
+    qids[rng.integers(0, n, size=3000)] = np.tile(np.array([-1, -2**31, 2**31 - 1], np.int32), 1000)
+    flags = (4 * rng.integers(0, 2, size=n)).astype(np.uint8)
+    rda = rng.integers(0, 256, size=n, dtype=np.uint8)
+    sub = rng.integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32)
+    by_record = np.zeros(n, np.int64)
+    by_record[p.msgs] = R.data_fields(p.run, p.data, p.msgs)[3]
+    out = (records, qids, flags, rda, sub, by_record[records])
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def _split(n, how):
+    """event_first of n messages: events of 3, every message its own event, one
+    event (None), or test_grid_regimes.py's split at the seal's boundary."""
+    if how == "of_3":
+        return np.array(G.events_of_3(n), np.uint64)
+    if how == "own":
+        return np.arange(n + 1, dtype=np.uint64)
+    if how == "boundary":
+        return np.array(G.boundary_split(n, G.regime(n).per_block), np.uint64)
+    assert how is None
+    return None
+
+
+def _large_kw(n, mode, how, **changes):
+    records, qids, flags, rda, sub, _ = _large_inputs()
+    kw = _kw(n, queue_ids=qids[:n], records=records[:n], flags=flags[:n], option_mode=mode,
+             rda=rda[:n] if mode in (1, 3) else None, sub_ids=sub[:n] if mode in (2, 3) else None,
+             event_first=_split(n, how), dst_bytes="room")
+    kw.update(changes)
+    return kw
+
+
+def _fast(run, d, kw, **changes):
+    """push_events_fast's answer to the call `kw`, the CRCs taken from the
+    pool's (`run` is the pool's journal)."""
+    kw = dict(kw, **changes)
+    kw.pop("dst_alloc", None)
+    return M.push_events_fast(run, d, record_crcs=R.pool().crcs, **kw)
+
+
+def _event_offsets(n, mode, first):
+    length = _large_inputs()[5][:n]
+    before = np.concatenate([[0], np.cumsum(32 + M.OPTION_BYTES[mode] + length + 4 - length % 4)])
+    first = np.asarray(first if first is not None else [0, n]).astype(np.int64)
+    return 8 * np.arange(first.size) + before[first]
+
+
+def _exact(cuda, run, d, kw, want, **how):
+    """The call into a destination of exactly the model's size."""
+    return _check(cuda, run, d, dict(kw, dst_bytes=want.result["total_bytes"]), model=want, **how)
+
+
+LARGE = {"waves-no_option-events_of_3": (G.N_WAVES, 0, "of_3"),
+         "full-packed_rda-one_event": (G.N_FULL, 1, None),
+         "tiles-sub_queue_info-own_events": (G.N_TILES, 3, "own"),
+         "frame-sub_queue_info-own_events": (G.N_FRAME, 3, "own"),
+         "frame-packed_rda-seal_boundary": (G.N_FRAME, 1, "boundary")}
+
+
+@pytest.mark.parametrize("name", sorted(LARGE))
+def test_past_one_tile_per_block(cuda, name):
+    # N_WAVES: 66 blocks, the 8-dword header loop in its second step.  N_FULL:
+    # all 256 blocks under one event.  N_TILES: two tiles a block; with an
+    # event per message seal_offsets searches event_first in global memory.
+    # N_FRAME: three tiles a block, the 11-dword header loop in its twelfth
+    # step, the per-message loop of k_ppk_frame in its second (message
+    # 524,288), records named a second time; the boundary split is one event
+    # past the seal's LDS array from block SEAL_BLOCK on.
+    n, mode, how = LARGE[name]
+    p = R.pool()
+    r = G.regime(n)
+    assert r.dwords_past_grid and r.cross_wave and r.units_past_grid == (n == G.N_FRAME)
+    kw = _large_kw(n, mode, how)
+    want = _fast(p.run, p.data, kw)
+    assert want.result["n_bad"] == 0 and sorted(set(kw["flags"].tolist())) == [0, 4]
+    assert {-1, -2**31, 2**31 - 1} <= set(kw["queue_ids"].tolist())
+    if n >= G.N_TILES:
+        assert want.lengths[list(LONG_MESSAGES)].tolist() == list(R.LONG)
+    if n == G.N_FRAME:
+        assert np.array_equal(kw["records"][p.msgs.size + 5000:], kw["records"][5000:n - p.msgs.size])
+    m, _ = _exact(cuda, p.run, p.data, kw, want)
+    assert m is want
+
+
+def test_past_one_tile_per_block_on_a_side_stream(cuda):
+    import torch
+    p = R.pool()
+    kw = _large_kw(G.N_TILES, 2, "of_3")
+    want = _fast(p.run, p.data, kw)
+    torch.cuda.synchronize(cuda)
+    s = _side_stream(cuda)
+    with torch.cuda.stream(s):
+        _exact(cuda, p.run, p.data, kw, want, sync=False, stream=s)
+
+
+def test_past_one_tile_per_block_without_a_gather(cuda):
+    # records == NULL over a journal of MESSAGE records alone, n_records == n
+    n = G.N_TILES
+    p = R.pool()
+    run = R.message_journal()
+    assert run.size == 60 * n
+    kw = _large_kw(n, 1, "of_3", records=None)
+    want = M.push_events_fast(run, p.data, record_crcs=p.crcs[p.msgs[:n]], **kw)
+    named = M.push_events_fast(p.run, p.data, record_crcs=p.crcs, **dict(kw, records=p.msgs[:n]))
+    assert np.array_equal(want.events, named.events) and want.result == named.result
+    assert int(want.lengths.max()) == R.LONG[0] and want.result["n_bad"] == 0
+    _exact(cuda, run, p.data, kw, want)
+
+
+def test_past_one_tile_per_block_in_a_window(cuda):
+    p = R.pool()
+    kw = _large_kw(G.N_TILES, 2, "of_3", data_file_pos=40)
+    want = _fast(p.run, p.data[40:], kw)
+    whole = _fast(p.run, p.data, dict(kw, data_file_pos=0))
+    assert np.array_equal(want.events, whole.events) and want.result == whole.result
+    _exact(cuda, p.run, p.data[40:], kw, want)
+
+
+@pytest.mark.parametrize("n,mode,how", [(G.N_TILES, 2, "of_3"), (G.N_FRAME, 3, "own")],
+                         ids=["tiles-events_of_3", "frame-own_events"])
+def test_size_only_past_one_tile_per_block(cuda, n, mode, how):
+    # k_ppk_seal's own block_prefix and its own loop over n_events + 1 entries:
+    # three steps at N_FRAME, with bpre[f / per_block] for blocks past the 64th.
+    # DST_TOO_SMALL does not apply: the call declares no destination at all
+    p = R.pool()
+    kw = _large_kw(n, mode, how)
+    full = _fast(p.run, p.data, kw)
+    sized = _fast(p.run, p.data, kw, dst_bytes=None)
+    assert isinstance(sized, M.Packed) and sized.result == dict(full.result, n_bad=0, first_bad=n)
+    assert np.array_equal(sized.event_offsets, full.event_offsets)
+    assert np.array_equal(full.event_offsets, _event_offsets(n, mode, kw["event_first"]))
+    for sync in (True, False):
+        m, host = _check(cuda, p.run, p.data, dict(kw, dst_bytes=None), sync=sync, model=sized)
+        assert "dst" not in host and _untouched("out", host["out"]) and \
+            _untouched("lengths", host["lengths"])
+        assert np.array_equal(host["event_offsets"][:len(full.event_offsets)], full.event_offsets)
+    # then the full call into exactly that many bytes
+    _exact(cuda, p.run, p.data, kw, full)
+
+
+def test_stored_crc_mismatches_in_every_step_of_the_frame_loop(cuda):
+    # the stored CRCs (journal bytes 52..55) flipped of the records that
+    # messages 999, 1,999, ..., message 1,003 of the same wave and message
+    # 524,288 name, which a frame thread reaches in its second step alone; a
+    # record named twice mismatches twice
+    n = G.N_FRAME
+    p = R.pool()
+    kw = _large_kw(n, 3, "own")
+    records = kw["records"].astype(np.int64)
+    chosen = np.concatenate([np.arange(999, n, 1000), [1003, n - 1]])
+    assert 999 // 64 == 1003 // 64 and n - 1 == 524288
+    victims = np.unique(records[chosen])
+    bad = p.run.copy()
+    bad[60 * victims[:, None] + 52 + np.arange(4)] ^= np.array([0x80, 1, 0, 0x10], np.uint8)
+    wrong = np.flatnonzero(np.isin(records, victims))
+    assert wrong.size > chosen.size and wrong[0] <= 999 and wrong[-1] == n - 1
+    want = _fast(bad, p.data, kw)
+    assert (want.result["n_bad"], want.result["first_bad"]) == (wrong.size, int(wrong[0]))
+    m, host = _exact(cuda, bad, p.data, kw, want)
+    assert np.array_equal(np.flatnonzero(host["out"][:n] != want.expected), wrong)
+    # delivered all the same: the bytes are those of the clean journal's call
+    clean = _fast(p.run, p.data, kw)
+    assert np.array_equal(host["dst"][:clean.events.size], clean.events)
+
+
+def _refused_both_ways(cuda, run, d, kw, want):
+    """The call refused as `want`, synchronous and asynchronous, into a
+    destination that would hold every event, with nothing written."""
+    n = len(kw["queue_ids"])
+    room = int(_event_offsets(n, kw["option_mode"], kw["event_first"])[-1])
+    kw = dict(kw, dst_alloc=room)
+    if kw["dst_bytes"] == "room":
+        kw["dst_bytes"] = room
+    for sync in (True, False):
+        m, _ = _check(cuda, run, d, kw, sync=sync, model=want)
+        assert m == want
+
+
+def _loop_model(run, d, kw, lo, hi):
+    """M.pack over messages [lo, hi) alone, as one event."""
+    part = {k: (v[lo:hi] if k in ("queue_ids", "records", "flags", "rda", "sub_ids")
+                and v is not None else v) for k, v in kw.items()}
+    part.pop("dst_alloc", None)
+    return M.pack(run, d, crc32c=CRC, **dict(part, event_first=None, dst_bytes=1 << 40))
+
+
+def test_message_refusals_across_tiles_and_blocks(cuda):
+    n = G.N_TILES
+    p = R.pool()
+    r = G.regime(n)
+    assert (r.nblocks, r.per_block) == (129, 2048) and p.run.size == 60 * G.N_FRAME
+    kw = _large_kw(n, 3, "of_3")
+    # (a) records[m] = n_records at message 1,024 + 5, in the second tile of
+    # block 0, and at message 2,048 + 3, in the first tile of block 1: the lower
+    records = kw["records"].copy()
+    records[[1029, 2051]] = G.N_FRAME
+    bad = dict(kw, records=records)
+    want = M.Refusal(M.RECORD_INDEX, 1029)
+    assert _loop_model(p.run, p.data, bad, 0, 2100) == want
+    _refused_both_ways(cuda, p.run, p.data, bad, want)
+    # (b) the last padding byte of the DATA record of a message below 100 made
+    # 9, and message 200,001 naming a CONFIRM record: the lower kind wins over
+    # the lower index.  (A message of 9 bytes or more with its padding: a check
+    # that lets it pass still finds a length inside the record)
+    early = kw["records"][:100].astype(np.int64)
+    at, lead, rec, length, _ = R.data_fields(p.run, p.data, early)
+    victim = int(np.flatnonzero(rec - lead >= 16)[3])
+    assert int((kw["records"][:n] == early[victim]).sum()) == 1
+    data = p.data.copy()
+    data[int(at[victim] + rec[victim]) - 1] = 9
+    want = M.Refusal(M.DATA_RECORD, victim)
+    assert _loop_model(p.run, data, kw, 0, 100) == want
+    _refused_both_ways(cuda, p.run, data, kw, want)
+    confirm = int(np.flatnonzero(p.run.reshape(-1, 60)[:, 0] >> 4 == S.REC_CONFIRM)[1000])
+    records = kw["records"].copy()
+    records[200001] = confirm
+    bad = dict(kw, records=records)
+    assert _loop_model(p.run, data, bad, 200001, 200002) == M.Refusal(M.RECORD, 0)
+    _refused_both_ways(cuda, p.run, data, bad, M.Refusal(M.RECORD, 200001))
+    # (c) the flags of the last message of the last block, the 1,025th of block 128
+    assert n - 1 - (r.nblocks - 1) * r.per_block == 1024
+    flags = kw["flags"].copy()
+    flags[n - 1] = 1
+    bad = dict(kw, flags=flags)
+    assert _loop_model(p.run, p.data, bad, n - 50, n) == M.Refusal(M.FLAGS, 49)
+    _refused_both_ways(cuda, p.run, p.data, bad, M.Refusal(M.FLAGS, n - 1))
+
+
+def test_payload_cap_at_the_long_message_of_a_second_tile(cuda):
+    n = G.N_TILES
+    p = R.pool()
+    kw = _large_kw(n, 1, "of_3")
+    visit = int(np.flatnonzero(kw["records"] == p.long[0])[0])
+    assert visit == LONG_MESSAGES[0] and 1024 <= visit < 2048
+    want = M.Refusal(M.PAYLOAD_TOO_BIG, visit)
+    cap = R.LONG[0]
+    assert _loop_model(p.run, p.data, dict(kw, max_payload_bytes=cap - 1), 0, 1600) == want
+    assert _fast(p.run, p.data, kw, max_payload_bytes=cap - 1) == want
+    _refused_both_ways(cuda, p.run, p.data, dict(kw, max_payload_bytes=cap - 1), want)
+    # the cap exactly the longest message
+    kw["max_payload_bytes"] = cap
+    _exact(cuda, p.run, p.data, kw, _fast(p.run, p.data, kw))
+
+
+def _shape_refusal(first, n):
+    """The lowest entry of event_first that breaks its shape."""
+    first = np.asarray(first).astype(np.int64)
+    bad = np.concatenate([first[:-1] >= first[1:], [first[-1] != n]])
+    bad[0] |= first[0] != 0
+    return M.Refusal(M.EVENT_FIRST, int(np.flatnonzero(bad)[0]))
+
+
+def test_event_first_refused_in_a_late_step_of_the_shape_loop(cuda):
+    # one event per message at N_FRAME: 175,104 threads over 524,290 entries.
+    # Every bad entry is itself an index below n
+    n = G.N_FRAME
+    p = R.pool()
+    threads = G.regime(n).nblocks * 1024
+    assert 2 * threads < n < 3 * threads
+    kw = _large_kw(n, 0, "own")
+    good = kw["event_first"]
+    room = int(_event_offsets(n, 0, good)[-1])
+
+    def refused(index, entries):
+        first = good.copy()
+        for e, v in entries.items():
+            first[e] = v
+        assert int(first.max()) <= n and all(v < n for v in entries.values())
+        want = M.Refusal(M.EVENT_FIRST, index)
+        assert _shape_refusal(first, n) == want
+        for sync in (True, False):
+            m, _ = _check(cuda, p.run, p.data, dict(kw, event_first=first, dst_bytes=room),
+                          sync=sync, model=want)
+            assert m == want
+
+    late = 2 * threads + 50000            # read in the third step alone
+    refused(late, {late: late + 1})       # equal to the next entry
+    # the last entry is n - 1, not n: the entry before it is then not below
+    # it either, and is the one named
+    refused(n - 1, {n: n - 1})
+    # a high entry of an early thread's third step, a lower one of a later
+    # thread's second step: the lower index
+    high, low = 2 * threads + 10, threads + 170000
+    refused(low, {high: high + 1, low: low + 1})
+
+
+def test_event_size_cap_past_one_tile_per_block(cuda):
+    # events of 3 at N_TILES but for two of 3,000 and 6,000 messages, whose
+    # first messages lie in the second tiles of blocks 70 and 100
+    n = G.N_TILES
+    p = R.pool()
+    per_block = G.regime(n).per_block
+    ia, ib = 70 * per_block + 1102, 100 * per_block + 1024
+    cuts = [c for c in G.events_of_3(n) if not ia < c < ia + 3000 and not ib < c < ib + 6000]
+    ea, eb = cuts.index(ia), cuts.index(ib)
+    for i in (ia, ib):
+        assert i % 3 == 0 and i % per_block >= 1024 and i // per_block in (70, 100)
+    kw = _large_kw(n, 2, None, event_first=np.array(cuts, np.uint64))
+    sizes = np.diff(_event_offsets(n, 2, cuts))
+    order = np.argsort(sizes)
+    assert [int(e) for e in order[-2:]] == [ea, eb] and sizes[order[-3]] < sizes[ea] - 4 and \
+        sizes[ea] < sizes[eb] - 4
+    # one event over the cap, then two: the lower index
+    for cap, event in ((int(sizes[eb]) - 4, eb), (int(sizes[ea]) - 4, ea)):
+        want = M.Refusal(M.EVENT_TOO_BIG, event)
+        assert _fast(p.run, p.data, kw, max_event_bytes=cap) == want
+        _refused_both_ways(cuda, p.run, p.data, dict(kw, max_event_bytes=cap), want)
+        # the size-only call refuses alike
+        for sync in (True, False):
+            _check(cuda, p.run, p.data, dict(kw, max_event_bytes=cap, dst_bytes=None), sync=sync,
+                   model=want)
+    # the cap exactly the largest event
+    kw["max_event_bytes"] = int(sizes[eb])
+    _exact(cuda, p.run, p.data, kw, _fast(p.run, p.data, kw))
+
+
+def test_destination_size_past_one_tile_per_block(cuda):
+    n = G.N_TILES
+    p = R.pool()
+    kw = _large_kw(n, 3, "of_3")
+    ev = _event_offsets(n, 3, kw["event_first"])
+    total, n_events = int(ev[-1]), ev.size - 1
+    want = M.Refusal(M.DST_TOO_SMALL, n_events - 1)
+    assert _fast(p.run, p.data, kw, dst_bytes=total - 4) == want
+    _refused_both_ways(cuda, p.run, p.data, dict(kw, dst_bytes=total - 4), want)
+    # half the image: the first event that ends past it, while every later one
+    # refuses as well
+    want = _fast(p.run, p.data, kw, dst_bytes=total // 2)
+    assert want.kind == M.DST_TOO_SMALL and n_events // 3 < want.index < 2 * n_events // 3
+    assert ev[want.index] <= total // 2 < ev[want.index + 1]
+    _refused_both_ways(cuda, p.run, p.data, dict(kw, dst_bytes=total // 2), want)
+    # one event per message at N_FRAME: some 260,000 events refuse, over three
+    # steps of every block of the check grid
+    n = G.N_FRAME
+    kw = _large_kw(n, 0, "own")
+    ev = _event_offsets(n, 0, kw["event_first"])
+    half = int(ev[-1]) // 2
+    index = int(np.searchsorted(ev[1:], half, side="right"))
+    assert ev[index] <= half < ev[index + 1] and n - index > 200000
+    _refused_both_ways(cuda, p.run, p.data, dict(kw, dst_bytes=half),
+                       M.Refusal(M.DST_TOO_SMALL, index))

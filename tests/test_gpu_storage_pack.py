@@ -21,8 +21,10 @@ from blazingmq_amd import synth
 import device_views as V
 import put_pack_model as P
 import put_unpack_model as PU
+import record_pool as R
 import storage_pack_cases as C
 import storage_pack_model as M
+import test_grid_regimes as G
 from records_pack_model import random_meta
 
 pytestmark = pytest.mark.gpu
@@ -104,8 +106,9 @@ def _raw(cuda, run, data, kw, sync=True, stream=None, skip=(), phases=None):
         if place is not None:
             arr = {"dst": place.fill("dst", kw["dst_bytes"] + SLACK, np.uint8, SENTINEL)}
         else:
-            arr = {"dst": torch.full((kw["dst_bytes"] + SLACK,), SENTINEL, dtype=torch.uint8,
-                                     device=cuda)}
+            # (`dst_alloc`: a destination declared shorter than its allocation)
+            size = max(kw["dst_bytes"], kw.get("dst_alloc", 0))
+            arr = {"dst": torch.full((size + SLACK,), SENTINEL, dtype=torch.uint8, device=cuda)}
         for name, dt in NP.items():
             if name in skip:
                 continue
@@ -585,3 +588,327 @@ def test_a_partitions_whole_life_on_one_device(cuda):
         if corrupt:
             index = int(u.record_index[res["first_bad"]].item())
             assert list(want["bad_record_offsets"]) == [JH + 60 * index] and index == victim + 1
+
+
+# ---- past one tile per block ----------------------------
+#
+# One run of N_FRAME records (record_pool.py: all five record types and four
+# queue ops in every block, DATA records of varied sizes behind headers of 12
+# to 28 bytes, two messages longer than a chunk of the copy), written once; the
+# smaller sizes are its prefixes.  The expected bytes are storage_events_fast's,
+# which test_storage_pack_model.py holds to the loop model and to
+# StorageEventBuilder.  A model is built for the case that needs it and dropped
+# with it: an image is up to 61 MB.
+
+def _split(n, how):
+    """event_first of n records: events of 3, every record its own event, one
+    event (None), or test_grid_regimes.py's split at the seal's boundary."""
+    if how == "of_3":
+        return np.array(G.events_of_3(n), np.uint64)
+    if how == "own":
+        return np.arange(n + 1, dtype=np.uint64)
+    if how == "boundary":
+        return np.array(G.boundary_split(n, G.regime(n).per_block), np.uint64)
+    assert how is None
+    return None
+
+
+def _fast(run, d, kw, **changes):
+    """storage_events_fast's answer to the call `kw` with room to spare, the
+    CRCs taken from the pool's."""
+    kw = dict(kw, **changes)
+    kw.pop("dst_alloc", None)
+    if kw["dst_bytes"] is None:
+        del kw["dst_bytes"]
+    return M.storage_events_fast(run, d, record_crcs=R.pool().crcs[:len(run) // 60], **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def _message_bytes():
+    """72 + the DATA record's bytes of every record of the pool."""
+    p = R.pool()
+    size = np.full(G.N_FRAME, 72, np.int64)
+    size[p.msgs] += R.data_fields(p.run, p.data, p.msgs)[2]
+    size.setflags(write=False)
+    return size
+
+
+def _event_offsets(n, first):
+    before = np.concatenate([[0], np.cumsum(_message_bytes()[:n])])
+    first = np.asarray(first).astype(np.int64)
+    return 8 * np.arange(first.size) + before[first]
+
+
+def _large_case(name):
+    """(records, DATA file as passed, keywords) of a large success case."""
+    n, how, changes = {
+        "waves-events_of_3-flags": (G.N_WAVES, "of_3", {}),
+        "full-one_event-header_fields": (G.N_FULL, None, dict(
+            event_type=E.EVENT_TYPE_PARTITION_SYNC, storage_protocol_version=2,
+            partition_id=65535)),
+        "tiles-own_events": (G.N_TILES, "own", {}),
+        "tiles-window": (G.N_TILES, "of_3", dict(data_file_pos=40)),
+        "tiles-largest_journal_pos": (G.N_TILES, "of_3", dict(
+            journal_pos=4 * ((1 << 32) - 1) - 60 * G.N_TILES)),
+        "frame-own_events": (G.N_FRAME, "own", {}),
+        "frame-events_of_3": (G.N_FRAME, "of_3", {}),
+        "frame-seal_boundary": (G.N_FRAME, "boundary", {}),
+    }[name]
+    run, d = R.records(n)
+    if name.startswith("waves"):
+        # eight random bits a record: the low five are sent
+        changes["flags"] = np.random.default_rng(30).integers(0, 256, size=n, dtype=np.uint8)
+    kw = _kw(run, d, event_first=_split(n, how), **changes)
+    return run, d[kw["data_file_pos"]:], kw
+
+
+LARGE = ["waves-events_of_3-flags", "full-one_event-header_fields", "tiles-own_events",
+         "tiles-window", "tiles-largest_journal_pos", "frame-own_events", "frame-events_of_3",
+         "frame-seal_boundary"]
+
+
+@pytest.mark.parametrize("name", LARGE)
+def test_past_one_tile_per_block(cuda, name):
+    # N_WAVES: 66 blocks, the 18-dword frame loop in its third step.  N_FULL:
+    # all 256 blocks under one event.  N_TILES: two tiles a block; with an
+    # event per record a block spans 2,048 events and seal_offsets searches
+    # event_first in global memory.  N_FRAME: three tiles a block, the
+    # per-record loop of k_spk_frame in its second step (record 524,288), three
+    # steps of the shape check and of events_check and two of event_headers;
+    # events of 3 fill the seal's LDS array exactly, the boundary split is one
+    # event past it from block SEAL_BLOCK on.
+    run, d, kw = _large_case(name)
+    n = len(run) // 60
+    r = G.regime(n)
+    assert r.dwords_past_grid and r.cross_wave and r.units_past_grid == (n == G.N_FRAME)
+    want = _fast(run, d, kw)
+    assert want.result["n_bad"] == 0 and want.result["n_data"] == int((R.pool().msgs < n).sum())
+    assert sorted(set(want.types.tolist())) == [1, 2, 3, 4, 5, 6]
+    if name == "tiles-largest_journal_pos":
+        at = int(want.event_offsets[-2]) + 8 + int(_message_bytes()[n - 3:n - 1].sum())
+        assert want.events[at + 8:at + 12].tolist() == [0xFF, 0xFF, 0xFF, 0xF0]
+    if name.startswith("waves"):
+        assert int((kw["flags"] > 31).sum()) > n // 2
+    m, _ = _check(cuda, run, d, kw, model=want)
+    assert m is want
+
+
+def test_past_one_tile_per_block_on_a_side_stream(cuda):
+    import torch
+    run, d = R.records(G.N_TILES)
+    kw = _kw(run, d, event_first=_split(G.N_TILES, "of_3"))
+    want = _fast(run, d, kw)
+    torch.cuda.synchronize(cuda)
+    s = _side_stream(cuda)
+    with torch.cuda.stream(s):
+        _check(cuda, run, d, kw, sync=False, stream=s, model=want)
+
+
+def test_stored_crc_mismatches_in_every_step_of_the_frame_loop(cuda):
+    # the stored CRC (journal bytes 52..55) of the MESSAGE record nearest to
+    # records 999, 1,999, ... flipped, of its next MESSAGE record in the same
+    # wave for the first, and of record 524,288, which a frame thread reaches
+    # in its second step alone
+    n = G.N_FRAME
+    run, d = R.records(n)
+    msgs = R.pool().msgs
+    at = np.searchsorted(msgs, np.arange(999, n, 1000))
+    at = np.unique(np.concatenate([at[at < msgs.size], [at[0] + 1, msgs.size - 1]]))
+    victims = msgs[at]
+    assert victims[0] // 64 == victims[1] // 64 == 999 // 64 and victims[-1] == n - 1 == 524288
+    assert victims.size == 526 and int(np.abs(victims[2:-1] - np.arange(1999, n, 1000)).max()) < 8
+    bad = run.copy()
+    bad[60 * victims[:, None] + 52 + np.arange(4)] ^= np.array([0x80, 1, 0, 0x10], np.uint8)
+    kw = _kw(run, d, event_first=_split(n, "own"))
+    want = _fast(bad, d, kw)
+    assert (want.result["n_bad"], want.result["first_bad"]) == (526, int(victims[0]))
+    m, host = _check(cuda, bad, d, kw, model=want)
+    assert np.array_equal(np.flatnonzero(host["out"][:n] != want.expected), victims)
+    # sent as stored: record i's bytes 52..55 behind event i's EventHeader and
+    # the StorageHeader
+    sent = host["dst"][want.event_offsets[victims].astype(np.int64)[:, None] + 8 + 12 + 52 +
+                       np.arange(4)]
+    assert np.array_equal(sent, bad.reshape(-1, 60)[victims, 52:56])
+    assert not np.array_equal(sent, run.reshape(-1, 60)[victims, 52:56])
+
+
+def _refused_both_ways(cuda, run, d, kw, want):
+    """The call refused as `want`, synchronous and asynchronous, into a
+    destination that would hold every event, with nothing written."""
+    n = len(run) // 60
+    first = kw["event_first"]
+    room = int(_event_offsets(n, first if first is not None else [0, n])[-1])
+    kw = dict(kw, dst_alloc=room)
+    if kw["dst_bytes"] is None:
+        kw["dst_bytes"] = room
+    for sync in (True, False):
+        m, _ = _check(cuda, run, d, kw, sync=sync, model=want)
+        assert m == want
+
+
+def test_record_refusals_across_tiles_and_blocks(cuda):
+    n = G.N_TILES
+    run, d = R.records(n)
+    types = run.reshape(-1, 60)[:, 0] >> 4
+    r = G.regime(n)
+    assert (r.nblocks, r.per_block) == (129, 2048)
+    kw = _kw(run, d, event_first=_split(n, "of_3"))
+    room = dict(dst_bytes=1 << 40, crc32c=CRC)
+    # (a) the magic of record 1,024 + 5, in the second tile of block 0, and of
+    # record 2,048 + 3, in the first tile of block 1: the lower one
+    bad = run.copy()
+    for i in (1029, 2051):
+        bad[60 * i + 59] ^= 0xFF
+    want = M.Refusal(M.RECORD_HEADER, 1029)
+    assert M.pack(bad[:60 * 2100], d, **dict(_kw(run, d), **room)) == want
+    _refused_both_ways(cuda, bad, d, kw, want)
+    # (b) the last padding byte of a DATA record below record 100 made 9 and
+    # primaryLeaseId 0 in record 200,001: the lower kind wins over the lower index
+    # (of 9 bytes or more with its padding: a check that lets it pass still
+    # finds a length inside the record)
+    early = R.pool().msgs[:60]
+    at, lead, rec, length, _ = R.data_fields(run, d, early)
+    pick = int(np.flatnonzero(rec - lead >= 16)[3])
+    victim, at, rec = int(early[pick]), at[pick:], rec[pick:]
+    assert 3 < victim < 100
+    data = d.copy()
+    data[int(at[0] + rec[0]) - 1] = 9
+    assert M.pack(run[:60 * 100], data, **dict(_kw(run, d), **room)) == M.Refusal(
+        M.DATA_RECORD, victim)
+    _refused_both_ways(cuda, run, data, kw, M.Refusal(M.DATA_RECORD, victim))
+    bad = run.copy()
+    bad[60 * 200001 + 8:60 * 200001 + 12] = 0
+    _refused_both_ways(cuda, bad, data, kw, M.Refusal(M.RECORD_HEADER, 200001))
+    # (c) the last record of the last block, the 1,025th record of block 128,
+    # and the last MESSAGE record: a data offset of 0
+    last = n - 1
+    assert last - (r.nblocks - 1) * r.per_block == 1024
+    last_msg = int(R.pool().msgs[R.pool().msgs < n][-1])
+    bad = run.copy()
+    C.put32(bad, 60 * last_msg + 32, 0)
+    tail = 60 * (n - 50)
+    assert last_msg >= n - 50
+    assert M.pack(bad[tail:], d, **dict(_kw(run, d), **room)) == M.Refusal(
+        M.DATA_OFFSET, last_msg - (n - 50))
+    _refused_both_ways(cuda, bad, d, kw, M.Refusal(M.DATA_OFFSET, last_msg))
+    if types[last] != S.REC_MESSAGE:
+        bad[60 * last + 59] ^= 0xFF
+        assert M.pack(bad[tail:], d, **dict(_kw(run, d), **room)) == M.Refusal(
+            M.RECORD_HEADER, 49)
+        _refused_both_ways(cuda, bad, d, kw, M.Refusal(M.RECORD_HEADER, last))
+    assert last_msg // r.per_block == r.nblocks - 1
+
+
+def test_payload_cap_at_the_long_message_of_a_second_tile(cuda):
+    n = G.N_TILES
+    run, d = R.records(n)
+    long = R.pool().long[0]
+    size = 60 + int(R.data_fields(run, d, np.array([long]))[2][0])
+    assert size == int(_message_bytes().max()) - 12 and 1024 <= long < 2048
+    kw = _kw(run, d, event_first=_split(n, "of_3"))
+    want = M.Refusal(M.PAYLOAD_TOO_BIG, long)
+    assert M.pack(run[:60 * 1600], d, crc32c=CRC,
+                  **dict(_kw(run, d), dst_bytes=1 << 40, max_payload_bytes=size - 4)) == want
+    assert _fast(run, d, kw, max_payload_bytes=size - 4) == want
+    _refused_both_ways(cuda, run, d, dict(kw, max_payload_bytes=size - 4), want)
+    # the cap exactly the longest message
+    kw["max_payload_bytes"] = size
+    _check(cuda, run, d, kw, model=_fast(run, d, kw))
+
+
+def _shape_refusal(first, n):
+    """The lowest entry of event_first that breaks its shape."""
+    first = np.asarray(first).astype(np.int64)
+    bad = np.concatenate([first[:-1] >= first[1:], [first[-1] != n]])
+    bad[0] |= first[0] != 0
+    return M.Refusal(M.EVENT_FIRST, int(np.flatnonzero(bad)[0]))
+
+
+def test_event_first_refused_in_a_late_step_of_the_shape_loop(cuda):
+    # one event per record at N_FRAME: 175,104 threads over 524,290 entries.
+    # Every bad entry is itself an index below n
+    n = G.N_FRAME
+    run, d = R.records(n)
+    threads = G.regime(n).nblocks * 1024
+    assert 2 * threads < n < 3 * threads
+    good = _split(n, "own")
+
+    def refused(index, entries):
+        first = good.copy()
+        for e, v in entries.items():
+            first[e] = v
+        assert int(first.max()) <= n and all(v < n for v in entries.values())
+        want = M.Refusal(M.EVENT_FIRST, index)
+        assert _shape_refusal(first, n) == want
+        kw = _kw(run, d, event_first=first)
+        room = int(_event_offsets(n, good)[-1])
+        for sync in (True, False):
+            m, _ = _check(cuda, run, d, dict(kw, dst_bytes=room), sync=sync, model=want)
+            assert m == want
+
+    late = 2 * threads + 50000            # read in the third step alone
+    refused(late, {late: late + 1})       # equal to the next entry
+    # the last entry is n - 1, not n: the entry before it is then not below
+    # it either, and is the one named
+    refused(n - 1, {n: n - 1})
+    # a high entry of an early thread's third step, a lower one of a later
+    # thread's second step: the lower index
+    high, low = 2 * threads + 10, threads + 170000
+    refused(low, {high: high + 1, low: low + 1})
+
+
+def test_event_size_cap_past_one_tile_per_block(cuda):
+    # events of 3 at N_TILES but for two of 3,000 and 4,500 records, whose first
+    # records lie in the second tiles of blocks 70 and 100: p0 there is off[f0],
+    # with the tile carry in it, plus bpre[f0 / 2048]
+    n = G.N_TILES
+    per_block = G.regime(n).per_block
+    run, d = R.records(n)
+    ia, ib = 70 * per_block + 1102, 100 * per_block + 1024
+    cuts = [c for c in G.events_of_3(n) if not ia < c < ia + 3000 and not ib < c < ib + 4500]
+    first = np.array(cuts, np.uint64)
+    ea, eb = cuts.index(ia), cuts.index(ib)
+    for i in (ia, ib):
+        assert i % 3 == 0 and i % per_block >= 1024 and i // per_block in (70, 100)
+    sizes = np.diff(_event_offsets(n, first))
+    order = np.argsort(sizes)
+    assert [int(e) for e in order[-2:]] == [ea, eb] and sizes[order[-3]] < sizes[ea] - 4 and \
+        sizes[ea] < sizes[eb] - 4
+    kw = _kw(run, d, event_first=first)
+    # one event over the cap, then two: the lower index
+    for cap, event in ((int(sizes[eb]) - 4, eb), (int(sizes[ea]) - 4, ea)):
+        want = M.Refusal(M.EVENT_TOO_BIG, event)
+        assert _fast(run, d, kw, max_event_bytes=cap) == want
+        _refused_both_ways(cuda, run, d, dict(kw, max_event_bytes=cap), want)
+    # the cap exactly the largest event
+    kw["max_event_bytes"] = int(sizes[eb])
+    _check(cuda, run, d, kw, model=_fast(run, d, kw))
+
+
+def test_destination_size_past_one_tile_per_block(cuda):
+    n = G.N_TILES
+    run, d = R.records(n)
+    first = _split(n, "of_3")
+    ev = _event_offsets(n, first)
+    total, n_events = int(ev[-1]), ev.size - 1
+    kw = _kw(run, d, event_first=first)
+    want = M.Refusal(M.DST_TOO_SMALL, n_events - 1)
+    assert _fast(run, d, kw, dst_bytes=total - 4) == want
+    _refused_both_ways(cuda, run, d, dict(kw, dst_bytes=total - 4), want)
+    # half the image: the first event that ends past it, while every later one
+    # refuses as well
+    want = _fast(run, d, kw, dst_bytes=total // 2)
+    assert want.kind == M.DST_TOO_SMALL and n_events // 3 < want.index < 2 * n_events // 3
+    assert ev[want.index] <= total // 2 < ev[want.index + 1]
+    _refused_both_ways(cuda, run, d, dict(kw, dst_bytes=total // 2), want)
+    # one event per record at N_FRAME: some 260,000 events refuse, over three
+    # steps of every block of the check grid
+    n = G.N_FRAME
+    run, d = R.records(n)
+    first = _split(n, "own")
+    ev = _event_offsets(n, first)
+    half = int(ev[-1]) // 2
+    index = int(np.searchsorted(ev[1:], half, side="right"))
+    assert ev[index] <= half < ev[index + 1] and n - index > 200000
+    kw = _kw(run, d, event_first=first)
+    _refused_both_ways(cuda, run, d, dict(kw, dst_bytes=half), M.Refusal(M.DST_TOO_SMALL, index))

@@ -17,8 +17,9 @@ units.  Above certain sizes the same code runs loops it never enters below:
 `layout_split` is restated here and the four constants are read from the text
 of bmqcrc_internal.h, so a changed constant fails this file instead of letting
 test_gpu_rollover.py, test_gpu_confirm_records.py, test_gpu_copy.py,
-test_gpu_put_pack.py and test_gpu_records_pack.py, which import the sizes
-below, quietly stop reaching their regimes."""
+test_gpu_put_pack.py, test_gpu_records_pack.py, test_gpu_storage_pack.py and
+test_gpu_push_pack.py (with pack_pool.py and record_pool.py, their inputs),
+which import the sizes below, quietly stop reaching their regimes."""
 import collections
 import os
 import re
@@ -145,6 +146,81 @@ def test_what_the_put_and_record_packers_reach():
     per_block = regime(N_TILES).per_block
     assert seal_events() == 1024
     assert per_block - 1 >= seal_events() > (per_block + 2) // 3 + 1
+
+
+def test_what_the_storage_and_push_packers_reach():
+    # test_gpu_storage_pack.py and test_gpu_push_pack.py: their frame kernels
+    # stride over 18 dwords per record and over 8..11 per message
+    k = constants()
+    grid = k["kPackFrameThreads"] * k["kPackFrameBlocks"]
+    assert steps(18 * 29127, grid) == 1 and steps(18 * 29128, grid) == 2    # StorageHeader + record
+    assert steps(8 * 65536, grid) == 1 and steps(8 * 65537, grid) == 2      # PushHeader alone
+    assert steps(11 * 47662, grid) == 1 and steps(11 * 47663, grid) == 2    # with a SubQueueInfo
+    for n in (N_WAVES, N_FULL, N_TILES, N_FRAME):
+        assert steps(18 * n, grid) >= 2 and steps(8 * n, grid) >= 2, n
+    # the per-unit loops of both, and k_ppk_seal's size-only loop over
+    # n_events + 1 entries of the layout grid
+    assert steps(N_TILES, grid) == 1 and steps(N_FRAME, grid) == 2
+    r = regime(N_FRAME)
+    assert steps(N_FRAME + 1, r.nblocks * k["kPackThreads"]) == 3
+    r = regime(N_TILES)
+    assert steps(N_TILES // 3 + 2, r.nblocks * k["kPackThreads"]) == 1
+
+
+def event_of(first, i):
+    """Last e with first[e] <= i, as crc32c_pack_layout.h's event_of finds it."""
+    lo, hi = 0, len(first) - 2
+    while lo < hi:
+        mid = lo + (hi - lo + 1) // 2
+        if first[mid] <= i:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def seal_range(first, n, per_block, block):
+    """(e1 - e0, staged) of seal_offsets for a block that owns units."""
+    lo, hi = block * per_block, min((block + 1) * per_block, n)
+    e0, e1 = event_of(first, lo), event_of(first, hi - 1)
+    return e1 - e0, e0 != e1 and e1 - e0 < seal_events()
+
+
+SEAL_BLOCK = 85      # the block whose first message is an event of its own in boundary_split
+
+
+def events_of_3(n):
+    return list(range(0, n, 3)) + [n]
+
+
+def boundary_split(n, per_block, block=SEAL_BLOCK):
+    """event_first of events of 3 but for one event of 1, the first message of
+    `block`; the last event takes the remainder."""
+    cut = block * per_block
+    assert cut % 3 == 0 and cut + 1 < n
+    return list(range(0, cut, 3)) + list(range(cut, cut + 1)) + list(range(cut + 1, n, 3)) + [n]
+
+
+def test_the_seal_stages_a_block_of_exactly_its_array_and_no_more():
+    r = regime(N_FRAME)
+    assert r.per_block == 3072 == 3 * seal_events() and 0 < SEAL_BLOCK < r.nblocks - 1 == 170
+    full = range(r.nblocks - 1)         # the last block owns 2,049 units
+    first = events_of_3(N_FRAME)
+    for b in full:      # e1 - e0 + 1 entries staged: every LDS entry used
+        assert seal_range(first, N_FRAME, r.per_block, b) == (seal_events() - 1, True), b
+    first = boundary_split(N_FRAME, r.per_block)
+    assert first[0] == 0 and first[-1] == N_FRAME and all(a < b for a, b in zip(first, first[1:]))
+    assert first.count(SEAL_BLOCK * r.per_block) == first.count(SEAL_BLOCK * r.per_block + 1) == 1
+    for b in full:
+        want = (seal_events() - 1, True) if b < SEAL_BLOCK else (seal_events(), False)
+        assert seal_range(first, N_FRAME, r.per_block, b) == want, b
+    assert seal_range(first, N_FRAME, r.per_block, r.nblocks - 1) == (683, True)
+    # and with an event per unit at N_TILES the last block's 1,025 units lie in
+    # exactly kSealEvents + 1 events: not staged either
+    r = regime(N_TILES)
+    assert seal_range(range(N_TILES + 1), N_TILES, r.per_block, r.nblocks - 1) == (
+        seal_events(), False)
+    assert seal_range(range(N_TILES + 1), N_TILES, r.per_block, 0) == (r.per_block - 1, False)
 
 
 def test_layout_split_below_one_grid_of_tiles():

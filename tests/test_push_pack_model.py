@@ -12,6 +12,7 @@ from blazingmq_amd import push_event as E
 from blazingmq_amd import storage as S
 import push_pack_cases as C
 import push_pack_model as M
+import record_pool
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CRC = Crc32c.calculate
@@ -260,3 +261,89 @@ def test_no_message():
     run, d, _ = C.base()
     p = M.pack(run, d, data_file_pos=0, records=[], queue_ids=[], dst_bytes=0, crc32c=CRC)
     assert p.result == M.refused_result(M.Refusal(0, 0), 0) and p.events.size == 0
+
+
+# ---- the numpy-only model of the large GPU cases --------------------------------
+
+N_POOL = 4101        # messages of the pool: four tiles and five messages
+SPLITS = {"own_events": np.arange(N_POOL + 1), "one_event": None,
+          "events_of_3": np.append(np.arange(0, N_POOL, 3), N_POOL),
+          "events_of_1024": np.append(np.arange(0, N_POOL, 1024), N_POOL),
+          "uneven": np.array([0, 1, 2, 1500, 1501, 1502, 3000, 4100, N_POOL])}
+
+
+def _pool_call(mode, with_flags, gather=True):
+    """(journal, DATA file, keywords) of N_POOL messages of the pool; message
+    1,500 and a repeat name the longest record."""
+    rng = np.random.default_rng(77)
+    p = record_pool.pool()
+    records = record_pool.push_records(N_POOL).copy()
+    records[[1500, 2900]] = p.long[0]
+    qids = rng.integers(-2**31, 2**31, size=N_POOL, dtype=np.int64).astype(np.int32)
+    qids[:3] = (-1, -2**31, 2**31 - 1)
+    kw = dict(data_file_pos=0, queue_ids=qids, records=records if gather else None,
+              option_mode=mode, flags=4 * rng.integers(0, 2, size=N_POOL) if with_flags else None,
+              rda=rng.integers(0, 256, size=N_POOL) if mode in (1, 3) else None,
+              sub_ids=rng.integers(0, 1 << 32, size=N_POOL, dtype=np.uint64) if mode in (2, 3)
+              else None)
+    run = p.run if gather else record_pool.message_journal()[:60 * N_POOL]
+    return run, p.data, kw
+
+
+def _same(got, want):
+    assert got.result == want.result
+    for name in ("events", "event_offsets", "crcs", "lengths", "expected"):
+        a, b = getattr(got, name), getattr(want, name)
+        assert a.dtype == b.dtype and np.array_equal(a, b), name
+
+
+@pytest.mark.parametrize("split", sorted(SPLITS))
+@pytest.mark.parametrize("mode", [0, 1, 2, 3])
+@pytest.mark.parametrize("with_flags", [False, True])
+def test_fast_model_is_the_loop_model_and_the_builder(split, mode, with_flags):
+    run, d, kw = _pool_call(mode, with_flags)
+    kw["event_first"] = SPLITS[split]
+    want = M.pack(run, d, crc32c=CRC, dst_bytes=1 << 40, **kw)
+    assert want.result["n_bad"] == 0 and int(want.lengths.max()) == record_pool.LONG[0]
+    _same(M.push_events_fast(run, d, crc32c=CRC, **kw), want)
+    _same(M.push_events_fast(run, d, record_crcs=record_pool.pool().crcs, **kw), want)
+    sized = M.pack(run, d, crc32c=CRC, **dict(kw, dst_bytes=None))
+    _same(M.push_events_fast(run, d, crc32c=CRC, **dict(kw, dst_bytes=None)), sized)
+
+
+@pytest.mark.parametrize("call", ["window", "identity"])
+def test_fast_model_in_a_window_and_without_a_gather(call):
+    run, d, kw = _pool_call(3, True, gather=call != "identity")
+    kw["event_first"] = SPLITS["events_of_3"]
+    if call == "window":
+        kw["data_file_pos"], d = 40, d[40:]
+    want = M.pack(run, d, crc32c=CRC, dst_bytes=1 << 40, **kw)
+    _same(M.push_events_fast(run, d, crc32c=CRC, **kw), want)
+
+
+def test_fast_model_counts_mismatches_and_refuses_like_the_loop_model():
+    run, d, kw = _pool_call(1, True)
+    kw["event_first"] = SPLITS["events_of_3"]
+    bad = run.copy()
+    victims = kw["records"][[5, 700]]
+    kw["records"][3000] = victims[1]               # named twice: counted twice
+    bad[60 * victims[:, None] + 52 + np.arange(4)] ^= 0x5A
+    want = M.pack(bad, d, crc32c=CRC, dst_bytes=1 << 40, **kw)
+    assert (want.result["n_bad"], want.result["first_bad"]) == (3, 5)
+    _same(M.push_events_fast(bad, d, crc32c=CRC, **kw), want)
+    total = want.result["total_bytes"]
+    flags = kw["flags"].copy()
+    flags[[4000, 4100]] = (1, 6)
+    for change in (dict(max_payload_bytes=record_pool.LONG[0]),
+                   dict(max_payload_bytes=record_pool.LONG[0] - 1), dict(max_event_bytes=1000),
+                   dict(dst_bytes=total - 1), dict(dst_bytes=total // 2), dict(dst_bytes=total),
+                   dict(flags=flags), dict(flags=flags, max_payload_bytes=10)):
+        want = M.pack(run, d, crc32c=CRC, **dict(dict(kw, dst_bytes=1 << 40), **change))
+        got = M.push_events_fast(run, d, crc32c=CRC, **dict(kw, **change))
+        if isinstance(want, M.Refusal):
+            assert got == want, change
+        else:
+            assert got.result == want.result, change
+    refused = M.push_events_fast(run, d, crc32c=CRC,
+                                 **dict(kw, max_payload_bytes=record_pool.LONG[0] - 1))
+    assert refused == M.Refusal(M.PAYLOAD_TOO_BIG, 1500)
