@@ -269,3 +269,82 @@ def malformed(name, seed=7):
     else:
         raise KeyError(name)
     return buf, offs
+
+
+# ---- the same without a Python loop per message ---------------------------------
+
+def unpack_fast(src, soff, lens, qids, guids, flags, event_first, crcs, *, stored=None,
+                msg_cap=None, corrupt=None, suspects=()):
+    """(buffer, event offsets, what ``model`` answers) for messages i = the
+    bytes src[soff[i]:soff[i] + lens[i]] with their queue ids, GUIDs and flags,
+    sent in the events ``event_first`` (entries may repeat: an empty event), in
+    numpy alone: the bytes are put_pack_model.model_bytes_fast's, the expected
+    outputs the inputs themselves and put_pack_model.layout's header offsets +
+    36.  ``crcs``: the CRC32C of every message's bytes; ``stored``: what the
+    PutHeaders carry instead.  ``corrupt(buf, offsets)`` may then change the
+    events in place (or return new offsets); the events it touched are to be
+    named in ``suspects``: only those are walked, with ``walk``."""
+    import put_pack_model as P
+    lens = np.asarray(lens, np.int64)
+    n = lens.size
+    first = np.asarray(event_first).astype(np.int64)
+    assert first[0] == 0 and first[-1] == n and bool((np.diff(first) >= 0).all())
+    crcs = np.asarray(crcs, np.uint32)
+    stored = crcs if stored is None else np.asarray(stored, np.uint32)
+    hdr, offs = P.layout(lens, first)
+    buf = P.model_bytes_fast(src, soff, lens, qids, guids, flags, first, stored)
+    offs = offs.astype(np.int64)
+    if corrupt is not None:
+        changed = corrupt(buf, offs)
+        offs = offs if changed is None else np.asarray(changed).astype(np.int64)
+    refused = refused_fast(buf, offs, first, suspects, msg_cap)
+    if refused:
+        return buf, offs, {"refused": refused}
+    return buf, offs, {
+        "refused": None, "n": n, "app_offsets": hdr + P.HDR, "lengths": lens.astype(np.uint32),
+        "queue_ids": np.asarray(qids, np.int32),
+        "guids": np.asarray(guids, np.uint8).reshape(n, 16),
+        "flags": np.asarray(flags, np.uint8) & 0xF, "expected": stored, "crcs": crcs,
+        "event_first": first}
+
+
+def refused_fast(buf, offs, first, suspects=(), msg_cap=None):
+    """The refusal (kind, event, offset) of the events ``unpack_fast`` built,
+    after changes to the events in `suspects`, or None: only those are walked."""
+    first = np.asarray(first).astype(np.int64)
+    refusals = []
+    for e in suspects:      # across events the lowest kind wins, within it the lowest event
+        b, t = int(offs[e]), int(offs[e + 1])
+        if b > t or t > buf.size or b % 4:
+            refusals.append((K_OFFSETS, e, b))
+            continue
+        hdrs, bad = walk(buf[b:t])
+        if bad:
+            refusals.append((bad[0], e, b + bad[1]))
+        else:
+            assert len(hdrs) == first[e + 1] - first[e]
+    if refusals:
+        return min(refusals)
+    if msg_cap is not None and first[-1] > msg_cap:     # the lowest event that ends past msg_cap
+        e = int(np.searchsorted(first[1:], msg_cap, side="right"))
+        return (K_MANY, e, int(offs[e]))
+    return None
+
+
+def spoil(buf, offs, hdr, lens, what, at):
+    """One plant, in place: "offsets" (event `at` starts 2 bytes late),
+    "event_length" (its EventHeader 4 bytes long), "header_words" (message
+    `at`'s PutHeader of 7 words), "padding" (its last padding byte 5)."""
+    if what == "offsets":
+        offs[at] += 2
+    elif what == "event_length":
+        put32(buf, int(offs[at]), int(offs[at + 1] - offs[at]) + 4)
+    elif what == "header_words":
+        buf[int(hdr[at]) + 7] = (int(buf[int(hdr[at]) + 7]) & 0xE0) | 7
+    elif what == "padding":
+        buf[int(hdr[at]) + 36 + int(lens[at]) + 3 - int(lens[at]) % 4] = 5
+    else:
+        raise KeyError(what)
+
+
+PLANTS = ("offsets", "event_length", "header_words", "padding")

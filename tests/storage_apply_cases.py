@@ -240,3 +240,75 @@ def precedence_cases():
         events, offsets, dict(kw, data_file_pos=DATA_POS + 8, journal_dst_bytes=0),
         M.Refusal(6, d_in_0.event, d_in_0.index, d_in_0.header))
     return cases
+
+
+# ---- large inputs: record_pool.py's run through storage_apply_model.apply_fast -----
+#
+# What the cases past one walk grid plant, as (what, where) pairs: a violation
+# of the walk in an event or at a message, or a value the checks behind the
+# walk compare.  `lay` is storage_apply_model.layout_fast's.
+
+WALK_PLANTS = ("offsets", "event_length", "partition", "padding")
+
+
+def spoil(events, offsets, lay, what, at):
+    """One plant, in place.  Of the walk's: "offsets" (event `at` starts 2
+    bytes late), "event_length" (its EventHeader 4 bytes long), "partition"
+    (message `at` names another partition), "padding" (DATA message `at` ends
+    with a padding byte of 9).  Of the checks': "data_offset" (MESSAGE record
+    `at` 8 bytes further in the DATA file), "journal_offset" (message `at` one
+    word further in the journal)."""
+    p = int(lay.pos[at]) if what not in ("offsets", "event_length") else 0
+    if what == "offsets":
+        offsets[at] += 2
+    elif what == "event_length":
+        beg = int(offsets[at])
+        put32(events, beg, int(offsets[at + 1]) - beg + 4)
+    elif what == "partition":
+        events[p + 7] ^= 1
+    elif what == "padding":
+        assert lay.size[at] > 0
+        events[p + 72 + int(lay.size[at]) - 1] = 9
+    elif what == "data_offset":
+        assert lay.size[at] > 0
+        put32(events, p + 12 + 32, M._be32(events, p + 12 + 32) + 1)
+    elif what == "journal_offset":
+        put32(events, p + 8, M._be32(events, p + 8) + 1)
+    else:
+        raise KeyError(what)
+
+
+def planted(lay, plants):
+    """(corrupt, suspects) for apply_fast of the (what, where) pairs `plants`."""
+    def corrupt(events, offsets):
+        for what, at in plants:
+            spoil(events, offsets, lay, what, at)
+    suspects = set()
+    for what, at in plants:
+        if what == "offsets":           # (event at - 1 ends 2 bytes late too)
+            suspects.update({at - 1, at})
+        elif what == "event_length":
+            suspects.add(at)
+        elif what in ("partition", "padding"):
+            suspects.add(int(lay.event[at]))
+    return corrupt, sorted(suspects)
+
+
+def sequence_gap(run, at):
+    """`run` with 1 added to the sequence number of every record from `at` on:
+    record `at` alone no longer follows its predecessor."""
+    recs = np.array(run, np.uint8).reshape(-1, 60)
+    seq = (recs[at:, 2:8].astype(np.int64) << (8 * np.arange(5, -1, -1))).sum(axis=1) + 1
+    recs[at:, 2:8] = (seq[:, None] >> (8 * np.arange(5, -1, -1))) & 0xFF
+    return recs.reshape(-1)
+
+
+def new_lease(run, at):
+    """`run` with the lease id raised by one from record `at` on and the
+    sequence numbers restarting at 1 there."""
+    recs = np.array(run, np.uint8).reshape(-1, 60)
+    lease = M._be32(recs[at], 8) + 1
+    seq = 1 + np.arange(recs.shape[0] - at, dtype=np.int64)
+    recs[at:, 2:8] = (seq[:, None] >> (8 * np.arange(5, -1, -1))) & 0xFF
+    recs[at:, 8:12] = np.frombuffer(int(lease).to_bytes(4, "big"), np.uint8)
+    return recs.reshape(-1)

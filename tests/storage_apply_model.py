@@ -144,6 +144,163 @@ def apply(events, event_offsets, *, partition_id, journal_pos, data_file_pos, le
                    expected, crcs, np.array(first, np.uint64), result)
 
 
+# ---- the same without a Python loop per message ---------------------------------
+
+def _be32_at(buf, at):
+    """The big-endian 32-bit values at the byte positions `at` of buf, as int64."""
+    rows = buf[np.asarray(at, np.int64)[:, None] + np.arange(4)]
+    return np.ascontiguousarray(rows).view(">u4")[:, 0].astype(np.int64)
+
+
+Layout = collections.namedtuple("Layout", "pos offsets size length event data_at")
+
+
+def layout_fast(run, data, event_first):
+    """Where ``storage_events_fast`` puts the records of `run`: Layout(every
+    message's StorageHeader, the event offsets, the DATA record's bytes and the
+    application data's by record (0: not a MESSAGE record), the event of every
+    record, where the first DATA record lies in `data`).  The DATA records lie
+    back to back (asserted)."""
+    import record_pool
+    recs = np.asarray(run, np.uint8).reshape(-1, 60)
+    n = recs.shape[0]
+    first = np.asarray(event_first).astype(np.int64)
+    where = np.flatnonzero(recs[:, 0] >> 4 == 1)
+    at, _, rec, app, _ = record_pool.data_fields(run, data, where)
+    assert where.size == 0 or np.array_equal(at[1:], (at + rec)[:-1])
+    size, length = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    size[where], length[where] = rec, app
+    before = np.concatenate([[0], np.cumsum(72 + size)])
+    event = np.searchsorted(first, np.arange(n), side="right") - 1
+    return Layout(before[:-1] + 8 * (event + 1), 8 * np.arange(first.size) + before[first], size,
+                  length, event, int(at[0]) if where.size else 0)
+
+
+Built = collections.namedtuple("Built", "events run lay types first flags journal_pos partition_id")
+
+
+def build_fast(run, data, event_first, *, journal_pos, partition_id, flags=None):
+    """The events of ``apply_fast`` and where everything lies in them, for
+    ``answer_fast``: built once for the cases that share an input."""
+    import storage_pack_model
+    first = np.asarray(event_first).astype(np.int64)
+    n = np.asarray(run).size // 60
+    packed = storage_pack_model.storage_events_fast(
+        run, data, journal_pos=journal_pos, data_file_pos=0, partition_id=partition_id,
+        event_first=first, flags=flags, record_crcs=np.zeros(n, np.uint32), empty_events=True)
+    lay = layout_fast(run, data, first)
+    assert np.array_equal(lay.offsets, packed.event_offsets.astype(np.int64))
+    assert np.array_equal(np.flatnonzero(packed.types == 1), np.flatnonzero(lay.size))
+    f = np.asarray(flags).astype(np.uint8) & 0x1F if flags is not None else np.zeros(n, np.uint8)
+    return Built(packed.events, np.asarray(run, np.uint8).reshape(-1), lay, packed.types, first, f,
+                 journal_pos, partition_id)
+
+
+def events_with(built, run):
+    """A copy of the built events with the records of `run` that differ from
+    the run they were built of written over theirs (the records' types and
+    DATA offsets stay what they were)."""
+    events = built.events.copy()
+    recs = np.asarray(run, np.uint8).reshape(-1, 60)
+    changed = np.flatnonzero((recs != built.run.reshape(-1, 60)).any(axis=1))
+    events[(built.lay.pos[changed] + 12)[:, None] + np.arange(60)] = recs[changed]
+    return events
+
+
+def answer_fast(built, events, offsets, run, data, *, data_file_pos, lease_id=0, seq=0, msg_cap,
+                journal_dst_bytes, data_dst_bytes, record_crcs, suspects=()):
+    """What ``apply`` answers to `events` / `offsets`: the built ones or a
+    changed copy of them, `run` and `data` being the records and the DATA file
+    they now carry.  Only the events in ``suspects`` are walked."""
+    lay, first = built.lay, built.first
+    pos, size, event = lay.pos, lay.size, lay.event
+    recs = np.asarray(run, np.uint8).reshape(-1, 60)
+    n, n_events = recs.shape[0], first.size - 1
+    where = np.flatnonzero(size)
+    q = np.concatenate([[0], np.cumsum(size)])
+    # the walk: across events the lowest kind wins, within it the lowest event
+    counts = np.diff(first)
+    bad = []
+    for e in suspects:
+        msgs, v = _walk_event(events, int(offsets[e]), int(offsets[e + 1]), built.partition_id)
+        if v:
+            counts[e] = len(msgs)
+            bad.append((v[0], e, v[1]))
+        else:
+            assert len(msgs) == counts[e]
+    if bad:
+        found = np.concatenate([[0], np.cumsum(counts)])
+        kind, e, offset = min(bad)
+        stopped = kind in (STORAGE_HEADER, DATA_RECORD)
+        return Refusal(kind, e, int(found[e + 1] if stopped else found[e]), offset)
+    if n > msg_cap:     # the lowest event whose last message lies past msg_cap
+        e = int(np.searchsorted(first, msg_cap, side="right")) - 1
+        return Refusal(TOO_MANY_MESSAGES, e, int(first[e]), int(offsets[e]))
+    # the checks that need a message's predecessor or the prefix q
+    i = np.arange(n, dtype=np.int64)
+    lease = _be32_at(events, pos + 12 + 8)
+    s = (_be32_at(events, pos + 12) & 0xFFFF) << 32 | _be32_at(events, pos + 12 + 4)
+    before_lease = np.concatenate([[lease_id], lease[:-1]])
+    before_s = np.concatenate([[seq], s[:-1]])
+    sync = (4 * _be32_at(events, pos + 8) == built.journal_pos + 60 * i) & (
+        lease >= before_lease) & ((lease > before_lease) | (s == before_s + 1))
+    sync[where] &= 8 * _be32_at(events, pos[where] + 12 + 32) == data_file_pos + q[where]
+    if not sync.all():
+        i = int(np.flatnonzero(~sync)[0])
+        return Refusal(OUT_OF_SYNC, int(event[i]), i, int(pos[i]))
+    if 60 * n > journal_dst_bytes:
+        i = journal_dst_bytes // 60
+        return Refusal(DST_TOO_SMALL, int(event[i]), i, int(pos[i]))
+    over = where[q[where + 1] > data_dst_bytes]
+    if over.size:
+        i = int(over[0])
+        return Refusal(DST_TOO_SMALL, int(event[i]), i, int(pos[i]))
+    lengths = lay.length
+    assert int((((lengths[where] + 15) >> 4) + 1)[lengths[where] > 0].sum()) <= 0xFFFFFFFF
+    crcs = np.asarray(record_crcs, np.uint32)
+    expected = np.zeros(n, np.uint32)
+    expected[where] = np.ascontiguousarray(recs[where, 52:56]).view(">u4")[:, 0]
+    wrong = where[expected[where] != crcs[where]]
+    assert not crcs[size == 0].any()
+    result = dict(n_events=n_events, n_msgs=n, n_data=int(where.size), journal_bytes=60 * n,
+                  data_bytes=int(q[n]), head_seq=int(s[-1]), head_lease_id=int(lease[-1]),
+                  refused_kind=0, n_bad=int(wrong.size),
+                  first_bad=int(wrong[0]) if wrong.size else n, refused_event=0, refused_index=0,
+                  refused_offset=0)
+    return Applied(
+        recs.reshape(-1), data[lay.data_at:lay.data_at + int(q[n])], built.types, built.flags,
+        (pos + 72).astype(np.uint64), size.astype(np.uint32), q.astype(np.uint64),
+        lengths.astype(np.uint32), expected, crcs, first.astype(np.uint64), result)
+
+
+def apply_fast(run, data, event_first, *, partition_id, journal_pos, data_file_pos, lease_id=0,
+               seq=0, msg_cap, journal_dst_bytes, data_dst_bytes, record_crcs, flags=None,
+               corrupt=None, suspects=()):
+    """(events, event offsets, what ``apply`` answers) for the record run `run`
+    with its DATA file `data` (whole, from byte 0), sent in the events
+    ``event_first`` (entries may repeat: an empty event) from ``journal_pos``,
+    in numpy alone.  The bytes are ``storage_events_fast``'s.  ``corrupt(events,
+    offsets)`` may then change them in place (or return new offsets); the events
+    it touched in a way the walk refuses are to be named in ``suspects``: only
+    those are walked, with ``_walk_event``, every other event's message count is
+    the split's.  Changes the walk accepts -- a sequence number, a journal or
+    DATA offset -- need no suspect: the checks behind the walk read the events'
+    own bytes.  ``record_crcs``: the CRC32C of every MESSAGE record's
+    application data (0 elsewhere).  The records' DATA records lie back to back
+    in `data` (asserted).  ``build_fast`` and ``answer_fast`` are its two
+    halves, for callers that share one input among many answers."""
+    built = build_fast(run, data, event_first, journal_pos=journal_pos,
+                       partition_id=partition_id, flags=flags)
+    events, offsets = built.events, built.lay.offsets.copy()
+    if corrupt is not None:
+        changed = corrupt(events, offsets)
+        offsets = offsets if changed is None else np.asarray(changed).astype(np.int64)
+    return events, offsets, answer_fast(
+        built, events, offsets, run, data, data_file_pos=data_file_pos, lease_id=lease_id, seq=seq,
+        msg_cap=msg_cap, journal_dst_bytes=journal_dst_bytes, data_dst_bytes=data_dst_bytes,
+        record_crcs=record_crcs, suspects=suspects)
+
+
 def refused_result(r, n_events):
     """The result struct's fields after the refusal `r`."""
     return dict(n_events=n_events, n_msgs=0, n_data=0, journal_bytes=0, data_bytes=0, head_seq=0,

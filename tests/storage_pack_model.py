@@ -142,14 +142,17 @@ def _be32s(rows):
 def storage_events_fast(journal, data, *, journal_pos, data_file_pos, partition_id,
                         event_first=None, flags=None, event_type=0,
                         storage_protocol_version=E.STORAGE_PROTOCOL_VERSION, max_event_bytes=0,
-                        max_payload_bytes=0, dst_bytes=None, crc32c=None, record_crcs=None):
+                        max_payload_bytes=0, dst_bytes=None, crc32c=None, record_crcs=None,
+                        empty_events=False):
     """``pack`` in numpy alone, for records that are well formed (asserted):
     the StorageHeaders and journal records as an (n, 72) array scattered to
     their offsets, the DATA records by one gather of dwords.  Of the refusals
     it knows PAYLOAD_TOO_BIG, EVENT_TOO_BIG and DST_TOO_SMALL (``dst_bytes``
     None: room for everything).  The CRCs are ``record_crcs`` (one per record,
     computed once by the caller) or ``crc32c`` of every MESSAGE record's
-    application data."""
+    application data.  ``empty_events``: ``event_first`` may repeat an entry --
+    an event of its EventHeader alone, which the packer refuses (EVENT_FIRST)
+    and the apply's tests feed to the apply."""
     from put_pack_model import be_bytes, byte_runs, scatter_frames
     recs = np.asarray(journal, np.uint8).reshape(-1, 60)
     data = np.asarray(data, np.uint8)
@@ -182,7 +185,8 @@ def storage_events_fast(journal, data, *, journal_pos, data_file_pos, partition_
     first = np.array([0, n], np.int64) if event_first is None else np.asarray(
         event_first).astype(np.int64)
     n_events = first.size - 1
-    assert first[0] == 0 and first[-1] == n and bool((np.diff(first) > 0).all())
+    assert first[0] == 0 and first[-1] == n
+    assert bool((np.diff(first) >= 0).all() if empty_events else (np.diff(first) > 0).all())
     before = np.concatenate([[0], np.cumsum(72 + size)])
     offsets = 8 * np.arange(n_events + 1) + before[first]
     big = np.flatnonzero(60 + size > (max_payload_bytes or E.MAX_PAYLOAD_SIZE_SOFT))

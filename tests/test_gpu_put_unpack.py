@@ -5,6 +5,7 @@ guard elements behind msg_cap: the guards are checked after every call, the
 slots the call leaves untouched after a successful one, and every element
 after a refused one."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -14,8 +15,10 @@ from blazingmq_amd import (BmqCrcError, Crc32c, _native as N, last_copy, last_la
                            pack_records, unpack_events)
 from blazingmq_amd import storage as S
 import device_views as V
+import pack_pool
 import put_pack_model as P
 import put_unpack_model as M
+import test_grid_regimes as G
 from records_pack_model import REC, wrap_partition
 
 pytestmark = pytest.mark.gpu
@@ -515,3 +518,208 @@ def test_put_events_to_verified_partition_without_host_descriptors(cuda):
         assert (got["recovery_rc"], got["n_messages"], got["n_bad"]) == (0, n, int(corrupt))
         if corrupt:
             assert list(got["bad_record_offsets"]) == [44 + 60 + REC * victim]
+
+
+# ---- past one walk grid ---------------------------------
+#
+# pack_pool.py's messages (lengths 0..40 with every padding count, a handful of
+# 200 to 700 bytes, one of 70,000 every 3,001) with random queue ids, GUIDs and
+# flags, sent in test_grid_regimes.py's event splits.  The events and what
+# walking them gives are put_unpack_model.unpack_fast's, which
+# test_put_unpack_model.py holds to the loop model field for field.
+
+@functools.lru_cache(maxsize=None)
+def _pool_messages(n):
+    src, soff, lens, ix = pack_pool.messages(n)
+    _, poff, plen = pack_pool.pool()
+    crcs = P.pooled_crcs(_pool_crcs(), ix)
+    qids, guids, flags = P.random_meta(np.random.default_rng(9), n)
+    for a in (crcs, qids, guids, flags):
+        a.setflags(write=False)
+    return (src, soff, lens, qids, guids, flags), crcs
+
+
+@functools.lru_cache(maxsize=None)
+def _pool_crcs():
+    src, poff, plen = pack_pool.pool()
+    return P.pool_crcs(src, poff, plen)
+
+
+@functools.lru_cache(maxsize=None)
+def _built(n, split):
+    """unpack_fast's (events, event offsets, model) of the first n messages of
+    the pool in the events G.ones or G.ragged: built once, shared, read-only."""
+    msgs, crcs = _pool_messages(n)
+    buf, offs, want = M.unpack_fast(*msgs, getattr(G, split)(n), crcs)
+    for a in (buf, offs) + tuple(v for v in want.values() if isinstance(v, np.ndarray)):
+        a.setflags(write=False)
+    return buf, offs, want
+
+
+BUILDS = [(G.N_WAVES, "ragged"), (G.N_FULL, "ragged"), (G.N_TILES, "ragged"),
+          (G.N_FRAME, "ragged"), (G.N_FRAME, "ones"), (G.N_TILES, "ones")]
+
+
+@pytest.fixture(scope="module")
+def large():
+    """The pool and every shared build, made before the first case that asks."""
+    for key in BUILDS:
+        _built(*key)
+
+
+def _refusal(n, split, plants=(), msg_cap=None):
+    """(events, event offsets, the refusal) of _built's events with `plants`."""
+    buf, offs, _ = _built(n, split)
+    buf, offs = buf.copy(), offs.copy()
+    corrupt, suspects, _ = _planted(n, getattr(G, split)(n), plants)
+    corrupt(buf, offs)
+    return buf, offs, M.refused_fast(buf, offs, getattr(G, split)(n), suspects, msg_cap)
+
+
+def _planted(n, first, plants):
+    """(corrupt, suspects, header offsets) for unpack_fast of the (what, where)
+    pairs `plants` (put_unpack_model.spoil)."""
+    lens = _pool_messages(n)[0][2]
+    hdr, _ = P.layout(lens, first)
+    event = np.searchsorted(first, np.arange(n), side="right") - 1
+
+    def corrupt(buf, offs):
+        for what, at in plants:
+            M.spoil(buf, offs, hdr, lens, what, at)
+    suspects = set()
+    for what, at in plants:
+        e = at if what in ("offsets", "event_length") else int(event[at])
+        suspects.update({e - 1, e} if what == "offsets" else {e})
+    return corrupt, sorted(suspects), hdr
+
+
+LARGE = {"waves-ragged": (G.N_WAVES, "ragged", 0),
+         "full-ragged": (G.N_FULL, "ragged", 0),
+         "tiles-ragged": (G.N_TILES, "ragged", 0),
+         "frame-ragged": (G.N_FRAME, "ragged", 0),
+         "frame-ones": (G.N_FRAME, "ones", 0),
+         "tiles-null_outputs": (G.N_TILES, "ragged", 0),
+         "frame-msg_cap_300000_above": (G.N_FRAME, "ragged", 300000)}
+
+
+@pytest.mark.parametrize("name", sorted(LARGE))
+def test_past_one_walk_grid(cuda, large, name):
+    # RAGGED: events of 1, 63, 64, 65, 130 and 7 messages with empty events
+    # first, last, 65 in a row and at event 4,096.  From N_FULL on a walk block
+    # walks a second event and the scan a fifth tile; at N_FRAME a publish
+    # thread copies a second message, and with an event per message a second
+    # event_first entry, and the scan runs 513 tiles.
+    n, split, above = LARGE[name]
+    crcs = _pool_messages(n)[1]
+    buf, offs, want = _built(n, split)
+    assert buf.size <= 61 << 20 and want["n"] == n
+    skip = ("queue_ids", "guids", "flags", "expected", "event_first") \
+        if name == "tiles-null_outputs" else ()
+    _, host = _ok(cuda, buf, offs, cap=n + above, model=want, skip=skip)
+    assert np.array_equal(host["out"][:n], crcs)
+
+
+def test_past_one_walk_grid_on_a_side_stream(cuda, large):
+    import torch
+    n = G.N_FULL
+    crcs = _pool_messages(n)[1]
+    buf, offs, want = _built(n, "ragged")
+    torch.cuda.synchronize(cuda)
+    s = _side_stream(cuda)
+    with torch.cuda.stream(s):
+        _, host = _ok(cuda, buf, offs, cap=n, model=want, sync=False, stream=s)
+    assert np.array_equal(host["out"][:n], crcs)
+
+
+def test_stored_crc_mismatches_in_both_steps_of_the_publish_loop(cuda, large):
+    n = G.N_FRAME
+    msgs, crcs = _pool_messages(n)
+    victims = [10, n // 2, 2048 * 256]
+    stored = crcs.copy()
+    stored[victims] ^= 0x01000080
+    buf, offs, want = _built(n, "ragged")
+    buf = buf.copy()    # the shared events with other CRCs in three PutHeaders
+    for v in victims:
+        M.put32(buf, int(want["app_offsets"][v]) - 36 + 28, int(stored[v]))
+    want = dict(want, expected=stored)
+    _, host = _ok(cuda, buf, offs, cap=n, model=want, n_bad=3, first_bad=10)
+    assert np.array_equal(host["out"][:n], crcs)
+    assert np.flatnonzero(host["out"][:n] != host["expected"][:n]).tolist() == victims
+
+
+def test_a_flipped_byte_of_the_long_message_is_counted(cuda, large):
+    n, victim = G.N_WAVES, pack_pool.LONG_VISIT
+    msgs, crcs = _pool_messages(n)
+    src, soff, lens = msgs[:3]
+    assert lens[victim] == pack_pool.LONG == 70000
+    app = src[soff[victim]:soff[victim] + 70000].copy()
+    app[60000] ^= 0x40
+    true = crcs.copy()
+    true[victim] = Crc32c.calculate(app.tobytes())
+    hdr, _ = P.layout(lens, G.ragged(n))
+
+    def flip(buf, offs):
+        buf[int(hdr[victim]) + 36 + 60000] ^= 0x40
+
+    buf, offs, want = M.unpack_fast(*msgs, G.ragged(n), true, stored=crcs, corrupt=flip)
+    _, host = _ok(cuda, buf, offs, cap=n, model=want, n_bad=1, first_bad=victim)
+    assert np.array_equal(host["out"][:n], true) and true[victim] != crcs[victim]
+
+
+@pytest.mark.parametrize("which", ["both", "higher_alone"])
+@pytest.mark.parametrize("what", M.PLANTS)
+def test_the_walk_refuses_in_a_blocks_second_and_third_event(cuda, large, what, which):
+    # one event per message: events 4,096.. are the walk blocks' second step,
+    # 8,192.. their third; two refused events of different steps, or the
+    # higher alone
+    n, lo, hi = G.N_TILES, 4099, 9000
+    lens = _pool_messages(n)[0][2]
+    kind = 1 + M.PLANTS.index(what)
+    plants, e = {"both": ([(what, hi), (what, lo)], lo), "higher_alone": ([(what, hi)], hi)}[which]
+    buf, offs, refused = _refusal(n, "ones", plants)
+    offset = int(offs[e]) + {"offsets": 0, "event_length": 0, "header_words": 8,
+                             "padding": 8 + 36 + int(lens[e]) + 3 - int(lens[e]) % 4}[what]
+    assert refused == (kind, e, offset)
+    _refused(cuda, buf, offs, n, want=refused)
+
+
+@pytest.mark.parametrize("which", ["alone", "next_to_the_lower_kind"])
+@pytest.mark.parametrize("what", ["event_length", "header_words", "padding"])
+def test_the_lower_kind_of_a_later_step_wins(cuda, large, what, which):
+    # RAGGED: message 99 of event 4,097, a block's second event of 130
+    # messages, refused alone, or next to a lower kind in a higher event of
+    # the first step of another block
+    n = G.N_TILES
+    first = G.ragged(n)
+    assert first[4098] - first[4097] == 130
+    lo, hi = int(first[4097]) + 99, int(first[4500]) + 3
+    hdr, _ = P.layout(_pool_messages(n)[0][2], first)
+    per_event = what == "event_length"
+    kind = 1 + M.PLANTS.index(what)
+    plants, want = [(what, 4097 if per_event else lo)], (kind, 4097)
+    if which != "alone":
+        lower = M.PLANTS[kind - 2]
+        plants.append((lower, 4500 if lower in ("offsets", "event_length") else hi))
+        want = (kind - 1, 4500)
+    buf, offs, refused = _refusal(n, "ragged", plants)
+    assert refused[:2] == want
+    if which == "alone" and not per_event:
+        assert int(hdr[lo]) <= refused[2] < int(hdr[lo + 1])
+    _refused(cuda, buf, offs, n, want=refused)
+
+
+@pytest.mark.parametrize("name", ["frame-ones-last_event", "tiles-ragged-third_tile"])
+def test_too_many_messages_from_late_tiles_of_the_scan(cuda, large, name):
+    if name == "frame-ones-last_event":
+        # one event per message at N_FRAME: the last event, in the scan's 513th tile
+        n, split, e = G.N_FRAME, "ones", G.N_FRAME - 1
+        cap = n - 1
+    else:
+        # RAGGED at N_TILES: msg_cap inside a 130-message event of the third tile
+        n, split = G.N_TILES, "ragged"
+        first = G.ragged(n)
+        e, cap = G.cap_inside_the_third_tile(first)
+        assert 2048 < e < 3072 and first[e] < cap < first[e + 1] - 1
+    buf, offs, refused = _refusal(n, split, msg_cap=cap)
+    assert refused == (M.K_MANY, e, int(offs[e]))
+    _refused(cuda, buf, offs, cap, want=refused)

@@ -21,8 +21,10 @@ from blazingmq_amd import synth
 import put_pack_model as P
 import put_unpack_model as PU
 import device_views as V
+import record_pool as R
 import storage_apply_cases as C
 import storage_apply_model as M
+import test_grid_regimes as G
 from records_pack_model import random_meta
 
 pytestmark = pytest.mark.gpu
@@ -590,3 +592,305 @@ def test_apply_select_and_verify_on_the_device(cuda):
             assert list(want["bad_record_offsets"]) == [JH + 60 * index] and index == victim
         assert np.array_equal(a.journal.cpu().numpy(), journal[JH:])
         assert np.array_equal(a.data.cpu().numpy(), df[40:])
+
+
+# ---- past one walk grid ---------------------------------
+#
+# record_pool.py's run of N_FRAME records (all five record types, DATA records
+# of varied sizes behind headers of 12 to 28 bytes, two messages longer than a
+# chunk of the copy), sent in test_grid_regimes.py's event splits.  The events
+# and what applying them gives are storage_apply_model.build_fast's and
+# answer_fast's, the two halves of apply_fast, which
+# test_storage_apply_model.py holds to the loop model field for field.  The
+# events of a size and split are built once (the `large` fixture, outside any
+# case's own time) and shared; a case that changes them works on a copy.
+
+BLOCK = 70 * 2048       # the first record of a layout block behind the 64th at N_TILES
+
+
+@functools.lru_cache(maxsize=None)
+def _split(n, name):
+    """G.ones, G.ragged, or ("between") G.ragged with record BLOCK an event of
+    its own between two empty events."""
+    if name != "between":
+        return getattr(G, name)(n)
+    first = G.ragged(n)
+    e = int(np.searchsorted(first, BLOCK, side="right")) - 1
+    assert first[e] < BLOCK and first[e + 1] > BLOCK + 1
+    return np.concatenate([first[:e + 1], [BLOCK, BLOCK, BLOCK + 1, BLOCK + 1], first[e + 1:]])
+
+
+@functools.lru_cache(maxsize=None)
+def _built(n, split):
+    run, data = R.records(n)
+    flags = np.random.default_rng(31).integers(0, 256, size=n, dtype=np.uint8)
+    b = M.build_fast(run, data, _split(n, split), journal_pos=JH, partition_id=1, flags=flags)
+    b.events.setflags(write=False)
+    return b
+
+
+BUILDS = [(G.N_WAVES, "ragged"), (G.N_FULL, "ragged"), (G.N_TILES, "ragged"),
+          (G.N_FRAME, "ragged"), (G.N_FRAME, "ones"), (G.N_TILES, "ones"),
+          (G.N_TILES, "between")]
+
+
+@pytest.fixture(scope="module")
+def large():
+    """The pool and every shared build, made before the first case that asks."""
+    for key in BUILDS:
+        _built(*key)
+
+
+def _pool_kw(n, split="ragged", **changes):
+    total = int(_built(n, split).lay.size.sum())
+    return dict(dict(partition_id=1, journal_pos=JH, data_file_pos=40, lease_id=4, seq=0,
+                     msg_cap=n, journal_dst_bytes=60 * n, data_dst_bytes=total), **changes)
+
+
+def _fast(n, split, plants=(), run=None, data=None, crcs=None, touch=None, **changes):
+    """(events, event offsets, keywords, the model's answer) for the first n
+    records of the pool in the events of `split`, with `plants`
+    (storage_apply_cases.planted) in them, the records of `run` in place of
+    the pool's, and `touch(events, layout)` applied (then `data` is the DATA
+    file the events carry)."""
+    b = _built(n, split)
+    pool_run, pool_data = R.records(n)
+    kw = _pool_kw(n, split, **changes)
+    events = b.events
+    if run is not None:
+        events = M.events_with(b, run)
+    elif plants or touch:
+        events = events.copy()
+    if touch:
+        touch(events, b.lay)
+    offsets = b.lay.offsets.copy()
+    corrupt, suspects = C.planted(b.lay, plants)
+    corrupt(events, offsets)
+    m = M.answer_fast(
+        b, events, offsets, pool_run if run is None else run, pool_data if data is None else data,
+        record_crcs=R.pool().crcs[:n] if crcs is None else crcs, suspects=suspects,
+        **{k: v for k, v in kw.items() if k not in ("partition_id", "journal_pos")})
+    return events, offsets.astype(np.uint64), kw, m
+
+
+def _refused_both_ways(cuda, events, offsets, kw, m, want):
+    """Refused as `want`, synchronous and asynchronous, with nothing written."""
+    assert m == M.Refusal(*want), m
+    for sync in (True, False):
+        _check(cuda, events, offsets, kw, sync=sync, model=m)
+
+
+LARGE = {"waves-ragged": (G.N_WAVES, "ragged", {}),
+         "full-ragged": (G.N_FULL, "ragged", {}),
+         "tiles-ragged": (G.N_TILES, "ragged", {}),
+         "frame-ragged": (G.N_FRAME, "ragged", {}),
+         "frame-ones": (G.N_FRAME, "ones", {}),
+         "tiles-null_outputs": (G.N_TILES, "ragged", {}),
+         "frame-msg_cap_300000_above": (G.N_FRAME, "ragged", dict(msg_cap=G.N_FRAME + 300000)),
+         "waves-msg_cap_of_tiles": (G.N_WAVES, "ragged", dict(msg_cap=G.N_TILES)),
+         "waves-msg_cap_of_frame": (G.N_WAVES, "ragged", dict(msg_cap=G.N_FRAME)),
+         "tiles-from_head_0_0": (G.N_TILES, "ragged", dict(lease_id=0, seq=0))}
+
+
+@pytest.mark.parametrize("name", sorted(LARGE))
+def test_past_one_walk_grid(cuda, large, name):
+    # RAGGED: events of 1, 63, 64, 65, 130 and 7 messages with empty events
+    # first, last, 65 in a row and at event 4,096.  From N_FULL on a walk block
+    # walks a second event and the scan a fifth tile; at N_FRAME a frame thread
+    # frames a second message, and with an event per record it copies a second
+    # event_first entry and the scan runs 513 tiles.  msg_cap, not the count,
+    # splits the layout grid: with N_WAVES messages under the msg_cap of another
+    # size the checks' blocks follow that size's split and most own nothing.
+    n, split, changes = LARGE[name]
+    events, offsets, kw, want = _fast(n, split, **changes)
+    assert events.size <= 61 << 20
+    assert want.result["n_bad"] == 0 and want.result["n_data"] == int((R.pool().msgs < n).sum())
+    assert (want.result["head_lease_id"], want.result["head_seq"]) == (4, n)
+    assert np.unique(want.types).tolist() == [1, 2, 3, 4, 5, 6]
+    # journal = the run, data = the DATA records: the pool's own bytes
+    assert np.shares_memory(want.journal, R.pool().run) and want.journal.size == 60 * n
+    assert np.shares_memory(want.data, R.pool().data[40:40 + want.result["data_bytes"]])
+    _check(cuda, events, offsets, kw, model=want,
+           skip=tuple(NP) if name == "tiles-null_outputs" else ())
+
+
+def test_past_one_walk_grid_on_a_side_stream(cuda, large):
+    import torch
+    events, offsets, kw, want = _fast(G.N_FULL, "ragged")
+    torch.cuda.synchronize(cuda)
+    s = _side_stream(cuda)
+    with torch.cuda.stream(s):
+        _check(cuda, events, offsets, kw, sync=False, stream=s, model=want)
+
+
+def test_a_new_lease_behind_the_64th_block_is_applied(cuda, large):
+    n = G.N_TILES
+    run = C.new_lease(R.records(n)[0], BLOCK)
+    events, offsets, kw, want = _fast(n, "ragged", run=run)
+    assert (want.result["head_lease_id"], want.result["head_seq"]) == (5, n - BLOCK)
+    _check(cuda, events, offsets, kw, model=want)
+
+
+def test_stored_crc_mismatches_in_both_steps_of_the_frame_loop(cuda, large):
+    n = G.N_FRAME
+    msgs = R.pool().msgs
+    victims = np.array([msgs[10], msgs[msgs.size // 2], n - 1])
+    assert victims[-1] == msgs[-1] == 2048 * 256 and victims[0] < 64
+    bad = R.records(n)[0].copy()
+    bad[60 * victims[:, None] + 52 + np.arange(4)] ^= np.array([0x80, 1, 0, 0x10], np.uint8)
+    events, offsets, kw, want = _fast(n, "ragged", run=bad)
+    assert (want.result["n_bad"], want.result["first_bad"]) == (3, int(victims[0]))
+    _, host = _check(cuda, events, offsets, kw, model=want)
+    assert np.array_equal(np.flatnonzero(host["out"][:n] != host["expected"][:n]), victims)
+    assert np.array_equal(host["out"][:n], R.pool().crcs)
+    assert np.array_equal(host["journal"][:60 * n], bad)     # applied as they are
+
+
+def test_a_flipped_byte_of_the_longest_message_is_counted_and_applied(cuda, large):
+    n = G.N_WAVES
+    run, data = R.records(n)
+    rec = R.pool().long[0]
+    at, lead, _, length, _ = R.data_fields(run, data, np.array([rec]))
+    app = int(at[0] + lead[0])
+    assert int(length[0]) == R.LONG[0] == 90000
+    flipped = data.copy()
+    flipped[app + 77777] ^= 0x20
+    crcs = R.pool().crcs[:n].copy()
+    crcs[rec] = CRC(flipped[app:app + 90000].tobytes())
+
+    def touch(events, lay):
+        events[int(lay.pos[rec]) + 72 + int(lead[0]) + 77777] ^= 0x20
+
+    events, offsets, kw, want = _fast(n, "ragged", data=flipped, crcs=crcs, touch=touch)
+    assert (want.result["n_bad"], want.result["first_bad"]) == (1, rec)
+    _, host = _check(cuda, events, offsets, kw, model=want)
+    assert host["expected"][rec] == R.pool().crcs[rec] != host["out"][rec] == crcs[rec]
+    assert np.flatnonzero(host["data"][:want.data.size] != data[40:40 + want.data.size]).tolist() \
+        == [app - 40 + 77777]
+
+
+@pytest.mark.parametrize("which", ["both", "higher_alone"])
+@pytest.mark.parametrize("what", C.WALK_PLANTS)
+def test_the_walk_refuses_in_a_blocks_second_and_third_event(cuda, large, what, which):
+    # one event per record: events 4,096.. are the walk blocks' second step,
+    # 8,192.. their third.  The events are those of the first MESSAGE records
+    # at or behind records 4,099 and 9,000 (a padding byte needs a DATA
+    # record): two refused events of different steps, or the higher alone
+    n = G.N_TILES
+    msgs = R.pool().msgs
+    lo, hi = int(msgs[np.searchsorted(msgs, 4099)]), int(msgs[np.searchsorted(msgs, 9000)])
+    assert 4096 < lo < 8192 < hi < 12288 and lo % 4096 != hi % 4096
+    kind = {"offsets": M.EVENT_OFFSETS, "event_length": M.EVENT_HEADER,
+            "partition": M.STORAGE_HEADER, "padding": M.DATA_RECORD}[what]
+    plants, e = {"both": ([(what, hi), (what, lo)], lo), "higher_alone": ([(what, hi)], hi)}[which]
+    events, offsets, kw, m = _fast(n, "ones", plants)
+    # (the event in front of a late start ends late: refused too, it counts nothing)
+    index = e - (what == "offsets")
+    offset = int(offsets[e]) + {"offsets": 0, "event_length": 0, "partition": 8,
+                                "padding": 80}[what]
+    _refused_both_ways(cuda, events, offsets, kw, m, (kind, e, index, offset))
+
+
+@pytest.mark.parametrize("which", ["alone", "next_to_the_lower_kind"])
+@pytest.mark.parametrize("what", ["event_length", "partition", "padding"])
+def test_the_lower_kind_of_a_later_step_wins(cuda, large, what, which):
+    # RAGGED: message 99 of event 4,097, a block's second event of 130
+    # messages, refused -- the messages in front of it are counted -- alone, or
+    # next to a lower kind in a higher event of the first step of another block
+    n = G.N_TILES
+    first = _split(n, "ragged")
+    assert first[4098] - first[4097] == 130
+    msgs = R.pool().msgs
+    lo = int(msgs[np.searchsorted(msgs, first[4097] + 99)])
+    hi = int(msgs[np.searchsorted(msgs, first[4500] + 3)])
+    assert first[4097] < lo < first[4098] and first[4500] < hi < first[4501]
+    per_event = what == "event_length"
+    kind = 1 + C.WALK_PLANTS.index(what)
+    plants = [(what, 4097 if per_event else lo)]
+    if which == "alone":
+        events, offsets, kw, m = _fast(n, "ragged", plants)
+        lay = _built(n, "ragged").lay
+        offset = int(offsets[4097]) if per_event else int(lay.pos[lo]) + (
+            72 if what == "padding" else 0)
+        _refused_both_ways(cuda, events, offsets, kw, m,
+                           (kind, 4097, int(first[4097]) if per_event else lo, offset))
+        return
+    lower = C.WALK_PLANTS[kind - 2]
+    at_hi = 4500 if lower in ("offsets", "event_length") else hi
+    events, offsets, kw, m = _fast(n, "ragged", plants + [(lower, at_hi)])
+    assert (m.kind, m.event) == (kind - 1, 4500)
+    for sync in (True, False):
+        _check(cuda, events, offsets, kw, sync=sync, model=m)
+
+
+@pytest.mark.parametrize("name", ["frame-ones-last_event", "tiles-ragged-third_tile"])
+def test_too_many_messages_from_late_tiles_of_the_scan(cuda, large, name):
+    if name == "frame-ones-last_event":
+        # one event per record at N_FRAME: the last event, in the scan's 513th tile
+        n, split, e = G.N_FRAME, "ones", G.N_FRAME - 1
+        cap = n - 1
+    else:
+        # RAGGED at N_TILES: msg_cap inside a 130-message event of the third tile
+        n, split = G.N_TILES, "ragged"
+        first = _split(n, split)
+        e, cap = G.cap_inside_the_third_tile(first)
+        assert 2048 < e < 3072 and first[e] < cap < first[e + 1] - 1
+    events, offsets, kw, m = _fast(n, split, msg_cap=cap)
+    _refused_both_ways(cuda, events, offsets, kw, m,
+                       (M.TOO_MANY_MESSAGES, e, int(_split(n, split)[e]), int(offsets[e])))
+
+
+def _check_case(name):
+    """(run or None, split, plants, keyword changes, the refused message) of a
+    refusal of k_sap_check at N_TILES: per_block 2,048, 129 blocks."""
+    n = G.N_TILES
+    run = R.records(n)[0]
+    p = R.pool()
+    tile = BLOCK + 1024
+    long_rec = p.long[1]
+    assert tile < long_rec < BLOCK + 2048
+    msgs = p.msgs[p.msgs < n]
+    q = np.concatenate([[0], np.cumsum(_built(n, "ragged").lay.size)])
+    inside = int(msgs[np.searchsorted(msgs, BLOCK + 1000)])
+    assert BLOCK < inside < tile
+    gap = C.sequence_gap
+    return {
+        "gap_first_of_block_70": lambda: (gap(run, BLOCK), "ragged", [], {}, BLOCK),
+        "gap_first_of_its_second_tile": lambda: (gap(run, tile), "ragged", [], {}, tile),
+        "gap_last_message": lambda: (gap(run, n - 1), "ragged", [], {}, n - 1),
+        "data_offset_second_tile_of_block_70": lambda: (
+            None, "ragged", [("data_offset", long_rec)], {}, long_rec),
+        "journal_offset_late": lambda: (None, "ragged", [("journal_offset", n - 5)], {}, n - 5),
+        "two_blocks_lowest_message": lambda: (
+            gap(run, 100 * 2048), "ragged", [("data_offset", long_rec)], {}, long_rec),
+        "journal_one_byte_short": lambda: (
+            None, "ragged", [], dict(journal_dst_bytes=60 * n - 1), n - 1),
+        "data_one_byte_short": lambda: (
+            None, "ragged", [], dict(data_dst_bytes=int(q[n]) - 1), int(msgs[-1])),
+        "data_ends_inside_block_70": lambda: (
+            None, "ragged", [], dict(data_dst_bytes=int(q[inside + 1]) - 1), inside),
+        "out_of_sync_beats_dst_too_small": lambda: (
+            gap(run, n - 1), "ragged", [], dict(data_dst_bytes=int(q[inside + 1]) - 1), n - 1),
+        "between_empty_events": lambda: (gap(run, BLOCK), "between", [], {}, BLOCK),
+    }[name]()
+
+
+CHECK_CASES = ["gap_first_of_block_70", "gap_first_of_its_second_tile", "gap_last_message",
+               "data_offset_second_tile_of_block_70", "journal_offset_late",
+               "two_blocks_lowest_message", "journal_one_byte_short", "data_one_byte_short",
+               "data_ends_inside_block_70", "out_of_sync_beats_dst_too_small",
+               "between_empty_events"]
+
+
+@pytest.mark.parametrize("name", CHECK_CASES)
+def test_the_checks_behind_the_walk_refuse_across_tiles_and_blocks(cuda, large, name):
+    n = G.N_TILES
+    run, split, plants, changes, i = _check_case(name)
+    events, offsets, kw, m = _fast(n, split, plants, run=run, **changes)
+    lay, first = _built(n, split).lay, _split(n, split)
+    kind = M.DST_TOO_SMALL if "short" in name or name.startswith("data_ends") else M.OUT_OF_SYNC
+    e = int(lay.event[i])
+    assert first[e] <= i < first[e + 1]
+    if name == "between_empty_events":
+        assert first[e - 1] == first[e] == i and first[e + 1] == first[e + 2] == i + 1
+    _refused_both_ways(cuda, events, offsets, kw, m, (kind, e, i, int(lay.pos[i])))

@@ -122,3 +122,104 @@ def test_header_variants_are_well_formed():
         else:
             assert np.array_equal(m["app_offsets"],
                                   base["app_offsets"] + 4 * np.arange(1, 5))
+
+
+# ---- unpack_fast, the model of the large GPU cases, against model ----------------
+
+N_SMALL = 4101      # the long message of pack_pool.py (message 1,500) among them
+
+
+def _pool_messages(n):
+    import pack_pool
+    import put_pack_model as P
+    src, soff, lens, ix = pack_pool.messages(n)
+    _, poff, plen = pack_pool.pool()
+    crcs = P.pooled_crcs(P.pool_crcs(src, poff, plen), ix)
+    qids, guids, flags = P.random_meta(np.random.default_rng(9), n)
+    return (src, soff, lens, qids, guids, flags), crcs
+
+
+def _same(fast, slow):
+    assert fast["refused"] == slow["refused"] and fast.keys() == slow.keys()
+    for name in fast:
+        if name not in ("refused", "n"):
+            assert fast[name].dtype == slow[name].dtype, name
+            assert np.array_equal(fast[name], slow[name]), name
+    assert fast.get("n") == slow.get("n")
+
+
+@pytest.mark.parametrize("split", ["ones", "ragged", "empties"])
+def test_unpack_fast_gives_what_the_model_gives(split):
+    import test_grid_regimes as G
+    import pack_pool
+    msgs, crcs = _pool_messages(N_SMALL)
+    first = {"ones": G.ones(N_SMALL), "ragged": G.ragged(N_SMALL, empties=False),
+             "empties": G.ragged(N_SMALL)}[split]
+    buf, offs, fast = M.unpack_fast(*msgs, first, crcs)
+    slow = M.model(buf, offs)
+    _same(fast, slow)
+    assert np.array_equal(slow["crcs"], slow["expected"])
+    assert int(fast["lengths"].max()) == pack_pool.LONG and len(set(fast["flags"].tolist())) == 16
+    assert bool((np.diff(offs) == 8).any()) == (split == "empties")
+    # stored CRCs that differ, and a flipped payload byte of the long message
+    stored = crcs.copy()
+    stored[[0, 2000, N_SMALL - 1]] ^= 0x01000000
+    at = int(fast["app_offsets"][pack_pool.LONG_VISIT]) + 60000
+
+    def flip(b, o):
+        b[at] ^= 0x40
+
+    buf, offs, fast = M.unpack_fast(*msgs, first, crcs, stored=stored, corrupt=flip)
+    slow = M.model(buf, offs)
+    fast["crcs"] = fast["crcs"].copy()
+    fast["crcs"][pack_pool.LONG_VISIT] = slow["crcs"][pack_pool.LONG_VISIT]
+    _same(fast, slow)
+    assert np.flatnonzero(slow["crcs"] != slow["expected"]).tolist() == [
+        0, pack_pool.LONG_VISIT, 2000, N_SMALL - 1]
+
+
+@pytest.mark.parametrize("what", M.PLANTS)
+def test_unpack_fast_refuses_like_the_model(what):
+    import put_pack_model as P
+    import test_grid_regimes as G
+    msgs, crcs = _pool_messages(N_SMALL)
+    first = G.ragged(N_SMALL)
+    lens = msgs[2]
+    hdr, _ = P.layout(lens, first)
+    event = np.searchsorted(first, np.arange(N_SMALL), side="right") - 1
+    lo, hi = 900, 3500
+    per_event = what in ("offsets", "event_length")
+    at = (lambda i: int(event[i])) if per_event else (lambda i: i)
+
+    def run(plants):
+        def corrupt(b, o):
+            for w, a in plants:
+                M.spoil(b, o, hdr, lens, w, a)
+        suspects = set()
+        for w, a in plants:
+            e = a if w in ("offsets", "event_length") else int(event[a])
+            suspects.update({e - 1, e} if w == "offsets" else {e})
+        buf, offs, fast = M.unpack_fast(*msgs, first, crcs, corrupt=corrupt,
+                                        suspects=sorted(suspects))
+        assert fast == M.model(buf, offs)
+        return fast["refused"]
+
+    kind = 1 + M.PLANTS.index(what)
+    assert run([(what, at(hi)), (what, at(lo))])[:2] == (kind, event[lo])
+    assert run([(what, at(hi))])[:2] == (kind, event[hi])
+    if what != "offsets":       # a lower kind in a higher event wins
+        lower = M.PLANTS[kind - 2]
+        at_hi = int(event[hi]) if lower in ("offsets", "event_length") else hi
+        assert run([(what, at(lo)), (lower, at_hi)])[:2] == (kind - 1, event[hi])
+
+
+def test_unpack_fast_refuses_too_many_messages_like_the_model():
+    import test_grid_regimes as G
+    msgs, crcs = _pool_messages(N_SMALL)
+    first = G.ragged(N_SMALL)
+    for cap in (2000, int(first[40]), int(first[40]) - 1, N_SMALL - 1, 0):
+        buf, offs, fast = M.unpack_fast(*msgs, first, crcs, msg_cap=cap)
+        assert fast == M.model(buf, offs, cap)
+        e = fast["refused"][1]
+        assert fast["refused"][0] == M.K_MANY and first[e] <= cap < first[e + 1]
+    assert M.unpack_fast(*msgs, first, crcs, msg_cap=N_SMALL)[2]["refused"] is None

@@ -259,3 +259,159 @@ def test_no_event_and_an_empty_event():
     assert a.result["n_events"] == 1 and a.result["n_msgs"] == 0 and a.journal.size == 0
     assert (a.result["head_lease_id"], a.result["head_seq"]) == (6, 77)
     assert a.event_first.tolist() == [0, 0] and a.record_offsets.tolist() == [0]
+
+
+# ---- apply_fast, the model of the large GPU cases, against apply ------------------
+
+N_SMALL = 4101      # the long message of record_pool.py (record 1,524) among them
+
+
+def _pool_kw(n, **changes):
+    import record_pool as R
+    p = R.pool()
+    total = int(R.data_fields(p.run, p.data, p.msgs[p.msgs < n])[2].sum())
+    return dict(dict(partition_id=1, journal_pos=S.PartitionWriter.JOURNAL_HEADER,
+                     data_file_pos=40, lease_id=4, seq=0, msg_cap=n, journal_dst_bytes=60 * n,
+                     data_dst_bytes=total), **changes)
+
+
+def _same(fast, slow):
+    assert type(fast) is type(slow), (fast, slow)
+    if isinstance(slow, M.Refusal):
+        assert fast == slow
+        return
+    assert fast.result == slow.result
+    for name in M.Applied._fields[:-1]:
+        a, b = getattr(fast, name), getattr(slow, name)
+        assert a.dtype == b.dtype and np.array_equal(a, b), name
+
+
+def _both(run, data, first, kw, plants=(), crcs=None, flags=None):
+    """apply_fast's answer, held to apply's over the same bytes."""
+    import record_pool as R
+    n = len(run) // 60
+    lay = M.layout_fast(run, data, first)
+    corrupt, suspects = C.planted(lay, plants)
+    events, offsets, fast = M.apply_fast(
+        run, data, first, record_crcs=R.pool().crcs[:n] if crcs is None else crcs, flags=flags,
+        corrupt=corrupt, suspects=suspects, **kw)
+    _same(fast, M.apply(events, offsets, crc32c=CRC, **kw))
+    return fast
+
+
+def _splits(n):
+    import test_grid_regimes as G
+    return {"ones": G.ones(n), "ragged": G.ragged(n, empties=False), "empties": G.ragged(n)}
+
+
+@pytest.mark.parametrize("split", ["ones", "ragged", "empties"])
+def test_apply_fast_applies_what_apply_applies(split):
+    import record_pool as R
+    run, data = R.records(N_SMALL)
+    first = _splits(N_SMALL)[split]
+    flags = np.random.default_rng(5).integers(0, 256, size=N_SMALL, dtype=np.uint8)
+    a = _both(run, data, first, _pool_kw(N_SMALL), flags=flags)
+    assert np.array_equal(a.journal, run) and np.array_equal(a.data, data[40:40 + a.data.size])
+    assert sorted(set(a.types.tolist())) == [1, 2, 3, 4, 5, 6] and a.result["n_bad"] == 0
+    assert a.result["head_lease_id"] == 4 and len(set(a.flags.tolist())) == 32
+    assert int(a.lengths.max()) == R.LONG[0]
+    # from a head of (0, 0) too, and not from the last record's own
+    _both(run, data, first, _pool_kw(N_SMALL, lease_id=0, seq=0))
+    r = _both(run, data, first, _pool_kw(N_SMALL, seq=1))
+    assert r[:1] + r[2:3] == (M.OUT_OF_SYNC, 0)
+
+
+def test_apply_fast_counts_mismatches_like_apply():
+    import record_pool as R
+    run, data = R.records(N_SMALL)
+    first = _splits(N_SMALL)["empties"]
+    msgs = R.pool().msgs
+    bad = run.copy()
+    victims = msgs[[3, 700, 2000]]
+    bad[60 * victims[:, None] + 52 + np.arange(4)] ^= np.array([0x80, 1, 0, 0x10], np.uint8)
+    a = _both(bad, data, first, _pool_kw(N_SMALL))
+    assert (a.result["n_bad"], a.result["first_bad"]) == (3, int(victims[0]))
+    assert np.array_equal(a.journal, bad)
+    # one payload byte of the long message: its true CRC is another
+    long_rec = R.pool().long[0]
+    at, lead, _, length, _ = R.data_fields(run, data, np.array([long_rec]))
+    flipped = data.copy()
+    flipped[int(at[0] + lead[0]) + 77777] ^= 0x20
+    crcs = R.pool().crcs[:N_SMALL].copy()
+    crcs[long_rec] = CRC(flipped[int(at[0] + lead[0]):int(at[0] + lead[0] + length[0])].tobytes())
+    a = _both(run, flipped, first, _pool_kw(N_SMALL), crcs=crcs)
+    assert (a.result["n_bad"], a.result["first_bad"]) == (1, long_rec)
+    assert np.flatnonzero(a.data != data[40:40 + a.data.size]).size == 1
+
+
+@pytest.mark.parametrize("what", C.WALK_PLANTS)
+def test_apply_fast_refuses_the_walks_violations_like_apply(what):
+    import record_pool as R
+    run, data = R.records(N_SMALL)
+    first = _splits(N_SMALL)["empties"]
+    lay = M.layout_fast(run, data, first)
+    msgs = R.pool().msgs
+    lo, hi = int(msgs[600]), int(msgs[3000])            # two MESSAGE records, events apart
+    assert lay.event[lo] + 2 < lay.event[hi] and first[lay.event[lo]] < lo
+    at = (lambda i: int(lay.event[i])) if what in ("offsets", "event_length") else (lambda i: i)
+    both = _both(run, data, first, _pool_kw(N_SMALL), [(what, at(hi)), (what, at(lo))])
+    one = _both(run, data, first, _pool_kw(N_SMALL), [(what, at(hi))])
+    kind = {"offsets": M.EVENT_OFFSETS, "event_length": M.EVENT_HEADER,
+            "partition": M.STORAGE_HEADER, "padding": M.DATA_RECORD}[what]
+    assert (both.kind, both.event) == (kind, lay.event[lo])
+    assert (one.kind, one.event) == (kind, lay.event[hi])
+    # a stopped walk reports the messages in front of the violation
+    stopped = what in ("partition", "padding")
+    # (the event in front of a late start ends late: refused too, it counts nothing)
+    assert both.index == (lo if stopped else first[lay.event[lo] - (what == "offsets")])
+    # a lower kind in a higher event beats a higher kind in a lower event
+    if what != "offsets":
+        lower = C.WALK_PLANTS[C.WALK_PLANTS.index(what) - 1]
+        at_hi = int(lay.event[hi]) if lower in ("offsets", "event_length") else hi
+        r = _both(run, data, first, _pool_kw(N_SMALL), [(what, at(lo)), (lower, at_hi)])
+        assert (r.kind, r.event) == (kind - 1, lay.event[hi])
+
+
+def test_apply_fast_refuses_what_the_checks_refuse_like_apply():
+    import record_pool as R
+    run, data = R.records(N_SMALL)
+    splits = _splits(N_SMALL)
+    first = splits["empties"]
+    lay = M.layout_fast(run, data, first)
+    msgs = R.pool().msgs
+    kw = _pool_kw(N_SMALL)
+    total = kw["data_dst_bytes"]
+    # TOO_MANY_MESSAGES: inside an event, at an event's first message, one short
+    for cap in (2000, int(first[40]), int(first[40]) - 1, N_SMALL - 1, 0):
+        r = _both(run, data, first, dict(kw, msg_cap=cap))
+        assert r.kind == M.TOO_MANY_MESSAGES and first[r.event] <= cap < first[r.event + 1]
+    # OUT_OF_SYNC: a sequence gap, a DATA offset, a journal offset, two at once
+    for at in (1, 2048, N_SMALL - 1):
+        r = _both(C.sequence_gap(run, at), data, first, kw)
+        assert (r.kind, r.index, r.event) == (M.OUT_OF_SYNC, at, lay.event[at])
+    a, b = int(msgs[900]), int(msgs[2500])
+    assert _both(run, data, first, kw, [("data_offset", b)])[:3] == (6, lay.event[b], b)
+    assert _both(run, data, first, kw, [("journal_offset", 3999)])[:3] == (6, lay.event[3999],
+                                                                           3999)
+    r = _both(C.sequence_gap(run, 3000), data, first, kw, [("data_offset", a)])
+    assert (r.kind, r.index) == (M.OUT_OF_SYNC, a)
+    # DST_TOO_SMALL: the journal one byte short, the data one byte short, the
+    # data ending inside the run; OUT_OF_SYNC first when both hold
+    r = _both(run, data, first, dict(kw, journal_dst_bytes=60 * N_SMALL - 1))
+    assert (r.kind, r.index) == (M.DST_TOO_SMALL, N_SMALL - 1)
+    r = _both(run, data, first, dict(kw, data_dst_bytes=total - 1))
+    assert (r.kind, r.index) == (M.DST_TOO_SMALL, int(msgs[msgs < N_SMALL][-1]))
+    r = _both(run, data, first, dict(kw, data_dst_bytes=total // 2))
+    assert r.kind == M.DST_TOO_SMALL and r.index in msgs and 0 < r.index < N_SMALL - 1
+    r = _both(C.sequence_gap(run, 4000), data, first, dict(kw, data_dst_bytes=total // 2))
+    assert (r.kind, r.index) == (M.OUT_OF_SYNC, 4000)
+    # a refused message between two empty events: its event and StorageHeader
+    at = int(first[20])
+    assert first[21] > at + 1
+    between = np.concatenate([first[:21], [at, at + 1, at + 1], first[21:]])
+    r = _both(C.sequence_gap(run, at), data, between, kw)
+    assert (r.kind, r.event, r.index) == (M.OUT_OF_SYNC, 21, at)
+    assert r.offset == int(M.layout_fast(run, data, between).pos[at])
+    # a new primary's lease from some record on is applied
+    ok = _both(C.new_lease(run, 2048), data, first, kw)
+    assert (ok.result["head_lease_id"], ok.result["head_seq"]) == (5, N_SMALL - 2048)
