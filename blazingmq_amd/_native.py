@@ -472,6 +472,40 @@ if hasattr(lib, "bmqcrc_confirm_records_pack"):  # ABI 2.19 (an older build load
                                                 ctypes.POINTER(ConfirmPackResult), _popts]
     lib.bmqcrc_last_confirm_records.restype = _int
     lib.bmqcrc_last_confirm_records.argtypes = [_int, _vp, ctypes.POINTER(ConfirmPackResult)]
+BMQCRC_EXPIRE_PACK_OK = 0
+BMQCRC_EXPIRE_PACK_RECORD_HEADER = 1
+BMQCRC_EXPIRE_PACK_DUPLICATE_MESSAGE = 2
+BMQCRC_EXPIRE_PACK_QUEUE_KEY = 3
+BMQCRC_EXPIRE_PACK_DST_TOO_SMALL = 4
+
+
+class ExpirePack(ctypes.Structure):
+    """bmqcrc_expire_pack (include/bmqcrc_protocol.h, ABI 2.20)."""
+    _fields_ = [("struct_size", _u32), ("reserved", _u32), ("journal", _vp),
+                ("journal_bytes", _u64), ("n_records", _u64), ("select", _vp),
+                ("queue_keys", _vp), ("ttl_seconds", _vp), ("n_queues", _u64), ("now", _u64),
+                ("first_seq", _u64), ("lease_id", _u32), ("reserved2", _u32),
+                ("journal_dst", _vp), ("journal_dst_bytes", _u64), ("expired", _vp),
+                ("new_index", _vp), ("select_out", _vp), ("queue_expired", _vp),
+                ("queue_front", _vp)]
+
+
+class ExpirePackResult(ctypes.Structure):
+    """bmqcrc_expire_pack_result (include/bmqcrc_protocol.h, ABI 2.20)."""
+    _fields_ = [("n_records", _u64), ("n_live", _u64), ("n_expired", _u64),
+                ("n_no_queue", _u64), ("journal_bytes", _u64), ("next_seq", _u64),
+                ("refused_kind", _u32), ("reserved", _u32), ("refused_index", _u64)]
+
+    def as_dict(self):
+        return {f[0]: int(getattr(self, f[0])) for f in self._fields_ if f[0] != "reserved"}
+
+
+if hasattr(lib, "bmqcrc_expire_records_pack"):  # ABI 2.20 (an older build loads for same-box A/B)
+    lib.bmqcrc_expire_records_pack.restype = _int
+    lib.bmqcrc_expire_records_pack.argtypes = [ctypes.POINTER(ExpirePack),
+                                               ctypes.POINTER(ExpirePackResult), _popts]
+    lib.bmqcrc_last_expire_records.restype = _int
+    lib.bmqcrc_last_expire_records.argtypes = [_int, _vp, ctypes.POINTER(ExpirePackResult)]
 lib.bmqcrc_journal_scan.restype = _i64
 lib.bmqcrc_journal_scan.argtypes = [_vp, _u64, _vp, _u64, _vp, _pint, _pu64, _vp, _vp, _vp, _vp,
                                     _u64]

@@ -255,6 +255,16 @@ struct Workspace {
     DevBuf cfm_zero, cfm_rec, cfm_hit, cfm_off, cfm_bsum;
     uint64_t cfm_n = 0, cfm_first_seq = 0;
     bool cfm_any = false;
+    // bmqcrc_expire_records_pack: the part of its workspace every call zeroes
+    // (the counters; the hash of the selected MESSAGE records, 8 to 16 bytes a
+    // record; the hash of the queue table, 8 to 16 bytes an entry; per entry
+    // the expired count, 4; per record dead, 1), per entry front (4, every byte
+    // 0xFF before the launch), per record the queue (4), the kind (1) and the
+    // place (8), the block sums; the records and first_seq of the last call
+    // enqueued
+    DevBuf exp_zero, exp_front, exp_rec, exp_off, exp_bsum;
+    uint64_t exp_n = 0, exp_first_seq = 0;
+    bool exp_any = false;
     // bmqcrc_journal_select: the part of its workspace every call zeroes (the
     // counters, the queue-key and GUID tables, the claims) and the rest (the
     // two record lists, the named DELETIONs, the states); the records of the
@@ -4003,6 +4013,183 @@ int bmqcrc_last_confirm_records(int device, void* stream, bmqcrc_confirm_pack_re
     return last_result(device, stream, confirm_records_result, result);
 }
 
+static_assert(BMQCRC_EXPIRE_PACK_RECORD_HEADER == BMQCRC_EXP_KIND_RECORD_HEADER &&
+                  BMQCRC_EXPIRE_PACK_DUPLICATE_MESSAGE == BMQCRC_EXP_KIND_DUPLICATE_MESSAGE &&
+                  BMQCRC_EXPIRE_PACK_QUEUE_KEY == BMQCRC_EXP_KIND_QUEUE_KEY &&
+                  BMQCRC_EXPIRE_PACK_DST_TOO_SMALL == BMQCRC_EXP_KIND_DST_TOO_SMALL,
+              "the kernels' refusal kinds are the public ones");
+
+// Result of the expire pack last enqueued on c's workspace, after everything
+// enqueued on its stream (w->mu held); zeros when there was none.
+static int expire_records_result(Ctx& c, bmqcrc_expire_pack_result* r)
+{
+    memset(r, 0, sizeof(*r));
+    if (!c.w->exp_any) {
+        return 0;
+    }
+    unsigned long long ctr[kExpCtrWords] = {0};
+    r->n_records = c.w->exp_n;
+    if (r->n_records) {
+        HIP_TRY(hipMemcpyAsync(ctr, c.w->exp_zero.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
+    }
+    HIP_TRY(hipStreamSynchronize(c.s));
+    if (ctr[kExpCtrRefusal]) {
+        refusal_of(ctr[kExpCtrRefusal], &r->refused_kind, &r->refused_index);
+        return 0;
+    }
+    r->n_live = ctr[kExpCtrLive];
+    r->n_expired = ctr[kExpCtrExpired];
+    r->n_no_queue = ctr[kExpCtrNoQueue];
+    r->journal_bytes = kJournalRecordBytes * r->n_expired;
+    r->next_seq = c.w->exp_first_seq + r->n_expired;
+    return 0;
+}
+
+static const char* const kExpirePackRefusals[5] = {
+    "", "BMQCRC_EXPIRE_PACK_RECORD_HEADER: record %llu has type 0 or above 5, lease id 0, "
+        "sequence number 0, a wrong magic or a QueueOpType outside 1..4",
+    "BMQCRC_EXPIRE_PACK_DUPLICATE_MESSAGE: selected MESSAGE record %llu shares its GUID and "
+    "queue key with another selected MESSAGE record",
+    "BMQCRC_EXPIRE_PACK_QUEUE_KEY: queue_keys entry %llu is all zero or stands in the table twice",
+    "BMQCRC_EXPIRE_PACK_DST_TOO_SMALL: the DELETION record of MESSAGE record %llu ends past "
+    "journal_dst_bytes"};
+
+int bmqcrc_expire_records_pack(const bmqcrc_expire_pack* p, bmqcrc_expire_pack_result* result,
+                               const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    bmqcrc_opts o;
+    int rc;
+    if ((rc = check_struct(p, "bmqcrc_expire_pack", p ? p->reserved2 : 0,
+                           ".reserved and reserved2 must be 0")) ||
+        (rc = device_call_opts(opts, "bmqcrc_expire_records_pack", &o))) {
+        return rc;
+    }
+    if ((rc = refuse_null({{!p->journal, "journal"},
+                           {!p->queue_keys && p->n_queues != 0, "queue_keys (with n_queues != 0)"},
+                           {!p->ttl_seconds && p->n_queues != 0,
+                            "ttl_seconds (with n_queues != 0)"},
+                           {!p->journal_dst && p->journal_dst_bytes != 0,
+                            "journal_dst (with journal_dst_bytes != 0)"}}))) {
+        return rc;
+    }
+    const uint64_t nrec = p->n_records, nq = p->n_queues;
+    const struct {
+        bool bad;
+        const char* what;
+    } checks[] = {
+        {((uintptr_t)p->journal & 3u) != 0, "journal must be 4-byte aligned"},
+        {((uintptr_t)p->journal_dst & 3u) != 0, "journal_dst must be 4-byte aligned"},
+        {((uintptr_t)p->ttl_seconds & 7u) != 0, "ttl_seconds must be 8-byte aligned"},
+        {((uintptr_t)p->new_index & 3u) != 0, "new_index must be 4-byte aligned"},
+        {((uintptr_t)p->queue_expired & 3u) != 0, "queue_expired must be 4-byte aligned"},
+        {((uintptr_t)p->queue_front & 3u) != 0, "queue_front must be 4-byte aligned"},
+        {nrec > 0xFFFFFFFFull, "n_records must be below 2^32"},
+        {nq > 0xFFFFFFFFull, "n_queues must be below 2^32"},
+        {p->journal_bytes != kJournalRecordBytes * nrec, "journal_bytes must be 60 n_records"},
+        {p->lease_id == 0, "lease_id must not be 0"},
+        {p->first_seq == 0 || p->first_seq > kMaxSeqNum || nrec > kMaxSeqNum - p->first_seq,
+         "first_seq must not be 0, and first_seq + n_records at most 2^48-1"}};
+    for (const auto& k : checks) {
+        if (k.bad) {
+            return fail(BMQCRC_EINVAL, k.what);
+        }
+    }
+    const NamedRange journal = {p->journal, p->journal_bytes, "[journal, journal+journal_bytes)"};
+    const NamedRange select = {p->select, p->select ? nrec : 0, "select"};
+    const NamedRange qkeys = {p->queue_keys, 5 * nq, "queue_keys"};
+    const NamedRange ttls = {p->ttl_seconds, 8 * nq, "ttl_seconds"};
+    const NamedRange jdst = {p->journal_dst, p->journal_dst_bytes,
+                             "[journal_dst, journal_dst+journal_dst_bytes)"};
+    const NamedRange expired = {p->expired, nrec, "expired"};
+    const NamedRange index = {p->new_index, 4 * nrec, "new_index"};
+    const NamedRange selout = {p->select_out, nrec, "select_out"};
+    const NamedRange qexp = {p->queue_expired, 4 * nq, "queue_expired"};
+    const NamedRange qfront = {p->queue_front, 4 * nq, "queue_front"};
+    if ((rc = refuse_overlap({jdst, expired, index, selout, qexp, qfront},
+                             {journal, select, qkeys, ttls})) ||
+        (rc = refuse_overlap({expired, index, selout, qexp, qfront}, {jdst})) ||
+        (rc = refuse_overlap({index, selout, qexp, qfront}, {expired})) ||
+        (rc = refuse_overlap({selout, qexp, qfront}, {index})) ||
+        (rc = refuse_overlap({qexp, qfront}, {selout})) ||
+        (rc = refuse_overlap({qfront}, {qexp}))) {
+        return rc;
+    }
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    w->exp_n = nrec;
+    w->exp_first_seq = p->first_seq;
+    w->exp_any = true;
+    if (nrec) {
+        // the hashes: a power of two, at least twice what they hold, so that a walk ends
+        const uint64_t gslots = pow2_at_least(2 * nrec);
+        const uint64_t qslots = nq ? pow2_at_least(2 * nq) : 0;
+        const uint64_t zero_bytes = 8ull * kExpCtrWords + 4 * gslots + 4 * qslots + 4 * nq + nrec;
+        if ((rc = w->exp_zero.ensure(zero_bytes)) ||
+            (rc = w->exp_front.ensure(4 * std::max<uint64_t>(nq, 1))) ||
+            (rc = w->exp_rec.ensure(5 * nrec)) || (rc = w->exp_off.ensure(8 * nrec)) ||
+            (rc = w->exp_bsum.ensure(8ull * 2 * kPackBlocks))) {
+            return rc;
+        }
+        HIP_TRY(hipMemsetAsync(w->exp_zero.p, 0, zero_bytes, c.s));
+        if (nq) {
+            HIP_TRY(hipMemsetAsync(w->exp_front.p, 0xFF, 4 * nq, c.s));  // kExpNone
+        }
+        ExpArgs a;
+        memset(&a, 0, sizeof(a));
+        a.journal = (const uint32_t*)p->journal;
+        a.n_records = nrec;
+        a.select = p->select;
+        a.queue_keys = p->queue_keys;
+        a.ttl_seconds = p->ttl_seconds;
+        a.n_queues = nq;
+        a.now = p->now;
+        a.first_seq = p->first_seq;
+        a.lease_id = p->lease_id;
+        a.size_only = p->journal_dst ? 0u : 1u;
+        a.journal_dst = (uint32_t*)p->journal_dst;
+        a.journal_dst_bytes = p->journal_dst_bytes;
+        a.expired = p->expired;
+        a.new_index = p->new_index;
+        a.select_out = p->select_out;
+        a.queue_expired = p->queue_expired;
+        a.queue_front = p->queue_front;
+        a.ctr = (unsigned long long*)w->exp_zero.p;
+        a.gslot = (uint32_t*)(a.ctr + kExpCtrWords);
+        a.gslots = gslots;
+        a.qslot = a.gslot + gslots;
+        a.qslots = qslots;
+        a.qcount = a.qslot + qslots;
+        a.dead = (uint8_t*)(a.qcount + nq);
+        a.front = (uint32_t*)w->exp_front.p;
+        a.queue = (uint32_t*)w->exp_rec.p;
+        a.kind = (uint8_t*)(a.queue + nrec);
+        a.off = (unsigned long long*)w->exp_off.p;
+        a.bsum = (unsigned long long*)w->exp_bsum.p;
+        layout_split(nrec, &a.per_block, &a.nblocks);
+        if (nq) {
+            layout_split(nq, &a.qper_block, &a.qnblocks);
+        }
+        if (bmqcrc_launch_expire_records_layout(&a, (void*)c.s)) {
+            return launch_failed("expire-records layout");
+        }
+        if (!a.size_only && bmqcrc_launch_expire_records_frame(&a, (void*)c.s)) {
+            return launch_failed("expire-records frame");
+        }
+    }
+    return sync_result_or_refusal(c, o, expire_records_result, result, kExpirePackRefusals);
+}
+
+int bmqcrc_last_expire_records(int device, void* stream, bmqcrc_expire_pack_result* result)
+{
+    return last_result(device, stream, expire_records_result, result);
+}
+
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,
                        uint32_t* seg_bytes)
 {
@@ -4176,7 +4363,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 19u;
+    return (2u << 16) | 20u;
 }
 
 }  // extern "C"

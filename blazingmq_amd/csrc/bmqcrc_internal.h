@@ -729,7 +729,77 @@ struct CfmArgs {
     uint64_t cper_block;            // confirms per block (multiple of kPackThreads)
 };
 
+// ---- bmqcrc_expire_records_pack (crc32c_expire_records.hip, ABI 2.20) ------
+// The classify grid and block are kPackBlocks x kPackThreads over contiguous
+// record ranges (layout_split over n_records) and, in the same blocks, over
+// contiguous queue-table ranges (layout_split over n_queues); the join, front,
+// check and seal kernels' the same over the records; the frame kernel's
+// kPackFrameBlocks x kPackFrameThreads.  ExpArgs::ctr words
+constexpr int kExpCtrRefusal = kLayoutCtrRefusal;
+constexpr int kExpCtrExpired = 1;   // DELETION records written (k_exp_seal)
+constexpr int kExpCtrLive = 2;      // live MESSAGE records (k_exp_seal)
+constexpr int kExpCtrNoQueue = 3;   // ... of them without a table entry (k_exp_seal)
+constexpr int kExpCtrWords = 4;
+constexpr uint32_t kExpNone = 0xFFFFFFFFu;  // no queue, no young message, no place
+constexpr uint32_t kExpLdsQueues = 2048;   // a table up to this long is reduced per block in LDS
+// ExpArgs::kind: what the join makes of a record of the run
+constexpr uint8_t kExpOther = 0;
+constexpr uint8_t kExpMessage = 1;   // a selected MESSAGE record: it is in the hash
+constexpr uint8_t kExpDeletion = 2;
+constexpr uint32_t kDeletionFlagTtl = 2;  // DeletionRecordFlag::e_TTL_EXPIRATION
+// BMQCRC_EXPIRE_PACK_* of bmqcrc_protocol.h, which the kernels do not include
+#define BMQCRC_EXP_KIND_RECORD_HEADER 1u
+#define BMQCRC_EXP_KIND_DUPLICATE_MESSAGE 2u
+#define BMQCRC_EXP_KIND_QUEUE_KEY 3u
+#define BMQCRC_EXP_KIND_DST_TOO_SMALL 4u
+
+struct ExpArgs {
+    const uint32_t* journal;        // device, 4-byte aligned: n_records records of 15 dwords
+    uint64_t n_records;
+    const uint8_t* select;          // device, n_records, or nullptr (every MESSAGE record)
+    const uint8_t* queue_keys;      // device, 5 n_queues
+    const uint64_t* ttl_seconds;    // device, n_queues
+    uint64_t n_queues;
+    uint64_t now;                   // secondsFromEpoch, and every written record's timestamp
+    uint64_t first_seq;
+    uint32_t lease_id;
+    uint32_t size_only;             // 1: journal_dst is null, DST_TOO_SMALL is never raised
+    uint32_t* journal_dst;          // device, 4-byte aligned
+    uint64_t journal_dst_bytes;
+    uint8_t* expired;               // the caller's arrays (device; n_records, n_records,
+    uint32_t* new_index;            // n_records, n_queues, n_queues), each may be nullptr:
+    uint8_t* select_out;            // written by k_exp_frame, when nothing was refused
+    uint32_t* queue_expired;
+    uint32_t* queue_front;
+    // workspace, zeroed before the launch
+    unsigned long long* ctr;        // kExpCtrWords
+    uint32_t* gslot;                // gslots: record + 1 of a selected MESSAGE record, hashed by
+    uint64_t gslots;                // GUID and queue key; a power of two
+    uint32_t* qslot;                // qslots: entry + 1 of the queue table, hashed by its key; a
+    uint64_t qslots;                // power of two (0 slots for an empty table)
+    uint32_t* qcount;               // n_queues: the queue's expired messages (k_exp_seal)
+    uint8_t* dead;                  // n_records: 1: a DELETION record of the run names it
+    // workspace, every byte 0xFF before the launch
+    uint32_t* front;                // n_queues: front(q), kExpNone without a young message
+    // workspace, written before it is read
+    uint32_t* queue;                // n_records: a selected MESSAGE record's entry, or kExpNone
+    uint8_t* kind;                  // n_records: kExp*
+    unsigned long long* off;        // n_records: the prefix of "expired", then the place j (~0:
+                                    // not expired)
+    unsigned long long* bsum;       // 2 * kPackBlocks: records written | (unused) per block
+    uint64_t per_block;             // records per block (multiple of kPackThreads)
+    uint32_t nblocks;               // blocks over the records (<= kPackBlocks)
+    uint32_t qnblocks;              // blocks over the queue table (<= kPackBlocks, 0: empty)
+    uint64_t qper_block;            // entries per block (multiple of kPackThreads)
+};
+
 }  // namespace bmqcrc
+
+// Launchers (crc32c_expire_records.hip).  Asynchronous on `stream`: the layout
+// decides everything, the frame stores; a size-only call launches the layout
+// alone.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_expire_records_layout(const bmqcrc::ExpArgs* a, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_expire_records_frame(const bmqcrc::ExpArgs* a, void* stream);
 
 // Launchers (crc32c_confirm_records.hip).  Asynchronous on `stream`: the layout
 // decides everything, the frame stores; a size-only call launches the layout

@@ -480,8 +480,11 @@ class PartitionWriter:
         return self._record(REC_CONFIRM, [(22, bytes(queue_key)), (27, bytes(app_key)),
                                           (32, bytes(guid))], flags=int(reason))
 
-    def deletion(self, guid, queue_key):
-        return self._record(REC_DELETION, [(23, bytes(queue_key)), (28, bytes(guid))])
+    def deletion(self, guid, queue_key, flags=0):
+        """`flags` is the DeletionRecordFlag in the RecordHeader's flags: 0
+        none, 1 IMPLICIT_CONFIRM, 2 TTL_EXPIRATION, 3 NO_SC_QUORUM."""
+        return self._record(REC_DELETION, [(23, bytes(queue_key)), (28, bytes(guid))],
+                            flags=int(flags))
 
     def files(self):
         journal = file_header(FILE_TYPE_JOURNAL, self.partition_id).tobytes() + \
@@ -1086,5 +1089,146 @@ def last_confirm_records(device, stream=None):
     stream."""
     r = N.ConfirmPackResult()
     N.check(N.lib.bmqcrc_last_confirm_records(
+        device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
+    return r.as_dict()
+
+
+# ----------------------------------------------------------------------------
+# Device-side TTL: the DELETION records of the messages that have expired.
+# ----------------------------------------------------------------------------
+ExpiredRecords = collections.namedtuple(
+    "ExpiredRecords",
+    "journal_dst expired new_index select_out queue_expired queue_front result")
+
+
+def expire_records(journal, queue_keys, ttl_seconds, *, now, lease_id, first_seq, select=None,
+                   journal_dst=None, stream=None, sync=True):
+    """Expire the messages of a device-resident partition whose TTL has run out
+    on the GPU (``bmqcrc_expire_records_pack``): the DELETION records, flagged
+    ``e_TTL_EXPIRATION``, that ``FileBackedStorage::gcExpiredMessages`` appends
+    through ``FileStore::writeDeletionRecord``.  There is no CRC in this call:
+    no payload byte is read.
+
+    The journal is the state, as for ``confirm_records``: ``journal`` (uint8,
+    4-byte aligned, whole 60-byte records) is the partition's run and ``select``
+    (uint8, one byte per record, or None for every MESSAGE record) says which
+    MESSAGE records count.  A message is live when it is selected and no
+    DELETION record of the run names it; reference counts play no part.
+
+    The queue table is ``queue_keys`` (uint8, 5 bytes per queue) and
+    ``ttl_seconds`` (int64 per queue, read as unsigned); it may be empty.  With
+    ``now`` the seconds from the epoch, a live message of queue q is young when
+    ``(now - timestamp) mod 2**64 <= ttl_seconds[q]`` -- unsigned, as the
+    reference computes it, so a timestamp in the future reads as expired -- and
+    a live message expires when no young message of its queue stands before it
+    in the run: the reference walks a queue from its head and stops at the
+    first message that has not expired.  A live message whose queue is not in
+    the table never expires.  Every expired message writes one DELETION record,
+    in journal order, sequence numbers from ``first_seq`` on under ``lease_id``
+    and with ``now`` as its timestamp.
+
+    ``journal_dst=None`` sizes the destination exactly with a size-only call
+    first, which takes ``sync=True``; ``journal_dst`` may be the tail of the
+    tensor ``journal`` is a slice of.
+
+    Returns the named tuple ``(journal_dst, expired, new_index, select_out,
+    queue_expired, queue_front, result)``: ``expired`` (uint8 per record),
+    ``new_index`` (int32, the DELETION record's place in ``journal_dst``, -1 for
+    none), ``select_out`` (uint8, 1 for the MESSAGE records that are live and
+    not expired: the next ``select``), ``queue_expired`` (int32 per queue) and
+    ``queue_front`` (int32 per queue: the record of the queue's first young
+    message, -1 for none), the last two None for an empty run, which launches
+    nothing; ``result`` the dict of ``last_expire_records`` (None with
+    ``sync=False``).  With ``sync=True`` ``journal_dst`` is sliced to the bytes
+    written.  All or nothing: a malformed record, two selected MESSAGE records
+    with one key, a null or repeated queue key in the table, or a destination
+    too small writes nothing and, with ``sync=True``, raises ``BmqCrcError``
+    (BMQCRC_EINVAL) naming kind and index.  Not meant to be captured into a
+    graph."""
+    import torch
+    for name, t in (("journal", journal), ("queue_keys", queue_keys), ("select", select),
+                    ("journal_dst", journal_dst)):
+        if t is None and name not in ("journal", "queue_keys"):
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise TypeError("%s must be a contiguous %s tensor" % (name, torch.uint8))
+    dev = journal.device
+    if not journal.is_cuda:
+        raise TypeError("expire_records takes device tensors only (journal is on %s)" % dev)
+    if not (isinstance(ttl_seconds, torch.Tensor) and ttl_seconds.dtype == torch.int64 and
+            ttl_seconds.is_contiguous()):
+        raise TypeError("ttl_seconds must be a contiguous %s tensor" % torch.int64)
+    for name, t in (("queue_keys", queue_keys), ("ttl_seconds", ttl_seconds), ("select", select),
+                    ("journal_dst", journal_dst)):
+        if t is not None and t.device != dev:
+            raise TypeError("%s must be on %s like journal" % (name, dev))
+    if journal.numel() % JOURNAL_RECORD_SIZE:
+        raise ValueError("journal must hold whole 60-byte records")
+    n_records = journal.numel() // JOURNAL_RECORD_SIZE
+    n_queues = ttl_seconds.numel()
+    if queue_keys.numel() != 5 * n_queues:
+        raise ValueError("queue_keys needs 5 bytes per entry of ttl_seconds")
+    if select is not None and select.numel() != n_records:
+        raise ValueError("select has the wrong size")
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    # (an empty tensor has no address: the call wants one for the required arrays)
+    spare = torch.empty(8, dtype=torch.uint8, device=dev)
+    p = N.ExpirePack()
+    p.struct_size = ctypes.sizeof(N.ExpirePack)
+    p.journal, p.journal_bytes = journal.data_ptr() or spare.data_ptr(), journal.numel()
+    p.n_records, p.n_queues = n_records, n_queues
+    p.select = select.data_ptr() if select is not None and n_records else None
+    p.queue_keys = queue_keys.data_ptr() if n_queues else None
+    p.ttl_seconds = ttl_seconds.data_ptr() if n_queues else None
+    p.now = int(now) & 0xFFFFFFFFFFFFFFFF
+    p.first_seq, p.lease_id = int(first_seq), int(lease_id)
+    dev_index = dev.index if dev.index is not None else -1
+    if journal_dst is None:
+        if not sync:
+            raise ValueError("journal_dst is required when sync=False: sizing it waits for a "
+                             "size-only call")
+        o = N.make_opts(device=dev_index, stream=stream.cuda_stream, flags=N.BMQCRC_F_DEVICE_PTRS)
+        r = N.ExpirePackResult()
+        N.check(N.lib.bmqcrc_expire_records_pack(ctypes.byref(p), ctypes.byref(r),
+                                                 ctypes.byref(o)))
+        journal_dst = torch.empty(int(r.journal_bytes), dtype=torch.uint8, device=dev)
+    expired = torch.empty(n_records, dtype=torch.uint8, device=dev)
+    new_index = torch.empty(n_records, dtype=torch.int32, device=dev)
+    select_out = torch.empty(n_records, dtype=torch.uint8, device=dev)
+    per_queue = n_records != 0
+    queue_expired = torch.empty(n_queues, dtype=torch.int32, device=dev) if per_queue else None
+    queue_front = torch.empty(n_queues, dtype=torch.int32, device=dev) if per_queue else None
+    p.journal_dst = journal_dst.data_ptr() or spare.data_ptr()
+    p.journal_dst_bytes = journal_dst.numel()
+    p.expired = expired.data_ptr() if n_records else None
+    p.new_index = new_index.data_ptr() if n_records else None
+    p.select_out = select_out.data_ptr() if n_records else None
+    p.queue_expired = queue_expired.data_ptr() if per_queue and n_queues else None
+    p.queue_front = queue_front.data_ptr() if per_queue and n_queues else None
+    o = N.make_opts(device=dev_index, stream=stream.cuda_stream,
+                    flags=N.BMQCRC_F_DEVICE_PTRS | (0 if sync else N.BMQCRC_F_ASYNC))
+    r = N.ExpirePackResult()
+    N.check(N.lib.bmqcrc_expire_records_pack(ctypes.byref(p), ctypes.byref(r), ctypes.byref(o)))
+    if not sync:
+        return ExpiredRecords(journal_dst, expired, new_index, select_out, queue_expired,
+                              queue_front, None)
+    return ExpiredRecords(journal_dst[:int(r.journal_bytes)], expired, new_index, select_out,
+                          queue_expired, queue_front, r.as_dict())
+
+
+def last_expire_records(device, stream=None):
+    """The result of the previous ``expire_records`` on (device, stream)
+    (bmqcrc_last_expire_records), as a dict; waits for it.  ``n_records``;
+    ``n_live`` live MESSAGE records, of which ``n_expired`` wrote a DELETION
+    record and ``n_no_queue`` have no entry in the queue table;
+    ``journal_bytes`` written (or, after a size-only call, needed);
+    ``next_seq``, the sequence number behind the last record; ``refused_kind``
+    (0, ``BMQCRC_EXPIRE_PACK_OK``, or the kind) and ``refused_index`` (a record
+    or a table entry, by kind).  After a refused call only ``n_records`` and the
+    two ``refused_*`` are set.  ``stream=None`` is the device's default
+    stream."""
+    r = N.ExpirePackResult()
+    N.check(N.lib.bmqcrc_last_expire_records(
         device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
     return r.as_dict()

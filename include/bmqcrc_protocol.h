@@ -1450,6 +1450,139 @@ int bmqcrc_confirm_records_pack(const bmqcrc_confirm_pack* p, bmqcrc_confirm_pac
  * stream); waits for it.  `result` may be NULL. */
 int bmqcrc_last_confirm_records(int device, void* stream, bmqcrc_confirm_pack_result* result);
 
+/* ABI 2.20.  The TTL: the messages of a device-resident partition whose
+ * time-to-live has run out become ON THE DEVICE the DELETION records the
+ * primary's garbage collection would append -- FileStore::gcExpiredMessages ->
+ * FileBackedStorage::gcExpiredMessages -> FileStore::writeDeletionRecord with
+ * DeletionRecordFlag::e_TTL_EXPIRATION -- byte for byte, in one asynchronous
+ * call.  THIS CALL HAS NO CRC IN IT: no payload byte is read.  It is here
+ * because a queue whose consumers are slow or gone would otherwise fill a
+ * device-resident partition for ever.
+ *
+ * The journal is the state, as in bmqcrc_confirm_records_pack: the run, select
+ *   and key = (GUID, queue key) mean what they mean there.
+ *   - live(m): MESSAGE record m is selected and no DELETION record anywhere in
+ *     the run has its key.  Reference counts play no part: the reference's loop
+ *     walks every message it still holds.
+ * The queue table is the domain configuration the reference holds per storage
+ *   as d_ttlSeconds: entry q = 0 .. n_queues - 1 is queue_keys[5 q .. +5) and
+ *   ttl_seconds[q].  n_queues == 0 is legal: nothing can expire.
+ *   - queue(m): the entry whose 5 bytes equal bytes 22..26 of m, or none.  A
+ *     live message without an entry is never expired and is counted in
+ *     n_no_queue: the reference would have no storage to walk for it.
+ *   - ts(m): bytes 12..19 of the record, big-endian: the RecordHeader's
+ *     timestamp.
+ *   - young(m): live(m), queue(m) = q exists and (now - ts(m)) mod 2^64 <=
+ *     ttl_seconds[q].  The subtraction is unsigned and wraps, exactly as the
+ *     reference's: a timestamp in the future reads as expired, unless an older
+ *     young message stands before it.
+ *   - front(q): the lowest record index of a young message of q, or n_records
+ *     when there is none.
+ *   - expired(m): live(m), queue(m) = q and m < front(q).
+ *   This is the reference's loop restated without order: it deletes from the
+ *   head of a queue's messages in arrival order and breaks at the first one
+ *   that has not expired, so younger-looking stragglers behind it survive.
+ *   After recovery, arrival order is journal order.
+ * What is written.  The j-th expired MESSAGE record in journal order writes a
+ *   DELETION record at journal_dst + 60 j: type 3, flags 2 (e_TTL_EXPIRATION),
+ *   sequence number first_seq + j, lease_id, timestamp `now`, the queue key at
+ *   byte 23 and the GUID at byte 28, every other byte behind the RecordHeader
+ *   zero, the magic 0x2A724563 at 56.  Apart from the flags these are the bytes
+ *   of bmqcrc_confirm_records_pack's DELETION records.
+ * Outputs, each may be NULL: expired[n_records] (1 or 0); new_index[n_records]
+ *   (j, or 0xFFFFFFFF); select_out[n_records] (1 exactly for MESSAGE records
+ *   that are live and not expired: the next select for every other call);
+ *   queue_expired[n_queues]; queue_front[n_queues] (front(q), 0xFFFFFFFF for
+ *   none: the caller reads from it when that queue is next due).
+ * Size only.  journal_dst == NULL with journal_dst_bytes == 0: everything is
+ *   decided, nothing is stored (no output array either) and the result says
+ *   what a real call would write.
+ * All or nothing, decided on the device.  One violation anywhere refuses the
+ *   call, and a refused call writes nothing.  The lowest kind wins and within
+ *   it the lowest index (BMQCRC_EXPIRE_PACK_* below), whatever the order the
+ *   device works in.  A synchronous call returns BMQCRC_EINVAL naming kind and
+ *   index; after an asynchronous call bmqcrc_last_expire_records reports them.
+ * What differs from the reference.
+ *   - There is no e_NO_SC_QUORUM branch: receipts are not in the journal.
+ *   - There is no `limit`: FileStore's own call passes none.
+ *   - Records come out in journal order.  The reference visits queues in its
+ *     storage map's order; inside a queue the order is the same.
+ *   - No stats, no queue-engine callback, no virtual-storage bookkeeping.
+ *   - Nothing is replicated: the output goes to bmqcrc_storage_event_pack.
+ * Options.  Device pointers only: BMQCRC_F_DEVICE_PTRS is required,
+ *   BMQCRC_F_ASYNC allowed; any other flag, ndevices > 1, a wrong struct_size or
+ *   a non-zero reserved field; journal null; queue_keys or ttl_seconds null
+ *   with n_queues != 0; journal_dst null with journal_dst_bytes != 0; journal,
+ *   journal_dst, new_index, queue_expired or queue_front not 4-byte aligned,
+ *   ttl_seconds not 8-byte aligned; journal_bytes != 60 n_records; n_records or
+ *   n_queues >= 2^32; lease_id 0; first_seq 0 or first_seq + n_records above
+ *   2^48 - 1; journal_dst or an output array meeting an input or one another is
+ *   BMQCRC_EINVAL, answered on the host before the device lookup.
+ *   n_records == 0 launches nothing, writes nothing (the per-queue arrays
+ *   neither, and the table is not looked at) and reports zeros behind
+ *   next_seq = first_seq.
+ * *result (may be NULL) is written by a synchronous call only.
+ * State.  As bmqcrc_confirm_records_pack: takes the workspace mutex of (device,
+ *   stream); restores the caller's current device; allocates its own workspace
+ *   on first use and when the call grows (14 bytes per record and 8 to 16 more
+ *   for the hash, 8 per table entry and 8 to 16 more for its hash), which
+ *   bmqcrc_reserve does not cover; is not meant to be captured into a hipGraph;
+ *   is deterministic.  The shape prediction and the records of every other
+ *   bmqcrc_last_* call are never touched. */
+#define BMQCRC_EXPIRE_PACK_OK 0
+#define BMQCRC_EXPIRE_PACK_RECORD_HEADER 1      /* BMQCRC_CONFIRM_PACK_RECORD_HEADER's conditions, on every
+                                                   record of the run.  Index: the record */
+#define BMQCRC_EXPIRE_PACK_DUPLICATE_MESSAGE 2  /* two selected MESSAGE records share a key.  Index: the
+                                                   lowest record among all that share theirs */
+#define BMQCRC_EXPIRE_PACK_QUEUE_KEY 3          /* a table entry whose key is all zero, or a key that stands
+                                                   in the table twice.  Index: the entry; for a repeat the
+                                                   lowest entry among all that share theirs */
+#define BMQCRC_EXPIRE_PACK_DST_TOO_SMALL 4      /* index: the lowest MESSAGE record whose DELETION record
+                                                   ends past journal_dst_bytes */
+
+typedef struct bmqcrc_expire_pack {
+    uint32_t struct_size, reserved;       /* sizeof, 0 */
+    const void* journal;                  /* device, 4-byte aligned: n_records 60-byte records, the record run */
+    uint64_t journal_bytes;               /* == 60 * n_records */
+    uint64_t n_records;                   /* < 2^32 */
+    const uint8_t* select;                /* device, n_records, may be NULL (every MESSAGE record) */
+    const uint8_t* queue_keys;            /* device, 5 n_queues (may be NULL when n_queues is 0) */
+    const uint64_t* ttl_seconds;          /* device, n_queues, 8-byte aligned (may be NULL likewise) */
+    uint64_t n_queues;                    /* < 2^32 */
+    uint64_t now;                         /* seconds from the epoch; every written record's timestamp */
+    uint64_t first_seq;                   /* sequence number of the first record written, not 0 */
+    uint32_t lease_id;                    /* primary lease id, not 0 */
+    uint32_t reserved2;                   /* 0 */
+    void* journal_dst;                    /* device, 4-byte aligned: the 60-byte records back to back;
+                                             NULL (journal_dst_bytes 0): size only */
+    uint64_t journal_dst_bytes;
+    uint8_t* expired;                     /* device, n_records, may be NULL */
+    uint32_t* new_index;                  /* device, n_records, may be NULL */
+    uint8_t* select_out;                  /* device, n_records, may be NULL */
+    uint32_t* queue_expired;              /* device, n_queues, may be NULL */
+    uint32_t* queue_front;                /* device, n_queues, may be NULL */
+} bmqcrc_expire_pack;
+
+/* All fields zero before the first call on (device, stream); after a refused
+ * call only n_records and the refused_* fields are set. */
+typedef struct bmqcrc_expire_pack_result {
+    uint64_t n_records;
+    uint64_t n_live;                      /* live MESSAGE records, the expired ones among them */
+    uint64_t n_expired;                   /* DELETION records written */
+    uint64_t n_no_queue;                  /* live MESSAGE records without a table entry */
+    uint64_t journal_bytes;               /* 60 n_expired */
+    uint64_t next_seq;                    /* first_seq + n_expired */
+    uint32_t refused_kind, reserved;
+    uint64_t refused_index;               /* a record or a table entry, by kind */
+} bmqcrc_expire_pack_result;
+
+int bmqcrc_expire_records_pack(const bmqcrc_expire_pack* p, bmqcrc_expire_pack_result* result,
+                               const bmqcrc_opts* opts);
+
+/* ABI 2.20.  Result of the previous bmqcrc_expire_records_pack on (device,
+ * stream); waits for it.  `result` may be NULL. */
+int bmqcrc_last_expire_records(int device, void* stream, bmqcrc_expire_pack_result* result);
+
 /* ---- cluster state ledger (mqbc_clusterstateledgerprotocol.h:76,272) ------ */
 
 /* mqbc::ClusterStateLedgerUtilRc values (mqbc_clusterstateledgerutil.h:65-124)
