@@ -15,9 +15,9 @@ from .put_event import (last_put_pack, last_put_unpack, pack_events,  # noqa: F4
 from .push_event import (PushEventBuilder, PushMessageIterator, last_push_pack,  # noqa: F401
                          pack_push_events)
 from .storage import (confirm_records, expire_records, last_confirm_records,  # noqa: F401
-                      last_expire_records, last_journal_select, last_records_pack,
-                      last_records_unpack, last_rollover, pack_records, rollover_records,
-                      select_records, unpack_records)
+                      last_expire_records, last_journal_select, last_pending_records,
+                      last_records_pack, last_records_unpack, last_rollover, pack_records,
+                      pending_records, rollover_records, select_records, unpack_records)
 from .storage_event import (StorageEventBuilder, StorageMessageIterator,  # noqa: F401
                             apply_events, last_storage_apply, last_storage_pack,
                             pack_storage_events)
@@ -31,5 +31,5 @@ __all__ = ["Blob", "BmqCrcError", "Crc32c", "HostRegistration", "PushEventBuilde
            "last_rollover", "last_storage_pack", "pack_events", "pack_records", "pack_storage_events",
            "reserve", "rollover_records", "select_records", "unpack_events", "unpack_records",
            "confirm_records", "last_confirm_records", "expire_records", "last_expire_records",
-           "ConfirmEventBuilder",
+           "pending_records", "last_pending_records", "ConfirmEventBuilder",
            "ConfirmMessageIterator", "confirm_arrays"]

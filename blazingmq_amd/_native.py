@@ -506,6 +506,44 @@ if hasattr(lib, "bmqcrc_expire_records_pack"):  # ABI 2.20 (an older build loads
                                                ctypes.POINTER(ExpirePackResult), _popts]
     lib.bmqcrc_last_expire_records.restype = _int
     lib.bmqcrc_last_expire_records.argtypes = [_int, _vp, ctypes.POINTER(ExpirePackResult)]
+BMQCRC_PENDING_LIST_OK = 0
+BMQCRC_PENDING_LIST_RECORD_HEADER = 1
+BMQCRC_PENDING_LIST_DUPLICATE_MESSAGE = 2
+BMQCRC_PENDING_LIST_QUEUE_KEY = 3
+BMQCRC_PENDING_LIST_APP_FIRST = 4
+BMQCRC_PENDING_LIST_APP_KEY = 5
+BMQCRC_PENDING_LIST_FROM_RECORD = 6
+BMQCRC_PENDING_LIST_LIST_TOO_SMALL = 7
+
+
+class PendingList(ctypes.Structure):
+    """bmqcrc_pending_list (include/bmqcrc_protocol.h, ABI 2.21)."""
+    _fields_ = [("struct_size", _u32), ("reserved", _u32), ("journal", _vp),
+                ("journal_bytes", _u64), ("n_records", _u64), ("select", _vp),
+                ("queue_keys", _vp), ("app_first", _vp), ("n_queues", _u64), ("app_keys", _vp),
+                ("queue_ids", _vp), ("sub_ids", _vp), ("from_record", _vp), ("limit", _vp),
+                ("n_apps", _u64), ("records", _vp), ("out_queue_ids", _vp),
+                ("out_sub_ids", _vp), ("list_cap", _u64), ("list_first", _vp),
+                ("app_pending", _vp), ("app_next", _vp), ("pending_mask", _vp)]
+
+
+class PendingListResult(ctypes.Structure):
+    """bmqcrc_pending_list_result (include/bmqcrc_protocol.h, ABI 2.21)."""
+    _fields_ = [("n_records", _u64), ("n_live", _u64), ("n_no_queue", _u64),
+                ("n_pending", _u64), ("n_listed", _u64), ("n_unknown_confirms", _u64),
+                ("n_not_found", _u64), ("refused_kind", _u32), ("reserved", _u32),
+                ("refused_index", _u64)]
+
+    def as_dict(self):
+        return {f[0]: int(getattr(self, f[0])) for f in self._fields_ if f[0] != "reserved"}
+
+
+if hasattr(lib, "bmqcrc_pending_records_list"):  # ABI 2.21 (an older build loads for same-box A/B)
+    lib.bmqcrc_pending_records_list.restype = _int
+    lib.bmqcrc_pending_records_list.argtypes = [ctypes.POINTER(PendingList),
+                                                ctypes.POINTER(PendingListResult), _popts]
+    lib.bmqcrc_last_pending_records.restype = _int
+    lib.bmqcrc_last_pending_records.argtypes = [_int, _vp, ctypes.POINTER(PendingListResult)]
 lib.bmqcrc_journal_scan.restype = _i64
 lib.bmqcrc_journal_scan.argtypes = [_vp, _u64, _vp, _u64, _vp, _pint, _pu64, _vp, _vp, _vp, _vp,
                                     _u64]

@@ -22,7 +22,7 @@ ORACLE = os.path.join(ROOT, "oracle")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-PRODUCT_SOURCES = ["crc32c_kernels.hip", "crc32c_copy.hip", "crc32c_put_pack.hip", "crc32c_records_pack.hip", "crc32c_put_unpack.hip", "crc32c_records_unpack.hip", "crc32c_journal_select.hip", "crc32c_storage_apply.hip", "crc32c_storage_pack.hip", "crc32c_push_pack.hip", "crc32c_rollover.hip", "crc32c_confirm_records.hip", "crc32c_expire_records.hip", "bmqcrc_host.cpp", "crc32c_cpu.cpp", "bmqp_crc32c.cpp",
+PRODUCT_SOURCES = ["crc32c_kernels.hip", "crc32c_copy.hip", "crc32c_put_pack.hip", "crc32c_records_pack.hip", "crc32c_put_unpack.hip", "crc32c_records_unpack.hip", "crc32c_journal_select.hip", "crc32c_storage_apply.hip", "crc32c_storage_pack.hip", "crc32c_push_pack.hip", "crc32c_rollover.hip", "crc32c_confirm_records.hip", "crc32c_expire_records.hip", "crc32c_pending_list.hip", "bmqcrc_host.cpp", "crc32c_cpu.cpp", "bmqp_crc32c.cpp",
                    "bmqcrc_protocol.cpp"]
 PRODUCT_DEPS = ["bmqcrc_internal.h", "crc32c_pack_layout.h", "crc32c_unpack_slots.h", "crc32c_journal_stage.h", "crc32c_join_key.h", "crc32c_consts.h", "crc32c_diag.h", "k_plan_map_body.inc"]
 

@@ -265,6 +265,16 @@ struct Workspace {
     DevBuf exp_zero, exp_front, exp_rec, exp_off, exp_bsum;
     uint64_t exp_n = 0, exp_first_seq = 0;
     bool exp_any = false;
+    // bmqcrc_pending_records_list: the part of its workspace every call zeroes
+    // (the counters; the two hashes as the expire call's; per record confirmed,
+    // 4, and dead, 1), per record the queue and the mask (4 each), the kind (1)
+    // and the prefix (8), the records' and the apps' block sums, per pair (app,
+    // message) the app and the record twice (16), the sort's digit counts
+    // (256 per block and 256 row totals), per app the list's start (8), its first pair and its
+    // length (4 each); the records of the last call enqueued
+    DevBuf pnd_zero, pnd_rec, pnd_off, pnd_bsum, pnd_pairs, pnd_hist, pnd_app;
+    uint64_t pnd_n = 0;
+    bool pnd_any = false;
     // bmqcrc_journal_select: the part of its workspace every call zeroes (the
     // counters, the queue-key and GUID tables, the claims) and the rest (the
     // two record lists, the named DELETIONs, the states); the records of the
@@ -4190,6 +4200,241 @@ int bmqcrc_last_expire_records(int device, void* stream, bmqcrc_expire_pack_resu
     return last_result(device, stream, expire_records_result, result);
 }
 
+static_assert(BMQCRC_PENDING_LIST_RECORD_HEADER == BMQCRC_PND_KIND_RECORD_HEADER &&
+                  BMQCRC_PENDING_LIST_DUPLICATE_MESSAGE == BMQCRC_PND_KIND_DUPLICATE_MESSAGE &&
+                  BMQCRC_PENDING_LIST_QUEUE_KEY == BMQCRC_PND_KIND_QUEUE_KEY &&
+                  BMQCRC_PENDING_LIST_APP_FIRST == BMQCRC_PND_KIND_APP_FIRST &&
+                  BMQCRC_PENDING_LIST_APP_KEY == BMQCRC_PND_KIND_APP_KEY &&
+                  BMQCRC_PENDING_LIST_FROM_RECORD == BMQCRC_PND_KIND_FROM_RECORD &&
+                  BMQCRC_PENDING_LIST_LIST_TOO_SMALL == BMQCRC_PND_KIND_LIST_TOO_SMALL,
+              "the kernels' refusal kinds are the public ones");
+
+// Result of the pending list last enqueued on c's workspace, after everything
+// enqueued on its stream (w->mu held); zeros when there was none.
+static int pending_list_result(Ctx& c, bmqcrc_pending_list_result* r)
+{
+    memset(r, 0, sizeof(*r));
+    if (!c.w->pnd_any) {
+        return 0;
+    }
+    unsigned long long ctr[kPndCtrWords] = {0};
+    r->n_records = c.w->pnd_n;
+    if (r->n_records) {
+        HIP_TRY(hipMemcpyAsync(ctr, c.w->pnd_zero.p, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
+    }
+    HIP_TRY(hipStreamSynchronize(c.s));
+    if (ctr[kPndCtrRefusal]) {
+        refusal_of(ctr[kPndCtrRefusal], &r->refused_kind, &r->refused_index);
+        return 0;
+    }
+    r->n_live = ctr[kPndCtrLive];
+    r->n_no_queue = ctr[kPndCtrNoQueue];
+    r->n_pending = ctr[kPndCtrPending];
+    r->n_listed = ctr[kPndCtrListed];
+    r->n_unknown_confirms = ctr[kPndCtrUnknown];
+    r->n_not_found = ctr[kPndCtrNotFound];
+    return 0;
+}
+
+static const char* const kPendingListRefusals[8] = {
+    "", "BMQCRC_PENDING_LIST_RECORD_HEADER: record %llu has type 0 or above 5, lease id 0, "
+        "sequence number 0, a wrong magic or a QueueOpType outside 1..4",
+    "BMQCRC_PENDING_LIST_DUPLICATE_MESSAGE: selected MESSAGE record %llu shares its GUID and "
+    "queue key with another selected MESSAGE record",
+    "BMQCRC_PENDING_LIST_QUEUE_KEY: queue_keys entry %llu is all zero or stands in the table twice",
+    "BMQCRC_PENDING_LIST_APP_FIRST: app_first entry %llu does not start at 0, falls, spans more "
+    "than 32 apps or does not end at n_apps",
+    "BMQCRC_PENDING_LIST_APP_KEY: app %llu shares its app key with another app of its queue",
+    "BMQCRC_PENDING_LIST_FROM_RECORD: from_record of app %llu is above n_records",
+    "BMQCRC_PENDING_LIST_LIST_TOO_SMALL: the listed entries of app %llu end past list_cap (app "
+    "n_apps: 2^32 pending entries or more)"};
+
+int bmqcrc_pending_records_list(const bmqcrc_pending_list* p, bmqcrc_pending_list_result* result,
+                                const bmqcrc_opts* opts)
+{
+    t_err.clear();
+    DeviceGuard keep_device;
+    // every refusal below answers before the device lookup (no GPU needed)
+    bmqcrc_opts o;
+    int rc;
+    if ((rc = check_struct(p, "bmqcrc_pending_list")) ||
+        (rc = device_call_opts(opts, "bmqcrc_pending_records_list", &o))) {
+        return rc;
+    }
+    const bool size_only = !p->records;
+    if ((rc = refuse_null({{!p->journal, "journal"},
+                           {!p->app_first, "app_first"},
+                           {!p->queue_keys && p->n_queues != 0, "queue_keys (with n_queues != 0)"},
+                           {!p->app_keys && p->n_apps != 0, "app_keys (with n_apps != 0)"},
+                           {!p->queue_ids && p->n_apps != 0, "queue_ids (with n_apps != 0)"},
+                           {size_only && p->list_cap != 0, "records (with list_cap != 0)"},
+                           {!size_only && !p->out_queue_ids, "out_queue_ids (with records)"},
+                           {!size_only && !p->list_first, "list_first (with records)"},
+                           {p->out_sub_ids && !p->sub_ids, "sub_ids (with out_sub_ids)"}}))) {
+        return rc;
+    }
+    const uint64_t nrec = p->n_records, nq = p->n_queues, na = p->n_apps, cap = p->list_cap;
+    const struct {
+        bool bad;
+        const char* what;
+    } checks[] = {
+        {((uintptr_t)p->journal & 3u) != 0, "journal must be 4-byte aligned"},
+        {((uintptr_t)p->app_first & 7u) != 0, "app_first must be 8-byte aligned"},
+        {((uintptr_t)p->queue_ids & 3u) != 0, "queue_ids must be 4-byte aligned"},
+        {((uintptr_t)p->sub_ids & 3u) != 0, "sub_ids must be 4-byte aligned"},
+        {((uintptr_t)p->from_record & 3u) != 0, "from_record must be 4-byte aligned"},
+        {((uintptr_t)p->limit & 3u) != 0, "limit must be 4-byte aligned"},
+        {((uintptr_t)p->records & 3u) != 0, "records must be 4-byte aligned"},
+        {((uintptr_t)p->out_queue_ids & 3u) != 0, "out_queue_ids must be 4-byte aligned"},
+        {((uintptr_t)p->out_sub_ids & 3u) != 0, "out_sub_ids must be 4-byte aligned"},
+        {((uintptr_t)p->list_first & 7u) != 0, "list_first must be 8-byte aligned"},
+        {((uintptr_t)p->app_pending & 3u) != 0, "app_pending must be 4-byte aligned"},
+        {((uintptr_t)p->app_next & 3u) != 0, "app_next must be 4-byte aligned"},
+        {((uintptr_t)p->pending_mask & 3u) != 0, "pending_mask must be 4-byte aligned"},
+        {nrec > 0xFFFFFFFFull, "n_records must be below 2^32"},
+        {nq > 0xFFFFFFFFull, "n_queues must be below 2^32"},
+        {na > 0xFFFFFFFFull, "n_apps must be below 2^32"},
+        {p->journal_bytes != kJournalRecordBytes * nrec, "journal_bytes must be 60 n_records"},
+        {cap > (1ull << 60), "list_cap must be at most 2^60"}};
+    for (const auto& k : checks) {
+        if (k.bad) {
+            return fail(BMQCRC_EINVAL, k.what);
+        }
+    }
+    const NamedRange journal = {p->journal, p->journal_bytes, "[journal, journal+journal_bytes)"};
+    const NamedRange select = {p->select, p->select ? nrec : 0, "select"};
+    const NamedRange qkeys = {p->queue_keys, 5 * nq, "queue_keys"};
+    const NamedRange afirst = {p->app_first, 8 * (nq + 1), "app_first"};
+    const NamedRange akeys = {p->app_keys, 5 * na, "app_keys"};
+    const NamedRange qids = {p->queue_ids, 4 * na, "queue_ids"};
+    const NamedRange sids = {p->sub_ids, p->sub_ids ? 4 * na : 0, "sub_ids"};
+    const NamedRange from = {p->from_record, p->from_record ? 4 * na : 0, "from_record"};
+    const NamedRange limit = {p->limit, p->limit ? 4 * na : 0, "limit"};
+    const NamedRange recs = {p->records, 4 * cap, "records"};
+    const NamedRange oqids = {p->out_queue_ids, 4 * cap, "out_queue_ids"};
+    const NamedRange osids = {p->out_sub_ids, 4 * cap, "out_sub_ids"};
+    const NamedRange lfirst = {p->list_first, 8 * (na + 1), "list_first"};
+    const NamedRange apend = {p->app_pending, 4 * na, "app_pending"};
+    const NamedRange anext = {p->app_next, 4 * na, "app_next"};
+    const NamedRange pmask = {p->pending_mask, 4 * nrec, "pending_mask"};
+    if ((rc = refuse_overlap({recs, oqids, osids, lfirst, apend, anext, pmask},
+                             {journal, select, qkeys, afirst, akeys, qids, sids, from, limit})) ||
+        (rc = refuse_overlap({oqids, osids, lfirst, apend, anext, pmask}, {recs})) ||
+        (rc = refuse_overlap({osids, lfirst, apend, anext, pmask}, {oqids})) ||
+        (rc = refuse_overlap({lfirst, apend, anext, pmask}, {osids})) ||
+        (rc = refuse_overlap({apend, anext, pmask}, {lfirst})) ||
+        (rc = refuse_overlap({anext, pmask}, {apend})) ||
+        (rc = refuse_overlap({pmask}, {anext}))) {
+        return rc;
+    }
+    LockedCtx c;
+    if ((rc = lock_on(o.device, o.stream, true, &c))) {
+        return rc;
+    }
+    Workspace* w = c.w;
+    // (a call that fails below leaves no record: its counters would be a half-run's)
+    w->pnd_any = false;
+    if (nrec) {
+        // the hashes: a power of two, at least twice what they hold, so that a walk ends
+        const uint64_t gslots = pow2_at_least(2 * nrec);
+        const uint64_t qslots = nq ? pow2_at_least(2 * nq) : 0;
+        const uint64_t zero_bytes = 8ull * kPndCtrWords + 4 * gslots + 4 * qslots + 5 * nrec;
+        if ((rc = w->pnd_zero.ensure(zero_bytes)) || (rc = w->pnd_rec.ensure(9 * nrec)) ||
+            (rc = w->pnd_off.ensure(8 * nrec)) ||
+            (rc = w->pnd_bsum.ensure(8ull * 4 * kPackBlocks)) ||
+            (rc = w->pnd_hist.ensure(4ull * kPndDigits * (kPackBlocks + 1))) ||
+            (rc = w->pnd_app.ensure(16 * std::max<uint64_t>(na, 1)))) {
+            return rc;
+        }
+        HIP_TRY(hipMemsetAsync(w->pnd_zero.p, 0, zero_bytes, c.s));
+        PndArgs a;
+        memset(&a, 0, sizeof(a));
+        a.journal = (const uint32_t*)p->journal;
+        a.n_records = nrec;
+        a.select = p->select;
+        a.queue_keys = p->queue_keys;
+        a.app_first = p->app_first;
+        a.n_queues = nq;
+        a.app_keys = p->app_keys;
+        a.queue_ids = p->queue_ids;
+        a.sub_ids = p->sub_ids;
+        a.from_record = p->from_record;
+        a.limit = p->limit;
+        a.n_apps = na;
+        a.size_only = size_only ? 1u : 0u;
+        for (uint64_t v = na ? na - 1 : 0; v; v >>= 8) {
+            ++a.passes;
+        }
+        a.records = p->records;
+        a.out_queue_ids = p->out_queue_ids;
+        a.out_sub_ids = p->out_sub_ids;
+        a.list_cap = cap;
+        a.list_first = p->list_first;
+        a.app_pending = p->app_pending;
+        a.app_next = p->app_next;
+        a.pending_mask = p->pending_mask;
+        a.ctr = (unsigned long long*)w->pnd_zero.p;
+        a.gslot = (uint32_t*)(a.ctr + kPndCtrWords);
+        a.gslots = gslots;
+        a.qslot = a.gslot + gslots;
+        a.qslots = qslots;
+        a.confirmed = a.qslot + qslots;
+        a.dead = (uint8_t*)(a.confirmed + nrec);
+        a.queue = (uint32_t*)w->pnd_rec.p;
+        a.mask = a.queue + nrec;
+        a.kind = (uint8_t*)(a.mask + nrec);
+        a.off = (unsigned long long*)w->pnd_off.p;
+        a.bsum = (unsigned long long*)w->pnd_bsum.p;
+        a.absum = a.bsum + 2 * kPackBlocks;
+        layout_split(nrec, &a.per_block, &a.nblocks);
+        const uint64_t table = std::max(nq + 1, na);
+        a.cblocks = std::max<uint32_t>(
+            a.nblocks, (uint32_t)std::min<uint64_t>((table + kPackThreads - 1) / kPackThreads,
+                                                    kPackBlocks));
+        if (bmqcrc_launch_pending_list_masks(&a, (void*)c.s)) {
+            return launch_failed("pending-list masks");
+        }
+        // the one word the sort's buffers are sized from (and the refusals so far:
+        // nothing more is launched over a refused table)
+        unsigned long long ctr[kPndCtrWords] = {0};
+        HIP_TRY(hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c.s));
+        HIP_TRY(hipStreamSynchronize(c.s));
+        if (!ctr[kPndCtrRefusal]) {
+            const uint64_t np = ctr[kPndCtrPending];  // below 2^32, or it was refused
+            if ((rc = w->pnd_pairs.ensure(16 * std::max<uint64_t>(np, 1)))) {
+                return rc;
+            }
+            a.n_pairs = np;
+            a.key[0] = (uint32_t*)w->pnd_pairs.p;
+            a.key[1] = a.key[0] + np;
+            a.val[0] = a.key[1] + np;
+            a.val[1] = a.val[0] + np;
+            a.hist = (uint32_t*)w->pnd_hist.p;
+            a.rowsum = a.hist + (uint64_t)kPndDigits * kPackBlocks;
+            if (np) {
+                layout_split(np, &a.sper_block, &a.snblocks);
+            }
+            a.aoff = (unsigned long long*)w->pnd_app.p;
+            a.afirst = (uint32_t*)(a.aoff + na);
+            a.acount = a.afirst + na;
+            if (na) {
+                layout_split(na, &a.aper_block, &a.anblocks);
+            }
+            if (bmqcrc_launch_pending_list_lists(&a, (void*)c.s)) {
+                return launch_failed("pending-list lists");
+            }
+        }
+    }
+    w->pnd_n = nrec;
+    w->pnd_any = true;
+    return sync_result_or_refusal(c, o, pending_list_result, result, kPendingListRefusals);
+}
+
+int bmqcrc_last_pending_records(int device, void* stream, bmqcrc_pending_list_result* result)
+{
+    return last_result(device, stream, pending_list_result, result);
+}
+
 int bmqcrc_last_launch(int device, void* stream, uint32_t* kernels, uint32_t* spec,
                        uint32_t* seg_bytes)
 {
@@ -4363,7 +4608,7 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc)
 
 uint32_t bmqcrc_version(void)
 {
-    return (2u << 16) | 20u;
+    return (2u << 16) | 21u;
 }
 
 }  // extern "C"

@@ -793,7 +793,104 @@ struct ExpArgs {
     uint64_t qper_block;            // entries per block (multiple of kPackThreads)
 };
 
+// ---- bmqcrc_pending_records_list (crc32c_pending_list.hip, ABI 2.21) -------
+// The classify grid and block are kPackBlocks x kPackThreads over contiguous
+// record ranges (layout_split over n_records) and, strided over the grid, the
+// queue table's n_queues + 1 app_first entries and the n_apps apps; the join, mask and emit kernels' the same over the records;
+// the sort's three legs over contiguous pair ranges (layout_split over
+// n_pairs); the bounds and check kernels' over the apps; the frame kernel's
+// kPackFrameBlocks x kPackFrameThreads.  PndArgs::ctr words
+constexpr int kPndCtrRefusal = kLayoutCtrRefusal;
+constexpr int kPndCtrPending = 1;    // pairs (app, message): the sum of |list(a)| (k_pnd_total)
+constexpr int kPndCtrLive = 2;       // live MESSAGE records (k_pnd_mask)
+constexpr int kPndCtrNoQueue = 3;    // ... of them without a table entry (k_pnd_mask)
+constexpr int kPndCtrListed = 4;     // entries a real call writes (k_pnd_check)
+constexpr int kPndCtrUnknown = 5;    // CONFIRM records whose app key no app of the queue has (k_pnd_join)
+constexpr int kPndCtrNotFound = 6;   // CONFIRM records without a message (k_pnd_join)
+constexpr int kPndCtrWords = 8;
+constexpr uint32_t kPndNone = 0xFFFFFFFFu;  // no queue
+constexpr uint32_t kPndMaxApps = 32;        // apps of one queue: a message's state is one word
+constexpr uint32_t kPndDigits = 256;        // the sort's radix: 8 bits a pass
+// PndArgs::kind: what the join makes of a record of the run
+constexpr uint8_t kPndOther = 0;
+constexpr uint8_t kPndMessage = 1;   // a selected MESSAGE record: it is in the hash
+constexpr uint8_t kPndDeletion = 2;
+constexpr uint8_t kPndConfirm = 3;
+// BMQCRC_PENDING_LIST_* of bmqcrc_protocol.h, which the kernels do not include
+#define BMQCRC_PND_KIND_RECORD_HEADER 1u
+#define BMQCRC_PND_KIND_DUPLICATE_MESSAGE 2u
+#define BMQCRC_PND_KIND_QUEUE_KEY 3u
+#define BMQCRC_PND_KIND_APP_FIRST 4u
+#define BMQCRC_PND_KIND_APP_KEY 5u
+#define BMQCRC_PND_KIND_FROM_RECORD 6u
+#define BMQCRC_PND_KIND_LIST_TOO_SMALL 7u
+
+struct PndArgs {
+    const uint32_t* journal;        // device, 4-byte aligned: n_records records of 15 dwords
+    uint64_t n_records;
+    const uint8_t* select;          // device, n_records, or nullptr (every MESSAGE record)
+    const uint8_t* queue_keys;      // device, 5 n_queues
+    const uint64_t* app_first;      // device, n_queues + 1
+    uint64_t n_queues;
+    const uint8_t* app_keys;        // device, 5 n_apps
+    const int32_t* queue_ids;       // device, n_apps
+    const uint32_t* sub_ids;        // device, n_apps, or nullptr
+    const uint32_t* from_record;    // device, n_apps, or nullptr (all 0)
+    const uint32_t* limit;          // device, n_apps, or nullptr (no limit)
+    uint64_t n_apps;
+    uint32_t size_only;             // 1: records is null, LIST_TOO_SMALL only for 2^32 pairs
+    uint32_t passes;                // 8-bit digits of n_apps - 1: the sort's passes
+    uint32_t* records;              // the caller's lists (device, list_cap each; out_sub_ids may be
+    int32_t* out_queue_ids;         // nullptr) and arrays (n_apps + 1, n_apps, n_apps, n_records,
+    uint32_t* out_sub_ids;          // each but list_first may be nullptr): written by k_pnd_frame,
+    uint64_t list_cap;              // when nothing was refused
+    uint64_t* list_first;
+    uint32_t* app_pending;
+    uint32_t* app_next;
+    uint32_t* pending_mask;
+    // workspace, zeroed before the launch
+    unsigned long long* ctr;        // kPndCtrWords
+    uint32_t* gslot;                // gslots: record + 1 of a selected MESSAGE record, hashed by
+    uint64_t gslots;                // GUID and queue key; a power of two
+    uint32_t* qslot;                // qslots: entry + 1 of the queue table, hashed by its key; a
+    uint64_t qslots;                // power of two (0 slots for an empty table)
+    uint32_t* confirmed;            // n_records: bit `ordinal`: a CONFIRM record names the message
+                                    // and that app
+    uint8_t* dead;                  // n_records: 1: a DELETION record of the run names it
+    // workspace, written before it is read
+    uint32_t* queue;                // n_records: a selected MESSAGE record's entry, or kPndNone
+    uint32_t* mask;                 // n_records: pending_mask
+    uint8_t* kind;                  // n_records: kPnd*
+    unsigned long long* off;        // n_records: the block-local prefix of popcount(mask)
+    unsigned long long* bsum;       // 2 * kPackBlocks: pairs | (unused) per block
+    uint64_t per_block;             // records per block (multiple of kPackThreads)
+    uint32_t nblocks;               // blocks over the records (<= kPackBlocks)
+    uint32_t cblocks;               // k_pnd_classify's grid: nblocks, or what the table's entries
+                                    // and apps, strided over, ask for (<= kPackBlocks)
+    // ... the sort and what follows it: sized by the host from ctr[kPndCtrPending]
+    uint64_t n_pairs;               // what the workspace holds of each of the four arrays below
+    uint32_t* key[2];               // n_pairs each: the pair's app, ping and pong
+    uint32_t* val[2];               // n_pairs each: the pair's record
+    uint32_t* hist;                 // kPndDigits * snblocks: digit-major, the scan's in and out
+    uint32_t* rowsum;               // kPndDigits: the pairs of each digit (k_pnd_scan)
+    uint64_t sper_block;            // pairs per block (multiple of kPackThreads)
+    uint32_t snblocks;              // blocks over the pairs (<= kPackBlocks, 0: no pair)
+    uint32_t anblocks;              // blocks over the apps (<= kPackBlocks, 0: no app)
+    uint64_t aper_block;            // apps per block (multiple of kPackThreads)
+    uint32_t* afirst;               // n_apps: first_pending(a), the app's first sorted pair
+    uint32_t* acount;               // n_apps: |list(a)|
+    unsigned long long* aoff;       // n_apps: the prefix of listed(a), then list_first[a]
+    unsigned long long* absum;      // 2 * kPackBlocks: listed entries | (unused) per block
+};
+
 }  // namespace bmqcrc
+
+// Launchers (crc32c_pending_list.hip).  Asynchronous on `stream`: the masks
+// decide every refusal but the last kind and count the pairs, which the host
+// reads to size the sort's buffers; the lists sort, bound and (unless size-only)
+// store.
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_pending_list_masks(const bmqcrc::PndArgs* a, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int bmqcrc_launch_pending_list_lists(const bmqcrc::PndArgs* a, void* stream);
 
 // Launchers (crc32c_expire_records.hip).  Asynchronous on `stream`: the layout
 // decides everything, the frame stores; a size-only call launches the layout

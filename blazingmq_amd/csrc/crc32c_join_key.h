@@ -1,10 +1,17 @@
 // crc32c_join_key.h -- the order-free join of journal records by GUID and
 // queue key: the key, its hash and the open-addressing table of MESSAGE records
-// two device calls build and probe (DESIGN.md sections 20 and 21).  Device
+// the device calls build and probe (DESIGN.md sections 20 to 23).  Device
 // only, in the anonymous namespace like the units' own code.
 //
 //   JoinKey, join_key, same_key, key_hash,      crc32c_rollover.hip,
-//   JoinTable, join_insert, join_find           crc32c_confirm_records.hip
+//   JoinTable, join_insert, join_find           crc32c_confirm_records.hip,
+//                                               crc32c_expire_records.hip,
+//                                               crc32c_pending_list.hip
+//   QueueTable, table_key, table_key_of,        crc32c_pending_list.hip
+//   table_insert, table_find                    (crc32c_expire_records.hip keeps
+//                                               its own queue_* over ExpArgs, whose
+//                                               text tests/expire_collisions.py
+//                                               mirrors; these are the same walk)
 //
 // A slot holds record + 1 of a MESSAGE record of the run (0: empty), so the
 // table stores no key: a probe compares with the record's own bytes, read by a
@@ -132,6 +139,67 @@ __device__ __forceinline__ uint32_t join_find(const JoinTable& t, const JoinKey&
         }
         if (same_key(k, join_key(t.journal + (uint64_t)kJournalRecordDwords * (cur - 1u),
                                  kMsgGuidDword))) {
+            return cur;
+        }
+    }
+    return 0;
+}
+
+// ---- a queue table's hash: a slot holds entry + 1 (0: empty) and no key, a
+// probe compares with the table's own 5-byte keys, read by an entry below the
+// table's length only.  A power of two of slots, at least twice the entries,
+// zeroed before the call; nothing is ever removed.  A queue key is hashed as a
+// JoinKey under the null GUID, so a record's (q0, q1) probes it as they are.
+
+struct QueueTable {
+    uint32_t* slot;       // slots words, zeroed before the call
+    uint64_t slots;       // a power of two, at least twice the entries (0: an empty table)
+    const uint8_t* keys;  // the table: 5 bytes an entry, at any alignment
+};
+
+// A queue key as the join holds one (q0, q1), under the null GUID.
+__device__ __forceinline__ JoinKey table_key(uint32_t q0, uint32_t q1)
+{
+    return {{0u, 0u, 0u, 0u}, q0, q1};
+}
+
+// Entry e's.
+__device__ __forceinline__ JoinKey table_key_of(const QueueTable& t, uint64_t e)
+{
+    const uint8_t null_guid[16] = {0};
+    return join_key_bytes(null_guid, t.keys + 5 * e);
+}
+
+// Entry e, whose key is k, into the table unless its key is there already:
+// returns 0 when e took a slot, otherwise entry + 1 of the one that holds it.
+__device__ __forceinline__ uint32_t table_insert(const QueueTable& t, const JoinKey& k, uint64_t e)
+{
+    const uint64_t mask = t.slots - 1;
+    uint64_t s = key_hash(k) & mask;
+    for (uint64_t step = 0; step < t.slots; ++step, s = (s + 1) & mask) {
+        const uint32_t cur = atomicCAS(&t.slot[s], 0u, (uint32_t)e + 1u);
+        if (cur == 0) {
+            return 0;
+        }
+        if (same_key(k, table_key_of(t, cur - 1u))) {
+            return cur;
+        }
+    }
+    return 0;
+}
+
+// Entry + 1 of the one that has this key, 0 when none has.  For a table that
+// is whole (or has no slot at all: no entry).
+__device__ __forceinline__ uint32_t table_find(const QueueTable& t, const JoinKey& k)
+{
+    const uint64_t mask = t.slots - 1;
+    uint64_t s = key_hash(k) & mask;
+    for (uint64_t step = 0; step < t.slots; ++step, s = (s + 1) & mask) {
+        const uint32_t cur = t.slot[s];
+        if (cur == 0) {
+            return 0;
+        }
+        if (same_key(k, table_key_of(t, cur - 1u))) {
             return cur;
         }
     }

@@ -1232,3 +1232,162 @@ def last_expire_records(device, stream=None):
     N.check(N.lib.bmqcrc_last_expire_records(
         device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
     return r.as_dict()
+
+
+# ----------------------------------------------------------------------------
+# Device-side delivery lists: each app's pending messages.
+# ----------------------------------------------------------------------------
+PendingRecords = collections.namedtuple(
+    "PendingRecords",
+    "records queue_ids sub_ids list_first app_pending app_next pending_mask result")
+
+
+def pending_records(journal, queue_keys, app_first, app_keys, queue_ids, *, sub_ids=None,
+                    from_record=None, limit=None, select=None, list_cap=None, stream=None,
+                    sync=True):
+    """List the messages of a device-resident partition that each consumer
+    still has to see, on the GPU (``bmqcrc_pending_records_list``): what
+    ``mqbi::Storage::getIterator(appKey)`` walks, as the ``records``,
+    ``queue_ids`` and ``sub_ids`` that ``pack_push_events`` takes.  There is no
+    CRC in this call: no payload byte is read.
+
+    The journal is the state, as for ``confirm_records`` and ``expire_records``:
+    ``journal`` (uint8, 4-byte aligned, whole 60-byte records) is the
+    partition's run and ``select`` (uint8, one byte per record, or None for
+    every MESSAGE record) says which MESSAGE records count.  A message is live
+    when it is selected and no DELETION record of the run names it.
+
+    The consumer table is in CSR form: queue q is ``queue_keys`` (uint8, 5 bytes
+    per queue) and owns the apps ``app_first[q] .. app_first[q + 1] - 1``
+    (int64, one entry more than there are queues; at most 32 apps a queue); an
+    app's ordinal is its position in that range.  App a is ``app_keys`` (uint8,
+    5 bytes per app, all zero for the null key), ``queue_ids[a]`` and
+    ``sub_ids[a]`` (int32, what the PUSH packer wants for this consumer; the
+    latter optional), ``from_record[a]`` (int32 read as unsigned, or None for
+    all 0: the delivery cursor, messages below it are not listed) and
+    ``limit[a]`` (int32 read as unsigned, or None for no limit).
+
+    A live message of a queue in the table is pending for an app of that queue
+    unless a CONFIRM record of the run (any reason, anywhere in the run) names
+    the message and the app's non-null key; an app with the null key sees every
+    live message of its queue.  Per-app PURGE records are not honoured.
+
+    ``list_cap=None`` sizes the lists exactly with a size-only call first,
+    which takes ``sync=True``.
+
+    Returns the named tuple ``(records, queue_ids, sub_ids, list_first,
+    app_pending, app_next, pending_mask, result)``: the three lists (int32;
+    ``sub_ids`` None without ``sub_ids``), grouped by app in table order and in
+    journal order inside an app, app a's entries at ``[list_first[a],
+    list_first[a + 1])`` (int64); ``app_pending`` (int32 per app: its pending
+    messages, listed or not), ``app_next`` (int32 per app: the first pending
+    record beyond its limit, the next call's ``from_record``; the number of
+    records when there is none), ``pending_mask`` (int32 per record: bit
+    ``ordinal`` for every app the message is pending for); ``result`` the dict
+    of ``last_pending_records`` (None with ``sync=False``).  With ``sync=True``
+    the lists are sliced to the entries written.  An empty run launches nothing
+    and leaves every array unwritten.  All or nothing: a malformed record or
+    table, or lists too small, writes nothing and, with ``sync=True``, raises
+    ``BmqCrcError`` (BMQCRC_EINVAL) naming kind and index.  The call waits for
+    its pair count on the host in either mode; ``sync=False`` leaves the sort
+    and the stores in flight.  Not meant to be captured into a graph."""
+    import torch
+    typed = (("journal", journal, torch.uint8, True), ("queue_keys", queue_keys, torch.uint8, True),
+             ("app_first", app_first, torch.int64, True), ("app_keys", app_keys, torch.uint8, True),
+             ("queue_ids", queue_ids, torch.int32, True), ("sub_ids", sub_ids, torch.int32, False),
+             ("from_record", from_record, torch.int32, False), ("limit", limit, torch.int32, False),
+             ("select", select, torch.uint8, False))
+    for name, t, dtype, required in typed:
+        if t is None and not required:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()):
+            raise TypeError("%s must be a contiguous %s tensor" % (name, dtype))
+    dev = journal.device
+    if not journal.is_cuda:
+        raise TypeError("pending_records takes device tensors only (journal is on %s)" % dev)
+    for name, t, _, _ in typed[1:]:
+        if t is not None and t.device != dev:
+            raise TypeError("%s must be on %s like journal" % (name, dev))
+    if journal.numel() % JOURNAL_RECORD_SIZE:
+        raise ValueError("journal must hold whole 60-byte records")
+    n_records = journal.numel() // JOURNAL_RECORD_SIZE
+    n_queues, n_apps = app_first.numel() - 1, queue_ids.numel()
+    if n_queues < 0 or queue_keys.numel() != 5 * n_queues:
+        raise ValueError("queue_keys needs 5 bytes per queue and app_first one entry more than "
+                         "there are queues")
+    if app_keys.numel() != 5 * n_apps:
+        raise ValueError("app_keys needs 5 bytes per entry of queue_ids")
+    for name, t in (("sub_ids", sub_ids), ("from_record", from_record), ("limit", limit)):
+        if t is not None and t.numel() != n_apps:
+            raise ValueError("%s needs one entry per app, like queue_ids" % name)
+    if select is not None and select.numel() != n_records:
+        raise ValueError("select has the wrong size")
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    # (an empty tensor has no address: the call wants one for the required arrays)
+    spare = torch.empty(8, dtype=torch.int64, device=dev)
+
+    def at(t, needed=True):
+        return (t.data_ptr() or spare.data_ptr()) if t is not None and needed else None
+
+    p = N.PendingList()
+    p.struct_size = ctypes.sizeof(N.PendingList)
+    p.journal, p.journal_bytes = at(journal), journal.numel()
+    p.n_records, p.n_queues, p.n_apps = n_records, n_queues, n_apps
+    p.select = at(select, n_records)
+    p.queue_keys, p.app_first = at(queue_keys, n_queues), at(app_first)
+    p.app_keys, p.queue_ids = at(app_keys, n_apps), at(queue_ids, n_apps)
+    p.sub_ids, p.from_record, p.limit = at(sub_ids, n_apps), at(from_record, n_apps), \
+        at(limit, n_apps)
+    dev_index = dev.index if dev.index is not None else -1
+    if list_cap is None:
+        if not sync:
+            raise ValueError("list_cap is required when sync=False: sizing the lists waits for a "
+                             "size-only call")
+        o = N.make_opts(device=dev_index, stream=stream.cuda_stream, flags=N.BMQCRC_F_DEVICE_PTRS)
+        r = N.PendingListResult()
+        N.check(N.lib.bmqcrc_pending_records_list(ctypes.byref(p), ctypes.byref(r),
+                                                  ctypes.byref(o)))
+        list_cap = int(r.n_listed)
+    list_cap = int(list_cap)
+    records = torch.empty(list_cap, dtype=torch.int32, device=dev)
+    out_queue_ids = torch.empty(list_cap, dtype=torch.int32, device=dev)
+    with_subs = sub_ids is not None and n_apps != 0
+    out_sub_ids = torch.empty(list_cap, dtype=torch.int32, device=dev) if with_subs else None
+    list_first = torch.empty(n_apps + 1, dtype=torch.int64, device=dev)
+    app_pending = torch.empty(n_apps, dtype=torch.int32, device=dev)
+    app_next = torch.empty(n_apps, dtype=torch.int32, device=dev)
+    pending_mask = torch.empty(n_records, dtype=torch.int32, device=dev)
+    p.records, p.out_queue_ids, p.out_sub_ids = at(records), at(out_queue_ids), at(out_sub_ids)
+    p.list_cap, p.list_first = list_cap, at(list_first)
+    p.app_pending, p.app_next = at(app_pending, n_apps), at(app_next, n_apps)
+    p.pending_mask = at(pending_mask, n_records)
+    o = N.make_opts(device=dev_index, stream=stream.cuda_stream,
+                    flags=N.BMQCRC_F_DEVICE_PTRS | (0 if sync else N.BMQCRC_F_ASYNC))
+    r = N.PendingListResult()
+    N.check(N.lib.bmqcrc_pending_records_list(ctypes.byref(p), ctypes.byref(r), ctypes.byref(o)))
+    if not sync:
+        return PendingRecords(records, out_queue_ids, out_sub_ids, list_first, app_pending,
+                              app_next, pending_mask, None)
+    n = int(r.n_listed)
+    return PendingRecords(records[:n], out_queue_ids[:n],
+                          out_sub_ids[:n] if out_sub_ids is not None else None, list_first,
+                          app_pending, app_next, pending_mask, r.as_dict())
+
+
+def last_pending_records(device, stream=None):
+    """The result of the previous ``pending_records`` on (device, stream)
+    (bmqcrc_last_pending_records), as a dict; waits for it.  ``n_records``;
+    ``n_live`` live MESSAGE records, of which ``n_no_queue`` have no queue in the
+    table; ``n_pending``, the pending (app, message) pairs; ``n_listed``, the
+    entries written (or, after a size-only call, needed); ``n_unknown_confirms``
+    and ``n_not_found``, the CONFIRM records whose app key no app of the queue
+    has and those without a message; ``refused_kind`` (0,
+    ``BMQCRC_PENDING_LIST_OK``, or the kind) and ``refused_index`` (a record, a
+    queue or an app, by kind).  After a refused call only ``n_records`` and the
+    two ``refused_*`` are set.  ``stream=None`` is the device's default
+    stream."""
+    r = N.PendingListResult()
+    N.check(N.lib.bmqcrc_last_pending_records(
+        device, stream.cuda_stream if stream is not None else None, ctypes.byref(r)))
+    return r.as_dict()

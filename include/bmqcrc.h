@@ -356,7 +356,7 @@ const char* bmqcrc_last_error(void);
 void bmqcrc_note_host_fallback(int32_t rc);
 uint64_t bmqcrc_host_fallbacks(int32_t* last_rc);
 
-/* ABI version: (major << 16) | minor (2.20).  What the last minors added:
+/* ABI version: (major << 16) | minor (2.21).  What the last minors added:
  *   (2.8)  BMQCRC_F_OFFSETS32, bmqcrc_last_offsets
  *   (2.9)  bmqcrc_crc32c_copy, bmqcrc_last_copy
  *   (2.10) bmqcrc_put_event_pack, bmqcrc_last_put_pack (bmqcrc_protocol.h)
@@ -369,7 +369,8 @@ uint64_t bmqcrc_host_fallbacks(int32_t* last_rc);
  *   (2.17) bmqcrc_push_event_pack, bmqcrc_last_push_pack (bmqcrc_protocol.h)
  *   (2.18) bmqcrc_partition_rollover, bmqcrc_last_rollover (bmqcrc_protocol.h)
  *   (2.19) bmqcrc_confirm_records_pack, bmqcrc_last_confirm_records (bmqcrc_protocol.h)
- *   (2.20) bmqcrc_expire_records_pack, bmqcrc_last_expire_records (bmqcrc_protocol.h) */
+ *   (2.20) bmqcrc_expire_records_pack, bmqcrc_last_expire_records (bmqcrc_protocol.h)
+ *   (2.21) bmqcrc_pending_records_list, bmqcrc_last_pending_records (bmqcrc_protocol.h) */
 uint32_t bmqcrc_version(void);
 
 #ifdef __cplusplus

@@ -1583,6 +1583,172 @@ int bmqcrc_expire_records_pack(const bmqcrc_expire_pack* p, bmqcrc_expire_pack_r
  * stream); waits for it.  `result` may be NULL. */
 int bmqcrc_last_expire_records(int device, void* stream, bmqcrc_expire_pack_result* result);
 
+/* ABI 2.21.  What to deliver to whom: the messages of a device-resident
+ * partition that each consumer (app) still has to see, listed ON THE DEVICE as
+ * the records[], queue_ids[] and sub_ids[] bmqcrc_push_event_pack takes, in one
+ * call.  In the reference this is mqbi::Storage::getIterator(appKey) --
+ * FileBackedStorage::getIterator, VirtualStorageCatalog::begin and
+ * VirtualStorageIterator::advance, which skips every message whose
+ * appMessageView(ordinal) is not pending -- over the state that
+ * FileBackedStorage::processMessageRecord, processConfirmRecord and
+ * processDeletionRecord rebuild record by record after a restart.  This call
+ * has no CRC in it: no payload byte is read.  It is here because it was the one
+ * step between the device calls that still needed the journal on the host.
+ *
+ * The journal is the state, as in bmqcrc_confirm_records_pack and
+ *   bmqcrc_expire_records_pack: the run (journal, journal_bytes == 60
+ *   n_records), select and key = (GUID, queue key) mean what they mean there.
+ * The consumer table has the shape of the reference's one storage per queue
+ *   with its virtual storages by ordinal, in CSR form: queue q = 0 .. n_queues
+ *   - 1 is queue_keys[5 q .. +5) and owns the apps app_first[q] ..
+ *   app_first[q + 1] - 1; an app's ORDINAL is its position in that range; a
+ *   queue has at most 32 apps, so that a message's per-app state is one word.
+ *   App a = 0 .. n_apps - 1 is app_keys[5 a .. +5) (all zero: the null key),
+ *   queue_ids[a] and sub_ids[a] (what bmqcrc_push_pack wants for this
+ *   consumer; sub_ids may be NULL), from_record[a] (may be NULL: all 0; the
+ *   delivery cursor, messages below it are not listed) and limit[a] (may be
+ *   NULL: no limit; the consumer's remaining maxUnconfirmedMessages).
+ * For a selected MESSAGE record m:
+ *   - live(m): no DELETION record anywhere in the run has its key.
+ *   - queue(m): the table's queue whose 5 bytes equal bytes 22..26 of m, or
+ *     none.  A live message without a queue is never listed and is counted in
+ *     n_no_queue.
+ *   - confirmed(m, a): a is an app of queue(m) with a NON-NULL app key, and some
+ *     CONFIRM record of the run has m's key and, in bytes 27..31, a's app key.
+ *     Any reason counts, e_AUTO_CONFIRMED included, wherever the record stands
+ *     in the run.  A CONFIRM record with a null app key marks nothing
+ *     (processConfirmRecord's `if (!appKey.isNull())`).  A CONFIRM record whose
+ *     message is found but whose app key no app of the queue has (or whose
+ *     queue is not in the table) is counted in n_unknown_confirms and has no
+ *     effect: the reference logs #STORAGE_INVALID_CONFIRM and ignores it.  A
+ *     CONFIRM record whose key no selected MESSAGE record has is counted in
+ *     n_not_found, whatever its app key.
+ *   - pending(m, a): live(m), a is an app of queue(m), not confirmed(m, a) and
+ *     m >= from_record[a].  An app with the null key therefore sees every live
+ *     message of its queue: the reference's getIterator(k_NULL_KEY).
+ *   - list(a): the pending records of a in journal order; listed(a): its first
+ *     min(|list(a)|, limit[a]); next(a): the record at position limit[a] of
+ *     list(a), or n_records when there is none -- the next call's
+ *     from_record[a].
+ * Outputs, grouped by app in table order and in journal order inside an app:
+ *   records[list_cap], out_queue_ids[list_cap] and out_sub_ids[list_cap] (may
+ *   be NULL, must be NULL when sub_ids is) hold listed(a) at [list_first[a],
+ *   list_first[a + 1]), list_first[n_apps + 1] being the prefix of |listed(a)|.
+ *   The three are exactly the arrays bmqcrc_push_event_pack takes.  list_first
+ *   has event_first's type, for a caller that cuts one event per app: an EMPTY
+ *   app repeats an entry, which event_first refuses, so such a caller drops the
+ *   repeats first.  Per app, each may be NULL: app_pending[n_apps] (|list(a)|)
+ *   and app_next[n_apps] (next(a)).  Per record, may be NULL:
+ *   pending_mask[n_records], bit `ordinal` set when pending(m, a), 0 for every
+ *   record that is not a live selected MESSAGE record with a queue.
+ * Size only.  records == NULL with list_cap == 0: everything is decided,
+ *   nothing is stored (no output array either) and the result says what a real
+ *   call would write.
+ * All or nothing, decided on the device.  One violation anywhere refuses the
+ *   call, and a refused call writes nothing.  The lowest kind wins and within
+ *   it the lowest index (BMQCRC_PENDING_LIST_* below), whatever the order the
+ *   device works in.  A synchronous call returns BMQCRC_EINVAL naming kind and
+ *   index; after an asynchronous call bmqcrc_last_pending_records reports them.
+ * What differs from the reference.
+ *   - Per-app PURGE records (a QueueOpType::e_PURGE with a non-null app key)
+ *     are NOT honoured: the reference's form carries a start lease and sequence
+ *     number, which the selection would have to learn first.  Whole-queue
+ *     purges and queue deletions are `select`'s (bmqcrc_journal_select).  This
+ *     is the first follow-up.
+ *   - No RDA counters, no receipts (hasReceipt), no in-flight "pushing" state:
+ *     the cursor and the limit are the caller's.
+ *   - An app added after a message was stored is handled by the caller's
+ *     from_record; in the reference this is d_defaultNonApplicableAppMessage.
+ * Options.  Device pointers only: BMQCRC_F_DEVICE_PTRS is required,
+ *   BMQCRC_F_ASYNC allowed; any other flag, ndevices > 1, a wrong struct_size or
+ *   a non-zero reserved field; journal, app_first or (unless size-only)
+ *   out_queue_ids or list_first null; queue_keys null with n_queues != 0;
+ *   app_keys or queue_ids null with n_apps != 0; records null with list_cap !=
+ *   0; out_sub_ids without sub_ids; journal or a uint32 / int32 array not 4-byte
+ *   aligned, app_first or list_first not 8-byte aligned (queue_keys, app_keys
+ *   and select may stand at any byte); journal_bytes != 60 n_records;
+ *   n_records, n_queues or n_apps >= 2^32; an output meeting an input or
+ *   another output is BMQCRC_EINVAL, answered on the host before the device
+ *   lookup.  n_records == 0 launches nothing, writes nothing (list_first
+ *   neither, and the table is not looked at) and reports zeros.
+ * *result (may be NULL) is written by a synchronous call only.
+ * State.  As bmqcrc_expire_records_pack: takes the workspace mutex of (device,
+ *   stream); restores the caller's current device; allocates its own workspace
+ *   on first use and when the call grows (22 bytes per record and 8 to 16 more
+ *   for the hash, 8 to 16 per queue, 16 per app, 16 per pair (app, message)
+ *   that is pending), which bmqcrc_reserve does not cover; is not meant to be
+ *   captured into a hipGraph; is deterministic.  The pairs are counted on the
+ *   device and that ONE WORD is read by the host, in the middle of the call, to
+ *   size the sort's buffers: the call therefore waits for its first four
+ *   kernels whether or not BMQCRC_F_ASYNC is set, and BMQCRC_F_ASYNC leaves the
+ *   sort and the stores in flight.  (Sizing by the bound of 32 pairs a message
+ *   would need no wait and 512 bytes a record.)  The shape prediction and the
+ *   records of every other bmqcrc_last_* call are never touched. */
+#define BMQCRC_PENDING_LIST_OK 0
+#define BMQCRC_PENDING_LIST_RECORD_HEADER 1      /* BMQCRC_CONFIRM_PACK_RECORD_HEADER's conditions, on
+                                                    every record of the run.  Index: the record */
+#define BMQCRC_PENDING_LIST_DUPLICATE_MESSAGE 2  /* two selected MESSAGE records share a key.  Index:
+                                                    the lowest record among all that share theirs */
+#define BMQCRC_PENDING_LIST_QUEUE_KEY 3          /* an all-zero queue key, or one that stands in the
+                                                    table twice.  Index: the lowest such queue */
+#define BMQCRC_PENDING_LIST_APP_FIRST 4          /* app_first[0] != 0 (index 0); app_first[q] >
+                                                    app_first[q + 1] or more than 32 apps (index q);
+                                                    app_first[n_queues] != n_apps (index n_queues).
+                                                    The lowest such index */
+#define BMQCRC_PENDING_LIST_APP_KEY 5            /* two apps of one queue share an app key (the null
+                                                    key may stand once too).  Index: the lowest app
+                                                    among them */
+#define BMQCRC_PENDING_LIST_FROM_RECORD 6        /* from_record[a] > n_records.  Index: the app */
+#define BMQCRC_PENDING_LIST_LIST_TOO_SMALL 7     /* index: the lowest app whose listed entries end past
+                                                    list_cap; n_apps when the sum of |list(a)| is 2^32
+                                                    or more (a size-only call raises only this) */
+
+typedef struct bmqcrc_pending_list {
+    uint32_t struct_size, reserved;       /* sizeof, 0 */
+    const void* journal;                  /* device, 4-byte aligned: n_records 60-byte records, the record run */
+    uint64_t journal_bytes;               /* == 60 * n_records */
+    uint64_t n_records;                   /* < 2^32 */
+    const uint8_t* select;                /* device, n_records, may be NULL (every MESSAGE record) */
+    const uint8_t* queue_keys;            /* device, 5 n_queues (may be NULL when n_queues is 0) */
+    const uint64_t* app_first;            /* device, n_queues + 1, 8-byte aligned */
+    uint64_t n_queues;                    /* < 2^32 */
+    const uint8_t* app_keys;              /* device, 5 n_apps (may be NULL when n_apps is 0) */
+    const int32_t* queue_ids;             /* device, n_apps (may be NULL likewise) */
+    const uint32_t* sub_ids;              /* device, n_apps, may be NULL */
+    const uint32_t* from_record;          /* device, n_apps, may be NULL (all 0) */
+    const uint32_t* limit;                /* device, n_apps, may be NULL (no limit) */
+    uint64_t n_apps;                      /* < 2^32 */
+    uint32_t* records;                    /* device, list_cap; NULL (list_cap 0): size only */
+    int32_t* out_queue_ids;               /* device, list_cap */
+    uint32_t* out_sub_ids;                /* device, list_cap, may be NULL; NULL when sub_ids is */
+    uint64_t list_cap;                    /* entries */
+    uint64_t* list_first;                 /* device, n_apps + 1, 8-byte aligned */
+    uint32_t* app_pending;                /* device, n_apps, may be NULL */
+    uint32_t* app_next;                   /* device, n_apps, may be NULL */
+    uint32_t* pending_mask;               /* device, n_records, may be NULL */
+} bmqcrc_pending_list;
+
+/* All fields zero before the first call on (device, stream); after a refused
+ * call only n_records and the refused_* fields are set. */
+typedef struct bmqcrc_pending_list_result {
+    uint64_t n_records;
+    uint64_t n_live;                      /* live MESSAGE records */
+    uint64_t n_no_queue;                  /* ... of them without a queue in the table */
+    uint64_t n_pending;                   /* the sum of |list(a)| */
+    uint64_t n_listed;                    /* entries written (or, size-only, that a real call writes) */
+    uint64_t n_unknown_confirms;          /* CONFIRM records whose app key no app of the queue has */
+    uint64_t n_not_found;                 /* CONFIRM records without a selected MESSAGE record */
+    uint32_t refused_kind, reserved;
+    uint64_t refused_index;               /* a record, a queue or an app, by kind */
+} bmqcrc_pending_list_result;
+
+int bmqcrc_pending_records_list(const bmqcrc_pending_list* p, bmqcrc_pending_list_result* result,
+                                const bmqcrc_opts* opts);
+
+/* ABI 2.21.  Result of the previous bmqcrc_pending_records_list on (device,
+ * stream); waits for it.  `result` may be NULL. */
+int bmqcrc_last_pending_records(int device, void* stream, bmqcrc_pending_list_result* result);
+
 /* ---- cluster state ledger (mqbc_clusterstateledgerprotocol.h:76,272) ------ */
 
 /* mqbc::ClusterStateLedgerUtilRc values (mqbc_clusterstateledgerutil.h:65-124)
